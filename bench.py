@@ -10,15 +10,25 @@ its own tables) per GPU; with N GPUs each rank evolves its own 1024 points
 collective on the data path.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c5|c3|c2|c1] [--points P]
+                  [--dump-outputs DIR] [--full]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N, or plain
 `python bench.py --gpus N`, which starts that launcher itself (N fresh rank processes, before any GPU
 call here) and exits with its status; a rank count that differs from --gpus is an error.
 
-Prints one JSON line (rank 0) with roofline (the dominant alpha-table kernel, fp64 VALU),
-roofline_cascade (the metric's cascade HBM GB/s) and the cpu_baseline (the C oracle on a
-thread pool over the host cores the job may use, bounded sample, Stage A / Stage B timed
-apart on one core).  c2 / c1 (single propagations) add the latency of one evolve() through
-the object API (nusi_evolve, host I/O included) beside the 1-point plan's device-resident rate.
+Prints one JSON line (rank 0) with roofline (the dominant alpha-table kernel, fp64 VALU) and
+roofline_cascade (the metric's cascade HBM GB/s), both from the timed steps' own HIP events.
+A plain run does no more: set-up, warm-up, the timed steps, the line.
+
+--dump-outputs DIR writes what the last timed step computed (the flux and fla arrays a caller
+of Plan.evolve_device receives) as DIR/flux.npy and DIR/fla.npy (float64, at most 64 MB in
+all: a seeded sample of the points where the arrays are larger, its indices in DIR/points.npy).
+
+--full adds, after the timed region, everything else the benchmark measures or checks: the
+parity object (the oracle's fluxes of a sample), the cpu_baseline (the C oracle on a thread
+pool over the host cores the job may use, bounded sample, Stage A / Stage B timed apart on one
+core), the secondary lines (C5, C3, C2 and the shared order, each a child process) and, for
+c2 / c1 (single propagations), the latency of one evolve() through the object API
+(nusi_evolve, host I/O included) beside the 1-point plan's device-resident rate.
 """
 import argparse
 import json
@@ -55,11 +65,18 @@ def parse():
                          "m_phi lie on the table axis' r^(-o/2) lattice; not the headline (its fluxes are held to 1e-9, "
                          "not bit-exact tables)")
     ap.add_argument("--points", type=int, default=0, help="points per GPU (default: 1024 for c4 and c3, 8192 for c5, 1 for c2)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the oracle CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the parity object, "
+                         "the oracle's cpu_baseline, the secondary lines (C4 only) and the object-API latency (c2, c1); "
+                         "--no-parity, --no-cpu-baseline and --no-secondary drop single parts of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (flux, fla: [points, 3, N_E] float64) to DIR/<name>.npy, "
+                         "at most 64 MB in all (a seeded sample of the points beyond that, indices in DIR/points.npy)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="(--full) budget of the oracle CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the cpu_baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the C5 and C3 lines the default C4 run adds (secondary_lines: each its own child "
-                         "process, a few steps, after the timed region)")
+                    help="(--full) skip the C5, C3, C2 and shared-order lines the C4 run adds (secondary_lines: each "
+                         "its own child process, a few steps, after the timed region)")
     ap.add_argument("--cascade", default="auto", choices=["auto", "mfma", "wf"],
                     help="cascade kernel: auto = the library default (= mfma: the wavefront with the push on the fp64 "
                          "matrix cores, block-synchronous k_cascade_bs), wf = the bit-exact scalar cascade k_cascade")
@@ -76,7 +93,7 @@ def parse():
                     help="NUSI_OPT_REFO_CORNER_MB (A/B): the reference order's member-corner block budget in MiB, "
                          "0 = the library's automatic choice")
     ap.add_argument("--reference-order", action="store_true", help="(the default; kept for old command lines)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity object (oracle fluxes of a sample)")
+    ap.add_argument("--no-parity", action="store_true", help="(--full) skip the parity object (oracle fluxes of a sample)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rank / reduction plumbing only, no GPU work (gloo; CPU tests): prints the JSON "
                          "line with value null")
@@ -87,6 +104,10 @@ def parse():
     if args.shared_order and args.reference_order:
         ap.error("--shared-order and --reference-order exclude each other")
     args.reference_order = not args.shared_order
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_parity = args.no_secondary = args.no_cpu_baseline = True
+    if args.steps < 1 and not args.dry_run:
+        ap.error("--steps must be >= 1 (the number of timed steps)")
     return args
 
 
@@ -459,7 +480,8 @@ def secondary_lines(local):
               "ROLE_RANK", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)   # each child is a plain single-GPU run, not a rank of this job
     for name, extra, steps in SECONDARY:
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", "1", "--no-secondary"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", "1", "--full",
+               "--no-secondary"] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env)
             d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -538,6 +560,34 @@ def dry_run(args, world, rank):
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: all arrays together
+DUMP_SEED = 20250213
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the timed path's outputs of the last timed step ({name: device tensor [P, ...] float64}, what
+    a caller of Plan.evolve_device holds afterwards) as dirname/<name>.npy.  Beyond DUMP_MAX_BYTES in all, the same
+    seeded, sorted sample of the points from every array, its indices in dirname/points.npy.  Returns the record
+    the result line carries."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    P = next(iter(arrays.values())).shape[0]
+    per_point = sum(t[0].numel() * 8 for t in arrays.values())
+    keep = min(P, max(1, (DUMP_MAX_BYTES - 4096) // (per_point + 8)))   # (4096: the .npy headers; 8: points.npy's entry)
+    idx = np.arange(P, dtype=np.int64)
+    if keep < P:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(P, size=keep, replace=False)).astype(np.int64)
+    nbytes = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.cpu().numpy()[idx], dtype=np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        nbytes += a.nbytes
+    np.save(os.path.join(dirname, "points.npy"), idx.astype(np.float64))
+    return {"dir": dirname, "arrays": {n: [len(idx)] + list(t.shape[1:]) for n, t in arrays.items()}, "dtype": "float64",
+            "points": len(idx), "of_points": P, "sampled": keep < P, "bytes": nbytes + 8 * len(idx),
+            "note": "outputs of the last timed step; points.npy = the rows' indices into the rank's batch"}
 
 
 def pmc_summary_path(workload, reference_order):
@@ -656,6 +706,7 @@ def run(args, world, rank, local, dist, plan, pts, desc, pp_tables):
     # a phi-phi lookup outside the table nodes (the reference's exit(1), interp.hpp:355-361) is flagged per
     # point by the kernels; the async evolve does not raise, so count them here
     oob = sum(1 for w in plan.warnings(P) if w & 8)
+    dumped = dump_outputs(args.dump_outputs, {"flux": flux, "fla": fla}) if args.dump_outputs and rank == 0 else None
 
     N, Nz = plan.N, plan.Nz
     alpha_kernel, casc_kernel = plan.kernels()   # what the library launched (nusi_plan_kernels)
@@ -702,6 +753,7 @@ def run(args, world, rank, local, dist, plan, pts, desc, pp_tables):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3,
+        "full": args.full,
         "higher_is_better": True,
         "scaling": global_scan(args, world)[1] if args.workload in ("c4", "c4s", "c5") else "weak",
         "vs_baseline": None,
@@ -802,10 +854,13 @@ def run(args, world, rank, local, dist, plan, pts, desc, pp_tables):
                          "note": "flavour fluxes of all ranks to rank 0 (dist._gather_blocks), not in the timed region"}
         if rank == 0:
             out["gather"]["points_gathered"] = int(sum(len(x) for x in parts))
-    if args.workload == "c1" and rank == 0:
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    # from here on --full only (a plain run has no_parity, no_secondary and no_cpu_baseline set: parse())
+    if args.full and args.workload == "c1" and rank == 0:
         out["single_propagation"], _ = single_point_latency(pts[0], max(20, args.steps), args.reference_order)
         out["single_propagation"]["plan_ms_per_step"] = dt / args.steps * 1e3
-    if args.workload == "c2" and rank == 0:   # both BASELINE config-2 cases through the object API
+    if args.full and args.workload == "c2" and rank == 0:   # both BASELINE config-2 cases through the object API
         out["single_propagation"], c2_fla = {}, {}
         for name, cp in C2_CASES.items():
             out["single_propagation"][name], c2_fla[name] = single_point_latency(cp, max(20, args.steps),

@@ -8,6 +8,7 @@
 #   profile=<wl>[,<wl>..]   rocprofv3 kernel stats + PMC passes (scripts/gpu_profile_all.sh) -> prof/<wl>/;
 #                           the summaries are copied to profiles/pmc_traffic_<wl>.json
 #   bench[=<a>,<b>,..]      python bench.py <a> <b> ..  (commas = spaces)           -> bench_<i>.json / .err
+#                           (bench=--full for the line with parity, CPU baseline and the secondary lines)
 #   prof=<a>,<b>,..         rocprofv3 --kernel-trace --stats of bench.py <a> <b> .. -> kt_<i>/
 #   py=<script>,<a>,..      python <script> <a> ..                                   -> py_<i>.out / .err
 #   vbench=<v>,<a>,..       bench.py <a> .. on the A/B library build/variants/libnusi_<v>.so (scripts/build_variant.sh)

@@ -124,3 +124,51 @@ def test_pmc_summary_must_match_library_and_table_order(tmp_path):
     assert bench.load_pmc(str(tmp_path / "missing.json"), sha, "reference") == ({}, None, None)
     assert bench.pmc_summary_path("c4", True).endswith("profiles/pmc_traffic_c4.json")
     assert bench.pmc_summary_path("c4", False).endswith("profiles/pmc_traffic_c4_shared.json")
+
+
+def test_plain_run_drops_what_full_adds(monkeypatch):
+    """Without --full the parity object, the cpu_baseline and the secondary lines are off; --full turns them on and
+    the --no-* options still drop single parts.  --steps is the number of timed steps and must be >= 1."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import pytest
+
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        return bench.parse()
+    a = parsed("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert not a.full and a.no_parity and a.no_secondary and a.no_cpu_baseline and a.steps == 7 and a.dump_outputs == ""
+    a = parsed("--full")
+    assert a.full and not (a.no_parity or a.no_secondary or a.no_cpu_baseline)
+    a = parsed("--full", "--no-parity", "--dump-outputs", "d")
+    assert a.full and a.no_parity and not a.no_secondary and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        parsed("--steps", "0")
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: every array whole while they fit the byte budget, otherwise the same seeded, sorted sample of
+    the points from each (points.npy), identical from call to call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    flux = torch.rand((37, 3, 11), dtype=torch.float64, generator=g)
+    fla = torch.rand((37, 3, 11), dtype=torch.float64, generator=g)
+    rec = bench.dump_outputs(str(tmp_path / "a"), {"flux": flux, "fla": fla})
+    assert not rec["sampled"] and rec["points"] == 37 and rec["arrays"] == {"flux": [37, 3, 11], "fla": [37, 3, 11]}
+    got = np.load(tmp_path / "a" / "flux.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, flux.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "fla.npy"), fla.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "points.npy"), np.arange(37.0))
+    # a budget of 10 points' rows (2 arrays x 33 doubles each, plus the index column) beside the file headers
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * (2 * 33 * 8 + 8) + 4096)
+    rec = bench.dump_outputs(str(tmp_path / "b"), {"flux": flux, "fla": fla})
+    idx = np.load(tmp_path / "b" / "points.npy").astype(int)
+    assert rec["sampled"] and rec["points"] == 10 == len(set(idx)) and np.all(np.diff(idx) > 0)
+    assert rec["bytes"] <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(np.load(tmp_path / "b" / "flux.npy"), flux.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "fla.npy"), fla.numpy()[idx])
+    bench.dump_outputs(str(tmp_path / "c"), {"flux": flux, "fla": fla})
+    assert np.array_equal(np.load(tmp_path / "c" / "points.npy"), idx)
