@@ -611,10 +611,6 @@ AlphaBatches alpha_batches(nusi_plan* pl, int ntab, std::vector<int>& perm)
 // NUSI_OPT_REFO_CORNER_MB (automatic: kMCornerBudget bytes and half the free memory) of tables, at least the largest
 // batch; launch_alpha runs the batches in chunks that fit
 constexpr size_t kMCornerBudget = size_t(8) << 30;
-#ifndef NUSI_GA_PRE   // A/B: 0 = the reference order's Gamma / alphaTilde of few tables without k_ga_dilogs
-#define NUSI_GA_PRE 1
-#endif
-constexpr bool kGaPre = NUSI_GA_PRE != 0;
 constexpr int kOverlapTables = 16;   // calls of at most this many tables overlap Gamma / alphaTilde with alpha
 constexpr size_t kStageBytes = size_t(4) << 20;   // nusi_plan_evolve_host's pinned output staging, at most
 constexpr int kSplitTables = 2;   // calls of at most this many tables (no phi-phi) run the k-split alpha path
@@ -1162,12 +1158,9 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
         pl->tabs.Kt = pl->d_kt;
     }
     // a call of few tables in the reference order: Gamma / alphaTilde's GSL dilogarithms one per work-item first
-    // (k_ga_dilogs; 2.2 MB per table at N_E = 300)
+    // (k_ga_dilogs; 2.2 MB per table at N_E = 300).  The one place "few" is decided: launch_gamma_alphat follows Gpre
     pl->tabs.Gpre = nullptr;
-#ifndef NUSI_GA_PRE_ALL
-#define NUSI_GA_PRE_ALL 0
-#endif
-    if (kGaPre && refo && nbase == 0 && nd > 0 && (nd <= kOverlapTables || NUSI_GA_PRE_ALL)) {
+    if (refo && nbase == 0 && nd > 0 && nd <= kOverlapTables) {
         const size_t need = nusi::gamma_alphat_pre_doubles(pl->gd.T, nd);
         if (pl->gpre_doubles < need) {
             hipFree(pl->d_gpre);

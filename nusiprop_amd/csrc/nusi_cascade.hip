@@ -353,10 +353,6 @@ __global__ __launch_bounds__(64) void k_cascade(GridDev g, const Point* __restri
 typedef double nusi_f64x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------
-#ifndef NUSI_BS_SRC_AHEAD   // A/B: 0 = the DSNB sources loaded and stored within one phase B
-#define NUSI_BS_SRC_AHEAD 1
-#endif
-constexpr bool kSrcAhead = NUSI_BS_SRC_AHEAD != 0;
 // Helpers of the MFMA cascade k_cascade_bs (below): the power-law source, the DSNB source table, the chain's
 // hand-off between redshift steps and the resonant-only running sum.
 // ---------------------------------------------------------------------------
@@ -486,18 +482,12 @@ __device__ unsigned int g_ws_hwid[kTrBlocks * kTrWaves];   // HW_ID (SE, CU, SIM
 // element's four columns in its own order whichever column it is, so a point's fluxes depend on its grouping only
 // through the step passes (to rounding).  Waves: push waves of 16 RT rows, the chain waves, the record wave.
 // ---------------------------------------------------------------------------
-#ifndef NUSI_BS_SIMDMAP   // the chain and record waves beside the least-busy push waves (wave w runs on SIMD f(w % 4),
-#define NUSI_BS_SIMDMAP 1    // HW_ID in the trace build): C5 cascade 3.19 -> 2.82 ms, C3 23.4 -> 21.4, C4 equal
-#endif                       // (profiles/r4/ab/r4u, r4v); 0 = the push waves' rows in wave order
-#ifndef NUSI_BS_LONG32   // A/B: step passes of 32 on long grids (<32, 1, 1, 6, 1>: 14 push waves of 96 rows)
-#define NUSI_BS_LONG32 0
-#endif
-#ifndef NUSI_BS_PRIO   // the chain and record waves at raised issue priority (s_setprio 3; the push waves 0): C5
-#define NUSI_BS_PRIO 1    // cascade 3.51 -> 3.25 ms, C3 29.1 -> 24.8, C4 0.555 -> 0.528 (profiles/r4/ab/r4n, r4o); 0 = off.
-#endif                    // Sleeping the push waves at phase B's start (to let the chain's loads first) measured no gain
-#ifndef NUSI_BS_PIPE   // A/B: k_cascade_bs's chain issues stage d + 1's loads before stage d's solve (two stages'
-#define NUSI_BS_PIPE 0  // operands live: spills at the 128-VGPR budget)
-#endif
+// Two shipped placements (measured against their absence, DESIGN.md "Retired build variants"):
+//   * the chain and record waves sit beside the least-busy push waves (wave w runs on SIMD f(w % 4), HW_ID in the
+//     trace build): C5 cascade 3.19 -> 2.82 ms, C3 23.4 -> 21.4, C4 equal (profiles/r4/ab/r4u, r4v);
+//   * the chain and record waves run at raised issue priority (s_setprio 3; the push waves 0): C5 cascade 3.51 ->
+//     3.25 ms, C3 29.1 -> 24.8, C4 0.555 -> 0.528 (profiles/r4/ab/r4n, r4o).  Sleeping the push waves at phase B's
+//     start (to let the chain's loads first) measured no gain.
 template <int NJ, int P, int SPL, int RT, int CW>
 struct BsCfg {
     static constexpr int LPP = NJ / SPL;   // chain lanes per point
@@ -528,15 +518,11 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
     const int N = g.N, Nz = g.Nz, T = g.T, nst = Nz - 1;
     // the wave index through readfirstlane: wave-uniform in an SGPR, so every role test and per-wave row base is scalar
     const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nthr >> 6;
-#if NUSI_BS_SIMDMAP
-    // the record wave before the chain waves, and the push row blocks dealt so that the push waves sharing a SIMD with
-    // a chain wave (wave w on SIMD w % 4) hold the top rows, which the wavefront consumes first (fewest MFMAs)
+    // the push waves, the record wave, then the CW chain waves; the push row blocks dealt so that the push waves
+    // sharing a SIMD with a chain wave (wave w on SIMD w % 4) hold the top rows, which the wavefront consumes first
+    // (fewest MFMAs)
     const int recw = nw - 1 - CW, chw = nw - CW;
     const bool is_chain = wave >= chw, is_rec = wave == recw;
-#else
-    const int chw = nw - 1 - CW, recw = nw - 1;   // push waves 0 .. chw-1, the CW chain waves, the record wave
-    const bool is_chain = wave >= chw && wave < recw, is_rec = wave == recw;
-#endif
     NUSI_WS_HWID();
     const int2 gr = grp ? grp[blockIdx.x] : make_int2((int)blockIdx.x, 1);
     const int R = gr.y;                                   // points of this workgroup (<= P), one table
@@ -623,9 +609,7 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
         // are issued before the solve of stage d, so one LDS latency per stage is hidden behind the dependent
         // solve.  The power-law sources are formed here (powerlaw_src_h), the DSNB ones read from srcb; the
         // finalise of the last pass goes to the record wave through `fin`
-#if NUSI_BS_PRIO
         __builtin_amdgcn_s_setprio(3);   // the chain's instructions (and LDS requests) before the push waves'
-#endif
         const int cw = wave - chw;
         const int cp = cw * PPW + lane / LPP, cjp = lane - LPP * (lane / LPP);
         const bool clane = lane < PPW * LPP && cp < R;
@@ -740,15 +724,6 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
                 NUSI_BS_STAMP(pass * nblk + q, 1);
                 __syncthreads();
                 NUSI_BS_STAMP(pass * nblk + q, 2);
-#if NUSI_BS_PIPE
-                {                                                    // phase B: stage d + 1 loaded before d solves
-                    StageIn in1 = load(q, 1), in2 = load(q, 2);
-                    if (4 * q + 1 < Ts) solve(q, 1, in1);
-                    in1 = load(q, 3);
-                    if (4 * q + 2 < Ts) solve(q, 2, in2);
-                    if (4 * q + 3 < Ts) solve(q, 3, in1);
-                }
-#else
 #pragma unroll
                 for (int d = 1; d < 4; ++d)                          // phase B
                     if (4 * q + d < Ts) {
@@ -757,16 +732,13 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
                         solve(q, d, in);
                         if (d < 3 && cw == 0) NUSI_BS_CSTAMP(pass * nblk + q, 2 * (d - 1) + 1);
                     }
-#endif
                 NUSI_BS_STAMP(pass * nblk + q, 3);
                 __syncthreads();
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the FIFO stores land before the next pass reads them
         }
     } else if (is_rec) {
-#if NUSI_BS_PRIO
         __builtin_amdgcn_s_setprio(3);
-#endif
         // ---- records and DSNB sources: block 0 (and the FIFO of blocks 0, 1) before the blocks; in block q the
         // records of block q + 1 (block q + 1's slot was last read in block q - 1): one round of 64 lanes goes wholly
         // into phase B, where the chain solves three stages (C5 / C3: phase A then waits on the chain alone); of
@@ -808,7 +780,7 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
         // block qb - 2, src_store into srcb in phase B of block qb - 1): the table's latency off the record wave's path
         // (sources() loaded and stored them within one phase B: C2a's cascade 0.295 against C2b's 0.176 ms).  The same
         // values in the same places.
-        constexpr bool kAhead = kSrcAhead && P == 1 && RT == 4;   // (one point, one pass shape: the others' registers)
+        constexpr bool kAhead = P == 1 && RT == 4;   // (one point, one pass shape: the others' registers)
         constexpr int SQL = (S4 * P + 63) / 64;
         auto src_valid = [&](int qb, int e, int& p, int& b, int& i) {
             p = e % P;
@@ -916,7 +888,6 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
     } else {
         // ---- push: block q adds columns c0+1-4q .. c0+4-4q (the T of stages 4q-1 .. 4q-4) into the rows below
         // r = c0-4q: in phase A the tiles holding rows r-1 .. r-4 (published to AX), in phase B the others
-#if NUSI_BS_SIMDMAP
         int rb = 0;   // this push wave's row block: the waves sharing no SIMD with a chain or the record wave take the
         {             // bottom rows (busiest), then those beside the record wave, then those beside a chain wave
             const int npush = nw - 1 - CW;
@@ -932,9 +903,6 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
             }
         }
         const int rw0 = rb * 16 * RT;
-#else
-        const int rw0 = wave * 16 * RT;
-#endif
 #pragma unroll 1
         for (int pass = 0; pass < npass; ++pass) {
             pass_geom(pass);
@@ -964,11 +932,7 @@ void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restric
                     if (crit == phase_a && rw0 + 16 * a < r)   // tiles wholly at or above r hold consumed rows only
 #pragma unroll
                         for (int s = 0; s < NB; ++s)
-#ifdef NUSI_BS_NOPUSH   // timing diagnostic only (wrong fluxes): the block pushes without the matrix core
-                            acc[a][s][0] += ab[a] * Tq[16 * s];
-#else
                             acc[a][s] = __builtin_amdgcn_mfma_f64_16x16x4f64(ab[a], Tq[16 * s], acc[a][s], 0, 0, 0);
-#endif
                 }
                 if (phase_a)
 #pragma unroll
@@ -1050,7 +1014,6 @@ int cascade_bs_config(const GridDev& g, int P, bool force_passes)
     if (P == 1) {
         if (nj && bs_fits_t<48, 1, 1, 4, 1>(g)) return nj;
         if (bs_fits_t<48, 1, 1, 4, 1>(g)) return 48;
-        if (NUSI_BS_LONG32 && bs_fits_t<32, 1, 1, 6, 1>(g)) return 32 + 2000;   // 96-row push waves, passes of 32
         if (bs_fits_t<16, 1, 1, 8, 1>(g)) return 16 + 1000;   // 128-row push waves
         return 0;
     }
@@ -1072,9 +1035,6 @@ hipError_t launch_cascade_bs(const GridDev& g, const Point* pts, int P, const in
         case 16: launch_bs_t<16, 1, 1, 4, 1>(g, pts, gidx, grp, nwg, t, fh, flux, flux_fla, s, all_nr); break;
         case 32: launch_bs_t<32, 1, 1, 4, 1>(g, pts, gidx, grp, nwg, t, fh, flux, flux_fla, s, all_nr); break;
         case 48: launch_bs_t<48, 1, 1, 4, 1>(g, pts, gidx, grp, nwg, t, fh, flux, flux_fla, s, all_nr); break;
-#if NUSI_BS_LONG32
-        case 2032: launch_bs_t<32, 1, 1, 6, 1>(g, pts, gidx, grp, nwg, t, fh, flux, flux_fla, s, all_nr); break;
-#endif
         default: launch_bs_t<16, 1, 1, 8, 1>(g, pts, gidx, grp, nwg, t, fh, flux, flux_fla, s, all_nr); break;
         }
     } else if (P == 2) {

@@ -36,15 +36,10 @@
 
 #include "nusi_libm.hpp"
 
-// The elementary functions inside the GSL functions: inline by default (each call from an out-of-line function costs
-// the callee's register save / restore and the call; NUSI_GSL_CALL_LIBM: calls, A/B builds).  The same functions.
-#ifdef NUSI_GSL_CALL_LIBM
-#define GSL_LOG nm::log
-#define GSL_ATAN2 nm::atan2
-#else
+// The elementary functions inside the GSL functions are inline (each call from an out-of-line function costs the
+// callee's register save / restore and the call).
 #define GSL_LOG nm::log_i
 #define GSL_ATAN2 nm::atan2_i
-#endif
 
 namespace nusi {
 namespace gsl {
@@ -87,10 +82,6 @@ constexpr KTab make_ktab()
     return t;
 }
 constexpr KTab kKT = make_ktab();
-#ifndef NUSI_S2_VLOAD   // A/B: 0 = waves of both complex series select each lane's row columns (scalar row)
-#define NUSI_S2_VLOAD 1
-#endif
-constexpr bool kS2VecRows = NUSI_S2_VLOAD != 0;
 
 // RN(a / d) for the series' terms.  kExact: the division; else fma(a, y, RN(a l)) from the two-part reciprocal
 // y + l (header comment), valid for a, d > 0 with a l normal (a >= 2^-900) -- the callers take kExact for arguments
@@ -357,7 +348,7 @@ NUSI_FN void cseries_t(bool s2, double r, double lr, double x, double y, double&
     KRow next = kKT.row[2];   // (the table row of the next iteration is loaded one iteration ahead; kmax <= 921)
     // kS2 == 2 (a wave of both series): each lane loads its own columns of the row (vector loads at its t2 offset from
     // the row's uniform address) instead of selecting between the scalar row's columns -- three 64-bit selects a term
-    constexpr bool vrow = kS2 == 2 && kS2VecRows;
+    constexpr bool vrow = kS2 == 2;
     const int toff = t2 ? 1 : 0;
     double nd = 0.0, ny = 0.0, nl = 0.0;
     if (vrow) {
@@ -373,11 +364,7 @@ NUSI_FN void cseries_t(bool s2, double r, double lr, double x, double y, double&
             nd = rp[toff]; ny = rp[2 + toff]; nl = rp[4 + toff];
         } else {
             const KRow kr = next;
-#ifdef NUSI_GSL_ROW_STUB   // timing A/B only (wrong values): every term reads row 2 (no table load in the loop)
-            (void)k;
-#else
             next = kKT.row[k + 1];
-#endif
             d = t2 ? kr.d2 : kr.d1;   // (double) k * k * (k + 1.0) or (double) k * k
             yk = t2 ? kr.y2 : kr.y1;
             lk = t2 ? kr.l2 : kr.l1;
@@ -395,13 +382,6 @@ NUSI_FN void cseries_t(bool s2, double r, double lr, double x, double y, double&
     auto stop = [&]() { return quot_lt<kExact>(dr * dr + di * di, real_sum * real_sum + imag_sum * imag_sum, 0x1p-104); };
     int k = 2;
     bool done = false;
-#ifdef NUSI_GSL_STUB_SERIES   // timing A/B only (wrong values): the complex series without its terms
-    if (k < kmax) {
-        re = real_sum;
-        im = imag_sum;
-        return;
-    }
-#endif
     if (!kExact) {
         // the first loop leaves together (wave votes), so k stays wave-uniform and the table rows scalar loads: at the
         // first k where a lane reaches its kmax (no term k), or where a lane's term falls below its bound (term k
@@ -596,10 +576,6 @@ NUSI_FN cd gsl_cli2_t(double x, double y)
 }
 
 NUSI_FN_OUT cd gsl_cli2(double x, double y) { return gsl_cli2_t<false>(x, y); }
-#ifndef NUSI_MC_CALL   // (A/B: the member-corner kernel's GSL call out of line, as before round 6)
-NUSI_FN cd gsl_cli2_inl(double x, double y) { return gsl_cli2_t<true>(x, y); }
-#else
-NUSI_FN cd gsl_cli2_inl(double x, double y) { return gsl_cli2(x, y); }
-#endif
+NUSI_FN cd gsl_cli2_inl(double x, double y) { return gsl_cli2_t<true>(x, y); }   // (the member-corner kernel's call)
 
 }  // namespace nusi

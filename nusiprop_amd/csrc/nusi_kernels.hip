@@ -30,9 +30,9 @@ __device__ __attribute__((noinline)) void warn_entry(int* warn, int* wmin, int T
             if ((w >> b) & 1) atomicMin(&wmin[((size_t)p * 4 + b) * T + n], m);
 }
 
-#ifndef NUSI_GA_WAVES   // Gamma / alphaTilde kernel waves per SIMD (A/B)
-#define NUSI_GA_WAVES 4   // with Gamma / alphaTilde split over work-items: 4 0.525, 3 0.535 ms (was 0.572 unsplit at 3)
-#endif
+// Gamma / alphaTilde kernel waves per SIMD; with Gamma / alphaTilde split over work-items: 4 0.525, 3 0.535 ms (was
+// 0.572 unsplit at 3)
+constexpr int kGaWaves = 4;
 // Gamma and alphaTilde: grid (T / 64, points, 2 quantities), 3 kParts waves per workgroup of 64 bins -- wave
 // (k, part) runs mass state k (gamma_k / alphat_k; kParts = 2: part 1 the s-t / s-u interference, part 0 every other
 // channel; kParts = 1: all), its channel terms go to LDS by slot, and wave 0 sums them in the reference's order
@@ -59,7 +59,7 @@ NUSI_FN cd shfl_dn(cd z) { return cd{__shfl_down(z.r, 1, 64), __shfl_down(z.i, 1
 // kPre (reference order, calls of few tables): every dilogarithm value from k_ga_dilogs' block pre (ga_pre_load)
 // instead of the lanes' own GSL calls
 template <bool kRef, int kParts, bool kPre = false>
-__global__ __launch_bounds__(192 * kParts) __attribute__((amdgpu_waves_per_eu(NUSI_GA_WAVES, NUSI_GA_WAVES))) void k_gamma_alphat(GridDev g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp,
+__global__ __launch_bounds__(192 * kParts) __attribute__((amdgpu_waves_per_eu(kGaWaves, kGaWaves))) void k_gamma_alphat(GridDev g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp,
                                                      double* __restrict__ G, double* __restrict__ At,
                                                      int* __restrict__ warn, int* __restrict__ wmin,
                                                      const double* __restrict__ pre = nullptr)
@@ -179,11 +179,9 @@ hipError_t spline_windows_build(const float* f, int n0, int n1, int n2, float* f
 }
 
 // one entry per work-item over the bins [nlo, T) x [nlo, T), n < m (nlo = 0: the whole table)
-#ifndef NUSI_PE_WAVES   // per-entry kernel waves per SIMD (A/B)
-#define NUSI_PE_WAVES 3   // 3: 20.05 vs 20.24 ms alpha stage (profiles/r1i/ab_occ_*)
-#endif
+constexpr int kPeWaves = 3;   // per-entry kernel waves per SIMD; 3: 20.05 vs 20.24 ms alpha stage (profiles/r1i/ab_occ_*)
 template <bool kRef>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NUSI_PE_WAVES, NUSI_PE_WAVES)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kPeWaves, kPeWaves)))
 void k_alpha(GridDev g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp, int nlo,
                                                double* __restrict__ A, int* __restrict__ warn, int* __restrict__ wmin)
 {
@@ -226,16 +224,13 @@ __global__ __launch_bounds__(64) void k_ga_dilogs(GridDev g, const Point* __rest
     if (nv == 2) o[T] = v[1];
 }
 
-#ifndef NUSI_GA_PRE_ALL   // A/B: 1 = scans too take the dilogarithm pre-pass (k_ga_dilogs)
-#define NUSI_GA_PRE_ALL 0
-#endif
 size_t gamma_alphat_pre_doubles(int T, int npts) { return (size_t)3 * kGaPreFields * T * npts; }
 
 hipError_t launch_gamma_alphat(const GridDev& g, const Point* pts, int npts, const SplineSet* spl, TablesDev t,
                                int* warn, hipStream_t s, bool ref)
 {
     dim3 grid((g.T + 62) / 63, npts, 2);   // (63 bins per workgroup: the edge-shared lanes)
-    if (ref && t.Gpre && (npts <= 16 || NUSI_GA_PRE_ALL)) {   // (the dilogarithms one per work-item first)
+    if (ref && t.Gpre) {   // (calls of few tables, the host layer's choice: the dilogarithms one per work-item first)
         hipLaunchKernelGGL(k_ga_dilogs, dim3((g.T + 63) / 64, npts, 3 * kGaPreSlots), dim3(64), 0, s, g, pts, t.Gpre);
         hipLaunchKernelGGL((k_gamma_alphat<true, 2, true>), grid, dim3(384), 0, s, g, pts, spl, t.G, t.At, warn, t.Wmin,
                            t.Gpre);
@@ -274,11 +269,9 @@ __host__ __device__ constexpr int alpha_tile_lds_doubles(int cs, int ct, int G)
 }
 
 // 3 waves per SIMD (<= 168 VGPRs): measured 38.5 ms vs 42.0 (2 waves, 222 VGPRs) and 42.4 (4 waves,
-// spills) per 1024-point table build (profiles/r1e/ab3_*.log); override with -DNUSI_TILE_WAVES=n
-#ifndef NUSI_TILE_WAVES
-#define NUSI_TILE_WAVES 3
-#endif
-#define NUSI_TILE_ATTR __attribute__((amdgpu_waves_per_eu(NUSI_TILE_WAVES, NUSI_TILE_WAVES)))
+// spills) per 1024-point table build (profiles/r1e/ab3_*.log)
+constexpr int kTileWaves = 3;
+#define NUSI_TILE_ATTR __attribute__((amdgpu_waves_per_eu(kTileWaves, kTileWaves)))
 // One workgroup per (tile, batch).  A batch is 1..G tables whose points share m_phi, the masses and
 // the channel flags (nusi_capi.cpp orders the tables so): the leaves of (S', t) alone -- the real
 // dilogarithms and most logarithms -- are evaluated once for the batch, the leaves that read
@@ -415,33 +408,12 @@ __global__ __launch_bounds__(kTileThreads) NUSI_TILE_ATTR void k_alpha_tile(Grid
 //   edg  [alpha_tile_edge_stride]  shared edge / m-bin leaves of the current k
 //   memb [kBatchQC][alpha_batch_memb_doubles]  member edge leaves of a chunk of points
 // ---------------------------------------------------------------------------
-#ifndef NUSI_BATCH_QC   // points per member-edge round (5: C4 alpha 6.05 -> 5.95 ms vs 4, profiles/r2q)
-#define NUSI_BATCH_QC 5
-#endif
-constexpr int kBatchQC = NUSI_BATCH_QC;   // kBatchQC (ct + cs + kAlphaTile) <= 256 jobs
-// NUSI_BATCH_PIPE (A/B): the member corners of point q + 1 are formed while point q combines (two mem buffers),
-// one barrier per point instead of two
-#ifndef NUSI_BATCH_PIPE
-#define NUSI_BATCH_PIPE 0
-#endif
-constexpr bool kBatchPipe = NUSI_BATCH_PIPE != 0;
-// NUSI_REFO_PREFETCH (A/B): the reference-order member corners of point q + 1 are loaded while point q combines
-#ifndef NUSI_REFO_PREFETCH
-#define NUSI_REFO_PREFETCH 1
-#endif
-constexpr bool kRefPrefetch = NUSI_REFO_PREFETCH != 0;
-#ifndef NUSI_BATCH_KLAUNCH   // A/B: 1 = the non-phi-phi batch kernels as one launch per mass state (kOneK)
-#define NUSI_BATCH_KLAUNCH 0
-#endif
-constexpr bool kBatchKLaunch = NUSI_BATCH_KLAUNCH != 0;
-#ifndef NUSI_REFO_BSTUB   // timing A/B only (wrong tables): bit 1 the batch kernel without the block's loads, bit 2
-                          // without the chunk's A (atan2 of the member quotient), bit 3 without the per-point combine
-#define NUSI_REFO_BSTUB 0
-#endif
+// points per member-edge round (5: C4 alpha 6.05 -> 5.95 ms vs 4, profiles/r2q)
+constexpr int kBatchQC = 5;   // kBatchQC (ct + cs + kAlphaTile) <= 256 jobs
 __host__ __device__ inline int alpha_batch_lds_doubles()
 {
     const int c1 = kAlphaTile + 1;
-    return (3 + kXFields + (kBatchPipe ? 4 : 2)) * c1 * c1 + alpha_tile_edge_stride(c1, c1) +
+    return (3 + kXFields + 2) * c1 * c1 + alpha_tile_edge_stride(c1, c1) +
            kBatchQC * alpha_batch_memb_doubles(c1, c1);
 }
 static_assert(kXFields * (kAlphaTile + 1) * (kAlphaTile + 1) >= 4 * (kAlphaTile + 1) * (kAlphaTile + 1) + kAlphaTile * 2 * (kAlphaTile + 1),
@@ -449,28 +421,19 @@ static_assert(kXFields * (kAlphaTile + 1) * (kAlphaTile + 1) >= 4 * (kAlphaTile 
 static_assert(kBatchQC * (2 * (kAlphaTile + 1) + kAlphaTile) <= kTileThreads, "one member-edge round per chunk");
 static_assert(3 + kBatchQC <= kXFields, "(kRef) the chunk's A fields fit X beside Dcr, Dci");
 
-#ifndef NUSI_BATCH_WAVES
-#define NUSI_BATCH_WAVES 4
-#endif
 // waves per SIMD of k_alpha_batch: 4 (128 VGPRs; the LDS holds four workgroups per CU), and 3 for the reference-order
-// instance without phi-phi (NUSI_BATCH_WAVES_REFO, 168 VGPRs): spills 82 -> 35, C4 7.28 -> 6.76 ms (profiles/r5/r6u,
+// instance without phi-phi (kBatchWavesRefo, 168 VGPRs): spills 82 -> 35, C4 7.28 -> 6.76 ms (profiles/r5/r6u,
 // r6v; shipped in round 6).  The default-order instance is equal at 3 and 4, the phi-phi reference-order one slower at
 // 3 (C3 11.1 -> 12.0 ms per chunk)
-#ifndef NUSI_BATCH_WAVES_REFO
-#define NUSI_BATCH_WAVES_REFO 3
-#endif
-constexpr int batch_waves(bool pp, bool ref) { return ref && !pp ? NUSI_BATCH_WAVES_REFO : NUSI_BATCH_WAVES; }
+constexpr int kBatchWaves = 4, kBatchWavesRefo = 3;
+constexpr int batch_waves(bool pp, bool ref) { return ref && !pp ? kBatchWavesRefo : kBatchWaves; }
 // the batch-shared phases out of line: they run once per batch, and inlined their working sets raise the register
 // pressure of the per-point loop (measured slower: round 1 profiles/r1e, round 2 profiles/r2s, r2aa)
 #define NUSI_BCOLD __device__ __attribute__((noinline))
 template <bool kRef>
 NUSI_BCOLD void b_corner(int j, const double* edgk, int ct, int cs, double* per, double* tmp)
 {
-#ifdef NUSI_REFO_SHARED_FAST   // timing A/B only: the reference-order batches' shared corners in the default arithmetic
-    alpha_batch_corner_job<false>(j, edgk, ct, cs, per, tmp);
-#else
     alpha_batch_corner_job<kRef>(j, edgk, ct, cs, per, tmp);
-#endif
 }
 // (kRef, kPP) A of a member corner, out of line (the phi-phi instance's point loop spills more with it inline)
 NUSI_BCOLD double b_marg(double S, double t, double gr) { return alpha_member_ref_arg(S, t, gr); }
@@ -521,18 +484,8 @@ __global__ __launch_bounds__(256) void k_alpha_medge(GridDev g, const Point* __r
 // only -- take similar GSL branches and series lengths (in the tile's corner order the lanes of a wave diverge: 0.21
 // ns per call against 0.06, scripts/dev/gsl_bench.hip).  The values pass through LDS to leave as runs of cb corners
 // per (field, table), the layout the batch kernel reads a tile's corner rows from.
-#ifndef NUSI_MC_JOBS   // A/B: jobs (corner x point) per k_alpha_mcorner workgroup on scans, a multiple of 256
-#define NUSI_MC_JOBS 1024
-#endif
-constexpr int kMcJobs = NUSI_MC_JOBS;
-#ifndef NUSI_MC_WAVES   // A/B: waves per SIMD the member-corner kernel is built for (0: the compiler's choice)
-#define NUSI_MC_WAVES 0
-#endif
-__global__ __launch_bounds__(256)
-#if NUSI_MC_WAVES
-__attribute__((amdgpu_waves_per_eu(NUSI_MC_WAVES, NUSI_MC_WAVES)))
-#endif
-void k_alpha_mcorner(const Point* __restrict__ pts, const int* __restrict__ batches,
+constexpr int kMcJobs = 1024;   // jobs (corner x point) per k_alpha_mcorner workgroup on scans, a multiple of 256
+__global__ __launch_bounds__(256) void k_alpha_mcorner(const Point* __restrict__ pts, const int* __restrict__ batches,
                                                        MCornerDev mc, int pc0, int jobs)
 {
     __shared__ double v[2 * kMcJobs];   // [q][cl][Dcr, Dci]
@@ -551,7 +504,7 @@ void k_alpha_mcorner(const Point* __restrict__ pts, const int* __restrict__ batc
         const int cl = j / nb, q = j - cl * nb;
         if (c0 + cl >= mc.NC) break;
         const double S = cst[0][cl], t = cst[1][cl], gr = pts[p0 + q].a_gr;
-        const cd Dc = NUSI_REFO_STUB == 2 ? C(0.0) : alpha_member_ref_dc_inl(S, t, gr);
+        const cd Dc = alpha_member_ref_dc_inl(S, t, gr);
         v[2 * (q * cb + cl)] = Dc.r;
         v[2 * (q * cb + cl) + 1] = Dc.i;
     }
@@ -599,14 +552,11 @@ __device__ unsigned long long g_bt[kBtWg * 4 * kBtN];
 // batch structure unchanged.  kSplit (calls of few tables, a single propagation): mass state k = blockIdx.z only,
 // its terms of every entry recorded into kt ([table][3][PT][8]: up to 7 terms, then their count, -1 for an entry
 // the resonant-only table does not compute) for k_alpha_ksum -- three times the workgroups, each a third as long
-// kOneK (NUSI_BATCH_KLAUNCH A/B): one mass state per launch, kone, the launches k = 0, 1, 2 in order on the stream
-// (the running sum through A as in the loop): no state lives across the k loop
-template <bool kPP, bool kRef, bool kSplit = false, bool kOneK = false>
+template <bool kPP, bool kRef, bool kSplit = false>
 __global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(batch_waves(kPP, kRef), batch_waves(kPP, kRef))))
 void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp, const int* __restrict__ tiles,
                    const int* __restrict__ batches, double* __restrict__ A, const double* __restrict__ med,
-                   int* __restrict__ warn, int* __restrict__ wmin, MCornerDev mc, int pc0, double* __restrict__ kt,
-                   int kone = 0)
+                   int* __restrict__ warn, int* __restrict__ wmin, MCornerDev mc, int pc0, double* __restrict__ kt)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const SplineSet& spl = *splp;
@@ -663,15 +613,15 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
     constexpr int ccmax = kCC;
     double* P3 = sm;                           // [3][cc]
     double* X = P3 + 3 * ccmax;                // [kXFields][cc] | LL TU1 TU2 G [4][cc] + mixed
-    double* mem = X + kXFields * ccmax;        // [2][cc] (kBatchPipe: [2][2][cc], by point parity)
-    double* edgk = mem + (kBatchPipe ? 4 : 2) * ccmax;   // [estride]
+    double* mem = X + kXFields * ccmax;        // [2][cc]
+    double* edgk = mem + 2 * ccmax;            // [estride]
     double* membq = edgk + alpha_tile_edge_stride(kAlphaTile + 1, kAlphaTile + 1);   // [kBatchQC][mbd]
     const int mbd = alpha_batch_memb_doubles(cs, ct);
     double* tmp = X;
     double* mix = X + 4 * kCC;
     const int mjobs = ct + cs + kAlphaTile;
     int wsh = 0;
-    const int kb = kSplit ? (int)blockIdx.z : kOneK ? kone : 0, ke = (kSplit || kOneK) ? kb + 1 : 3;
+    const int kb = kSplit ? (int)blockIdx.z : 0, ke = kSplit ? kb + 1 : 3;
 #ifdef NUSI_BATCH_TRACE
     int bt_i = 0;
 #endif
@@ -718,7 +668,8 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
         // member edges: thread (mq, mjob) copies job mjob of point mq of each chunk (loading the next chunk's
         // values a chunk ahead measured slower: their registers stay live through the combine)
         const int mq = tid / mjobs, mjob = tid - mq * mjobs;
-        // (kRef) thread tid < cc carries corner tid's member leaves one point ahead, from k_alpha_mcorner's block:
+        // (kRef) thread tid < cc carries corner tid's member leaves one point ahead (loaded while the point before
+        // combines), from k_alpha_mcorner's block:
         // the corner's numbering c (only corners with ut <= us are read by the entries n < m; the others stay unset)
         const double2* const mcb =   // (uniform: the block of this batch and mass state, [q][c] of (Dcr, Dci))
             kRef ? reinterpret_cast<const double2*>(mc.buf + (size_t)(p0 - pc0) * 6 * mc.NC + (size_t)k * 2 * nb * mc.NC)
@@ -730,7 +681,7 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
             const int us = mc.eu[ssrc[si]], ut = mc.eu[tsrc[ti]];
             if (ut <= us) {
                 moff = us * (us + 1) / 2 + ut;
-                if (kRefPrefetch && !(NUSI_REFO_BSTUB & 2)) mcv = mcb[moff];
+                mcv = mcb[moff];
             }
         }
 #pragma unroll 1
@@ -753,17 +704,9 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
 #pragma unroll 1
                 for (int qq = 0; qq < nq; ++qq)   // (inline: C4 7.42 -> 7.28 ms, r6p; kPP, whose point loop holds
                     X[(3 + qq) * kCC + tid] =     // the phi-phi term too, as a call: C3 12.33 -> 11.24 ms, r6q)
-                        (NUSI_REFO_BSTUB & 4) ? S + t : kPP ? b_marg(S, t, pts[p0 + q0 + qq].a_gr)
-                                                            : alpha_member_ref_arg(S, t, pts[p0 + q0 + qq].a_gr);
+                        kPP ? b_marg(S, t, pts[p0 + q0 + qq].a_gr) : alpha_member_ref_arg(S, t, pts[p0 + q0 + qq].a_gr);
             }
-            constexpr bool pipe = kBatchPipe && !kRef;
             NUSI_BT();
-            if (pipe) {
-                __syncthreads();   // member edges written
-                if (cornered)
-                    for (int j = tid; j < cc; j += kTileThreads)
-                        alpha_batch_mcorner_job(pts[p0 + q0], j, edgk, ct, cs, X, membq, mem);
-            }
 #pragma unroll 1
             for (int qq = 0; qq < nq; ++qq) {
                 const int q = q0 + qq;
@@ -771,39 +714,28 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
                 const double* memb = membq + qq * mbd;
                 double tot = tnext;   // after states < k
                 if (reload && q + 1 < nb) tnext = A[(size_t)(p0 + q + 1) * g.PT + eidx];
-                double* memq = mem;
-                if (pipe) {
-                    memq = mem + (qq & 1) * 2 * ccmax;
-                    __syncthreads();   // mem of q written / the previous point's combine is done with the other buffer
-                    if (cornered && qq + 1 < nq)
-                        for (int j = tid; j < cc; j += kTileThreads)
-                            alpha_batch_mcorner_job(pts[p0 + q + 1], j, edgk, ct, cs, X, memb + mbd,
-                                                    mem + ((qq + 1) & 1) * 2 * ccmax);
-                } else {
-                    __syncthreads();   // member edges written / the previous point's combine is done with mem
-                    NUSI_BT();
-                    if (cornered) {
-                        if (kRef) {
-                            if (moff >= 0) {
-                                const size_t o = (size_t)q * mc.NC + moff;
-                                if (!kRefPrefetch) mcv = mcb[o];
-                                X[tid] = mcv.x; X[kCC + tid] = mcv.y;
-                                if (kRefPrefetch && q + 1 < nb && !(NUSI_REFO_BSTUB & 2)) mcv = mcb[o + mc.NC];
-                            }
+                __syncthreads();   // member edges written / the previous point's combine is done with mem
+                NUSI_BT();
+                if (cornered) {
+                    if (kRef) {
+                        if (moff >= 0) {
+                            const size_t o = (size_t)q * mc.NC + moff;
+                            X[tid] = mcv.x; X[kCC + tid] = mcv.y;
+                            if (q + 1 < nb) mcv = mcb[o + mc.NC];
                         }
-                        else
-                            for (int j = tid; j < cc; j += kTileThreads) alpha_batch_mcorner_job(Q, j, edgk, ct, cs, X, memb, mem);
                     }
-                    __syncthreads();   // mem of q written
-                    NUSI_BT();
+                    else
+                        for (int j = tid; j < cc; j += kTileThreads) alpha_batch_mcorner_job(Q, j, edgk, ct, cs, X, memb, mem);
                 }
+                __syncthreads();   // mem of q written
+                NUSI_BT();
                 int w = 0;
                 TermRec rec;
-                if (needed && !(kRef && (NUSI_REFO_BSTUB & 8))) {
+                if (needed) {
                     SplitLeavesT<kRef> lv;
                     lv.cf[0] = P3; lv.cf[1] = P3; lv.cf[2] = P3; lv.cf[3] = P3; lv.cf[4] = P3;
                     lv.cf[5] = P3 + kCC; lv.cf[6] = P3 + 2 * kCC;   // (LL, TU1, TU2, G are not read with pre)
-                    lv.corm = kRef ? X : memq;
+                    lv.corm = kRef ? X : mem;
                     lv.cc = cc; lv.ct = ct; lv.cs = cs; lv.mb = lm; lv.nb = ln;
                     lv.sidx[0] = sl[lm]; lv.sidx[1] = sh[lm]; lv.tidx[0] = tl[ln]; lv.tidx[1] = th[ln];
                     lv.ted = edgk; lv.sed = edgk + kTEdgeFields * ct; lv.mbv = lv.sed + kSEdgeFields * cs;
@@ -918,7 +850,7 @@ hipError_t alpha_tiles_create(int T, const unsigned char* shared, AlphaTilesDev*
     // class 0: both sides <= 16 edges; 1: t side <= 16, S' side <= 30; 2: both <= 30.  From the
     // first tile t0 whose bins do not share edges (the redshift-extended bins) on, tiles of class 2
     // save no corner (4 per entry, like the per-entry path) and their 80-KB LDS footprint halves the
-    // occupancy: the bins [15 t0, T) x [15 t0, T) go to the per-entry kernel instead (ext_lo).
+    // occupancy.
     const int cap_core = kAlphaTile + 1, cap_ext = 2 * kAlphaTile;
     int t0 = nt;
     for (int t = 0; t < nt; ++t)
@@ -927,18 +859,16 @@ hipError_t alpha_tiles_create(int T, const unsigned char* shared, AlphaTilesDev*
     for (int n = t0 * kAlphaTile; n + 1 < T; ++n) tail_ext = tail_ext && !shared[n];
     // the extended triangle runs as quarter tiles (8 x 8 bins, batched with the core tiles; round 1: alpha
     // stage 14.68 -> 14.55 ms per 1024 points against the per-entry kernel)
-    constexpr bool ext_tiles = true;
-    out->ext_lo = (tail_ext && t0 < nt && !ext_tiles) ? t0 * kAlphaTile : T;
-    const int qlo = (tail_ext && t0 < nt && ext_tiles) ? t0 : nt;   // tiles from qlo on: split on both sides
+    const int qlo = (tail_ext && t0 < nt) ? t0 : nt;   // tiles from qlo on: split on both sides
     // Class-1 tiles (t side core, S' side extended: 30 S' edges) are split into their first 8 and last
     // 7 m bins (16 / 14 S' edges): the halves fit the core tiles' LDS footprint and join class 0,
-    // whose launch builds batches of tables (16.0 -> 14.8 ms when introduced).
-    constexpr bool split_ext = true;
+    // whose launch builds batches of tables (16.0 -> 14.8 ms when introduced).  So cls[1] stays empty:
+    // c == 1 needs ne[tn] <= cap_core < ne[tm], hence tn < tm, and every such tile is split below (as
+    // quarter tiles from qlo on, as m halves before it).  The launchers keep their three-class loop.
     std::vector<int> cls[3];
     for (int tm = 0; tm < nt; ++tm)
         for (int tn = 0; tn <= tm; ++tn) {
             const int c = (ne[tn] <= cap_core && ne[tm] <= cap_core) ? 0 : (ne[tn] <= cap_core) ? 1 : 2;
-            if (tn * kAlphaTile >= out->ext_lo) continue;   // per-entry region
             const int w = tn | (tm << 14);
             if (tn >= qlo) {   // both sides extended: up to 4 quarter tiles (n half, m half)
                 for (int nh = 1; nh <= 2; ++nh)
@@ -948,7 +878,7 @@ hipError_t alpha_tiles_create(int T, const unsigned char* shared, AlphaTilesDev*
                         if (nb0 >= T || mb0 >= T || nb0 >= mb1 - 1) continue;   // no entry n < m
                         cls[0].push_back((int)((unsigned)w | ((unsigned)mh << 28) | ((unsigned)nh << 30)));
                     }
-            } else if (c == 1 && split_ext && tn < tm) {
+            } else if (c == 1) {
                 cls[0].push_back(w | (1 << 28));
                 if (tm * kAlphaTile + 8 < T) cls[0].push_back(w | (2 << 28));
             } else {
@@ -987,11 +917,6 @@ static hipError_t launch_alpha_t(const GridDev& g, const Point* pts, int npts, c
     if (kernel == 0 && batches) {
         t_alpha_kernel = kRef ? "k_alpha_mcorner + k_alpha_batch[refo]" : "k_alpha_batch";
         // class 0 on the big-batch kernel (batches of up to gmax tables), classes 1 / 2 per table
-        if (at.ext_lo < g.T) {
-            const long long L = g.T - at.ext_lo, ne = L * (L - 1) / 2;
-            hipLaunchKernelGGL(k_alpha<kRef>, dim3((unsigned)((ne + 255) / 256), npts), dim3(256), 0, s, g, pts, spl,
-                               at.ext_lo, t.A, warn, t.Wmin);
-        }
         int off = 0;
         for (int c = 0; c < 3; ++c) {
             if (at.ncls[c] == 0) continue;
@@ -1004,7 +929,6 @@ static hipError_t launch_alpha_t(const GridDev& g, const Point* pts, int npts, c
                     hipLaunchKernelGGL(k_alpha_medge, dim3((unsigned)((5 * g.T + 255) / 256), npts, 3), dim3(256), 0, s,
                                        g, pts, t.Med);
                 }
-                // (NUSI_BATCH_KLAUNCH: the non-phi-phi batches as three launches, one per mass state)
                 // t.Kt (calls of few tables, no phi-phi channel): the k-split instance, its mass states' workgroups at
                 // once, and k_alpha_ksum's ordered sums
                 const bool split = t.Kt && nb_plain == nbatches;
@@ -1015,11 +939,6 @@ static hipError_t launch_alpha_t(const GridDev& g, const Point* pts, int npts, c
                                            t.Wmin, MCornerDev{}, 0, t.Kt);
                         hipLaunchKernelGGL(k_alpha_ksum, dim3(at.ncls[0], nbatches), dim3(kTileThreads), 0, s, g, at.tiles,
                                            batches, t.Kt, t.A);
-                    } else if (nb_plain > 0 && kBatchKLaunch) {
-                        for (int kk = 0; kk < 3; ++kk)
-                            hipLaunchKernelGGL((k_alpha_batch<false, false, false, true>), dim3(at.ncls[0], nb_plain),
-                                               dim3(kTileThreads), lds, s, g, pts, spl, at.tiles, batches, t.A, t.Med, warn,
-                                               t.Wmin, MCornerDev{}, 0, nullptr, kk);
                     } else if (nb_plain > 0)
                         hipLaunchKernelGGL((k_alpha_batch<false, false>), dim3(at.ncls[0], nb_plain), dim3(kTileThreads),
                                            lds, s, g, pts, spl, at.tiles, batches, t.A, t.Med, warn, t.Wmin, MCornerDev{}, 0, nullptr);
@@ -1057,11 +976,6 @@ static hipError_t launch_alpha_t(const GridDev& g, const Point* pts, int npts, c
                                                warn, t.Wmin, *mc, pc0, t.Kt);
                             hipLaunchKernelGGL(k_alpha_ksum, dim3(at.ncls[0], e - b), dim3(kTileThreads), 0, s, g,
                                                at.tiles, batches + b, t.Kt, t.A);
-                        } else if (b < nb_plain && kBatchKLaunch) {
-                            for (int kk = 0; kk < 3; ++kk)
-                                hipLaunchKernelGGL((k_alpha_batch<false, true, false, true>), dim3(at.ncls[0], e - b),
-                                                   dim3(kTileThreads), lds, s, g, pts, spl, at.tiles, batches + b, t.A,
-                                                   t.Med, warn, t.Wmin, *mc, pc0, nullptr, kk);
                         } else if (b < nb_plain)
                             hipLaunchKernelGGL((k_alpha_batch<false, true>), dim3(at.ncls[0], e - b), dim3(kTileThreads),
                                                lds, s, g, pts, spl, at.tiles, batches + b, t.A, t.Med, warn, t.Wmin, *mc,
@@ -1082,19 +996,14 @@ static hipError_t launch_alpha_t(const GridDev& g, const Point* pts, int npts, c
         }
         return hipGetLastError();
     }
-    const bool per_entry = kernel == 2;
-    auto per_entry_region = [&](int nlo) {
-        const long long L = g.T - nlo, ne = L * (L - 1) / 2;
-        if (ne <= 0) return;
-        dim3 grid((unsigned)((ne + 255) / 256), npts);
-        hipLaunchKernelGGL(k_alpha<kRef>, grid, dim3(256), 0, s, g, pts, spl, nlo, t.A, warn, t.Wmin);
-    };
-    if (per_entry) {
+    if (kernel == 2) {   // one entry per work-item, the whole table
         t_alpha_kernel = kRef ? "k_alpha[refo]" : "k_alpha";
-        per_entry_region(0);
+        const long long ne = g.PT;
+        if (ne > 0)
+            hipLaunchKernelGGL(k_alpha<kRef>, dim3((unsigned)((ne + 255) / 256), npts), dim3(256), 0, s, g, pts, spl, 0,
+                               t.A, warn, t.Wmin);
         return hipGetLastError();
     }
-    per_entry_region(at.ext_lo);
     int off = 0;
     for (int c = 0; c < 3; ++c) {
         if (at.ncls[c] == 0) continue;

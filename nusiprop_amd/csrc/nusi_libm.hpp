@@ -24,12 +24,8 @@
 
 // log/log1p/exp/atan/atan2 are real calls by default: inlined at their ~60 call
 // sites they made the alpha kernel 225 KB of code (I-cache bound; 154 vs 95 ms
-// per 1024-point step measured).  -DNUSI_INLINE_LIBM inlines them (A/B builds).
-#ifndef NUSI_INLINE_LIBM
+// per 1024-point step measured).
 #define NUSI_LM __host__ __device__ inline __attribute__((noinline))
-#else
-#define NUSI_LM NUSI_FN
-#endif
 
 #include "nusi_logtab.hpp"
 
@@ -316,17 +312,12 @@ NUSI_FN bool wave_all_l(bool p)
 #endif
 }
 // the rare waves' fdlibm atan2 as a call: inlined at every atan2 site it was most of k_alpha_mcorner's code (~1 700
-// of its 8 600 instructions per site, against an instruction cache shared by two CUs); NUSI_ATAN2_RARE_INLINE: inline
+// of its 8 600 instructions per site, against an instruction cache shared by two CUs)
 NUSI_LM double atan2_rare(double y, double x) { return atan2_full(y, x); }
 NUSI_FN double atan2_i(double y, double x)
 {
-#ifndef NUSI_ATAN2_FULL   // (A/B: fdlibm's branches only)
     if (wave_all_l(atan2_plain(y, x))) return atan2_sel(y, x);
-#ifndef NUSI_ATAN2_RARE_INLINE
     return atan2_rare(y, x);
-#endif
-#endif
-    return atan2_full(y, x);
 }
 
 // Out-of-line entry points (see NUSI_LM); the *_i bodies above are inlined where a caller wants

@@ -27,24 +27,14 @@
 
 #define NUSI_FN __host__ __device__ inline
 // Polylogarithms are called from many sites; outlining them keeps the table
-// kernels' code small (NUSI_INLINE_POLYLOG inlines them everywhere, A/B builds).
-#ifdef NUSI_INLINE_POLYLOG
-#define NUSI_FN_OUT NUSI_FN
-#else
+// kernels' code small.
 #define NUSI_FN_OUT __host__ __device__ inline __attribute__((noinline))
-#endif
 
 // Inside the (out-of-line) polylogarithms the elementary functions are inlined: a call there
-// costs a register save/restore round trip per log (-DNUSI_POLY_CALL_LIBM: calls, A/B builds).
-#ifdef NUSI_POLY_CALL_LIBM
-#define NUSI_PLOG nm::log
-#define NUSI_PLOG1P nm::log1p
-#define NUSI_PATAN2 nm::atan2
-#else
+// costs a register save/restore round trip per log.
 #define NUSI_PLOG nm::log_i
 #define NUSI_PLOG1P nm::log1p_i
 #define NUSI_PATAN2 nm::atan2_i
-#endif
 
 namespace nusi {
 

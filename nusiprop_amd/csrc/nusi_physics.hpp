@@ -17,12 +17,8 @@
 
 // The three-mass loops (j/k = 0..2) are kept rolled by default: unrolled, the
 // alpha kernel is ~225 KB of code (instruction-cache thrashing) and 300+
-// VGPRs.  -DNUSI_MASS_UNROLLED restores full unrolling (A/B builds).
-#ifdef NUSI_MASS_UNROLLED
-#define NUSI_MASS_LOOP
-#else
+// VGPRs.
 #define NUSI_MASS_LOOP _Pragma("unroll 1")
-#endif
 
 namespace nusi {
 
@@ -645,30 +641,21 @@ struct AlphaCorner {
     double Dcr, Dci;   // cli2((1+S+t)/(2 - i gr + t))
     double A;          // arg(-(-1 + i gr + S)/(2 - i gr + t))
 };
-// the corner leaves' own elementary functions: inline by default (-DNUSI_CORNER_CALL_LIBM: calls)
-#ifdef NUSI_CORNER_CALL_LIBM
-#define NUSI_CLOG nm::log
-#define NUSI_CLOG1P nm::log1p
-#define NUSI_CARG carg
-#else
-#define NUSI_CLOG nm::log_i
-#define NUSI_CLOG1P nm::log1p_i
-#define NUSI_CARG carg_i
-#endif
+// (the corner leaves' own elementary functions are inline: nm::log_i, nm::log1p_i)
 // The leaves split into those of (S', t) alone ("shared": every point with the same m_phi and
 // masses has them, bit for bit) and those that also read gr = Gamma_phi / m_phi ("member").  kRef:
 // NUSI_OPT_REFERENCE_ORDER (GSL's dilogarithms)
 template <bool kRef = false>
 NUSI_FN void alpha_corner_shared(double S, double t, AlphaCorner& c)
 {
-    c.L = NUSI_CLOG1P(S + t);
-    c.LL = NUSI_CLOG(1 + S + t);
+    c.L = nm::log1p_i(S + t);
+    c.LL = nm::log_i(1 + S + t);
     if (t < -1) {
         c.TU1 = li2_t<kRef>((1 + S + t) / S);
         c.TU2 = 0.0;
     } else {
         c.TU1 = li2_t<kRef>(S / (1 + S + t));
-        c.TU2 = NUSI_CLOG((1 + S + t) / S);
+        c.TU2 = nm::log_i((1 + S + t) / S);
     }
     c.G = li2_t<kRef>((1 + S + t) / (2 + S));
     const cd Dr = cli2_real_t<kRef>((1 + S + t) / (1 + t));
@@ -738,19 +725,16 @@ NUSI_FN void alpha_member_corner(const MemberShared& M, double S, double t, doub
 // nuSIprop.hpp:1432-1438, 1444-1451), by GSL's algorithm (gsl_cli2), and A = carg(-((-1 + i gr + S) / (2 - i gr + t)))
 // (:1456); no Taylor expansion about the real point and no sum of edge arguments.  The oracle's
 // member_dc_ref / member_arg_ref (ora_set_reference_order(1)).
-#ifndef NUSI_REFO_STUB   // timing A/B only: 1 = the member corners without the dilogarithm (Dc = z), 2 = nothing
-#define NUSI_REFO_STUB 0
-#endif
 NUSI_FN cd alpha_member_ref_dc(double S, double t, double gr)
 {
     const cd z = (1 + S + t) / C(2 + t, -gr);
-    return NUSI_REFO_STUB == 1 ? z : gsl_cli2(z.r, z.i);
+    return gsl_cli2(z.r, z.i);
 }
 // the same, with GSL's call inline (k_alpha_mcorner's single call site)
 NUSI_FN cd alpha_member_ref_dc_inl(double S, double t, double gr)
 {
     const cd z = (1 + S + t) / C(2 + t, -gr);
-    return NUSI_REFO_STUB == 1 ? z : gsl_cli2_inl(z.r, z.i);
+    return gsl_cli2_inl(z.r, z.i);
 }
 NUSI_FN double alpha_member_ref_arg(double S, double t, double gr)
 {
@@ -758,7 +742,6 @@ NUSI_FN double alpha_member_ref_arg(double S, double t, double gr)
 }
 NUSI_FN void alpha_member_ref(double S, double t, double gr, double& Dcr, double& Dci, double& A)
 {
-    if (NUSI_REFO_STUB == 2) { Dcr = Dci = A = 0.0; return; }
     const cd Dc = alpha_member_ref_dc(S, t, gr);
     Dcr = Dc.r;
     Dci = Dc.i;
@@ -859,10 +842,7 @@ using DirectLeaves = DirectLeavesT<false>;
 //   ted[v * ct + t], sed[v * cs + s], mbv[v * kAlphaTile + j] (shared edge / m-bin fields),
 //   tedm[t] = L2, sedm[s] = Ls, sedm[cs + s] = cS, mbm[j] = atd (this point's member fields),
 //   xl[s * kAlphaTile + n bin], yl[m bin * ct + t]
-#ifndef NUSI_ALPHA_TILE   // A/B: bins per alpha tile side (the edges of a core tile side are kAlphaTile + 1 <= 17)
-#define NUSI_ALPHA_TILE 15
-#endif
-constexpr int kAlphaTile = NUSI_ALPHA_TILE;
+constexpr int kAlphaTile = 15;   // bins per alpha tile side (the edges of a core tile side are kAlphaTile + 1 <= 17)
 constexpr int kCornerShared = 7, kCornerMember = 3;   // L LL TU1 TU2 G Drr Dri | Dcr Dci A
 struct TileLeaves {
     const double *cor, *corm, *ted, *sed, *mbv, *tedm, *sedm, *mbm, *xl, *yl;

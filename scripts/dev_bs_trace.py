@@ -40,7 +40,7 @@ def main():
     waves = [w for w in range(TW - 1) if a[w, 5, 0] != 0]   # (slot 15: the chain segments)
     nw = len(waves)
     ncw = 2 if wl == "c5" else 1   # chain waves of the workload's instance (the gamma batch: two)
-    # roles (NUSI_BS_SIMDMAP, the default): push waves, the record wave, then the chain waves
+    # roles: push waves, the record wave, then the chain waves
     rec, chain0, chain = waves[-1 - ncw], waves[-ncw], waves[-1]
     nb = int(np.max(np.nonzero(a[chain, :, 3])[0])) + 1
     sl = slice(4, nb - 4)

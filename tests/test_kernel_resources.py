@@ -20,7 +20,7 @@ BUDGET = {
     r"k_alpha_batchILb[01]ELb0E": (64, 1024),  # call frames of the out-of-line per-batch phases
     # the reference-order instances: the member-corner offset and one point's prefetched corner (k_alpha_mcorner's
     # block) live across the point loop, and (non-phi-phi instance) the chunk's A inline -- faster than as a call
-    # despite the spills (profiles/r5/r6p); 128 VGPRs (4 waves per SIMD; NUSI_BATCH_WAVES_REFO=3 gives the non-phi-phi
+    # despite the spills (profiles/r5/r6p); 128 VGPRs (4 waves per SIMD; kBatchWavesRefo = 3 gives the non-phi-phi
     # instance 168, shipped since round 6: spills 82 -> 35) held by keeping the complex GSL series out of the kernel's
     # call graph (gsl_cli2_real)
     r"k_alpha_batchILb1ELb1E": (96, 1024),
@@ -77,6 +77,12 @@ def test_hot_kernels_within_register_budget(tmp_path):
     assert any("k_cascade_bs" in k for k in ks), "no cascade kernels in the code object"
     # round 5: the per-stage kernels of rounds 1-3 are out of the product library
     assert not any(re.search(r"k_cascade_(ws|wsp|gb|wf|reg)I", k) for k in ks), "a superseded cascade kernel is back"
+    # the retired A/B variants stay out (DESIGN.md "Retired build variants"): k_alpha_batch is <kPP, kRef, kSplit> --
+    # plain and phi-phi in both arithmetics, the k-split instance of each arithmetic -- with no one-launch-per-mass-state
+    # instances, and no cascade instance has the 96-row push waves (RT = 6)
+    batch = sorted(k for k in ks if "k_alpha_batchI" in k)
+    assert len(batch) == 6, batch
+    assert not any(re.search(r"k_cascade_bsILi\d+ELi\d+ELi\d+ELi6E", k) for k in ks), "a retired cascade instance is back"
     for pat, (spill, priv) in BUDGET.items():
         hits = {k: v for k, v in ks.items() if re.search(pat, k)}
         assert hits, pat
@@ -84,5 +90,5 @@ def test_hot_kernels_within_register_budget(tmp_path):
             assert v.get("vgpr_spill_count", 0) <= spill, (k, v)
             assert v.get("private_segment_fixed_size", 0) <= priv, (k, v)
             if "k_alpha_batch" in k:   # (the launch bound batch_waves: 4 waves per SIMD; the reference order's
-                # non-phi-phi instance may be built at 3, NUSI_BATCH_WAVES_REFO)
+                # non-phi-phi instance may be built at 3, kBatchWavesRefo)
                 assert v.get("vgpr_count", 0) <= (168 if "k_alpha_batchILb0ELb1E" in k else 128), (k, v)
