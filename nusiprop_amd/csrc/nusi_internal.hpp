@@ -46,9 +46,9 @@ struct TablesDev {
 // Tiles of the alpha table for k_alpha_tile: kAlphaTile x kAlphaTile (n, m) bin blocks with
 // tn <= tm, in three launch classes by how many distinct bin edges a side has
 // (bins of the first N share edges, redshift-extended bins do not), which sets
-// each class's LDS footprint.  tiles[] packs tn | tm << 16.
+// each class's LDS footprint.  tiles[]: kTileWords words per tile (alpha_tile_decode, nusi_alpha_tiles.hpp).
 struct AlphaTilesDev {
-    int* tiles = nullptr;   // device [ncore + nmixed + nfull]
+    int* tiles = nullptr;   // device [ncore + nmixed + nfull][kTileWords]
     int ncls[3] = {0, 0, 0};
     int cs_max[3] = {0, 0, 0}, ct_max[3] = {0, 0, 0};
 };

@@ -259,8 +259,6 @@ hipError_t launch_gamma_alphat(const GridDev& g, const Point* pts, int npts, con
 // path evaluates 4 per entry: the dilogarithms, complex dilogarithms and
 // mixed logarithms that dominate the table cost are ~3.5x fewer.
 // ---------------------------------------------------------------------------
-constexpr int kTileThreads = 256;
-static_assert(kAlphaTile * kAlphaTile <= kTileThreads, "one entry per work-item");
 
 // dynamic LDS of a tile for batches of up to G points: corner block, edge blocks, per-point sums
 __host__ __device__ constexpr int alpha_tile_lds_doubles(int cs, int ct, int G)
@@ -293,18 +291,12 @@ __global__ __launch_bounds__(kTileThreads) NUSI_TILE_ATTR void k_alpha_tile(Grid
     const int tid = threadIdx.x, T = g.T;
     const int bw = batches ? batches[blockIdx.y] : (int)blockIdx.y | (1 << 24);
     const int p0 = bw & 0xffffff, nb = (G == 1) ? 1 : bw >> 24;   // tables p0 .. p0 + nb - 1 (nb <= G)
-    const int tw = tiles[blockIdx.x];
-    // tile word: tn | tm << 14 | mhalf << 28 | nhalf << 30; half 1 / 2 = the first 8 / last 7 bins of
-    // that side of the tile only (redshift-extended sides are split so that their at most 16 edges fit
+    // the tile's bins (nusi_alpha_tiles.hpp; redshift-extended sides are cut so that their at most 16 edges fit
     // the core tiles' LDS)
-    const unsigned tu = (unsigned)tw;
-    const int half = (tu >> 28) & 3, nhalf = (tu >> 30) & 3;
-    const int n0 = (tu & 0x3fff) * kAlphaTile + (nhalf == 2 ? 8 : 0);
-    const int m0 = ((tu >> 14) & 0x3fff) * kAlphaTile + (half == 2 ? 8 : 0);
-    const int mcnt = half == 0 ? kAlphaTile : (half == 1 ? 8 : kAlphaTile - 8);
-    const int ncnt = nhalf == 0 ? kAlphaTile : (nhalf == 1 ? 8 : kAlphaTile - 8);
-    const int Tm = (m0 + mcnt < T) ? m0 + mcnt : T;   // bins of the m side: [m0, Tm)
-    const int Tn = (n0 + ncnt < T) ? n0 + ncnt : T;   // bins of the n side: [n0, Tn)
+    const AlphaTile tile = alpha_tile_decode(tiles + kTileWords * blockIdx.x);
+    const int n0 = tile.n0, m0 = tile.m0;
+    const int Tm = (m0 + tile.mcnt < T) ? m0 + tile.mcnt : T;   // bins of the m side: [m0, Tm)
+    const int Tn = (n0 + tile.ncnt < T) ? n0 + tile.ncnt : T;   // bins of the n side: [n0, Tn)
     const Point& P = pts[p0];   // the batch's shared fields (m_phi, masses, flags)
     if (tid < 2 * kAlphaTile) {
         const int side = tid / kAlphaTile, j = tid - side * kAlphaTile, b = (side ? m0 : n0) + j;
@@ -317,7 +309,7 @@ __global__ __launch_bounds__(kTileThreads) NUSI_TILE_ATTR void k_alpha_tile(Grid
     const int ct = cnt[0], cs = cnt[1], cc = cs * ct;
     const int ln = tid % kAlphaTile, lm = tid / kAlphaTile;
     const int n = n0 + ln, m = m0 + lm;
-    const bool valid = tid < kAlphaTile * kAlphaTile && n < m && m < Tm && n < Tn;
+    const bool valid = alpha_tile_slot_valid(tile, T, tid);
     if (cs > cs_max || ct > ct_max || nb > G) {   // host classification guarantees this never happens
         if (valid)
             for (int q = 0; q < nb; ++q) A[(size_t)(p0 + q) * g.PT + (size_t)m * (m - 1) / 2 + n] = __builtin_nan("");
@@ -404,9 +396,14 @@ __global__ __launch_bounds__(kTileThreads) NUSI_TILE_ATTR void k_alpha_tile(Grid
 //   P3   [3][cc]   L, Drr, Dri of the current k
 //   X    [10][cc]  the current k's member coefficients (alpha_batch_xshared_job); while the brackets are
 //                  formed it holds LL, TU1, TU2, G [4][cc] and the mixed logs [kAlphaTile (cs + ct)]
-//   mem  [2][cc]   member corner leaves Dcr, Dci of the current (point, k)
+//   mem  [2][cc]   member corner leaves Dcr, Dci of the current (point, k).  In the reference order they are in X's
+//                  fields 0, 1 (and the chunk's A in fields 3 ..), and mem is free: the paired tiles keep the
+//                  pair's second point there
 //   edg  [alpha_tile_edge_stride]  shared edge / m-bin leaves of the current k
-//   memb [kBatchQC][alpha_batch_memb_doubles]  member edge leaves of a chunk of points
+//   memb [kBatchQC][alpha_batch_memb_doubles]  member edge leaves of a chunk of points (the paired tiles: 4)
+// 256 threads per workgroup whatever the tile holds: a full core tile fills 225 of them, and the tiles of at most
+// kPairEntries = 128 entries (the diagonal tiles' 105, an 8-bin run of extended bins against a core tile's 120) fill
+// both halves with two points (kPair, below).  38.5 KB of LDS: four workgroups per CU, three at kBatchWavesRefo.
 // ---------------------------------------------------------------------------
 // points per member-edge round (5: C4 alpha 6.05 -> 5.95 ms vs 4, profiles/r2q)
 constexpr int kBatchQC = 5;   // kBatchQC (ct + cs + kAlphaTile) <= 256 jobs
@@ -539,7 +536,7 @@ constexpr int kBtWg = 16, kBtN = 512;
 __device__ unsigned long long g_bt[kBtWg * 4 * kBtN];
 #define NUSI_BT()                                                                                                   \
     do {                                                                                                            \
-        if (kRef && !kPP && !kSplit && blockIdx.x < 4 && blockIdx.y < 4 && (threadIdx.x & 63) == 0 && bt_i < kBtN) \
+        if (kRef && !kPP && !kSplit && kPair == 1 && blockIdx.x < 4 && blockIdx.y < 4 && (threadIdx.x & 63) == 0 && bt_i < kBtN) \
             g_bt[((blockIdx.y * 4 + blockIdx.x) * 4 + (threadIdx.x >> 6)) * kBtN + bt_i] = __builtin_amdgcn_s_memtime(); \
         ++bt_i;                                                                                                     \
     } while (0)
@@ -552,33 +549,46 @@ __device__ unsigned long long g_bt[kBtWg * 4 * kBtN];
 // batch structure unchanged.  kSplit (calls of few tables, a single propagation): mass state k = blockIdx.z only,
 // its terms of every entry recorded into kt ([table][3][PT][8]: up to 7 terms, then their count, -1 for an entry
 // the resonant-only table does not compute) for k_alpha_ksum -- three times the workgroups, each a third as long
-template <bool kPP, bool kRef, bool kSplit = false>
-__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(batch_waves(kPP, kRef), batch_waves(kPP, kRef))))
-void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp, const int* __restrict__ tiles,
-                   const int* __restrict__ batches, double* __restrict__ A, const double* __restrict__ med,
-                   int* __restrict__ warn, int* __restrict__ wmin, MCornerDev mc, int pc0, double* __restrict__ kt)
+//
+// kPair = 2 (the reference order without phi-phi, tiles flagged AlphaTile::pair): a tile of at most kPairEntries entries -- the
+// diagonal core tiles, the runs of 8 extended bins -- holds its entries in the first half of the workgroup through a
+// compact entry list (alpha_tile_entry_rank), and the second half holds them again: threads 0-127 combine point q
+// of the batch, threads 128-255 point q + 1 (the point index uniform per wave), so the point loop has half the
+// iterations and half the barriers.  A corner thread publishes both points' member corners per iteration (the
+// second pair in the mem block, which the reference order does not use otherwise); the chunks are of 4 points, so
+// that a pair never straddles two.  Each half carries its own entry sums through the mass states in A, as a thread
+// of a full tile does: the same functions on the same leaves in the same order.
+template <bool kPP, bool kRef, bool kSplit, int kPair>
+__device__ __forceinline__ void alpha_batch_body(const GridDev& g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp,
+                                                 const int* __restrict__ tiles, const int* __restrict__ batches,
+                                                 double* __restrict__ A, const double* __restrict__ med,
+                                                 int* __restrict__ warn, int* __restrict__ wmin, const MCornerDev& mc,
+                                                 int pc0, double* __restrict__ kt)
 {
+    static_assert(kPair == 1 || (kPair == 2 && kRef && !kPP && !kSplit), "paired points: the reference order without phi-phi");
+    constexpr int kQC = kPair == 2 ? 4 : kBatchQC;   // points per member-edge round (a whole number of pairs)
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const SplineSet& spl = *splp;
     __shared__ double tE[2 * kAlphaTile], sE[2 * kAlphaTile];
     __shared__ int tl[kAlphaTile], th[kAlphaTile], sl[kAlphaTile], sh[kAlphaTile];
     __shared__ int cnt[2];
     __shared__ double elo[2][kAlphaTile], ehi[2][kAlphaTile];
+    __shared__ unsigned char elist[kPair == 2 ? kPairEntries : 1];   // (kPair = 2) thread slot of each listed entry
     const int tid = threadIdx.x, T = g.T;
     // (an XCD-contiguous remap of the blocks measured slower than the dealt order: C4 alpha 5.97 -> 6.09 ms,
     // profiles/r2s)
     const int bx = blockIdx.x, by = blockIdx.y;
     const int bw = batches[by];
     const int p0 = bw & 0xffffff, nb = (int)((unsigned)bw >> 24);   // tables p0 .. p0 + nb - 1
-    const unsigned tu = (unsigned)tiles[bx];                         // tile word, as in k_alpha_tile
-    const int half = (tu >> 28) & 3, nhalf = (tu >> 30) & 3;
-    const int n0 = (tu & 0x3fff) * kAlphaTile + (nhalf == 2 ? 8 : 0);
-    const int m0 = ((tu >> 14) & 0x3fff) * kAlphaTile + (half == 2 ? 8 : 0);
-    const int mcnt = half == 0 ? kAlphaTile : (half == 1 ? 8 : kAlphaTile - 8);
-    const int ncnt = nhalf == 0 ? kAlphaTile : (nhalf == 1 ? 8 : kAlphaTile - 8);
-    const int Tm = (m0 + mcnt < T) ? m0 + mcnt : T;
-    const int Tn = (n0 + ncnt < T) ? n0 + ncnt : T;
+    const AlphaTile tile = alpha_tile_decode(tiles + kTileWords * bx);   // the tile's bins, as in k_alpha_tile
+    const int n0 = tile.n0, m0 = tile.m0;
+    const int Tm = (m0 + tile.mcnt < T) ? m0 + tile.mcnt : T;
+    const int Tn = (n0 + tile.ncnt < T) ? n0 + tile.ncnt : T;
     const Point& P = pts[p0];
+    if (kPair == 2) {
+        const int r = alpha_tile_entry_rank(tile, T, tid);
+        if (r >= 0 && r < kPairEntries) elist[r] = (unsigned char)tid;   // (read after the barriers below)
+    }
     if (tid < 2 * kAlphaTile) {
         const int side = tid / kAlphaTile, j = tid - side * kAlphaTile, b = (side ? m0 : n0) + j;
         if (b < (side ? Tm : Tn)) { elo[side][j] = g.lo[b]; ehi[side][j] = g.hi[b]; }
@@ -599,13 +609,26 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
             if (j == 0 || il[j] != ih[j - 1]) src[il[j]] = 2 * (b0 + j);   // else the previous bin's upper edge
         }
     }
-    const int ln = tid % kAlphaTile, lm = tid / kAlphaTile;
+    // this thread's entry: thread slot `slot` of the tile -- the thread's own, or (kPair = 2) the one the entry list
+    // gives its half; hq: the point of a pair this wave combines
+    const int hq = kPair == 2 ? __builtin_amdgcn_readfirstlane(tid / kPairEntries) : 0;
+    const int nent = kPair == 2 ? alpha_tile_entries(tile, T) : 0;
+    int slot = tid;
+    if (kPair == 2) {
+        const int e = tid % kPairEntries;
+        slot = (e < nent && nent <= kPairEntries) ? elist[e] : kTileThreads - 1;   // (the last slot holds no entry)
+    }
+    const int ln = slot % kAlphaTile, lm = slot / kAlphaTile;
     const int n = n0 + ln, m = m0 + lm;
-    const bool valid = tid < kAlphaTile * kAlphaTile && n < m && m < Tm && n < Tn;
+    const bool valid = alpha_tile_slot_valid(tile, T, slot);
     const size_t eidx = (size_t)m * (m - 1) / 2 + n;
-    if (cs > kAlphaTile + 1 || ct > kAlphaTile + 1) {   // host classification guarantees this never happens
-        if (valid)
-            for (int q = 0; q < nb; ++q) A[(size_t)(p0 + q) * g.PT + eidx] = __builtin_nan("");
+    // host classification guarantees this never happens
+    if (cs > kAlphaTile + 1 || ct > kAlphaTile + 1 || (kPair == 2 && nent > kPairEntries)) {
+        if (alpha_tile_slot_valid(tile, T, tid)) {
+            const int md = m0 + tid / kAlphaTile;
+            for (int q = 0; q < nb; ++q)
+                A[(size_t)(p0 + q) * g.PT + (size_t)md * (md - 1) / 2 + n0 + tid % kAlphaTile] = __builtin_nan("");
+        }
         return;
     }
     const bool nonres = P.non_resonant, maj = P.majorana, cornered = nonres && maj;
@@ -638,7 +661,7 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
         if (cornered) {
             for (int j = tid; j < cc; j += kTileThreads) b_corner<kRef>(j, edgk, ct, cs, P3, tmp);
             for (int j = tid; j < kAlphaTile * (cs + ct); j += kTileThreads)
-                alpha_batch_mixed_job(j, edgk, ct, cs, tl, th, sl, sh, n0, m0, T, Tm, mix, mix + kAlphaTile * cs);
+                alpha_batch_mixed_job(j, edgk, ct, cs, tl, th, sl, sh, n0, m0, Tn, Tm, mix, mix + kAlphaTile * cs);
             __syncthreads();
             NUSI_BT();
             if (needed) {
@@ -664,7 +687,7 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
         // A point's entry accumulates over the mass states in A; the sum of the states < k is loaded one
         // point ahead (timed equal to loading it in place, profiles/r2m: four blocks per CU already hide it).
         const bool reload = !kSplit && k > 0 && needed;
-        double tnext = reload ? A[(size_t)p0 * g.PT + eidx] : 0.0;
+        double tnext = reload && hq < nb ? A[(size_t)(p0 + hq) * g.PT + eidx] : 0.0;
         // member edges: thread (mq, mjob) copies job mjob of point mq of each chunk (loading the next chunk's
         // values a chunk ahead measured slower: their registers stay live through the combine)
         const int mq = tid / mjobs, mjob = tid - mq * mjobs;
@@ -675,18 +698,19 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
             kRef ? reinterpret_cast<const double2*>(mc.buf + (size_t)(p0 - pc0) * 6 * mc.NC + (size_t)k * 2 * nb * mc.NC)
                  : nullptr;
         int moff = -1;   // this thread's corner c, or -1 (point q's pair at q NC + c)
-        double2 mcv = make_double2(0.0, 0.0);
+        double2 mcv = make_double2(0.0, 0.0), mcv2 = mcv;   // (mcv2, kPair = 2: the pair's second point)
         if (kRef && cornered && tid < cc) {
             const int si = tid / ct, ti = tid - si * ct;
             const int us = mc.eu[ssrc[si]], ut = mc.eu[tsrc[ti]];
             if (ut <= us) {
                 moff = us * (us + 1) / 2 + ut;
                 mcv = mcb[moff];
+                if (kPair == 2 && nb > 1) mcv2 = mcb[mc.NC + moff];
             }
         }
 #pragma unroll 1
-        for (int q0 = 0; q0 < nb; q0 += kBatchQC) {
-            const int nq = (nb - q0 < kBatchQC) ? nb - q0 : kBatchQC;
+        for (int q0 = 0; q0 < nb; q0 += kQC) {
+            const int nq = (nb - q0 < kQC) ? nb - q0 : kQC;
             __syncthreads();   // the previous chunk is done with membq (and mem)
             NUSI_BT();
             if (mq < nq) {
@@ -708,20 +732,25 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
             }
             NUSI_BT();
 #pragma unroll 1
-            for (int qq = 0; qq < nq; ++qq) {
-                const int q = q0 + qq;
-                const Point& Q = pts[p0 + q];
-                const double* memb = membq + qq * mbd;
+            for (int qq = 0; qq < nq; qq += kPair) {
+                // (kPair = 2: this half's point of the pair q0 + qq, q0 + qq + 1; an odd batch's last pair leaves
+                // the second half idle, act false -- uniform per wave)
+                const int q = q0 + qq + hq;
+                const bool act = kPair == 1 || q < nb;
+                const Point& Q = pts[p0 + (act ? q : nb - 1)];
+                const double* memb = membq + (qq + hq) * mbd;
                 double tot = tnext;   // after states < k
-                if (reload && q + 1 < nb) tnext = A[(size_t)(p0 + q + 1) * g.PT + eidx];
+                if (reload && q + kPair < nb) tnext = A[(size_t)(p0 + q + kPair) * g.PT + eidx];
                 __syncthreads();   // member edges written / the previous point's combine is done with mem
                 NUSI_BT();
                 if (cornered) {
                     if (kRef) {
                         if (moff >= 0) {
-                            const size_t o = (size_t)q * mc.NC + moff;
+                            const size_t o = (size_t)(q0 + qq) * mc.NC + moff;
                             X[tid] = mcv.x; X[kCC + tid] = mcv.y;
-                            if (q + 1 < nb) mcv = mcb[o + mc.NC];
+                            if (kPair == 2) { mem[tid] = mcv2.x; mem[kCC + tid] = mcv2.y; }
+                            if (q0 + qq + kPair < nb) mcv = mcb[o + kPair * mc.NC];
+                            if (kPair == 2 && q0 + qq + 3 < nb) mcv2 = mcb[o + 3 * mc.NC];
                         }
                     }
                     else
@@ -731,16 +760,16 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
                 NUSI_BT();
                 int w = 0;
                 TermRec rec;
-                if (needed) {
+                if (needed && act) {
                     SplitLeavesT<kRef> lv;
                     lv.cf[0] = P3; lv.cf[1] = P3; lv.cf[2] = P3; lv.cf[3] = P3; lv.cf[4] = P3;
                     lv.cf[5] = P3 + kCC; lv.cf[6] = P3 + 2 * kCC;   // (LL, TU1, TU2, G are not read with pre)
-                    lv.corm = kRef ? X : mem;
+                    lv.corm = kRef && hq == 0 ? X : mem;
                     lv.cc = cc; lv.ct = ct; lv.cs = cs; lv.mb = lm; lv.nb = ln;
                     lv.sidx[0] = sl[lm]; lv.sidx[1] = sh[lm]; lv.tidx[0] = tl[ln]; lv.tidx[1] = th[ln];
                     lv.ted = edgk; lv.sed = edgk + kTEdgeFields * ct; lv.mbv = lv.sed + kSEdgeFields * cs;
                     lv.tedm = memb; lv.sedm = memb + ct; lv.mbm = memb + ct + 2 * cs;
-                    lv.marg = kRef ? X + (3 + qq) * kCC : memb + ct + 2 * cs + kAlphaTile + 2 * ct;   // sT | fT | sS | fS
+                    lv.marg = kRef ? X + (3 + qq + hq) * kCC : memb + ct + 2 * cs + kAlphaTile + 2 * ct;   // sT | fT | sS | fS
                     lv.xl = mix; lv.yl = mix;   // (not read with pre)
                     if (kSplit)
                         alpha_k<SplitLeavesT<kRef>, kPP>(Q, spl, k, g.lo[n], g.hi[n], g.lo[m], g.hi[m], lv, rec, w,
@@ -756,7 +785,7 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
                         for (int j = 0; j < 7; ++j) o[j] = rec.v[j];
                         o[7] = needed ? (double)rec.n : -1.0;
                     }
-                } else if (valid) A[(size_t)(p0 + q) * g.PT + eidx] = needed ? tot : 0.0;
+                } else if (valid && act) A[(size_t)(p0 + q) * g.PT + eidx] = needed ? tot : 0.0;
                 if (w) warn_entry(warn, wmin, T, p0 + q, w, n, m);
                 NUSI_BT();
             }
@@ -764,6 +793,22 @@ void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __
     }
     if (wsh)   // (the batch-shared phi-phi term of this thread's entry)
         for (int q = 0; q < nb; ++q) warn_entry(warn, wmin, T, p0 + q, wsh, n, m);
+}
+template <bool kPP, bool kRef, bool kSplit = false>
+__global__ __launch_bounds__(kTileThreads) __attribute__((amdgpu_waves_per_eu(batch_waves(kPP, kRef), batch_waves(kPP, kRef))))
+void k_alpha_batch(GridDev g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp, const int* __restrict__ tiles,
+                   const int* __restrict__ batches, double* __restrict__ A, const double* __restrict__ med,
+                   int* __restrict__ warn, int* __restrict__ wmin, MCornerDev mc, int pc0, double* __restrict__ kt)
+{
+    // the reference order without phi-phi: a tile of at most kPairEntries entries (AlphaTile::pair, uniform over the
+    // workgroup) takes the body of two points per iteration.  One launch over both kinds of tile: a launch of their
+    // own for the paired tiles measured slower (C4 alpha stage 14.80 against 14.48 ms: two tails, and the full tiles
+    // alone fill the CUs less evenly)
+    if (!kPP && kRef && !kSplit && alpha_tile_decode(tiles + kTileWords * blockIdx.x).pair) {
+        alpha_batch_body<false, true, false, 2>(g, pts, splp, tiles, batches, A, med, warn, wmin, mc, pc0, nullptr);
+        return;
+    }
+    alpha_batch_body<kPP, kRef, kSplit, 1>(g, pts, splp, tiles, batches, A, med, warn, wmin, mc, pc0, kt);
 }
 
 // The k-split path's sums (k_alpha_batch<.., kSplit>): every class-0 entry of the batches' tables, its mass states'
@@ -777,15 +822,9 @@ __global__ __launch_bounds__(kTileThreads) void k_alpha_ksum(GridDev g, const in
     const int tid = threadIdx.x, T = g.T;
     const int bw = batches[blockIdx.y];
     const int p0 = bw & 0xffffff, nb = (int)((unsigned)bw >> 24);
-    const unsigned tu = (unsigned)tiles[blockIdx.x];
-    const int half = (tu >> 28) & 3, nhalf = (tu >> 30) & 3;
-    const int n0 = (tu & 0x3fff) * kAlphaTile + (nhalf == 2 ? 8 : 0);
-    const int m0 = ((tu >> 14) & 0x3fff) * kAlphaTile + (half == 2 ? 8 : 0);
-    const int mcnt = half == 0 ? kAlphaTile : (half == 1 ? 8 : kAlphaTile - 8);
-    const int ncnt = nhalf == 0 ? kAlphaTile : (nhalf == 1 ? 8 : kAlphaTile - 8);
-    const int Tm = (m0 + mcnt < T) ? m0 + mcnt : T, Tn = (n0 + ncnt < T) ? n0 + ncnt : T;
-    const int n = n0 + tid % kAlphaTile, m = m0 + tid / kAlphaTile;
-    if (!(tid < kAlphaTile * kAlphaTile && n < m && m < Tm && n < Tn)) return;
+    const AlphaTile tile = alpha_tile_decode(tiles + kTileWords * blockIdx.x);
+    const int n = tile.n0 + tid % kAlphaTile, m = tile.m0 + tid / kAlphaTile;
+    if (!alpha_tile_slot_valid(tile, T, tid)) return;
     const size_t eidx = (size_t)m * (m - 1) / 2 + n;
     for (int q = 0; q < nb; ++q) {
         double tot = 0.0;
@@ -841,59 +880,17 @@ hipError_t launch_table_shift(const GridDev& g, const GridDev& gb, const int2* m
 
 hipError_t alpha_tiles_create(int T, const unsigned char* shared, AlphaTilesDev* out)
 {
-    const int nt = (T + kAlphaTile - 1) / kAlphaTile;
-    // distinct edges of each tile side, exactly as alpha_edge_list counts them on the device
-    std::vector<int> ne(nt, 0);
-    for (int t = 0; t < nt; ++t)
-        for (int j = t * kAlphaTile; j < (t + 1) * kAlphaTile && j < T; ++j)
-            ne[t] += (j > t * kAlphaTile && shared[j - 1]) ? 1 : 2;
-    // class 0: both sides <= 16 edges; 1: t side <= 16, S' side <= 30; 2: both <= 30.  From the
-    // first tile t0 whose bins do not share edges (the redshift-extended bins) on, tiles of class 2
-    // save no corner (4 per entry, like the per-entry path) and their 80-KB LDS footprint halves the
-    // occupancy.
+    const AlphaTileList tl = alpha_tiles_build(T, shared);   // (nusi_alpha_tiles.hpp)
     const int cap_core = kAlphaTile + 1, cap_ext = 2 * kAlphaTile;
-    int t0 = nt;
-    for (int t = 0; t < nt; ++t)
-        if (ne[t] > cap_core) { t0 = t; break; }
-    bool tail_ext = true;   // no bin from tile t0 on shares an edge with its neighbour
-    for (int n = t0 * kAlphaTile; n + 1 < T; ++n) tail_ext = tail_ext && !shared[n];
-    // the extended triangle runs as quarter tiles (8 x 8 bins, batched with the core tiles; round 1: alpha
-    // stage 14.68 -> 14.55 ms per 1024 points against the per-entry kernel)
-    const int qlo = (tail_ext && t0 < nt) ? t0 : nt;   // tiles from qlo on: split on both sides
-    // Class-1 tiles (t side core, S' side extended: 30 S' edges) are split into their first 8 and last
-    // 7 m bins (16 / 14 S' edges): the halves fit the core tiles' LDS footprint and join class 0,
-    // whose launch builds batches of tables (16.0 -> 14.8 ms when introduced).  So cls[1] stays empty:
-    // c == 1 needs ne[tn] <= cap_core < ne[tm], hence tn < tm, and every such tile is split below (as
-    // quarter tiles from qlo on, as m halves before it).  The launchers keep their three-class loop.
-    std::vector<int> cls[3];
-    for (int tm = 0; tm < nt; ++tm)
-        for (int tn = 0; tn <= tm; ++tn) {
-            const int c = (ne[tn] <= cap_core && ne[tm] <= cap_core) ? 0 : (ne[tn] <= cap_core) ? 1 : 2;
-            const int w = tn | (tm << 14);
-            if (tn >= qlo) {   // both sides extended: up to 4 quarter tiles (n half, m half)
-                for (int nh = 1; nh <= 2; ++nh)
-                    for (int mh = 1; mh <= 2; ++mh) {
-                        const int nb0 = tn * kAlphaTile + (nh == 2 ? 8 : 0), mb0 = tm * kAlphaTile + (mh == 2 ? 8 : 0);
-                        const int mb1 = std::min(T, tm * kAlphaTile + (mh == 1 ? 8 : kAlphaTile));
-                        if (nb0 >= T || mb0 >= T || nb0 >= mb1 - 1) continue;   // no entry n < m
-                        cls[0].push_back((int)((unsigned)w | ((unsigned)mh << 28) | ((unsigned)nh << 30)));
-                    }
-            } else if (c == 1) {
-                cls[0].push_back(w | (1 << 28));
-                if (tm * kAlphaTile + 8 < T) cls[0].push_back(w | (2 << 28));
-            } else {
-                cls[c].push_back(w);
-            }
-        }
     const int csm[3] = {cap_core, cap_ext, cap_ext}, ctm[3] = {cap_core, cap_core, cap_ext};
     std::vector<int> all;
     for (int c = 0; c < 3; ++c) {
-        out->ncls[c] = (int)cls[c].size();
+        out->ncls[c] = tl.count(c);
         out->cs_max[c] = csm[c];
         out->ct_max[c] = ctm[c];
-        all.insert(all.end(), cls[c].begin(), cls[c].end());
+        all.insert(all.end(), tl.cls[c].begin(), tl.cls[c].end());
     }
-    hipError_t e = hipMalloc(&out->tiles, sizeof(int) * all.size());
+    hipError_t e = hipMalloc(&out->tiles, sizeof(int) * std::max<size_t>(1, all.size()));
     if (e != hipSuccess) return e;
     return hipMemcpy(out->tiles, all.data(), sizeof(int) * all.size(), hipMemcpyHostToDevice);
 }
@@ -990,7 +987,7 @@ static hipError_t launch_alpha_t(const GridDev& g, const Point* pts, int npts, c
             } else {
                 const size_t lds = sizeof(double) * (size_t)alpha_tile_lds_doubles(cs, ct, 1);
                 hipLaunchKernelGGL((k_alpha_tile<1, kRef>), dim3(at.ncls[c], npts), dim3(kTileThreads), lds, s, g, pts,
-                                   spl, at.tiles + off, cs, ct, nullptr, t.A, warn, t.Wmin);
+                                   spl, at.tiles + kTileWords * off, cs, ct, nullptr, t.A, warn, t.Wmin);
             }
             off += at.ncls[c];
         }
@@ -1017,14 +1014,14 @@ static hipError_t launch_alpha_t(const GridDev& g, const Point* pts, int npts, c
         const dim3 grid(at.ncls[c], batched ? nbatches : npts), blk(kTileThreads);
         const int* bt = batched ? batches : nullptr;
         if (kRef) {
-            hipLaunchKernelGGL((k_alpha_tile<1, true>), grid, blk, lds, s, g, pts, spl, at.tiles + off, cs, ct, bt, t.A,
+            hipLaunchKernelGGL((k_alpha_tile<1, true>), grid, blk, lds, s, g, pts, spl, at.tiles + kTileWords * off, cs, ct, bt, t.A,
                                warn, t.Wmin);
         } else {
             switch (G) {
-            case 1: hipLaunchKernelGGL((k_alpha_tile<1, false>), grid, blk, lds, s, g, pts, spl, at.tiles + off, cs, ct, bt, t.A, warn, t.Wmin); break;
-            case 2: hipLaunchKernelGGL((k_alpha_tile<2, false>), grid, blk, lds, s, g, pts, spl, at.tiles + off, cs, ct, bt, t.A, warn, t.Wmin); break;
-            case 3: hipLaunchKernelGGL((k_alpha_tile<3, false>), grid, blk, lds, s, g, pts, spl, at.tiles + off, cs, ct, bt, t.A, warn, t.Wmin); break;
-            default: hipLaunchKernelGGL((k_alpha_tile<4, false>), grid, blk, lds, s, g, pts, spl, at.tiles + off, cs, ct, bt, t.A, warn, t.Wmin); break;
+            case 1: hipLaunchKernelGGL((k_alpha_tile<1, false>), grid, blk, lds, s, g, pts, spl, at.tiles + kTileWords * off, cs, ct, bt, t.A, warn, t.Wmin); break;
+            case 2: hipLaunchKernelGGL((k_alpha_tile<2, false>), grid, blk, lds, s, g, pts, spl, at.tiles + kTileWords * off, cs, ct, bt, t.A, warn, t.Wmin); break;
+            case 3: hipLaunchKernelGGL((k_alpha_tile<3, false>), grid, blk, lds, s, g, pts, spl, at.tiles + kTileWords * off, cs, ct, bt, t.A, warn, t.Wmin); break;
+            default: hipLaunchKernelGGL((k_alpha_tile<4, false>), grid, blk, lds, s, g, pts, spl, at.tiles + kTileWords * off, cs, ct, bt, t.A, warn, t.Wmin); break;
             }
         }
         off += at.ncls[c];

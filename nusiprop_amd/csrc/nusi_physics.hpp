@@ -14,6 +14,7 @@
 
 #include "nusi_math.hpp"
 #include "nusi_spline.hpp"
+#include "nusi_alpha_tiles.hpp"
 
 // The three-mass loops (j/k = 0..2) are kept rolled by default: unrolled, the
 // alpha kernel is ~225 KB of code (instruction-cache thrashing) and 300+
@@ -842,7 +843,7 @@ using DirectLeaves = DirectLeavesT<false>;
 //   ted[v * ct + t], sed[v * cs + s], mbv[v * kAlphaTile + j] (shared edge / m-bin fields),
 //   tedm[t] = L2, sedm[s] = Ls, sedm[cs + s] = cS, mbm[j] = atd (this point's member fields),
 //   xl[s * kAlphaTile + n bin], yl[m bin * ct + t]
-constexpr int kAlphaTile = 15;   // bins per alpha tile side (the edges of a core tile side are kAlphaTile + 1 <= 17)
+// (kAlphaTile, the bins per alpha tile side: nusi_alpha_tiles.hpp)
 constexpr int kCornerShared = 7, kCornerMember = 3;   // L LL TU1 TU2 G Drr Dri | Dcr Dci A
 struct TileLeaves {
     const double *cor, *corm, *ted, *sed, *mbv, *tedm, *sedm, *mbm, *xl, *yl;
