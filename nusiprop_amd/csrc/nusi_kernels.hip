@@ -397,10 +397,11 @@ __global__ __launch_bounds__(kTileThreads) NUSI_TILE_ATTR void k_alpha_tile(Grid
 //   X    [10][cc]  the current k's member coefficients (alpha_batch_xshared_job); while the brackets are
 //                  formed it holds LL, TU1, TU2, G [4][cc] and the mixed logs [kAlphaTile (cs + ct)]
 //   mem  [2][cc]   member corner leaves Dcr, Dci of the current (point, k).  In the reference order they are in X's
-//                  fields 0, 1 (and the chunk's A in fields 3 ..), and mem is free: the paired tiles keep the
-//                  pair's second point there
+//                  fields 0, 1 (and the chunk's A in fields 3 ..), and mem is free.  The reference order without
+//                  phi-phi stages a whole chunk of kStageQC = 4 points instead: point j of the chunk owns fields
+//                  3 j, 3 j + 1 (Dcr, Dci) and 3 j + 2 (A) of the 12 contiguous fields X | mem
 //   edg  [alpha_tile_edge_stride]  shared edge / m-bin leaves of the current k
-//   memb [kBatchQC][alpha_batch_memb_doubles]  member edge leaves of a chunk of points (the paired tiles: 4)
+//   memb [kBatchQC][alpha_batch_memb_doubles]  member edge leaves of a chunk of points (the staged chunks: 4)
 // 256 threads per workgroup whatever the tile holds: a full core tile fills 225 of them, and the tiles of at most
 // kPairEntries = 128 entries (the diagonal tiles' 105, an 8-bin run of extended bins against a core tile's 120) fill
 // both halves with two points (kPair, below).  38.5 KB of LDS: four workgroups per CU, three at kBatchWavesRefo.
@@ -417,6 +418,10 @@ static_assert(kXFields * (kAlphaTile + 1) * (kAlphaTile + 1) >= 4 * (kAlphaTile 
               "the bracket phase's blocks fit X");
 static_assert(kBatchQC * (2 * (kAlphaTile + 1) + kAlphaTile) <= kTileThreads, "one member-edge round per chunk");
 static_assert(3 + kBatchQC <= kXFields, "(kRef) the chunk's A fields fit X beside Dcr, Dci");
+// points per chunk of the reference-order instance without phi-phi: each owns three fields (Dcr, Dci, A) of X | mem
+constexpr int kStageQC = 4;
+static_assert(3 * kStageQC <= kXFields + 2, "(staged chunks) the chunk's Dcr, Dci, A fields fit X and the mem block after it");
+static_assert(kStageQC <= kBatchQC && kStageQC % 2 == 0, "the staged chunk fits memb, and a pair never straddles two");
 
 // waves per SIMD of k_alpha_batch: 4 (128 VGPRs; the LDS holds four workgroups per CU), and 3 for the reference-order
 // instance without phi-phi (kBatchWavesRefo, 168 VGPRs): spills 82 -> 35, C4 7.28 -> 6.76 ms (profiles/r5/r6u,
@@ -529,8 +534,9 @@ void mcorner_edges(int T, const double* lo, const double* hi, std::vector<int>& 
 // Diagnostic build only (-DNUSI_BATCH_TRACE, scripts/build_variant.sh): s_memtime stamps of the reference-order batch
 // kernel's phases in workgroups (x < 4, y < 4), per wave, in program order (per mass state: its start, the edge
 // leaves' barrier, the shared corners' barrier, the brackets' barrier; per chunk: its start, its member edges and A
-// done; per point: its two barriers and its combine done).  nusi_debug_batch_trace() copies them out; compiled out of
-// the product.
+// done; per point: its two barriers and its combine done -- with the staged chunks, which have no per-point barrier:
+// per iteration of the point loop, one or two points, its combine done).  nusi_debug_batch_trace() copies them out;
+// compiled out of the product.
 #ifdef NUSI_BATCH_TRACE
 constexpr int kBtWg = 16, kBtN = 512;
 __device__ unsigned long long g_bt[kBtWg * 4 * kBtN];
@@ -554,10 +560,19 @@ __device__ unsigned long long g_bt[kBtWg * 4 * kBtN];
 // diagonal core tiles, the runs of 8 extended bins -- holds its entries in the first half of the workgroup through a
 // compact entry list (alpha_tile_entry_rank), and the second half holds them again: threads 0-127 combine point q
 // of the batch, threads 128-255 point q + 1 (the point index uniform per wave), so the point loop has half the
-// iterations and half the barriers.  A corner thread publishes both points' member corners per iteration (the
-// second pair in the mem block, which the reference order does not use otherwise); the chunks are of 4 points, so
+// iterations.  Each half reads its point's fields of the staged chunk (below); the chunks are of 4 points, so
 // that a pair never straddles two.  Each half carries its own entry sums through the mass states in A, as a thread
 // of a full tile does: the same functions on the same leaves in the same order.
+//
+// Staged chunks (kStage: the reference order without phi-phi, kPair = 1 and 2): per chunk of kStageQC = 4 points the
+// corner threads load each point's (Dcr, Dci) from mc, form its A while the load is in flight, and store the three
+// into the point's own fields of X | mem; after one barrier the chunk's combines run in a row without the waves
+// meeting.  Two barriers per chunk, 2 ceil(nb / 4) per mass state (a batch of 32: 16, against 7 (1 + 2 x 5) = 77 of
+// the point-by-point loop that the other instances keep: barrier, publish one point's Dcr, Dci, barrier, combine).
+// In the full tiles (kPair = 1) a thread then takes the chunk's points two at a time through alpha_k_two, each section
+// of the combine for both before the next fence (C4: k_alpha_batch[refo] 5.38 -> 4.97 ms per launch).  The paired
+// tiles keep one point per thread and iteration: with two in flight there as well the C4 step measured another
+// ~0.1 ms shorter, but the kernel spills 49 VGPRs (both bodies' spill slots add up), over the 40 of its register budget.
 template <bool kPP, bool kRef, bool kSplit, int kPair>
 __device__ __forceinline__ void alpha_batch_body(const GridDev& g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp,
                                                  const int* __restrict__ tiles, const int* __restrict__ batches,
@@ -565,8 +580,9 @@ __device__ __forceinline__ void alpha_batch_body(const GridDev& g, const Point* 
                                                  int* __restrict__ warn, int* __restrict__ wmin, const MCornerDev& mc,
                                                  int pc0, double* __restrict__ kt)
 {
-    static_assert(kPair == 1 || (kPair == 2 && kRef && !kPP && !kSplit), "paired points: the reference order without phi-phi");
-    constexpr int kQC = kPair == 2 ? 4 : kBatchQC;   // points per member-edge round (a whole number of pairs)
+    constexpr bool kStage = kRef && !kPP && !kSplit;   // the chunk's member corners staged in X | mem (above)
+    static_assert(kPair == 1 || (kPair == 2 && kStage), "paired points: the reference order without phi-phi");
+    constexpr int kQC = kStage ? kStageQC : kBatchQC;   // points per member-edge round (a whole number of pairs)
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const SplineSet& spl = *splp;
     __shared__ double tE[2 * kAlphaTile], sE[2 * kAlphaTile];
@@ -692,26 +708,25 @@ __device__ __forceinline__ void alpha_batch_body(const GridDev& g, const Point* 
         // values a chunk ahead measured slower: their registers stay live through the combine)
         const int mq = tid / mjobs, mjob = tid - mq * mjobs;
         // (kRef) thread tid < cc carries corner tid's member leaves one point ahead (loaded while the point before
-        // combines), from k_alpha_mcorner's block:
+        // combines; kStage: loads them chunk by chunk, below), from k_alpha_mcorner's block:
         // the corner's numbering c (only corners with ut <= us are read by the entries n < m; the others stay unset)
         const double2* const mcb =   // (uniform: the block of this batch and mass state, [q][c] of (Dcr, Dci))
             kRef ? reinterpret_cast<const double2*>(mc.buf + (size_t)(p0 - pc0) * 6 * mc.NC + (size_t)k * 2 * nb * mc.NC)
                  : nullptr;
         int moff = -1;   // this thread's corner c, or -1 (point q's pair at q NC + c)
-        double2 mcv = make_double2(0.0, 0.0), mcv2 = mcv;   // (mcv2, kPair = 2: the pair's second point)
+        double2 mcv = make_double2(0.0, 0.0);
         if (kRef && cornered && tid < cc) {
             const int si = tid / ct, ti = tid - si * ct;
             const int us = mc.eu[ssrc[si]], ut = mc.eu[tsrc[ti]];
             if (ut <= us) {
                 moff = us * (us + 1) / 2 + ut;
-                mcv = mcb[moff];
-                if (kPair == 2 && nb > 1) mcv2 = mcb[mc.NC + moff];
+                if (!kStage) mcv = mcb[moff];
             }
         }
 #pragma unroll 1
         for (int q0 = 0; q0 < nb; q0 += kQC) {
             const int nq = (nb - q0 < kQC) ? nb - q0 : kQC;
-            __syncthreads();   // the previous chunk is done with membq (and mem)
+            __syncthreads();   // the previous chunk is done with membq (and mem; kStage: with X | mem)
             NUSI_BT();
             if (mq < nq) {
                 MedVals mv{};
@@ -722,56 +737,79 @@ __device__ __forceinline__ void alpha_batch_body(const GridDev& g, const Point* 
             // (kRef) A of this thread's corner for the chunk's points, into X's fields 3 .. 3 + nq - 1 (free in the
             // point loop): the reference's carg of the member quotient, out of the per-point phases (formed per point
             // between their barriers, out of line, it cost 1.23 ms of C4's 7.96; here 7.28 ms in all, profiles/r5/r6p)
+            // kStage: point qq of the chunk owns fields 3 qq, 3 qq + 1 (Dcr, Dci, loaded here -- forming A hides the
+            // load) and 3 qq + 2 (A) of X | mem, so the point loop below has neither a barrier nor a publish step
             if (kRef && moff >= 0) {
                 const int si = tid / ct, ti = tid - si * ct;
                 const double S = edgk[kTEdgeFields * ct + kSEdgeVal * cs + si], t = edgk[kTEdgeVal * ct + ti];
 #pragma unroll 1
-                for (int qq = 0; qq < nq; ++qq)   // (inline: C4 7.42 -> 7.28 ms, r6p; kPP, whose point loop holds
-                    X[(3 + qq) * kCC + tid] =     // the phi-phi term too, as a call: C3 12.33 -> 11.24 ms, r6q)
-                        kPP ? b_marg(S, t, pts[p0 + q0 + qq].a_gr) : alpha_member_ref_arg(S, t, pts[p0 + q0 + qq].a_gr);
+                for (int qq = 0; qq < nq; ++qq) {
+                    if (kStage) {
+                        const double2 v = mcb[(size_t)(q0 + qq) * mc.NC + moff];
+                        const double a = alpha_member_ref_arg(S, t, pts[p0 + q0 + qq].a_gr);
+                        double* const f = X + 3 * qq * kCC + tid;
+                        f[0] = v.x; f[kCC] = v.y; f[2 * kCC] = a;
+                    } else              // (inline: C4 7.42 -> 7.28 ms, r6p; kPP, whose point loop holds
+                        X[(3 + qq) * kCC + tid] =     // the phi-phi term too, as a call: C3 12.33 -> 11.24 ms, r6q)
+                            kPP ? b_marg(S, t, pts[p0 + q0 + qq].a_gr) : alpha_member_ref_arg(S, t, pts[p0 + q0 + qq].a_gr);
+                }
             }
             NUSI_BT();
+            if (kStage) __syncthreads();   // the chunk's member edges and corners written
 #pragma unroll 1
-            for (int qq = 0; qq < nq; qq += kPair) {
+            for (int qq = 0, step = kPair; qq < nq; qq += step) {
                 // (kPair = 2: this half's point of the pair q0 + qq, q0 + qq + 1; an odd batch's last pair leaves
                 // the second half idle, act false -- uniform per wave)
                 const int q = q0 + qq + hq;
                 const bool act = kPair == 1 || q < nb;
                 const Point& Q = pts[p0 + (act ? q : nb - 1)];
                 const double* memb = membq + (qq + hq) * mbd;
+                // (kStage, the full tiles) two: this thread's next point of the chunk, q + kPair, goes through the
+                // combine together with q (alpha_k_two); uniform over the workgroup, and the staged point loop has no
+                // barrier.  The second point's sum of the states < k is loaded in place
+                const bool two = kStage && kPair == 1 && cornered && qq + hq + kPair < nq;
+                step = two ? 2 * kPair : kPair;
                 double tot = tnext;   // after states < k
-                if (reload && q + kPair < nb) tnext = A[(size_t)(p0 + q + kPair) * g.PT + eidx];
-                __syncthreads();   // member edges written / the previous point's combine is done with mem
-                NUSI_BT();
-                if (cornered) {
-                    if (kRef) {
-                        if (moff >= 0) {
-                            const size_t o = (size_t)(q0 + qq) * mc.NC + moff;
-                            X[tid] = mcv.x; X[kCC + tid] = mcv.y;
-                            if (kPair == 2) { mem[tid] = mcv2.x; mem[kCC + tid] = mcv2.y; }
-                            if (q0 + qq + kPair < nb) mcv = mcb[o + kPair * mc.NC];
-                            if (kPair == 2 && q0 + qq + 3 < nb) mcv2 = mcb[o + 3 * mc.NC];
+                double tot2 = two && reload ? A[(size_t)(p0 + q + kPair) * g.PT + eidx] : 0.0;
+                if (reload && q + step < nb) tnext = A[(size_t)(p0 + q + step) * g.PT + eidx];
+                if (!kStage) {
+                    __syncthreads();   // member edges written / the previous point's combine is done with mem
+                    NUSI_BT();
+                    if (cornered) {
+                        if (kRef) {
+                            if (moff >= 0) {
+                                const size_t o = (size_t)(q0 + qq) * mc.NC + moff;
+                                X[tid] = mcv.x; X[kCC + tid] = mcv.y;
+                                if (q0 + qq + 1 < nb) mcv = mcb[o + mc.NC];
+                            }
                         }
+                        else
+                            for (int j = tid; j < cc; j += kTileThreads) alpha_batch_mcorner_job(Q, j, edgk, ct, cs, X, memb, mem);
                     }
-                    else
-                        for (int j = tid; j < cc; j += kTileThreads) alpha_batch_mcorner_job(Q, j, edgk, ct, cs, X, memb, mem);
+                    __syncthreads();   // mem of q written
+                    NUSI_BT();
                 }
-                __syncthreads();   // mem of q written
-                NUSI_BT();
-                int w = 0;
+                int w = 0, w2 = 0;
                 TermRec rec;
                 if (needed && act) {
                     SplitLeavesT<kRef> lv;
                     lv.cf[0] = P3; lv.cf[1] = P3; lv.cf[2] = P3; lv.cf[3] = P3; lv.cf[4] = P3;
                     lv.cf[5] = P3 + kCC; lv.cf[6] = P3 + 2 * kCC;   // (LL, TU1, TU2, G are not read with pre)
-                    lv.corm = kRef && hq == 0 ? X : mem;
+                    lv.corm = kStage ? X + 3 * (qq + hq) * kCC : kRef ? X : mem;
                     lv.cc = cc; lv.ct = ct; lv.cs = cs; lv.mb = lm; lv.nb = ln;
                     lv.sidx[0] = sl[lm]; lv.sidx[1] = sh[lm]; lv.tidx[0] = tl[ln]; lv.tidx[1] = th[ln];
                     lv.ted = edgk; lv.sed = edgk + kTEdgeFields * ct; lv.mbv = lv.sed + kSEdgeFields * cs;
                     lv.tedm = memb; lv.sedm = memb + ct; lv.mbm = memb + ct + 2 * cs;
-                    lv.marg = kRef ? X + (3 + qq + hq) * kCC : memb + ct + 2 * cs + kAlphaTile + 2 * ct;   // sT | fT | sS | fS
+                    lv.marg = kStage ? X + (3 * (qq + hq) + 2) * kCC   // sT | fT | sS | fS:
+                              : kRef ? X + (3 + qq) * kCC : memb + ct + 2 * cs + kAlphaTile + 2 * ct;
                     lv.xl = mix; lv.yl = mix;   // (not read with pre)
-                    if (kSplit)
+                    if (kStage && two) {
+                        SplitLeavesT<kRef> lv2 = lv;   // (the next point's member leaves: kPair fields and rows on)
+                        lv2.corm = lv.corm + 3 * kPair * kCC; lv2.marg = lv.marg + 3 * kPair * kCC;
+                        lv2.tedm = lv.tedm + kPair * mbd; lv2.sedm = lv.sedm + kPair * mbd; lv2.mbm = lv.mbm + kPair * mbd;
+                        alpha_k_two(Q, pts[p0 + q + kPair], k, g.lo[n], g.hi[n], g.lo[m], g.hi[m], lv, lv2, tot, tot2, w, w2, pre);
+                    }
+                    else if (kSplit)
                         alpha_k<SplitLeavesT<kRef>, kPP>(Q, spl, k, g.lo[n], g.hi[n], g.lo[m], g.hi[m], lv, rec, w,
                                                          cornered ? &pre : nullptr, kPP && cornered ? &ppt : nullptr);
                     else
@@ -785,8 +823,12 @@ __device__ __forceinline__ void alpha_batch_body(const GridDev& g, const Point* 
                         for (int j = 0; j < 7; ++j) o[j] = rec.v[j];
                         o[7] = needed ? (double)rec.n : -1.0;
                     }
-                } else if (valid && act) A[(size_t)(p0 + q) * g.PT + eidx] = needed ? tot : 0.0;
+                } else if (valid && act) {
+                    A[(size_t)(p0 + q) * g.PT + eidx] = needed ? tot : 0.0;
+                    if (kStage && two) A[(size_t)(p0 + q + kPair) * g.PT + eidx] = needed ? tot2 : 0.0;
+                }
                 if (w) warn_entry(warn, wmin, T, p0 + q, w, n, m);
+                if (kStage && w2) warn_entry(warn, wmin, T, p0 + q + kPair, w2, n, m);
                 NUSI_BT();
             }
         }

@@ -1563,6 +1563,107 @@ NUSI_FN void alpha_k(const Point& P, const SplineSet& spl, int k, double Em, dou
         warn |= kWarnAlpha;
 }
 
+// Two points a, b of a batch through one entry's combine of mass state k (k_alpha_batch's staged chunks): alpha_k's
+// Majorana, non-resonant path with the batch's shared brackets and no phi-phi channel, each NUSI_PHASE section run for
+// both points before the next fence, so that one point's chain of LDS loads and divisions hides the other's.  la and
+// lb differ in the member pointers only: the leaves the points share are loaded once per section.  Per point the
+// operations of alpha_k in alpha_k's order, so the same bits.
+template <class Lv>
+NUSI_FN void alpha_k_two(const Point& Pa, const Point& Pb, int k, double Em, double Ep, double Emp, double Epp,
+                         const Lv& la, const Lv& lb, double& tota, double& totb, int& warna, int& warnb,
+                         const AlphaPre& pre)
+{
+    struct Pt { double g4, m4, gr, uk, wgt, as, at, atu, ast; };
+    // (t, S' of the entry's edges: leaves of the batch, the same for both points)
+    const double m2a = Pa.mphi * Pa.mphi, mka = Pa.mn[k];
+    const double tp = la.tval(1, mka, Ep, m2a), tm = la.tval(0, mka, Em, m2a);
+    const double Sp = la.Sval(1, mka, Epp, m2a), Sm = la.Sval(0, mka, Emp, m2a);
+    auto head = [&](const Point& P, const Lv& lv, Pt& s, double& tot) {
+        const double g = P.g, mphi = P.mphi;
+        s.g4 = (g * g) * (g * g);
+        s.m4 = (mphi * mphi) * (mphi * mphi);
+        s.gr = P.a_gr;
+        const double gr = s.gr, gr2 = gr * gr;
+        s.uk = P.u[k];
+        s.wgt = P.a_wgt[k];
+        const AlphaMBin mb = lv.mbin(Sm, Sp);
+        double as;
+        if (Sp < 1e-5)
+            as = P.a_s * (tm - tp) *
+                 ((gr * (1 + gr2 + 2 * Sm)) / ((1 + gr2) * (1 + gr2)) * (Sp - Sm) + gr / ((1 + gr2) * (1 + gr2)) * ((Sp - Sm) * (Sp - Sm)));
+        else
+            as = P.a_s * (tm - tp) * mb.atd;
+        as *= s.uk;
+        s.as = as;
+        tot += s.wgt * as;
+    };
+    auto tu = [&](Pt& s, double& tot) {   // alpha_t, alpha_u
+        double at = s.at;
+        at *= s.uk;
+        s.at = at;
+        tot += s.wgt * at;
+        tot += s.wgt * at;
+    };
+    auto tuu = [&](Pt& s, double& tot) {   // alpha_tu (a negative one stays, as in alpha_k)
+        double atu = s.g4 / pre.Dtu * pre.Btu;
+        atu *= s.uk;
+        s.atu = atu;
+        tot += s.wgt * atu;
+    };
+    auto st = [&](const Point& P, const Lv& lv, Pt& s) {   // the s-t interference (alpha_k's third section)
+        const double gr = s.gr;
+        const AlphaCorner cmm = lv.corner(0, 0, Sm, tm), cpm = lv.corner(1, 0, Sp, tm);
+        const AlphaCorner cmq = lv.corner(0, 1, Sm, tp), cpq = lv.corner(1, 1, Sp, tp);
+        const AlphaSEdge fSm = lv.sedge(0, Sm), fSp = lv.sedge(1, Sp);
+        const AlphaTEdge fTm = lv.tedge(0, tm), fTp = lv.tedge(1, tp);
+        const double Lmm = cmm.L, Lpm = cpm.L, Lmq = cmq.L, Lpq = cpq.L;
+        const double lSm = fSm.lS, lSp = fSp.lS, Lmt = fTm.Lm1, Lmp = fTp.Lm1;
+        const double Lsm = fSm.Ls, Lsp = fSp.Ls;
+        const double cm = fTm.cm, cp = fTp.cm;
+        const double L2m = fTm.L2, L2p = fTp.L2;
+        const double am = fTm.am, ap = fTp.am;
+        s.ast = P.a_st *
+                (2 * gr * (cmm.Dri - cmm.Dci - cpm.Dri + cpm.Dci - cmq.Dri + cmq.Dci + cpq.Dri - cpq.Dci)
+                 - 2 * (cmm.Drr - cmm.Dcr - cpm.Drr + cpm.Dcr - cmq.Drr + cmq.Dcr + cpq.Drr - cpq.Dcr)
+                 + 2 * gr * (cm - cmm.A) * Lmm
+                 - 2 * gr * (cm - cpm.A) * Lpm
+                 + 2 * gr * (cp - cpq.A) * Lpq
+                 - 2 * gr * (cp - cmq.A) * Lmq
+                 + 2 * (gr * fSm.cS - gr * fSp.cS + Lsp / 2. - Lsm / 2. + lSm - lSp) * (2 * (tm - tp) + (Lmt - Lmp))
+                 + Lmm * (Lsm - L2m - 2 * (lSm - am)) - Lpm * (Lsp - L2m - 2 * (lSp - am))
+                 - Lmq * (Lsm - L2p - 2 * (lSm - ap)) + Lpq * (Lsp - L2p - 2 * (lSp - ap)));
+    };
+    auto tail = [&](const Point& P, Pt& s, double& tot, int& warn) {
+        double ast = s.ast;
+        ast *= s.uk;
+        tot += s.wgt * ast;
+        tot += s.wgt * ast;   // alpha_su
+        const double app = 0.0;
+        tot += s.wgt * app;
+        const double nrm = P.a_nrm, as = s.as, at = s.at, au = s.at, atu = s.atu;
+        const double sst = ast + as + at;
+        if (as < 0 || ((at < 0 || au < 0 || atu < 0 || sst < 0) &&
+                       (at / nrm < -1e-11 || au / nrm < -1e-11 || atu / nrm < -1e-11 || sst / nrm < -1e-11)))
+            warn |= kWarnAlpha;
+    };
+    Pt a, b;
+    head(Pa, la, a, tota); head(Pb, lb, b, totb);
+    // (the fallback's quadrature reads the entry's t, S' alone: one call serves both points)
+    a.at = a.g4 / pre.Dt * pre.Bt; b.at = b.g4 / pre.Dt * pre.Bt;
+    if (a.at < 0 || b.at < 0) {
+        const double r = gl33_rect(0, tp, tm, Sm, Sp);
+        if (a.at < 0) a.at = r * (a.g4 / (16 * kPi * a.m4));
+        if (b.at < 0) b.at = r * (b.g4 / (16 * kPi * b.m4));
+    }
+    tu(a, tota); tu(b, totb);
+    NUSI_PHASE();
+    tuu(a, tota); tuu(b, totb);
+    NUSI_PHASE();
+    st(Pa, la, a); st(Pb, lb, b);
+    NUSI_PHASE();
+    tail(Pa, a, tota, warna); tail(Pb, b, totb, warnb);
+}
+
 template <bool kRef = false>
 NUSI_FN double alpha_entry(const Point& P, const SplineSet& spl, double Em, double Ep, double Emp, double Epp, int& warn)
 {

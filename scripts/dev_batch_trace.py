@@ -1,7 +1,8 @@
 """Phase timing of the reference-order batch kernel k_alpha_batch[refo] from the diagnostic build's s_memtime stamps
 (NUSI_BT: workgroups x < 4, y < 4, each wave; per mass state its start, the edge leaves' barrier, the shared corners'
-barrier, the brackets' barrier; per chunk of kBatchQC points its start and its member edges + A done; per point its
-two barriers and its combine done):
+barrier, the brackets' barrier; per chunk of kStageQC = 4 points its start and its member edges + staged corners
+done; per iteration of the point loop -- two points, the last of an odd chunk one; the first includes the wait at the
+chunk's staging barrier -- its combine done):
   bash scripts/build_variant.sh btrace -DNUSI_BATCH_TRACE
   NUSIPROP_LIB=build/variants/libnusi_btrace.so python scripts/dev_batch_trace.py
 Prints the median cycles of each phase over the traced waves and mass states."""
@@ -16,7 +17,7 @@ import numpy as np  # noqa: E402
 import nusiprop_amd as nu  # noqa: E402
 from nusiprop_amd import _lib, scan  # noqa: E402
 
-WG, WV, N, QC = 16, 4, 512, 5
+WG, WV, N, QC = 16, 4, 512, 4
 
 
 def main():
@@ -32,8 +33,9 @@ def main():
     a = np.frombuffer(buf, dtype=np.uint64).reshape(WG, WV, N).astype(np.int64)
     nb = 32   # C4: 32 couplings per m_phi (one batch)
     chunks = [min(QC, nb - q0) for q0 in range(0, nb, QC)]
-    per_k = 4 + 2 * len(chunks) + 3 * nb
-    ph = {k: [] for k in ("edge", "corners", "brackets", "chunk_setup", "chunk_medge_A", "pt_barrier1", "pt_xwrite_barrier2",
+    iters = [(nq + 1) // 2 for nq in chunks]
+    per_k = 4 + 2 * len(chunks) + sum(iters)
+    ph = {k: [] for k in ("edge", "corners", "brackets", "chunk_setup", "chunk_medge_A",
                           "pt_combine", "k_total", "wg_total")}
     for w in range(WG):
         for v in range(WV):
@@ -48,17 +50,15 @@ def main():
                 ph["brackets"].append(s[b + 3] - s[b + 2])
                 i = b + 4
                 prev = s[b + 3]
-                for nq in chunks:
+                for nit in iters:
                     ph["chunk_setup"].append(s[i] - prev)
                     ph["chunk_medge_A"].append(s[i + 1] - s[i])
                     prev = s[i + 1]
                     i += 2
-                    for _ in range(nq):
-                        ph["pt_barrier1"].append(s[i] - prev)
-                        ph["pt_xwrite_barrier2"].append(s[i + 1] - s[i])
-                        ph["pt_combine"].append(s[i + 2] - s[i + 1])
-                        prev = s[i + 2]
-                        i += 3
+                    for _ in range(nit):
+                        ph["pt_combine"].append(s[i] - prev)
+                        prev = s[i]
+                        i += 1
                 ph["k_total"].append(prev - s[b])
     print("traced waves: %d" % len(ph["wg_total"]))
     tot = np.median(ph["k_total"]) * 3
@@ -67,7 +67,7 @@ def main():
             continue
         x = np.array(x)
         n_per_k = {"edge": 1, "corners": 1, "brackets": 1, "chunk_setup": len(chunks), "chunk_medge_A": len(chunks),
-                   "pt_barrier1": nb, "pt_xwrite_barrier2": nb, "pt_combine": nb, "k_total": 1}.get(k)
+                   "pt_combine": sum(iters), "k_total": 1}.get(k)
         share = "" if n_per_k is None else "  ~%4.1f %% of a workgroup" % (100.0 * np.mean(x) * n_per_k * 3 / tot)
         print("%-20s median %8.0f  mean %8.0f  p90 %8.0f cycles%s" % (k, np.median(x), x.mean(), np.quantile(x, 0.9), share))
 
