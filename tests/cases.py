@@ -52,6 +52,43 @@ def scan_points(n_mphi=32, n_g=32, si=2.5, lEmin=12.0, lEmax=17.0, N=300, mphi_r
     return pts
 
 
+# Mixed and edge batches of the alpha batch kernel (tests/test_alpha_batch_mixed_gpu.py, the alpha_k_two host check
+# in tests/test_hostcheck_tables.py).  Grid N_E = 45, lE 12 -> 12.75 (T = 91: full, diagonal and paired tiles), power-law
+# source; couplings from logspace(-3, 0, 9) by index.  The points of one group share (phi-phi, m_phi, masses, majorana,
+# non_resonant) -- alpha_batches()'s key -- and so form one batch; A .. E share m_phi, only masses and flags keep them
+# apart.  Not in SMALL_CASES: group E's neighbours in g have a NaN oracle flux.
+MIXED_GRID = (45, 12.0, 12.75)
+MIXED_M1, MIXED_M2 = 10 ** 6.5, 1e8
+MIXED_G9 = np.logspace(-3, 0, 9)
+
+
+def mixed_batch_groups():
+    """{group: [points]} -- A: Majorana, NO, mntot 0.1, five couplings, flavour, si and norm varying with the point;
+    B: Dirac, the last six couplings (g = 1 among them: warnings 0, .., 0, 2); C: inverted ordering, mntot 0.2;
+    D / Dp: Majorana / Dirac resonant-only; E: Majorana with a nearly massless lightest state (mntot = MSUM_MIN_NO:
+    state 0 takes the S'+ < 1e-5 Taylor branch everywhere, ~1020 negative alpha entries per table), the five smallest
+    couplings (warnings 3, 3, 1, 1, 3) -- at indices 5, 6, 7 (g = 0.075, 0.178, 0.422) the oracle's own flux is NaN
+    (Gamma goes negative), at index 8 (g = 1) it is finite but has diverged to -1.6e268; F: Majorana, mntot 0.06,
+    m_phi = 1e8, the couplings from index 2 on (warnings 1, 1, 1, 1, 0, 0, 0)."""
+    N, lo, hi = MIXED_GRID
+    base = scan_points(n_mphi=1, n_g=1, N=N, lEmin=lo, lEmax=hi)[0]
+
+    def grp(idx, **over):
+        return [dict(base, mphi=MIXED_M1, g=float(MIXED_G9[i]), **over) for i in idx]
+    A = grp([0, 2, 4, 6, 8])
+    for k, p in enumerate(A):
+        p.update(flav=(0, 1, 2, 0, 1)[k], si=(2.0, 2.25, 2.5, 2.75, 3.0)[k], norm=(1.0, 6.0, 0.5, 2.0, 1.0)[k])
+    return {
+        "A": A,
+        "B": grp(range(3, 9), majorana=False),
+        "C": grp([1, 3, 5, 7], mntot=0.2, normal_ordering=False),
+        "D": grp([0, 4, 8], non_resonant=False),
+        "Dp": grp([2, 5, 7], non_resonant=False, majorana=False),
+        "E": grp(range(0, 5), mntot=MSUM_MIN_NO),
+        "F": [dict(p, mphi=MIXED_M2) for p in grp(range(2, 9), mntot=0.06)],
+    }
+
+
 # GPU fluxes vs the oracle (north-star bound 1e-9).  The cascade sums in a different order
 # (right-looking pushes, multiplied reciprocals, power-law source powers shared along table
 # edges): <= 2e-12 observed up to N_E = 1200.

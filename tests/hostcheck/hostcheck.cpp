@@ -223,6 +223,39 @@ int hc_alpha_tiled_ref(const double* pt, const int* flags, int T, const double* 
     return alpha_tiled_t<true>(pt, flags, T, lo, hi, A);
 }
 
+// Host run of alpha_k_two (k_alpha_batch's staged chunks, two points of a batch per thread): points a and b with one
+// set of flags and masses (Majorana, non-resonant: the only path alpha_k_two has), the leaves evaluated on the spot
+// as alpha_entry<true> builds them, the batch's shared brackets formed once FROM a'S LEAVES (the kernel forms them
+// from the batch's first point pts[p0]) and handed to both.  Aa, Ab: dense T*T, m > n; wa, wb: the warning words.
+// Returns the number of (entry, k) at which the shared fallback a.at < 0 || b.at < 0 fired (one gl33_rect call
+// serving both points).
+int hc_alpha_two_ref(const double* pta, const double* ptb, const int* flags, int T, const double* lo, const double* hi,
+                     double* Aa, double* Ab, int* wa, int* wb)
+{
+    using namespace nusi;
+    const Point Pa = mk(pta, flags), Pb = mk(ptb, flags);
+    if (!(Pa.majorana && Pa.non_resonant) || Pa.phiphi) return -1;
+    const DirectLeavesT<true> la{Pa.Ga / Pa.mphi, (Pa.Ga / Pa.mphi) * (Pa.Ga / Pa.mphi), Pa.mphi, Pa.Ga};
+    const DirectLeavesT<true> lb{Pb.Ga / Pb.mphi, (Pb.Ga / Pb.mphi) * (Pb.Ga / Pb.mphi), Pb.mphi, Pb.Ga};
+    const double g4a = (Pa.g * Pa.g) * (Pa.g * Pa.g), g4b = (Pb.g * Pb.g) * (Pb.g * Pb.g);
+    int fallbacks = 0;
+    *wa = 0;
+    *wb = 0;
+    for (int n = 0; n < T; ++n)
+        for (int m = n + 1; m < T; ++m) {
+            double ta = 0, tb = 0;
+            for (int k = 0; k < 3; ++k) {
+                AlphaPre pre{};
+                alpha_k_pre(Pa, k, lo[n], hi[n], lo[m], hi[m], la, pre);
+                if (g4a / pre.Dt * pre.Bt < 0 || g4b / pre.Dt * pre.Bt < 0) ++fallbacks;
+                alpha_k_two(Pa, Pb, k, lo[n], hi[n], lo[m], hi[m], la, lb, ta, tb, *wa, *wb, pre);
+            }
+            Aa[(size_t)n * T + m] = ta;
+            Ab[(size_t)n * T + m] = tb;
+        }
+    return fallbacks;
+}
+
 double hc_lum(const double* pt, const int* flags, double z, double sfr_z, double Em, double Ep)
 {
     return nusi::lum(mk(pt, flags), z, sfr_z, Em, Ep);

@@ -124,6 +124,77 @@ def test_reference_order_tables_bit_identical(oracle_mod, name):
             assert np.any(al0[iu] != al[iu])
 
 
+def _two_pairs():
+    """(a, b) of one batch -- the same m_phi, masses and flags; Majorana, non-resonant -- on N_E = 31 of the mixed
+    batches' grid"""
+    _, lo, hi = cases.MIXED_GRID
+    g = cases.mixed_batch_groups()
+    A = [dict(p, N_bins_E=31, lEmin=lo, lEmax=hi, flav=2, si=2.5, norm=1.0) for p in g["A"]]
+    E = [dict(p, N_bins_E=31, lEmin=lo, lEmax=hi) for p in g["E"]]
+    return {
+        "g": (A[2], A[3]),
+        "flav": (A[2], dict(A[2], flav=0)),
+        "g_flav_si_norm": (A[1], dict(A[4], flav=1, si=2.0, norm=6.0)),
+        "same": (A[3], A[3]),
+        "massless_lightest": (E[2], E[4]),
+    }
+
+
+TWO_PAIRS = ["g", "flav", "g_flav_si_norm", "same", "massless_lightest"]
+_two_cache = {}
+
+
+def _two_run(oracle_mod, pair):
+    """hc_alpha_two_ref on the pair, once: (Aa, Ab, wa, wb, fallbacks, oracle alpha of a, of b, oracle warnings)"""
+    if pair not in _two_cache:
+        from tests.hostcheck import build_hostcheck
+        H = build_hostcheck()
+        a, b = _two_pairs()[pair]
+        tabs, warn, pts = [], [], []
+        for kw in (a, b):
+            o = oracle_mod.Oracle(**cases.oracle_kwargs(kw))
+            with oracle_mod.reference_order(1):
+                tabs.append(o.tables()[2])
+            warn.append(o.warnings())
+            pts.append(point_array(o, kw))
+            lo, hi = extended_axis(o)
+            T = o.T
+        assert list(pts[0][1]) == list(pts[1][1]) and np.array_equal(pts[0][0][7:10], pts[1][0][7:10])   # one batch
+        Aa, Ab = np.zeros((T, T)), np.zeros((T, T))
+        wa, wb = ctypes.c_int(-1), ctypes.c_int(-1)
+        H.hc_alpha_two_ref.restype = ctypes.c_int
+        nf = H.hc_alpha_two_ref(_dp(pts[0][0]), _dp(pts[1][0]), pts[0][1], T, _dp(lo), _dp(hi), _dp(Aa), _dp(Ab),
+                                ctypes.byref(wa), ctypes.byref(wb))
+        _two_cache[pair] = (Aa, Ab, wa.value, wb.value, nf, tabs[0], tabs[1], warn)
+    return _two_cache[pair]
+
+
+@pytest.mark.parametrize("pair", TWO_PAIRS)
+def test_alpha_k_two_bit_identical(oracle_mod, pair):
+    """alpha_k_two (k_alpha_batch's staged chunks: two points of a batch through one entry's combine, the batch's
+    shared brackets formed from ANOTHER point's leaves -- here from a's, for both) on the host, leaves evaluated on the
+    spot: both tables against the reference-order oracle's alpha of a and of b bit for bit, both warning words'
+    kWarnAlpha bit against the oracle's (the predicate: on the GPU no scanned batch raises it, so the routing of the
+    second point's word is pinned nowhere else).  The pairs differ in g, in the flavour row, in both (and si, norm),
+    not at all, and one pair has the nearly massless lightest state of cases.mixed_batch_groups()'s group E (the
+    Taylor branch of alpha_s, negative entries)."""
+    Aa, Ab, wa, wb, nf, ala, alb, warn = _two_run(oracle_mod, pair)
+    assert nf >= 0
+    iu = np.triu_indices(Aa.shape[0], 1)
+    assert np.array_equal(Aa[iu], ala[iu]), "a: %d alpha entries differ" % np.sum(Aa[iu] != ala[iu])
+    assert np.array_equal(Ab[iu], alb[iu]), "b: %d alpha entries differ" % np.sum(Ab[iu] != alb[iu])
+    assert (wa & 4) == (warn[0] & 4) and (wb & 4) == (warn[1] & 4)
+    assert (wa & ~4) == 0 and (wb & ~4) == 0   # (alpha_k_two raises no other bit)
+
+
+def test_alpha_k_two_fallback_fired(oracle_mod):
+    """At least one of the pairs reaches alpha_k_two's shared fallback (a.at < 0 || b.at < 0: one gl33_rect
+    quadrature serving both points); without it that call is not exercised.  (The massless-lightest pair takes it at
+    908 (entry, k); the mntot = 0.1 pairs never do.)"""
+    nf = {pair: _two_run(oracle_mod, pair)[4] for pair in TWO_PAIRS}
+    assert max(nf.values()) > 0, nf
+
+
 @pytest.mark.parametrize("parts", [1, 2])
 @pytest.mark.parametrize("ref", [0, 1])
 @pytest.mark.parametrize("name", sorted(cases.SMALL_CASES))
