@@ -31,9 +31,17 @@
 //     functions against the oracle's divisions).  GSL's (k - 1)/k squared of series_1 is a table of the same values;
 //   * both rewrites need their operands in the normal range; a series whose argument is below 2^-400 (which the
 //     tables never meet) runs a second instance of its loop with GSL's divisions (kExact), so the loops have no
-//     per-iteration branch.
+//     per-iteration branch;
+//   * the member-corner kernel's inline instance (kW = true; kW = false is the code above, out of line) takes its
+//     divisions from nusi_div.hpp -- one refined reciprocal per divisor, without the division's scale and fixup
+//     instructions.  kW's contract, the *member window*: every active lane's argument of gsl_cli2_t is finite and
+//     nonzero with |x|, |y| in [2^-201, 2^100]; alpha_member_ref_dc_inl votes it per wave on Smith's operands, and a
+//     wave that fails it calls the out-of-line gsl_cli2.  What follows from the window is written at each division;
+//     three numerators that it does not bound (hypot's residual, t_x's and t_y's) take a vote of their own.  The
+//     host build divides with / throughout.
 #pragma once
 
+#include "nusi_div.hpp"
 #include "nusi_libm.hpp"
 
 // The elementary functions inside the GSL functions are inline (each call from an out-of-line function costs the
@@ -104,11 +112,22 @@ NUSI_FN bool quot_lt(double a, double b, double c)
 
 // hypot(x, y) (libm; dilogc_unitdisk): sqrt(a^2 + b^2) and one correction step from the exact residual
 // (oracle/ora_gsl.c ora_hypot)
+// kW: the caller bounds every active lane's operands, 2^-500 <= |x|, |y| <= 2^+100 (or the smaller one 0) -- the common
+// case without its vote, and the correction r / (2 h) by nm::div_v when every lane's r is at least 2^-900 (|r| <=
+// 2^-51 h^2, h in [2^-500, 2^101]: the numerator above 2^-969, the quotient normal, the exponents less than 768 apart)
+template <bool kW = false>
 NUSI_FN double hypot(double x, double y)
 {
     double a = fabs(x), b = fabs(y);
     if (a < b) { const double t = a; a = b; b = t; }
 #ifdef __HIP_DEVICE_COMPILE__
+    if (kW) {
+        const double a2 = a * a, ea = fma(a, a, -a2), b2 = b * b, eb = fma(b, b, -b2);
+        double h = sqrt(a2 + b2);
+        const double h2 = h * h, eh = fma(h, h, -h2);
+        const double r = ((a2 - h2) + b2) + ((ea + eb) - eh);
+        return h + nm::div_v(nm::div_vote(fabs(r) >= 0x1p-900), r, 2.0 * h);
+    }
     // the common case (2^-500 <= b <= a <= 2^500) voted once per wave: the same operations without the scaling
     // branches, whose exec masks stayed live in SGPRs
     if (__all(b >= 0x1p-500 && a <= 0x1p+500)) {
@@ -130,6 +149,11 @@ NUSI_FN double hypot(double x, double y)
     h = h + r / (2.0 * h);
     return h * s;
 }
+
+// atan2 of the member window's instance (kW; the sites' operands are within atan2_w's bounds by the window's), else
+// the inline atan2
+template <bool kW>
+NUSI_FN double atan2_t(double y, double x) { return kW ? nm::atan2_w(y, x) : GSL_ATAN2(y, x); }
 
 // Wave-uniform votes for the series' first loops (below): every active lane's predicate / any active lane's.  On the
 // host (tests/hostcheck) a "wave" is the one call.
@@ -334,17 +358,24 @@ NUSI_FN_OUT double clausen(double x)
 // sk^2)^(1/2) with q = RN(r^k / d_k) and the rotated (ck, sk) of modulus 1 to ~1e-13 (<= 1000 rotations); so while q
 // >= 2^-50 r (2.4 times the bound's 1.645 2^-52 r) the test is false, and the loop runs without it until the first
 // term below, whose test is GSL's test at that k (the values are unchanged: the same terms, the same break).
-template <bool kExact, int kS2>
+//
+// kW (the member window, header comment; fundamental_body's bounds): |x|, |y| in [2^-403, 2^1] (x possibly +0) and r in
+// [2^-400, 0.98], so x / r and y / r share r's reciprocal (numerators above 2^-969, exponents at most 403 apart), and
+// -log r in [0.02, 278] divides the constant of kmax
+template <bool kExact, int kS2, bool kW = false>
 NUSI_FN void cseries_t(bool s2, double r, double lr, double x, double y, double& re, double& im)
 {
     const bool t2 = kS2 == 2 ? s2 : kS2 == 1;
-    const double cos_theta = x / r, sin_theta = y / r;
+    double cos_theta, sin_theta;
+    if (kW) nm::div2_v(true, x, y, r, cos_theta, sin_theta);
+    else { cos_theta = x / r; sin_theta = y / r; }
     const double alpha = 1.0 - cos_theta, beta = sin_theta;
     double ck = cos_theta, sk = sin_theta, rk = r;
     double real_sum = t2 ? 0.5 * r * ck : r * ck;
     double imag_sum = t2 ? 0.5 * r * sk : r * sk;
     const double nlr = -lr;   // -log(r)
-    const int kmax = (t2 ? 30 : 50) + (int)((t2 ? 18.0 : 22.0) / nlr);   // (one division for a wave of both series)
+    const double kq = kW ? nm::div_v(true, t2 ? 18.0 : 22.0, nlr) : (t2 ? 18.0 : 22.0) / nlr;
+    const int kmax = (t2 ? 30 : 50) + (int)kq;   // (one division for a wave of both series)
     KRow next = kKT.row[2];   // (the table row of the next iteration is loaded one iteration ahead; kmax <= 921)
     // kS2 == 2 (a wave of both series): each lane loads its own columns of the row (vector loads at its t2 offset from
     // the row's uniform address) instead of selecting between the scalar row's columns -- three 64-bit selects a term
@@ -421,6 +452,7 @@ NUSI_FN void cseries_t(bool s2, double r, double lr, double x, double y, double&
 }
 // (the terms r^k stay above 2^-960 and |sum|^2 above 2^-900 unless r < 2^-400: the series breaks at a term
 // below 2^-52 of the sum, and kmax bounds r^k for larger r)
+template <bool kW = false>
 NUSI_FN void cseries(bool s2, double r, double lr, double x, double y, double& re, double& im)
 {
     if (r < 0x1p-400) {
@@ -429,11 +461,11 @@ NUSI_FN void cseries(bool s2, double r, double lr, double x, double y, double& r
     }
 #ifdef __HIP_DEVICE_COMPILE__
     const unsigned long long act = __ballot(1), two = __ballot(s2);
-    if (two == act) cseries_t<false, 1>(s2, r, lr, x, y, re, im);
-    else if (two == 0) cseries_t<false, 0>(s2, r, lr, x, y, re, im);
-    else cseries_t<false, 2>(s2, r, lr, x, y, re, im);
+    if (two == act) cseries_t<false, 1, kW>(s2, r, lr, x, y, re, im);
+    else if (two == 0) cseries_t<false, 0, kW>(s2, r, lr, x, y, re, im);
+    else cseries_t<false, 2, kW>(s2, r, lr, x, y, re, im);
 #else
-    cseries_t<false, 2>(s2, r, lr, x, y, re, im);
+    cseries_t<false, 2, kW>(s2, r, lr, x, y, re, im);
 #endif
 }
 // dilogc_series_3: |z| near 1, sum_{n <= 6} (log r)^n / n! H_n(theta)
@@ -473,6 +505,12 @@ NUSI_FN void cseries_3(double r, double lr, double x, double y, double& re, doub
 // dilogc_fundamental (r < 1, x <= 0.732): series_3 above r = 0.98, dilogc_series_2 above 0.25, else series_1.  Every
 // branch takes log(r) (series_3's expansion variable, the series' kmax): formed once, and returned in lr for
 // unitdisk's log(1 - z) of a reflected argument (the same call on the same value)
+//
+// kW (the member window; unitdisk's bounds): |x|, |y| in [2^-403, 2^1] (x possibly +0), x <= 0.732, r their hypot.  Then in
+// the series_2 correction (lanes with 0.25 < r <= 0.98) 1 - x is in [0.268, 2], so mx is too and mn in [2^-403, 2]:
+// mn / mx needs no vote; the numerators of t_x and t_y, at most 5 in modulus, can cancel to anything, so their pair
+// over r^2 in (2^-4, 1) takes a vote of its own (both at least 2^-700)
+template <bool kW = false>
 NUSI_FN cd fundamental_body(double r, double x, double y, double& lr)
 {
     double re, im;
@@ -482,24 +520,38 @@ NUSI_FN cd fundamental_body(double r, double x, double y, double& lr)
         return cd{re, im};
     }
     const bool s2 = r > 0.25;
-    cseries(s2, r, lr, x, y, re, im);
+    cseries<kW>(s2, r, lr, x, y, re, im);
     if (!s2) return cd{re, im};
     // dilogc_series_2: + (1 - z) log(1 - z) / z + 1, log(1 - z) by gsl_sf_complex_log_e
     const double zr = 1.0 - x, zi = -y;
     const double ax = fabs(zr), ay = fabs(zi);
     const double mn = ax < ay ? ax : ay, mx = ax > ay ? ax : ay;
-    const double ln_r = GSL_LOG(mx) + 0.5 * GSL_LOG(1.0 + (mn / mx) * (mn / mx));
-    const double ln_t = GSL_ATAN2(zi, zr);
-    const double t_x = (ln_r * x + ln_t * y) / (r * r);
-    const double t_y = (-ln_r * y + ln_t * x) / (r * r);
+    double t_x, t_y, ln_r, ln_t;
+    if (kW) {
+        const double mq = nm::div_v(true, mn, mx);
+        ln_r = GSL_LOG(mx) + 0.5 * GSL_LOG(1.0 + mq * mq);
+        ln_t = nm::atan2_w(zi, zr);   // (zi = -y, zr in [0.268, 2])
+        const double n_x = ln_r * x + ln_t * y, n_y = -ln_r * y + ln_t * x;
+        const bool wt = nm::div_vote(fabs(n_x) >= 0x1p-700 && fabs(n_y) >= 0x1p-700);
+        nm::div2_v(wt, n_x, n_y, r * r, t_x, t_y);
+    } else {
+        ln_r = GSL_LOG(mx) + 0.5 * GSL_LOG(1.0 + (mn / mx) * (mn / mx));
+        ln_t = GSL_ATAN2(zi, zr);
+        t_x = (ln_r * x + ln_t * y) / (r * r);
+        t_y = (-ln_r * y + ln_t * x) / (r * r);
+    }
     const double r_x = (1.0 - x) * t_x + y * t_y;
     const double r_y = (1.0 - x) * t_y - y * t_x;
     return cd{re + r_x + 1.0, im + r_y};
 }
 NUSI_FN_OUT cd fundamental(double r, double x, double y, double& lr) { return fundamental_body(r, x, y, lr); }
-// dilogc_unitdisk: |z| < 1; x > 0.732 reflected, Li2(z) = -Li2(1 - z) + zeta2 - log(z) log(1 - z).  kInl: fundamental
+// dilogc_unitdisk: |z| < 1; x > 0.732 reflected, Li2(z) = -Li2(1 - z) + zeta2 - log(z) log(1 - z).  kW: fundamental
 // inline (the member-corner kernel's single call site, gsl_cli2_inl), else the out-of-line instance
-template <bool kInl = false>
+//
+// kW (the member window): the unit-disk argument has |x|, |y| in [2^-403, 2^1] nonzero (gsl_cli2_t), and so has the
+// fundamental region's: a reflected 1 - x is at least 2^-53, or +0 (never -0) -- for which hypot's residual is 0 (its
+// own vote) and the series' +0 / r comes out +0 by the short sequence too (q = +0, residual +0)
+template <bool kW = false>
 NUSI_FN cd unitdisk(double x, double y)
 {
     const double zeta2 = kPiD * kPiD / 6.0;
@@ -508,13 +560,13 @@ NUSI_FN cd unitdisk(double x, double y)
     // the fundamental region's argument and its modulus: one hypot call site (GSL forms |z| and, reflected,
     // |1 - z|); |z| of a reflected argument after the call
     const double fx = refl ? x_tmp : x, fy = refl ? y_tmp : y;
-    const double rf = gsl::hypot(fx, fy);
+    const double rf = gsl::hypot<kW>(fx, fy);
     double lr;
-    const cd f = kInl ? fundamental_body(rf, fx, fy, lr) : fundamental(rf, fx, fy, lr);   // one call site
+    const cd f = kW ? fundamental_body<true>(rf, fx, fy, lr) : fundamental(rf, fx, fy, lr);   // one call site
     if (!refl) return f;
-    const double r = gsl::hypot(x, y);
+    const double r = gsl::hypot<kW>(x, y);
     const double lnz = GSL_LOG(r), lnomz = lr;   // log(r_tmp)
-    const double argz = GSL_ATAN2(y, x), argomz = GSL_ATAN2(y_tmp, x_tmp);
+    const double argz = atan2_t<kW>(y, x), argomz = atan2_t<kW>(y_tmp, x_tmp);   // (kW: x_tmp >= 2^-53, or +0)
     return cd{-f.r + zeta2 - lnz * lnomz + argz * argomz, -f.i - argz * lnomz - argomz * lnz};
 }
 
@@ -553,7 +605,12 @@ NUSI_FN cd gsl_cli2_real(double x) { return cd{gsl_li2(x), (x >= 1.0) ? -gsl::kP
 // whole call inline -- the member-corner kernel's one call site, where the call boundaries' argument moves, SGPR
 // lane spills and callee-saved register traffic were VALU work of their own; gsl_cli2 the out-of-line instance the
 // table kernels call from many sites
-template <bool kInl>
+//
+// kW (the member window): |x|, |y| in [2^-201, 2^100] nonzero, so r2 is in [2^-402, 2^201], and on an inverted
+// lane (r2 >= 1) x / r2 and -y / r2 share r2's reciprocal (numerators above 2^-969, exponents at most 402 apart,
+// quotients in [2^-403, 2^1]): the pair runs under the lanes' inv mask, not at all in a wave without an
+// inverted lane
+template <bool kW>
 NUSI_FN cd gsl_cli2_t(double x, double y)
 {
     const double zeta2 = gsl::kPiD * gsl::kPiD / 6.0;
@@ -565,10 +622,17 @@ NUSI_FN cd gsl_cli2_t(double x, double y)
         return cd{zeta2 + term1 - term2, gsl::clausen(theta)};
     }
     const bool inv = !(r2 < 1.0);
-    const cd u = gsl::unitdisk<kInl>(inv ? x / r2 : x, inv ? -y / r2 : y);   // one instance
+    cd u;
+    if (kW) {
+        double ux = x, uy = y;
+        if (inv) nm::div2_v(true, x, -y, r2, ux, uy);
+        u = gsl::unitdisk<true>(ux, uy);   // one instance
+    } else {
+        u = gsl::unitdisk<false>(inv ? x / r2 : x, inv ? -y / r2 : y);   // one instance
+    }
     if (!inv) return u;
     const double r = sqrt(r2);
-    const double theta = GSL_ATAN2(y, x), theta_abs = fabs(theta), theta_sgn = (theta < 0.0 ? -1.0 : 1.0);
+    const double theta = gsl::atan2_t<kW>(y, x), theta_abs = fabs(theta), theta_sgn = (theta < 0.0 ? -1.0 : 1.0);
     const double ln_minusz_re = GSL_LOG(r), ln_minusz_im = theta_sgn * (theta_abs - gsl::kPiD);
     const double lmz2_re = ln_minusz_re * ln_minusz_re - ln_minusz_im * ln_minusz_im;
     const double lmz2_im = 2.0 * ln_minusz_re * ln_minusz_im;
@@ -576,6 +640,7 @@ NUSI_FN cd gsl_cli2_t(double x, double y)
 }
 
 NUSI_FN_OUT cd gsl_cli2(double x, double y) { return gsl_cli2_t<false>(x, y); }
-NUSI_FN cd gsl_cli2_inl(double x, double y) { return gsl_cli2_t<true>(x, y); }   // (the member-corner kernel's call)
+// (the member-corner kernel's call; every lane of the wave is inside the member window, voted by the caller)
+NUSI_FN cd gsl_cli2_inl(double x, double y) { return gsl_cli2_t<true>(x, y); }
 
 }  // namespace nusi

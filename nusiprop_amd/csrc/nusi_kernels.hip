@@ -1082,7 +1082,98 @@ hipError_t launch_alpha(const GridDev& g, const Point* pts, int npts, const Spli
                                  mc);
 }
 
+// Test only (tests/test_div_shared_gpu.py): nusi_div.hpp's device path on arrays of operands -- element i is lane
+// i % 64 of wave i / 64.  q0, q1: div_shared2(a0, a1, b); s: div_shared(a0, b); p0, p1: the device's a0 / b, a1 / b;
+// fast: whether the element's wave voted the pair onto the short sequence
+__global__ __launch_bounds__(256) void k_debug_div_shared(const double* __restrict__ a0, const double* __restrict__ a1,
+                                                          const double* __restrict__ b, int n, double* __restrict__ q0,
+                                                          double* __restrict__ q1, double* __restrict__ s,
+                                                          double* __restrict__ p0, double* __restrict__ p1,
+                                                          int* __restrict__ fast)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x0 = a0[i], x1 = a1[i], d = b[i];
+    double r0, r1;
+    nm::div_shared2(x0, x1, d, r0, r1);
+    q0[i] = r0;
+    q1[i] = r1;
+    s[i] = nm::div_shared(x0, d);
+    p0[i] = x0 / d;
+    p1[i] = x1 / d;
+    fast[i] = nm::div_vote(nm::div_in_window(x0) && nm::div_in_window(x1) && nm::div_in_window(d)) ? 1 : 0;
+}
+
+// forced = 1: the short sequence without a vote, div2_v(true, ..) and div_v(true, ..), as k_alpha_mcorner's call chain
+// runs it on operands its callers bound themselves (fast: 1 everywhere)
+__global__ __launch_bounds__(256) void k_debug_div_forced(const double* __restrict__ a0, const double* __restrict__ a1,
+                                                          const double* __restrict__ b, int n, double* __restrict__ q0,
+                                                          double* __restrict__ q1, double* __restrict__ s,
+                                                          double* __restrict__ p0, double* __restrict__ p1,
+                                                          int* __restrict__ fast)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x0 = a0[i], x1 = a1[i], d = b[i];
+    double r0, r1;
+    nm::div2_v(true, x0, x1, d, r0, r1);
+    q0[i] = r0;
+    q1[i] = r1;
+    s[i] = nm::div_v(true, x0, d);
+    p0[i] = x0 / d;
+    p1[i] = x1 / d;
+    fast[i] = 1;
+}
+
 }  // namespace nusi
+
+// Test only, not declared in nusi.h: host arrays of n operands through k_debug_div_shared (forced = 0) or
+// k_debug_div_forced (forced = 1) on the current device
+static int debug_div(int forced, const double* a0, const double* a1, const double* b, int n, double* q0, double* q1,
+                     double* s, double* p0, double* p1, int* fast);
+extern "C" int nusi_debug_div_shared(const double* a0, const double* a1, const double* b, int n, double* q0, double* q1,
+                                     double* s, double* p0, double* p1, int* fast)
+{
+    return debug_div(0, a0, a1, b, n, q0, q1, s, p0, p1, fast);
+}
+extern "C" int nusi_debug_div_forced(const double* a0, const double* a1, const double* b, int n, double* q0, double* q1,
+                                     double* s, double* p0, double* p1, int* fast)
+{
+    return debug_div(1, a0, a1, b, n, q0, q1, s, p0, p1, fast);
+}
+static int debug_div(int forced, const double* a0, const double* a1, const double* b, int n, double* q0, double* q1,
+                     double* s, double* p0, double* p1, int* fast)
+{
+    if (n <= 0) return -1;
+    const size_t nb = sizeof(double) * (size_t)n;
+    double* d = nullptr;
+    int* f = nullptr;
+    if (hipMalloc(&d, 8 * nb) != hipSuccess) return -2;
+    if (hipMalloc(&f, sizeof(int) * (size_t)n) != hipSuccess) {
+        hipFree(d);
+        return -2;
+    }
+    bool ok = hipMemcpy(d, a0, nb, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + n, a1, nb, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + 2 * (size_t)n, b, nb, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        const size_t N = (size_t)n;
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (forced)
+            hipLaunchKernelGGL(nusi::k_debug_div_forced, grid, dim3(256), 0, 0, d, d + N, d + 2 * N, n, d + 3 * N,
+                               d + 4 * N, d + 5 * N, d + 6 * N, d + 7 * N, f);
+        else
+            hipLaunchKernelGGL(nusi::k_debug_div_shared, grid, dim3(256), 0, 0, d, d + N, d + 2 * N, n, d + 3 * N,
+                               d + 4 * N, d + 5 * N, d + 6 * N, d + 7 * N, f);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    }
+    double* const out[5] = {q0, q1, s, p0, p1};
+    for (int j = 0; ok && j < 5; ++j) ok = hipMemcpy(out[j], d + (3 + j) * (size_t)n, nb, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(fast, f, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
+    hipFree(d);
+    hipFree(f);
+    return ok ? 0 : -5;
+}
 
 #ifdef NUSI_BATCH_TRACE
 // diagnostic build: the batch kernel's phase stamps of the latest launch, [workgroup][wave][stamp]

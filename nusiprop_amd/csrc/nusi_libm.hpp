@@ -27,6 +27,7 @@
 // per 1024-point step measured).
 #define NUSI_LM __host__ __device__ inline __attribute__((noinline))
 
+#include "nusi_div.hpp"
 #include "nusi_logtab.hpp"
 
 namespace nusi {
@@ -276,19 +277,23 @@ NUSI_FN bool atan2_plain(double y, double x)
     return ix < 0x7ff00000 && iy < 0x7ff00000 && ((unsigned)ix | low(x)) != 0u && ((unsigned)iy | low(y)) != 0u &&
            !(hx == 0x3ff00000 && low(x) == 0u) && k <= 60 && k >= -60;
 }
-NUSI_FN double atan2_sel(double y, double x)
+// kW (atan2_w below): the two divisions by nusi_div.hpp's short sequence.  The caller's bounds put y / x inside its
+// conditions; num is nonzero and at least 2^-61 in modulus, or the +0 of an exact difference (never -0), which the
+// short sequence divides by den >= 1 to +0 as the division does
+template <bool kW>
+NUSI_FN double atan2_sel_t(double y, double x)
 {
     constexpr double pi = 3.1415926535897931160E+00, pi_lo = 1.2246467991473531772E-16;
     constexpr double aT[11] = {3.33333333333329318027e-01,  -1.99999999998764832476e-01, 1.42857142725034663711e-01,
                                -1.11111104054623557880e-01, 9.09088713343650656196e-02,  -7.69187620504482999495e-02,
                                6.66107313738753120669e-02,  -5.83357013379057348645e-02, 4.97687799461593236017e-02,
                                -3.65315727442169155270e-02, 1.62858201153657823623e-02};
-    const double t = fabs(y / x);   // s_atan.c's argument, >= 0 and finite here
+    const double t = fabs(div_v(kW, y, x));   // s_atan.c's argument, >= 0 and finite here
     const int it = hiw(t);
     const bool r_1 = it < 0x3fdc0000, r0 = it < 0x3fe60000, r1 = it < 0x3ff30000, r2 = it < 0x40038000;
     const double num = r_1 ? t : r0 ? 2.0 * t - 1.0 : r1 ? t - 1.0 : r2 ? t - 1.5 : -1.0;
     const double den = r_1 ? 1.0 : r0 ? 2.0 + t : r1 ? t + 1.0 : r2 ? 1.0 + 1.5 * t : t;
-    const double xr = num / den;
+    const double xr = div_v(kW, num, den);
     const double z = xr * xr;
     const double w = z * z;
     const double s1 = z * (aT[0] + w * (aT[2] + w * (aT[4] + w * (aT[6] + w * (aT[8] + w * aT[10])))));
@@ -303,6 +308,7 @@ NUSI_FN double atan2_sel(double y, double x)
     const double zz = at - pi_lo;
     return m == 0 ? at : m == 1 ? -at : m == 2 ? pi - zz : zz - pi;
 }
+NUSI_FN double atan2_sel(double y, double x) { return atan2_sel_t<false>(y, x); }
 NUSI_FN bool wave_all_l(bool p)
 {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -317,6 +323,18 @@ NUSI_LM double atan2_rare(double y, double x) { return atan2_full(y, x); }
 NUSI_FN double atan2_i(double y, double x)
 {
     if (wave_all_l(atan2_plain(y, x))) return atan2_sel(y, x);
+    return atan2_rare(y, x);
+}
+// atan2_i for a caller that bounds its operands (the member-corner kernel's chain inside the member window,
+// nusi_gsl.hpp): every active lane's x and y finite with modulus at most 2^500, y nonzero and at least 2^-500, x
+// at least 2^-500 or 0.  The vote for the common path is then three compares on two products: |y| <= 2^59 |x| and
+// |x| <= 2^59 |y| put the exponents at most 59 apart, so atan2_plain's k = (iy - ix) >> 20, which is that difference
+// or one less, is within +-60 (and x = 0 fails the first); x != 1.  Its divisions take the short sequence: the
+// quotient's operands are nonzero, at least 2^-500 and their exponents 59 apart at most
+NUSI_FN double atan2_w(double y, double x)
+{
+    const double ax = fabs(x), ay = fabs(y);
+    if (wave_all_l(ay <= ax * 0x1p59 && ax <= ay * 0x1p59 && x != 1.0)) return atan2_sel_t<true>(y, x);
     return atan2_rare(y, x);
 }
 

@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "nusi_coeffs.hpp"
+#include "nusi_div.hpp"
 #include "nusi_libm.hpp"
 
 #define NUSI_FN __host__ __device__ inline
@@ -72,6 +73,22 @@ NUSI_FN cd operator/(cd a, cd b)
     return cd{((a.i * ratio) + a.r) / den, (a.i - (a.r * ratio)) / den};
 }
 NUSI_FN cd operator/(double s, cd b) { return C(s) / b; }
+// a / b as above -- the same two cases, operands and operation order -- with each case's divisions from nusi_div.hpp:
+// the ratio a single one, re and im a pair over den.  w: wave-uniform; true only if in every active lane the operands
+// of all three are within that header's conditions (the caller's vote; the plain / otherwise, and on the host)
+NUSI_FN cd cdiv_v(bool w, cd a, cd b)
+{
+    const double c = b.r, d = b.i;
+    cd q;
+    if (fabs(c) < fabs(d)) {
+        const double ratio = nm::div_v(w, c, d), den = (c * ratio) + d;
+        nm::div2_v(w, (a.r * ratio) + a.i, (a.i * ratio) - a.r, den, q.r, q.i);
+        return q;
+    }
+    const double ratio = nm::div_v(w, d, c), den = (d * ratio) + c;
+    nm::div2_v(w, (a.i * ratio) + a.r, a.i - (a.r * ratio), den, q.r, q.i);
+    return q;
+}
 NUSI_FN cd conj(cd a) { return cd{a.r, -a.i}; }
 NUSI_FN double carg(cd z) { return nm::atan2(z.i, z.r); }
 NUSI_FN double carg_i(cd z) { return nm::atan2_i(z.i, z.r); }
