@@ -156,6 +156,18 @@ public:
     // (faster; up to ~1e-6 from the reference's fluxes where its closed forms cancel); kept by copies
     void set_reference_order(bool on) { check(nusi_set_option(h_, NUSI_OPT_REFERENCE_ORDER, on ? 1 : 0)); }
 
+    // extensions (no reference counterpart: the reference's source is fixed at compile time in Lum()): a
+    // user-tabulated source phi(E') W(z) (include/nusi.h, nusi_set_source).  source_axis: M = N_bins_E + N_steps_z - 1
+    // and the bin edges lo / hi [M] of the source axis, the redshift grid z [N_steps_z]; any pointer may be null.
+    // set_source: S [M] the spectrum's integral over each source-axis bin, w [N_steps_z] the redshift weight (null =
+    // the star-formation rate); norm is then an absolute factor and si is ignored.  set_source(nullptr) returns to the
+    // constructor's source.  Kept by copies.
+    void source_axis(int* M, double* lo = nullptr, double* hi = nullptr, double* z = nullptr)
+    {
+        check(nusi_source_axis(h_, M, lo, hi, z));
+    }
+    void set_source(const double* S, const double* w = nullptr) { check(nusi_set_source(h_, S, w)); }
+
 private:
     nusi_handle* h_ = nullptr;
     int N_ = 0;

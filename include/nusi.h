@@ -41,6 +41,15 @@ extern "C" {
  * BASELINE workloads. */
 #define NUSI_SOURCE_DSNB 0
 #define NUSI_SOURCE_POWER_LAW 1
+/* Extension (the reference fixes its source at compile time, Lum() of
+ * nuSIprop.hpp:648-662): source_model = NUSI_SOURCE_TABULATED + slot selects
+ * the user-tabulated source phi(E') W(z) registered in that slot of the plan
+ * (nusi_plan_set_source / nusi_set_source below).  For such a point `norm` is
+ * absolute (no flux_FS_E0 division) and `si` is ignored; like both built-in
+ * sources, the three mass states get equal thirds.  The source term of bin b
+ * at redshift step i is, for each mass state,
+ *     step_c[i] * ((norm / 3.0) * (w[i] / (1 + z[i])) * S[b + i]). */
+#define NUSI_SOURCE_TABULATED 2
 
 /* warning bits (negative cross sections, nuSIprop.hpp:909-918, 1215-1231, 1505-1516) */
 #define NUSI_WARN_GAMMA 1
@@ -66,7 +75,7 @@ typedef struct nusi_params {
     double zmax;
     int flav;           /* 0=e 1=mu 2=tau */
     int phiphi;
-    int source_model;   /* NUSI_SOURCE_* */
+    int source_model;   /* NUSI_SOURCE_*; NUSI_SOURCE_TABULATED + slot */
 } nusi_params;
 
 /* Fills the reference C++ constructor defaults (nuSIprop.hpp:61-65) around
@@ -99,6 +108,16 @@ int nusi_get_params(const nusi_handle *h, double *mphi_g_mntot_si_norm /* [5] */
 int nusi_evolve(nusi_handle *h);
 /* check_energy_conservation()  (nuSIprop.hpp:339-357): calls evolve() */
 int nusi_check_energy_conservation(nusi_handle *h, double *out);
+/* Tabulated source of one object (no reference counterpart).  nusi_source_axis
+ * is nusi_plan_source_axis on the object's grid.  nusi_set_source registers S
+ * (and w, or NULL) in slot 0 of the object's plan and switches the object to
+ * it; S == NULL returns the object to its constructor's source_model.
+ * nusi_copy keeps the source.  nusi_check_energy_conservation on an object
+ * with a tabulated source returns NUSI_EPARAM: its free-streaming energy is
+ * defined for the power law only, and bin integrals do not determine the
+ * spectrum's energy integral. */
+int nusi_source_axis(const nusi_handle *h, int *M, double *lo, double *hi, double *z);
+int nusi_set_source(nusi_handle *h, const double *S, const double *w);
 /* results of the last evolve(), row-major [k][b] (mass basis) / [f][b] (flavour) */
 int nusi_get_flux(const nusi_handle *h, double *out_3xN);      /* get_flux(i,j)     :359-381 */
 int nusi_get_flux_fla(const nusi_handle *h, double *out_3xN);  /* get_flux_fla(i,j) :383-405 */
@@ -129,6 +148,31 @@ void nusi_plan_destroy(nusi_plan *plan);
 int nusi_plan_load_phiphi(nusi_plan *plan, const char *alphatilde_path, const int *alphatilde_dims,
                           const char *alpha_path, const int *alpha_dims);
 int nusi_plan_grid(const nusi_plan *plan, int *N, int *Nz, double *Enu /* [N] or NULL */);
+/* Tabulated sources (no reference counterpart).  A plan holds numbered source
+ * slots; a point with source_model = NUSI_SOURCE_TABULATED + slot reads its
+ * source from that slot.
+ * The SOURCE AXIS has M = N + Nz - 1 bins: bins 0 .. N-1 are the energy bins,
+ * bin N-1+j is [Emin[N-1] (1 + z_j), Emax[N-1] (1 + z_j)] for j = 1 .. Nz-1 --
+ * the bins a redshifted energy bin can come from.  nusi_plan_source_axis
+ * returns M, the bin edges lo / hi [M] and the redshift grid z [Nz]; any
+ * pointer may be NULL.
+ * nusi_plan_set_source fills `slot` (0 .. NUSI_SOURCE_SLOTS_MAX - 1; storage
+ * grows on demand) with
+ *   S [M]   the spectrum's integral over each source-axis bin, in the
+ *           source's frame (bin 0 is never read: there is no source at
+ *           redshift step 0);
+ *   w [Nz]  the redshift weight W(z_i) in place of the star-formation rate
+ *           get_SFR(z_i) (nuSIprop.hpp:591-605); NULL = get_SFR.
+ * The vectors are copied (the caller may free them).  The call is ordered
+ * with the plan's calls: earlier evolves finish with the old contents, later
+ * ones see the new.  S == NULL clears the slot.  NUSI_EPARAM for a slot out
+ * of range or a non-finite or negative entry (the cascade relies on every
+ * summed term being non-negative), and -- from the evolve calls -- for a point
+ * whose slot is empty. */
+#define NUSI_SOURCE_SLOTS_MAX 65536
+int nusi_plan_source_axis(const nusi_plan *plan, int *M, double *lo /* [M] */, double *hi /* [M] */,
+                          double *z /* [Nz] */);
+int nusi_plan_set_source(nusi_plan *plan, int slot, const double *S /* [M] */, const double *w /* [Nz] or NULL */);
 /* Evolve n points (their grid fields must equal the plan's).  d_flux /
  * d_flux_fla are DEVICE pointers of n*3*N doubles ([point][k][b]); either may
  * be NULL.  stream is a hipStream_t (NULL = the plan's own stream).  The call
@@ -152,7 +196,7 @@ int nusi_plan_profile_end(nusi_plan *plan, double *sum_ms3, int *ncalls);
  * AUTO (default, also for the object API) = MFMA.
  * MFMA = the block-synchronous wavefront with the push on the fp64 matrix
  *   cores (k_cascade_bs: one pass up to 48 redshift steps, step passes
- *   beyond), for both sources and both scattering modes; points sharing a
+ *   beyond), for every source and both scattering modes; points sharing a
  *   Stage-A table share one workgroup (multi-RHS: pairs, or the gamma batch
  *   of up to 16).  Grids beyond its limits (T - 1 > 14 x 128 rows) fall back
  *   to the scalar kernel.

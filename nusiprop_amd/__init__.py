@@ -4,10 +4,11 @@ The hot path of quarkquartet/nuSIprop, calculate_flux::evolve() (nuSIprop.hpp:
 176-337), as hand-written HIP kernels for gfx950 behind a C ABI (include/nusi.h,
 libnusi.so), with the reference's Python surface (``pyprop``) on top.
 """
-from ._lib import (NusiError, NusiParams, SOURCE_DSNB, SOURCE_POWER_LAW, WARN_ALPHA, WARN_ALPHATILDE,  # noqa: F401
-                   WARN_GAMMA, make_params, load)
+from ._lib import (NusiError, NusiParams, SOURCE_DSNB, SOURCE_POWER_LAW, SOURCE_TABULATED, WARN_ALPHA,  # noqa: F401
+                   WARN_ALPHATILDE, WARN_GAMMA, make_params, load)
+from . import sources  # noqa: F401
 from .plan import Plan, unpack_alpha  # noqa: F401
 from .pyprop import pyprop  # noqa: F401
 
-__all__ = ["pyprop", "Plan", "unpack_alpha", "NusiError", "NusiParams", "make_params", "load",
-           "SOURCE_DSNB", "SOURCE_POWER_LAW"]
+__all__ = ["pyprop", "Plan", "unpack_alpha", "NusiError", "NusiParams", "make_params", "load", "sources",
+           "SOURCE_DSNB", "SOURCE_POWER_LAW", "SOURCE_TABULATED"]

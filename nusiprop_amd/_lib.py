@@ -20,6 +20,8 @@ NUSI_ESTATE = -6
 
 SOURCE_DSNB = 0
 SOURCE_POWER_LAW = 1
+SOURCE_TABULATED = 2        # + slot: a user-tabulated source of the plan (Plan.set_source, nusiprop_amd.sources)
+SOURCE_SLOTS_MAX = 65536
 
 WARN_GAMMA = 1
 WARN_ALPHATILDE = 2
@@ -52,6 +54,7 @@ EXPORTS = [
     "nusi_plan_evolve_host", "nusi_plan_stage_ms", "nusi_plan_profile_begin", "nusi_plan_profile_end",
     "nusi_plan_warnings", "nusi_plan_tables", "nusi_evolve_batch", "nusi_plan_set_cascade",
     "nusi_plan_kernels", "nusi_plan_set_option",
+    "nusi_plan_source_axis", "nusi_plan_set_source", "nusi_source_axis", "nusi_set_source",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -109,6 +112,10 @@ def load():
         "nusi_plan_set_cascade": (i, [vp, i]),
         "nusi_plan_set_option": (i, [vp, i, i]),
         "nusi_plan_kernels": (i, [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p)]),
+        "nusi_plan_source_axis": (i, [vp, ip, dp, dp, dp]),
+        "nusi_plan_set_source": (i, [vp, i, dp, dp]),
+        "nusi_source_axis": (i, [vp, ip, dp, dp, dp]),
+        "nusi_set_source": (i, [vp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -435,8 +435,12 @@ struct nusi_plan {
     int2* d_smap = nullptr;         // per shifted table: base index in `shift`, bin offset
     int2* h_smap = nullptr;         // pinned
     AlphaBatches shift_batches;     // the base plan's alpha batches of the last call
-    double* d_src = nullptr;        // DSNB source terms of the MFMA cascade [src_cap][cascade_src_doubles]
+    double* d_src = nullptr;        // source terms of the MFMA cascade's points that are not the power law
+                                    // [src_cap][cascade_src_doubles] (k_source_dsnb, k_source_tab)
     int src_cap = 0;
+    double* d_slots = nullptr;      // tabulated sources (nusi_plan_set_source): [slot_cap][cascade_slot_doubles], S then w
+    int slot_cap = 0;
+    std::vector<unsigned char> slot_set;   // [slot_cap]: the slot holds a source
     std::vector<int> slot_of;       // table slot of each point of the last call
     int last_ntab = 0;
     int* d_warn = nullptr;
@@ -499,8 +503,13 @@ int build_point(nusi_plan* pl, const nusi_params& p, nusi::Point& P)
     if (p.N_bins_E != G.N || p.lEmin != G.lEmin || p.lEmax != G.lEmax || p.zmax != G.zmax_in)
         return fail(NUSI_EPARAM, "point grid (N_bins_E, lEmin, lEmax, zmax) differs from the plan's");
     if (p.flav < 0 || p.flav > 2) return fail(NUSI_EPARAM, "flav must be 0, 1 or 2");
-    if (p.source_model != NUSI_SOURCE_DSNB && p.source_model != NUSI_SOURCE_POWER_LAW)
-        return fail(NUSI_EPARAM, "unknown source_model");
+    if (p.source_model < 0) return fail(NUSI_EPARAM, "unknown source_model");
+    const bool tab = p.source_model >= NUSI_SOURCE_TABULATED;
+    if (tab) {
+        const long long slot = (long long)p.source_model - NUSI_SOURCE_TABULATED;
+        if (slot >= (long long)pl->slot_set.size() || !pl->slot_set[(size_t)slot])
+            return fail(NUSI_EPARAM, "source_model names a tabulated source slot that is empty (nusi_plan_set_source)");
+    }
     const int no = p.normal_ordering ? 1 : 0;
     // masses, nuSIprop.hpp:184-203
     const double dmq21 = 7.42e-5;
@@ -528,15 +537,19 @@ int build_point(nusi_plan* pl, const nusi_params& p, nusi::Point& P)
         }
         it = pl->mass_cache.emplace(key, mn).first;
     }
-    auto fit = pl->fs_cache.find(p.si);
-    if (fit == pl->fs_cache.end()) fit = pl->fs_cache.emplace(p.si, flux_fs_e0(p.si, G.zmax_eff)).first;
+    // a tabulated source's norm is absolute and its si unused: no free-streaming normalisation
+    auto fit = pl->fs_cache.end();
+    if (!tab) {
+        fit = pl->fs_cache.find(p.si);
+        if (fit == pl->fs_cache.end()) fit = pl->fs_cache.emplace(p.si, flux_fs_e0(p.si, G.zmax_eff)).first;
+    }
     memset(&P, 0, sizeof(P));
     P.mphi = p.mphi;
     P.g = p.g;
     P.mntot = p.mntot;
-    P.si = p.si;
+    P.si = tab ? 0.0 : p.si;   // (only the power-law source reads it)
     P.norm = p.norm;
-    P.norm_total = p.norm / fit->second;
+    P.norm_total = tab ? p.norm : p.norm / fit->second;
     P.Ga = p.majorana ? sq(p.g) * p.mphi / (16.0 * M_PI) : sq(p.g) * p.mphi / (8.0 * M_PI);
     for (int k = 0; k < 3; ++k) P.mn[k] = it->second[k];
     for (int k = 0; k < 9; ++k) P.U2[k] = pl->U2[no][k];
@@ -833,6 +846,7 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->tabs.Wmin);
     hipFree(pl->d_nospl);
     hipFree(pl->d_src);
+    hipFree(pl->d_slots);
     hipFree(pl->d_smap);
     if (pl->h_smap) hipHostFree(pl->h_smap);
     hipFree(pl->d_fh);
@@ -997,6 +1011,70 @@ int nusi_plan_grid(const nusi_plan* pl, int* N, int* Nz, double* Enu)
     return NUSI_OK;
 }
 
+// The source axis: the table axis of make_grid continued by one bin (a bin b <= N - 1 at step i <= Nz - 1 reads
+// source-axis bin b + i <= T).
+int nusi_plan_source_axis(const nusi_plan* pl, int* M, double* lo, double* hi, double* z)
+{
+    if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
+    const HostGrid& G = pl->grid;
+    if (M) *M = G.T + 1;
+    if (lo) {
+        memcpy(lo, G.lo.data(), sizeof(double) * G.T);
+        lo[G.T] = G.Emin[G.N - 1] * (1 + G.z[G.Nz - 1]);
+    }
+    if (hi) {
+        memcpy(hi, G.hi.data(), sizeof(double) * G.T);
+        hi[G.T] = G.Emax[G.N - 1] * (1 + G.z[G.Nz - 1]);
+    }
+    if (z) memcpy(z, G.z.data(), sizeof(double) * G.Nz);
+    return NUSI_OK;
+}
+
+int nusi_plan_set_source(nusi_plan* pl, int slot, const double* S, const double* w)
+{
+    if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
+    if (slot < 0 || slot >= NUSI_SOURCE_SLOTS_MAX) return fail(NUSI_EPARAM, "source slot outside [0, NUSI_SOURCE_SLOTS_MAX)");
+    if (!S) {   // clear (the storage stays; build_point refuses the slot)
+        if ((size_t)slot < pl->slot_set.size()) pl->slot_set[(size_t)slot] = 0;
+        return NUSI_OK;
+    }
+    const HostGrid& G = pl->grid;
+    const int M = G.T + 1;
+    for (int n = 0; n < M; ++n)
+        if (!(S[n] >= 0.0) || !std::isfinite(S[n])) return fail(NUSI_EPARAM, "source spectrum: a bin integral is negative or not finite");
+    if (w)
+        for (int i = 0; i < G.Nz; ++i)
+            if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(NUSI_EPARAM, "source redshift weight: an entry is negative or not finite");
+    HIPCHECK(hipSetDevice(pl->device));
+    // ordered with the plan's calls: the earlier ones (on whatever stream they ran) finish with the old contents,
+    // and the copies below are complete when this returns
+    if (pl->ran) HIPCHECK(hipEventSynchronize(pl->ev_done));
+    const size_t per = nusi::cascade_slot_doubles(pl->gd);
+    if (slot >= pl->slot_cap) {   // grow: doubled, at least 16 and the slot asked for
+        const int cap = std::min(NUSI_SOURCE_SLOTS_MAX, std::max({16, 2 * pl->slot_cap, slot + 1}));
+        double* d = nullptr;
+        HIPCHECK(hipMalloc(&d, sizeof(double) * per * cap));
+        if (pl->slot_cap) {
+            const hipError_t e = hipMemcpy(d, pl->d_slots, sizeof(double) * per * pl->slot_cap, hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) {
+                hipFree(d);
+                HIPCHECK(e);
+            }
+        }
+        hipFree(pl->d_slots);
+        pl->d_slots = d;
+        pl->slot_cap = cap;
+        pl->slot_set.resize((size_t)cap, 0);
+    }
+    pl->slot_set[(size_t)slot] = 0;   // (empty if a copy fails half way)
+    std::vector<double> v(per);
+    memcpy(v.data(), S, sizeof(double) * M);
+    memcpy(v.data() + M, w ? w : G.sfr.data(), sizeof(double) * G.Nz);
+    HIPCHECK(hipMemcpy(pl->d_slots + per * (size_t)slot, v.data(), sizeof(double) * per, hipMemcpyHostToDevice));
+    pl->slot_set[(size_t)slot] = 1;
+    return NUSI_OK;
+}
+
 int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flux, double* d_fla, void* stream)
 {
     if (n < 1 || n > pl->max_points) return fail(NUSI_EPARAM, "number of points outside [1, max_points]");
@@ -1080,9 +1158,12 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
     // step-pass instance), any source and scattering mode, step passes on long grids.  WAVEFRONT / REG / LDS, and a
     // grid k_cascade_bs does not fit: the bit-exact scalar cascade k_cascade.
     const int kind = pl->cascade_kind == NUSI_CASCADE_AUTO ? NUSI_CASCADE_MFMA : pl->cascade_kind;
-    bool any_dsnb = false, all_nr = true;
+    // (every point that is not the power law reads its source from tabs.Src: the DSNB's from k_source_dsnb, the
+    // tabulated ones' from k_source_tab)
+    bool any_dsnb = false, any_tab = false, all_nr = true;
     for (int i = 0; i < n; ++i) {
         any_dsnb = any_dsnb || pl->h_pts[i].source == NUSI_SOURCE_DSNB;
+        any_tab = any_tab || pl->h_pts[i].source >= NUSI_SOURCE_TABULATED;
         all_nr = all_nr && pl->h_pts[i].non_resonant;
     }
     const bool force_passes = pl->step_passes == 1;
@@ -1124,7 +1205,7 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
             pl->fh_doubles = fhd;
         }
     }
-    if (bs && any_dsnb && pl->src_cap < pl->max_points) {
+    if (bs && (any_dsnb || any_tab) && pl->src_cap < pl->max_points) {
         hipFree(pl->d_src);
         pl->d_src = nullptr;
         pl->src_cap = 0;
@@ -1234,6 +1315,7 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
     }
     HIPCHECK(hipEventRecord(ev[2], s));
     if (bs && any_dsnb) HIPCHECK(nusi::launch_source_dsnb(pl->gd, pl->d_pts, n, pl->d_src, s));
+    if (bs && any_tab) HIPCHECK(nusi::launch_source_tab(pl->gd, pl->d_pts, n, pl->d_slots, pl->d_src, s));
     const char* gb_name = nullptr;
     if (bs) {
         const int Pk[3] = {16, 2, 1};
@@ -1253,7 +1335,7 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
         }
         gb_name = names[mask];
     } else {
-        HIPCHECK(nusi::launch_cascade_exact(pl->gd, pl->d_pts, n, pl->tabs, d_flux, d_fla, s));
+        HIPCHECK(nusi::launch_cascade_exact(pl->gd, pl->d_pts, n, pl->tabs, pl->d_slots, d_flux, d_fla, s));
     }
     HIPCHECK(hipEventRecord(ev[3], s));
     HIPCHECK(hipEventRecord(pl->ev_done, s));
@@ -1508,6 +1590,7 @@ void pool_give(nusi_plan* pl)
         pl->ref_order = 1;
         pl->cascade_kind = NUSI_CASCADE_AUTO;
         pl->prof_max = pl->prof_n = 0;
+        std::fill(pl->slot_set.begin(), pl->slot_set.end(), 0);   // no tabulated sources
         pl->spl.reset();
         PlanPool& pp = plan_pool();
         std::lock_guard<std::mutex> lock(pp.mu);
@@ -1528,6 +1611,11 @@ struct nusi_handle {
     bool evolved = false;      // an evolve() has run (norm_total is set)
     int warn = 0;
     std::map<int, int> opts;   // the last value nusi_set_option set per option, replayed by nusi_copy
+    // nusi_set_source: the tabulated source in slot 0 of the plan (kept for nusi_copy) and the constructor's
+    // source_model, to which S == NULL returns
+    bool tab = false, tab_w = false;
+    int source0 = NUSI_SOURCE_DSNB;
+    std::vector<double> tab_S, tab_wv;
     std::string alpha_kernel, cascade_kernel;   // what this object's last evolve() launched (copied by nusi_copy;
                                                 // the pooled plan of a copy may have run another object's call)
     ~nusi_handle() { pool_give(plan); }
@@ -1543,6 +1631,7 @@ static int open_handle(const nusi_params* p, const std::shared_ptr<SplineStore>*
     if (const char* e = getenv("NUSI_DEVICE")) dev = atoi(e);
     std::unique_ptr<nusi_handle> h(new nusi_handle);
     h->p = *p;
+    h->source0 = p->source_model;
     int r = NUSI_OK;
     h->plan = pool_take(dev, p->N_bins_E, p->lEmin, p->lEmax, p->zmax);
     if (!h->plan) r = nusi_plan_create(dev, p->N_bins_E, p->lEmin, p->lEmax, p->zmax, 1, &h->plan);
@@ -1583,6 +1672,37 @@ int nusi_copy(const nusi_handle* src, nusi_handle** out)
             *out = nullptr;
             return r;
         }
+    }
+    (*out)->source0 = src->source0;
+    if (src->tab) {   // the copy's own plan gets the source
+        r = nusi_set_source(*out, src->tab_S.data(), src->tab_w ? src->tab_wv.data() : nullptr);
+        if (r) {
+            nusi_destroy(*out);
+            *out = nullptr;
+            return r;
+        }
+    }
+    return NUSI_OK;
+}
+
+int nusi_source_axis(const nusi_handle* h, int* M, double* lo, double* hi, double* z)
+{
+    return nusi_plan_source_axis(h->plan, M, lo, hi, z);
+}
+
+int nusi_set_source(nusi_handle* h, const double* S, const double* w)
+{
+    const int r = nusi_plan_set_source(h->plan, 0, S, w);
+    if (r) return r;
+    h->tab = S != nullptr;
+    h->tab_w = S && w;
+    if (S) {
+        const HostGrid& G = h->plan->grid;
+        h->tab_S.assign(S, S + G.T + 1);
+        if (w) h->tab_wv.assign(w, w + G.Nz);
+        h->p.source_model = NUSI_SOURCE_TABULATED;
+    } else {
+        h->p.source_model = h->source0;
     }
     return NUSI_OK;
 }
@@ -1626,6 +1746,9 @@ int nusi_evolve(nusi_handle* h)
 int nusi_check_energy_conservation(nusi_handle* h, double* out)
 {
     const HostGrid& G = h->plan->grid;
+    if (h->p.source_model >= NUSI_SOURCE_TABULATED)
+        return fail(NUSI_EPARAM, "check_energy_conservation: not defined for a tabulated source (the free-streaming "
+                                 "energy is the power law's; bin integrals do not determine the spectrum's energy integral)");
     // the reference evaluates E_FS with the previous evolve()'s norm_total (nuSIprop.hpp:341-343)
     const bool unset = !h->evolved;
     const double E_FS = energy_fs(h->p.si, h->norm_total, G.zmax_eff, G.lEmin, G.lEmax);

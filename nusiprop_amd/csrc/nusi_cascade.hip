@@ -5,6 +5,7 @@
 //                         roles; one point, two or up to 16 points sharing a table per workgroup, step passes on
 //                         long grids (NUSI_CASCADE_AUTO / MFMA, every shape)
 //   k_source_dsnb         the DSNB source terms it reads
+//   k_source_tab          ... and the tabulated sources' (nusi_plan_set_source)
 //   k_cascade             the bit-exact scalar cascade, one wavefront per point, any N (NUSI_CASCADE_WAVEFRONT /
 //                         REG / LDS).  (The per-stage kernels of rounds 1-3 -- k_cascade_wf, _reg, _ws, _wsp, _gb --
 //                         are gone; DESIGN.md Appendix A keeps their measurements.)
@@ -234,8 +235,22 @@ NUSI_FN void cascade_solve_id(double f0, double f1, double f2, double add, doubl
     x0 = x0 - u01 * x1 - u02 * x2;
 }
 
+// The tabulated source term of bin b at step i (NUSI_SOURCE_TABULATED + slot, include/nusi.h): c = step_c[i],
+// w = the slot's redshift weight w[i] (get_SFR(z_i) where none was given), z = z[i], S = the slot's bin integral
+// S[b + i] -- the source-frame bin [E_b (1 + z_i), E_{b+1} (1 + z_i)] is source-axis bin b + i (the index-shift
+// identity of pw[]).  The one place the expression is written: k_source_tab (the MFMA cascade's table) and the scalar
+// k_cascade both call it, so the two cascades see the same source bits.
+NUSI_FN double tabulated_src(double c, double norm, double w, double z, double S)
+{
+    return c * ((norm / 3.0) * (w / (1 + z)) * S);
+}
+// a source slot in the plan's slot storage: S [T + 1] (the source axis), then w [Nz]
+NUSI_FN size_t source_slot_doubles(int T, int Nz) { return (size_t)T + 1 + Nz; }
+
+// slots: the plan's source slots (source_slot_doubles each), read by tabulated points only (else may be nullptr)
 __global__ __launch_bounds__(64) void k_cascade(GridDev g, const Point* __restrict__ pts, TablesDev t,
-                                                double* __restrict__ flux, double* __restrict__ flux_fla)
+                                                const double* __restrict__ slots, double* __restrict__ flux,
+                                                double* __restrict__ flux_fla)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int N = g.N, Nz = g.Nz, T = g.T;
@@ -253,6 +268,9 @@ __global__ __launch_bounds__(64) void k_cascade(GridDev g, const Point* __restri
     const double* __restrict__ At = t.At + (size_t)P.tslot * T;
     const double* __restrict__ Al = t.A + (size_t)P.tslot * g.PT;
     const bool nonres = P.non_resonant;
+    const bool tab = P.source >= NUSI_SOURCE_TABULATED;   // (lum() would take any such source for the DSNB)
+    const double* __restrict__ tS = tab ? slots + (size_t)(P.source - NUSI_SOURCE_TABULATED) * source_slot_doubles(T, Nz) : nullptr;
+    const double* __restrict__ tw = tab ? tS + T + 1 : nullptr;
 
     for (int b = lane; b < N; b += 64) F0[b] = F1[b] = F2[b] = 0.0;
 
@@ -275,7 +293,8 @@ __global__ __launch_bounds__(64) void k_cascade(GridDev g, const Point* __restri
                         for (int l = 0; l < 3; ++l) M[k][l] = (k == l) ? 1.0 : (Aw * uk[k] * uk[l] / dEb) / Zd[k];
                     int pm[3];
                     lu3_factor(M, pm);
-                    const double src0 = c * lum(P, zi, sfri, g.Emin[b], g.Emax[b]);
+                    const double src0 = tab ? tabulated_src(c, P.norm_total, tw[i], zi, tS[b + i])
+                                            : c * lum(P, zi, sfri, g.Emin[b], g.Emax[b]);
                     pre[PR_RZ0 * 64 + lane] = 1.0 / Zd[0];
                     pre[PR_RZ1 * 64 + lane] = 1.0 / Zd[1];
                     pre[PR_RZ2 * 64 + lane] = 1.0 / Zd[2];
@@ -393,6 +412,31 @@ hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, doub
     hipLaunchKernelGGL(k_source_dsnb, dim3((ne + 255) / 256, npts), dim3(256), 0, s, g, pts, src);
     return hipGetLastError();
 }
+// The tabulated points' rows of the same table, from their slots' vectors (tabulated_src).  One work-item per
+// element of the row in storage order, o = d (Nz - 1) + J with d = b - J + Nz - 2: consecutive lanes write
+// consecutive doubles, and b + i = d + 1, so a diagonal's Nz - 1 elements share one S.  Elements whose bin lies
+// off the grid are never read and stay unwritten, like k_source_dsnb's.
+__global__ __launch_bounds__(256) void k_source_tab(GridDev g, const Point* __restrict__ pts,
+                                                    const double* __restrict__ slots, double* __restrict__ src)
+{
+    const int p = blockIdx.y, N = g.N, Nz = g.Nz, T = g.T, nst = Nz - 1;
+    const Point& P = pts[p];
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (P.source < NUSI_SOURCE_TABULATED || o >= T * nst) return;
+    const int d = o / nst, J = o - d * nst, b = d + J - (Nz - 2), i = Nz - 1 - J;
+    if (b < 0 || b >= N) return;
+    const double* __restrict__ S = slots + (size_t)(P.source - NUSI_SOURCE_TABULATED) * source_slot_doubles(T, Nz);
+    const double* __restrict__ w = S + T + 1;
+    src[(size_t)p * T * nst + o] = tabulated_src(g.step_c[i], P.norm_total, w[i], g.z[i], S[d + 1]);
+}
+hipError_t launch_source_tab(const GridDev& g, const Point* pts, int npts, const double* slots, double* src,
+                             hipStream_t s)
+{
+    const int ne = (g.Nz - 1) * g.T;
+    hipLaunchKernelGGL(k_source_tab, dim3((ne + 255) / 256, npts), dim3(256), 0, s, g, pts, slots, src);
+    return hipGetLastError();
+}
+size_t cascade_slot_doubles(const GridDev& g) { return source_slot_doubles(g.T, g.Nz); }
 
 // The chain's hand-off between steps: step slot j solves bin b at stage sg, right after slot j-1 solved the same
 // bin at stage sg-1 (nuSIprop.hpp:257-315: step i starts from step i+1's F[:, b]).  wave_shr1 moves each lane's
@@ -1052,12 +1096,12 @@ hipError_t launch_cascade_bs(const GridDev& g, const Point* pts, int P, const in
 }
 
 // the bit-exact scalar cascade (NUSI_CASCADE_WAVEFRONT / REG / LDS): k_cascade, one wavefront per point, any N
-hipError_t launch_cascade_exact(const GridDev& g, const Point* pts, int npts, TablesDev t, double* flux,
-                                double* flux_fla, hipStream_t s)
+hipError_t launch_cascade_exact(const GridDev& g, const Point* pts, int npts, TablesDev t, const double* slots,
+                                double* flux, double* flux_fla, hipStream_t s)
 {
     t_cascade_kernel = "k_cascade";
     const size_t lds = cascade_lds_bytes(g.N);
-    hipLaunchKernelGGL(k_cascade, dim3(npts), dim3(64), lds, s, g, pts, t, flux, flux_fla);
+    hipLaunchKernelGGL(k_cascade, dim3(npts), dim3(64), lds, s, g, pts, t, slots, flux, flux_fla);
     return hipGetLastError();
 }
 

@@ -33,7 +33,8 @@ struct TablesDev {
     double* At;   // [npts][T]
     double* A;    // [npts][PT]
     double* Med;  // [npts][3][kMedFields T]: member edge leaves of every bin edge (k_alpha_medge)
-    double* Src;  // [npts][T (Nz-1)]: DSNB source terms c_i Lum (k_source_dsnb, diagonal layout), or nullptr
+    double* Src;  // [npts][T (Nz-1)]: the source terms c_i Lum of every point that is not the power law (k_source_dsnb,
+                  // k_source_tab; diagonal layout), or nullptr
     int* Wmin;    // [npts][4][T] or nullptr (only the base plan of NUSI_OPT_SHIFT_REUSE): per warning bit b and table
                   // row n, the smallest column m of an entry (n, m) that raised it (Gamma / alphaTilde: m = n), so
                   // that k_table_shift passes on exactly the warnings of the rows a shifted slot reads
@@ -103,10 +104,17 @@ hipError_t launch_cascade_bs(const GridDev& g, const Point* pts, int P, const in
                              bool force_passes);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
+// Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,
+// cascade_slot_doubles per slot (S [T + 1], then w [Nz]), passed by pointer (an indexed by-value aggregate ends up in
+// scratch).  launch_source_tab fills the t.Src rows of the call's tabulated points for the MFMA cascade.
+size_t cascade_slot_doubles(const GridDev& g);
+hipError_t launch_source_tab(const GridDev& g, const Point* pts, int npts, const double* slots, double* src,
+                             hipStream_t s);
 // The bit-exact scalar cascade k_cascade (NUSI_CASCADE_WAVEFRONT / REG / LDS all select it): one wavefront per
-// point, any N.
-hipError_t launch_cascade_exact(const GridDev& g, const Point* pts, int npts, TablesDev t, double* flux,
-                                double* flux_fla, hipStream_t s);
+// point, any N.  It reads no t.Src: a tabulated point's source comes straight from `slots` (nullptr where the call
+// has no such point), through the expression k_source_tab uses.
+hipError_t launch_cascade_exact(const GridDev& g, const Point* pts, int npts, TablesDev t, const double* slots,
+                                double* flux, double* flux_fla, hipStream_t s);
 
 // 4 x 4 windows of a 3-D spline table f [n0][n1][n2] into fw [n0 n1 n2][16] (synchronous)
 hipError_t spline_windows_build(const float* f, int n0, int n1, int n2, float* fw);

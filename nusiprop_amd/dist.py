@@ -56,6 +56,9 @@ def evolve_sharded(points, evolve_block, group=None, gather=True):
     rank this is Plan.evolve (nusiprop_amd.plan).  Returns the full
     (flux, flux_fla) in the input order on the group's rank 0 (None, None
     elsewhere) when `gather`, else this rank's block and its [lo, hi).
+
+    Tabulated sources (Plan.set_source) belong to a plan: each rank registers
+    the slots its points name on its own plan before evolving.
     """
     import torch.distributed as dist
     lo, hi = local_block(points, group)

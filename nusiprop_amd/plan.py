@@ -65,6 +65,36 @@ class Plan:
         d3 = (ctypes.c_int * 3)(*alpha_dims) if alpha_dims else None
         _lib.check(_lib.load().nusi_plan_load_phiphi(self._h, alphatilde_path.encode(), d2, alpha_path.encode(), d3))
 
+    def source_axis(self):
+        """(lo, hi, z): the bin edges [M = N + Nz - 1] of the source axis -- the energy bins, then the top bin
+        redshifted by each step -- and the redshift grid [Nz] (nusi_plan_source_axis)."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        M = self.T + 1
+        lo, hi, z = np.zeros(M), np.zeros(M), np.zeros(self.Nz)
+        m = ctypes.c_int()
+        _lib.check(_lib.load().nusi_plan_source_axis(self._h, ctypes.byref(m), lo.ctypes.data_as(dp),
+                                                     hi.ctypes.data_as(dp), z.ctypes.data_as(dp)))
+        assert m.value == M
+        return lo, hi, z
+
+    def set_source(self, slot, spectrum, z_weight=None):
+        """Register a tabulated source phi(E') W(z) in ``slot``; points select it with
+        ``source_model = sources.tabulated(slot)`` (their norm is then absolute, their si ignored).
+        spectrum: the bin integrals of dN/dE' over the source axis [M], or a callable dN/dE(E) (integrated per bin,
+        sources.bin_integrals); None clears the slot.  z_weight: W(z_i) [Nz] or a callable of z; None = the
+        star-formation rate.  Later calls see the new source, earlier results are untouched."""
+        from . import sources
+        dp = ctypes.POINTER(ctypes.c_double)
+        L = _lib.load()
+        if spectrum is None:
+            _lib.check(L.nusi_plan_set_source(self._h, int(slot), None, None))
+            return
+        lo, hi, z = self.source_axis()
+        S = sources.spectrum_vector(spectrum, lo, hi)
+        w = sources.weight_vector(z_weight, z)
+        _lib.check(L.nusi_plan_set_source(self._h, int(slot), S.ctypes.data_as(dp),
+                                          w.ctypes.data_as(dp) if w is not None else None))
+
     def params_array(self, points):
         """points: sequence of dicts (calculate_flux keyword arguments) or NusiParams."""
         return params_array(points, self.grid_args)

@@ -112,6 +112,37 @@ class pyprop:  # noqa: N801  (name of the reference class)
         _lib.load().nusi_get_energies(self._h, E.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
         return E
 
+    def source_axis(self):
+        """Extension (no reference counterpart): (lo, hi, z), the bin edges of the source axis
+        [N_bins_E + N_steps_z - 1] and the redshift grid (Plan.source_axis)."""
+        L = _lib.load()
+        dp = ctypes.POINTER(ctypes.c_double)
+        M = self._n() + L.nusi_get_N_steps_z(self._h) - 1
+        lo, hi, z = np.zeros(M), np.zeros(M), np.zeros(L.nusi_get_N_steps_z(self._h))
+        m = ctypes.c_int()
+        _lib.check(L.nusi_source_axis(self._h, ctypes.byref(m), lo.ctypes.data_as(dp), hi.ctypes.data_as(dp),
+                                      z.ctypes.data_as(dp)))
+        assert m.value == M
+        return lo, hi, z
+
+    def set_source(self, spectrum, z_weight=None):
+        """Extension (no reference counterpart): evolve a tabulated source phi(E') W(z) instead of the
+        constructor's source_model (Plan.set_source: spectrum = bin integrals over the source axis or a callable
+        dN/dE(E); z_weight = W(z_i), a callable of z, or None for the star-formation rate).  norm is then an
+        absolute factor and si is ignored.  ``set_source(None)`` returns to the constructor's source.  Resets the
+        evolved flag."""
+        from . import sources
+        L = _lib.load()
+        dp = ctypes.POINTER(ctypes.c_double)
+        if spectrum is None:
+            _lib.check(L.nusi_set_source(self._h, None, None))
+        else:
+            lo, hi, z = self.source_axis()
+            S = sources.spectrum_vector(spectrum, lo, hi)
+            w = sources.weight_vector(z_weight, z)
+            _lib.check(L.nusi_set_source(self._h, S.ctypes.data_as(dp), w.ctypes.data_as(dp) if w is not None else None))
+        self.evolved = False
+
     def kernels(self):
         """Extension (no reference counterpart): names of the alpha-table and cascade kernels the last
         evolve() launched, e.g. ('k_alpha_batch', 'k_cascade_bs')."""
