@@ -289,6 +289,27 @@ int nusi_plan_set_cascade(nusi_plan *plan, int kind);
  *                          automatic (8 GiB, at most half the free memory).
  *                          Any value gives the same tables bit for bit. */
 #define NUSI_OPT_REFO_CORNER_MB 8
+/*   NUSI_OPT_GA_BATCH      the reference order's Gamma / alphaTilde path:
+ *                          0 = automatic (the batch path for calls of more
+ *                          than 16 tables), 1 = the per-table kernel,
+ *                          2 = the batch path whenever alpha batches exist
+ *                          (NUSI_OPT_ALPHA_KERNEL 0), also for calls of few
+ *                          tables.  The batch path evaluates the
+ *                          dilogarithms that do not read the coupling once
+ *                          per batch and the others with a batch's tables on
+ *                          neighbouring lanes (k_ga_dilogs_batch).  Any value
+ *                          gives the same tables bit for bit.
+ *   NUSI_OPT_GA_PRE_MB     the batch path's block of dilogarithm values: at
+ *                          most this many MiB, the batches run in chunks
+ *                          that fit (at least one batch); 0 = 512.  Any
+ *                          value gives the same tables bit for bit.
+ *   NUSI_OPT_GA_PRE_KB     the same budget in KiB (> 0: it holds instead of
+ *                          NUSI_OPT_GA_PRE_MB): a small grid's batch takes
+ *                          far less than a MiB (21 KB per table at N_E = 45),
+ *                          and the tests cut such a call into chunks. */
+#define NUSI_OPT_GA_BATCH 9
+#define NUSI_OPT_GA_PRE_MB 10
+#define NUSI_OPT_GA_PRE_KB 11
 int nusi_plan_set_option(nusi_plan *plan, int option, int value);
 /* per-point NUSI_WARN_* bits of the last call */
 int nusi_plan_warnings(nusi_plan *plan, int *out, int n);
@@ -296,6 +317,10 @@ int nusi_plan_warnings(nusi_plan *plan, int *out, int n);
  * "k_alpha_batch", "k_cascade_bs"); for reports -- bench.py's roofline lines.  No reference
  * counterpart. */
 int nusi_plan_kernels(const nusi_plan *plan, const char **alpha, const char **cascade);
+/* The Gamma / alphaTilde path of the last call (a static string): "k_gamma_alphat" (the per-table kernel),
+ * "k_ga_dilogs + k_gamma_alphat[pre]" (calls of few tables) or "k_ga_dilogs_batch + k_gamma_alphat[pre]" (the batch
+ * path, NUSI_OPT_GA_BATCH). */
+int nusi_plan_ga_kernel(const nusi_plan *plan, const char **ga);
 /* Copy point `i`'s Stage-A tables of the last call to the host (parity
  * tests): Gamma[T], alphaTilde[T], alpha packed transposed [T(T-1)/2] with
  * alpha(n,m), n<m, at m(m-1)/2+n.  Any pointer may be NULL. */

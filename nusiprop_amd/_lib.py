@@ -53,7 +53,7 @@ EXPORTS = [
     "nusi_plan_create", "nusi_plan_destroy", "nusi_plan_load_phiphi", "nusi_plan_grid", "nusi_plan_evolve",
     "nusi_plan_evolve_host", "nusi_plan_stage_ms", "nusi_plan_profile_begin", "nusi_plan_profile_end",
     "nusi_plan_warnings", "nusi_plan_tables", "nusi_evolve_batch", "nusi_plan_set_cascade",
-    "nusi_plan_kernels", "nusi_plan_set_option",
+    "nusi_plan_kernels", "nusi_plan_ga_kernel", "nusi_plan_set_option",
     "nusi_plan_source_axis", "nusi_plan_set_source", "nusi_source_axis", "nusi_set_source",
 ]
 
@@ -63,6 +63,7 @@ OPT_ALPHA_BATCH, OPT_ALPHA_KERNEL, OPT_CASCADE_RHS, OPT_STEP_PASSES, OPT_SHIFT_R
 OPT_REFERENCE_ORDER = 6
 OPT_CASCADE_SYNC = 7
 OPT_REFO_CORNER_MB = 8
+OPT_GA_BATCH, OPT_GA_PRE_MB, OPT_GA_PRE_KB = 9, 10, 11
 
 _lib = None
 
@@ -112,6 +113,7 @@ def load():
         "nusi_plan_set_cascade": (i, [vp, i]),
         "nusi_plan_set_option": (i, [vp, i, i]),
         "nusi_plan_kernels": (i, [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p)]),
+        "nusi_plan_ga_kernel": (i, [vp, ctypes.POINTER(ctypes.c_char_p)]),
         "nusi_plan_source_axis": (i, [vp, ip, dp, dp, dp]),
         "nusi_plan_set_source": (i, [vp, i, dp, dp]),
         "nusi_source_axis": (i, [vp, ip, dp, dp, dp]),

@@ -430,6 +430,10 @@ struct nusi_plan {
                                     // 0 = the shared-algorithm order (opt-in fast mode)
     int cascade_sync = 0;           // NUSI_OPT_CASCADE_SYNC: 0 = auto, 2 = block-synchronous (the same kernel; 1 is refused)
     int corner_mb = 0;              // NUSI_OPT_REFO_CORNER_MB: the member-corner block's budget (0 = automatic)
+    int ga_batch = 0;               // NUSI_OPT_GA_BATCH: 0 = auto, 1 = the per-table Gamma / alphaTilde kernel, 2 = the
+                                    // batch path (k_ga_dilogs_batch) whenever batches exist
+    int ga_pre_mb = 0;              // NUSI_OPT_GA_PRE_MB: the batch path's block budget (0 = kGaPreBudget)
+    int ga_pre_kb = 0;              // NUSI_OPT_GA_PRE_KB: the same in KiB (> 0: it holds instead)
     size_t fh_doubles = 0;          // capacity of d_fh in doubles (the block-synchronous kernels' FIFOs)
     nusi_plan* shift = nullptr;     // ... its plan: the same grid with K more redshift steps (axis T + K)
     int2* d_smap = nullptr;         // per shifted table: base index in `shift`, bin offset
@@ -465,6 +469,8 @@ struct nusi_plan {
     double* d_kt = nullptr;        // the k-split alpha path's term buffer (TablesDev::Kt), kt_doubles doubles
     size_t kt_doubles = 0;
     double* d_gpre = nullptr;      // the reference order's Gamma / alphaTilde dilogarithms (TablesDev::Gpre)
+    nusi::GaBatchDev gab{};        // ... per alpha batch, of scans (ga_batch_ensure, launch_gamma_alphat)
+    const char* ga_kernel = "";    // the Gamma / alphaTilde path of the latest call (nusi_plan_ga_kernel)
     size_t gpre_doubles = 0;
     std::shared_ptr<SplineStore> spl;
     nusi::SplineSet* d_nospl = nullptr;   // an empty spline set in device memory (no phi-phi tables loaded)
@@ -627,20 +633,60 @@ constexpr size_t kMCornerBudget = size_t(8) << 30;
 constexpr int kOverlapTables = 16;   // calls of at most this many tables overlap Gamma / alphaTilde with alpha
 constexpr size_t kStageBytes = size_t(4) << 20;   // nusi_plan_evolve_host's pinned output staging, at most
 constexpr int kSplitTables = 2;   // calls of at most this many tables (no phi-phi) run the k-split alpha path
+// the plan's distinct bin edges in device memory (MCornerDev::eu, ue, ub), uploaded once by whoever needs them first:
+// the member-corner block or the Gamma / alphaTilde batch path
+int edges_ensure(nusi_plan* p)
+{
+    nusi::MCornerDev& mc = p->mc;
+    if (mc.eu) return NUSI_OK;
+    std::vector<int> eu, ub;
+    std::vector<double> ue;
+    nusi::mcorner_edges(p->grid.T, p->grid.lo.data(), p->grid.hi.data(), eu, ue);
+    nusi::ga_batch_edge_bins(p->grid.T, eu, (int)ue.size(), ub);
+    HIPCHECK(hipMalloc(&mc.ue, sizeof(double) * ue.size()));
+    HIPCHECK(hipMemcpy(mc.ue, ue.data(), sizeof(double) * ue.size(), hipMemcpyHostToDevice));
+    HIPCHECK(hipMalloc(&mc.ub, sizeof(int) * ub.size()));
+    HIPCHECK(hipMemcpy(mc.ub, ub.data(), sizeof(int) * ub.size(), hipMemcpyHostToDevice));
+    mc.U = (int)ue.size();
+    mc.NC = (long long)mc.U * (mc.U + 1) / 2;
+    HIPCHECK(hipMalloc(&mc.eu, sizeof(int) * eu.size()));   // (last: mc.eu marks the set complete)
+    HIPCHECK(hipMemcpy(mc.eu, eu.data(), sizeof(int) * eu.size(), hipMemcpyHostToDevice));
+    return NUSI_OK;
+}
+
+// The Gamma / alphaTilde batch path's block (GaBatchDev) for a call of ntab tables in nbatch batches: the whole call
+// where that fits the budget (NUSI_OPT_GA_PRE_MB, or NUSI_OPT_GA_PRE_KB in KiB; default kGaPreBudget, C4 72 + 4 MB),
+// else the budget and at least the largest batch -- launch_gamma_alphat then runs chunks of whole batches.  Grown
+// on demand; an explicit budget also shrinks it, so that a test can hold it to a size.
+constexpr size_t kGaPreBudget = size_t(512) << 20;
+int ga_batch_ensure(nusi_plan* p, int ntab, int nbatch, int budget_mb, int budget_kb)
+{
+    if (int r = edges_ensure(p)) return r;
+    nusi::GaBatchDev& gb = p->gab;
+    const int T = p->grid.T, U = p->mc.U;
+    int nbmax = 1;
+    for (int b = 0; b < nbatch; ++b) nbmax = std::max(nbmax, (int)((unsigned)p->h_batches[b] >> 24));
+    const bool set = budget_mb > 0 || budget_kb > 0;
+    const size_t budget = budget_kb > 0 ? ((size_t)budget_kb << 10) : budget_mb > 0 ? ((size_t)budget_mb << 20) : kGaPreBudget;
+    const size_t want = std::max(std::min(nusi::ga_batch_bytes(T, U, ntab, nbatch), budget), nusi::ga_batch_bytes(T, U, nbmax, 1));
+    if (gb.bytes < want || (set && gb.bytes != want)) {
+        hipFree(gb.buf);
+        gb.buf = nullptr;
+        gb.bytes = 0;
+        HIPCHECK(hipMalloc(&gb.buf, want));
+        gb.bytes = want;
+    }
+    gb.eu = p->mc.eu;
+    gb.ue = p->mc.ue;
+    gb.ub = p->mc.ub;
+    gb.U = U;
+    return NUSI_OK;
+}
+
 int mcorner_ensure(nusi_plan* p, int ntab, const AlphaBatches& ab, int budget_mb)
 {
     nusi::MCornerDev& mc = p->mc;
-    if (!mc.eu) {
-        std::vector<int> eu;
-        std::vector<double> ue;
-        nusi::mcorner_edges(p->grid.T, p->grid.lo.data(), p->grid.hi.data(), eu, ue);
-        HIPCHECK(hipMalloc(&mc.eu, sizeof(int) * eu.size()));
-        HIPCHECK(hipMemcpy(mc.eu, eu.data(), sizeof(int) * eu.size(), hipMemcpyHostToDevice));
-        HIPCHECK(hipMalloc(&mc.ue, sizeof(double) * ue.size()));
-        HIPCHECK(hipMemcpy(mc.ue, ue.data(), sizeof(double) * ue.size(), hipMemcpyHostToDevice));
-        mc.U = (int)ue.size();
-        mc.NC = (long long)mc.U * (mc.U + 1) / 2;
-    }
+    if (int r = edges_ensure(p)) return r;
     const size_t per = sizeof(double) * 6 * (size_t)mc.NC;
     if (mc.buf && budget_mb == 0 && mc.cap_tables >= ntab && per * mc.cap_tables <= kMCornerBudget)
         return NUSI_OK;   // every table of the call fits the block already (no hipMemGetInfo per call)
@@ -854,6 +900,8 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->mc.buf);
     hipFree(pl->mc.eu);
     hipFree(pl->mc.ue);
+    hipFree(pl->mc.ub);
+    hipFree(pl->gab.buf);
     hipFree(pl->d_scratch);
     hipFree(pl->d_kt);
     hipFree(pl->d_gpre);
@@ -1240,8 +1288,16 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
     }
     // a call of few tables in the reference order: Gamma / alphaTilde's GSL dilogarithms one per work-item first
     // (k_ga_dilogs; 2.2 MB per table at N_E = 300).  The one place "few" is decided: launch_gamma_alphat follows Gpre
+    // Scans in the reference order with batches formed: the dilogarithms per alpha batch instead (k_ga_dilogs_batch;
+    // NUSI_OPT_GA_BATCH).  Automatic: every call of more than kOverlapTables tables, whatever its batches' sizes -- 32
+    // m_phi x {1, 2, 3, 4, 8, 32} couplings at N_E = 300 all measured faster than the per-table kernel, batches of
+    // one table included (0.31 -> 0.17 ms).  The shift-reuse base plan keeps the per-table kernel.
+    const bool ga_batch = refo && pl->alpha_kind == 0 && nd > 0 && nbatch > 0 && pl->ga_batch != 1 &&
+                          (pl->ga_batch == 2 || nd > kOverlapTables);
+    if (ga_batch)
+        if (int r = ga_batch_ensure(pl, nd, nbatch, pl->ga_pre_mb, pl->ga_pre_kb)) return r;
     pl->tabs.Gpre = nullptr;
-    if (refo && nbase == 0 && nd > 0 && nd <= kOverlapTables) {
+    if (refo && !ga_batch && nbase == 0 && nd > 0 && nd <= kOverlapTables) {
         const size_t need = nusi::gamma_alphat_pre_doubles(pl->gd.T, nd);
         if (pl->gpre_doubles < need) {
             hipFree(pl->d_gpre);
@@ -1292,11 +1348,18 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
         HIPCHECK(hipEventRecord(pl->ev_fork, s));
         HIPCHECK(hipStreamWaitEvent(pl->side, pl->ev_fork, 0));
         join.armed = true;
-        HIPCHECK(nusi::launch_gamma_alphat(pl->gd, pl->d_tpts, nd, spl, pl->tabs, pl->d_warn, pl->side, refo));
+        HIPCHECK(nusi::launch_gamma_alphat(pl->gd, pl->d_tpts, nd, spl, pl->tabs, pl->d_warn, pl->side, refo,
+                                           ga_batch ? &pl->gab : nullptr, pl->d_batches, pl->h_batches, nbatch));
+        pl->ga_kernel = nusi::last_ga_kernel();
         HIPCHECK(hipEventRecord(ev[1], pl->side));
     } else {
-        if (nd) HIPCHECK(nusi::launch_gamma_alphat(pl->gd, pl->d_tpts, nd, spl, pl->tabs, pl->d_warn, s, refo));
+        if (nd) {
+            HIPCHECK(nusi::launch_gamma_alphat(pl->gd, pl->d_tpts, nd, spl, pl->tabs, pl->d_warn, s, refo,
+                                               ga_batch ? &pl->gab : nullptr, pl->d_batches, pl->h_batches, nbatch));
+            pl->ga_kernel = nusi::last_ga_kernel();
+        }
         if (sp) HIPCHECK(nusi::launch_gamma_alphat(sp->gd, sp->d_tpts, nbase, spl, sp->tabs, sp->d_warn, s, refo));
+        if (sp && !nd) pl->ga_kernel = nusi::last_ga_kernel();
         HIPCHECK(hipEventRecord(ev[1], s));
     }
     if (nd) {
@@ -1432,6 +1495,18 @@ int nusi_plan_set_option(nusi_plan* pl, int option, int value)
         if (value < 0 || value > (1 << 20)) return fail(NUSI_EPARAM, "NUSI_OPT_REFO_CORNER_MB outside [0, 2^20]");
         pl->corner_mb = value;
         return NUSI_OK;
+    case NUSI_OPT_GA_BATCH:
+        if (value < 0 || value > 2) return fail(NUSI_EPARAM, "NUSI_OPT_GA_BATCH outside [0, 2]");
+        pl->ga_batch = value;
+        return NUSI_OK;
+    case NUSI_OPT_GA_PRE_MB:
+        if (value < 0 || value > (1 << 20)) return fail(NUSI_EPARAM, "NUSI_OPT_GA_PRE_MB outside [0, 2^20]");
+        pl->ga_pre_mb = value;
+        return NUSI_OK;
+    case NUSI_OPT_GA_PRE_KB:
+        if (value < 0 || value > (1 << 30)) return fail(NUSI_EPARAM, "NUSI_OPT_GA_PRE_KB outside [0, 2^30]");
+        pl->ga_pre_kb = value;
+        return NUSI_OK;
     case NUSI_OPT_REFERENCE_ORDER:
         if (value < 0 || value > 1) return fail(NUSI_EPARAM, "NUSI_OPT_REFERENCE_ORDER outside [0, 1]");
         pl->ref_order = value;
@@ -1474,6 +1549,13 @@ int nusi_plan_kernels(const nusi_plan* pl, const char** alpha, const char** casc
     if (!pl->ran) return fail(NUSI_ESTATE, "no evolve has run on this plan");
     if (alpha) *alpha = pl->alpha_kernel;
     if (cascade) *cascade = pl->cascade_kernel;
+    return NUSI_OK;
+}
+
+int nusi_plan_ga_kernel(const nusi_plan* pl, const char** ga)
+{
+    if (!pl->ran) return fail(NUSI_ESTATE, "no evolve has run on this plan");
+    if (ga) *ga = pl->ga_kernel;
     return NUSI_OK;
 }
 
@@ -1586,7 +1668,7 @@ void pool_give(nusi_plan* pl)
     if (pl->max_points == 1 && !pl->shift) {
         // the defaults of nusi_plan_create
         pl->alpha_batch = pl->alpha_kind = pl->cascade_rhs = pl->step_passes = pl->shift_max = 0;
-        pl->cascade_sync = pl->corner_mb = 0;
+        pl->cascade_sync = pl->corner_mb = pl->ga_batch = pl->ga_pre_mb = pl->ga_pre_kb = 0;
         pl->ref_order = 1;
         pl->cascade_kind = NUSI_CASCADE_AUTO;
         pl->prof_max = pl->prof_n = 0;

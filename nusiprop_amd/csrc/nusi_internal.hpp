@@ -69,12 +69,39 @@ struct MCornerDev {
     double* ue = nullptr;    // [U]: the energy of each edge
     long long NC = 0;
     int U = 0, cap_tables = 0;
+    int* ub = nullptr;       // [2 U]: the bins an edge bounds (ga_batch_edge_bins; k_ga_dilogs_batch)
 };
+// Scans in the reference order: Gamma / alphaTilde's dilogarithms per alpha batch (k_ga_dilogs_batch) in one
+// plan-owned block buf of `bytes`, laid out per launch chunk of whole batches (nt tables, nk batches; ga_batch_bytes):
+// [nt][3][ga_gdep_doubles] the values that read gr, [nk][3][ga_shared_doubles] the batch's shared ones, [nt] ints: the
+// batch of each table.  eu, ue, ub, U: the plan's distinct edges (MCornerDev's).
+struct GaBatchDev {
+    char* buf = nullptr;
+    size_t bytes = 0;
+    const int* eu = nullptr;
+    const double* ue = nullptr;
+    const int* ub = nullptr;
+    int U = 0;
+};
+struct GaBatchView {   // one chunk's blocks as k_gamma_alphat<true, 1, true> reads them (pc0: its first table)
+    const double* gd = nullptr;
+    const double* sh = nullptr;
+    const int* tb = nullptr;
+    const int* eu = nullptr;
+    int U = 0, pc0 = 0;
+};
+size_t ga_batch_bytes(int T, int U, int ntab, int nbatch);
+void ga_batch_edge_bins(int T, const std::vector<int>& eu, int U, std::vector<int>& ub);
 // ref: NUSI_OPT_REFERENCE_ORDER (the kernels' kRef instances: the reference's own operation order for the complex
 // dilogarithms and the s-t interference member leaves, bit-identical to the oracle's ora_set_reference_order(1))
 size_t gamma_alphat_pre_doubles(int T, int npts);   // TablesDev::Gpre's size
+// gb != nullptr (ref only): the batch path -- k_ga_dilogs_batch over the call's alpha batches (device `batches`, the
+// same in host memory h_batches; they cover the tables 0 .. npts - 1 in order), then k_gamma_alphat<true, 1, true>,
+// in chunks of whole batches that fit gb->bytes (one chunk, and one dispatch of each kernel, where the call fits)
 hipError_t launch_gamma_alphat(const GridDev& g, const Point* pts, int npts, const SplineSet* spl, TablesDev t,
-                               int* warn, hipStream_t s, bool ref);
+                               int* warn, hipStream_t s, bool ref, const GaBatchDev* gb = nullptr,
+                               const int* batches = nullptr, const int* h_batches = nullptr, int nbatches = 0);
+const char* last_ga_kernel();   // what the latest launch_gamma_alphat on this thread ran (nusi_plan_ga_kernel)
 // batches: device [nbatches] of first table | count << 24 (count <= gmax), tables of a batch sharing
 // m_phi, the masses and the channel flags (nullptr: every table alone).  kernel = NUSI_OPT_ALPHA_KERNEL:
 // 0 -- core tiles on the big-batch kernel k_alpha_batch (any count < 256; the first nb_plain batches without

@@ -56,20 +56,22 @@ struct LdsSink {
 NUSI_FN double shfl_dn(double x) { return __shfl_down(x, 1, 64); }
 NUSI_FN double shfl_upd(double x) { return __shfl_up(x, 1, 64); }
 NUSI_FN cd shfl_dn(cd z) { return cd{__shfl_down(z.r, 1, 64), __shfl_down(z.i, 1, 64)}; }
-// kPre (reference order, calls of few tables): every dilogarithm value from k_ga_dilogs' block pre (ga_pre_load)
-// instead of the lanes' own GSL calls
+// kPre (reference order): every dilogarithm value from memory instead of the lanes' own GSL calls -- kParts = 2 (calls
+// of few tables): k_ga_dilogs' block pre (ga_pre_load); kParts = 1 (scans): k_ga_dilogs_batch's blocks bv_
+// (ga_pre_load_batch), the grid's y the tables of one launch chunk from bv_.pc0 on.  A value no branch of the bin
+// uses was not evaluated; its field is loaded and enters no result
 template <bool kRef, int kParts, bool kPre = false>
 __global__ __launch_bounds__(192 * kParts) __attribute__((amdgpu_waves_per_eu(kGaWaves, kGaWaves))) void k_gamma_alphat(GridDev g, const Point* __restrict__ pts, const SplineSet* __restrict__ splp,
                                                      double* __restrict__ G, double* __restrict__ At,
                                                      int* __restrict__ warn, int* __restrict__ wmin,
-                                                     const double* __restrict__ pre = nullptr)
+                                                     const double* __restrict__ pre = nullptr, GaBatchView bv_ = GaBatchView{})
 {
     __shared__ double v[3][kGaTerms][64], raw[kParts == 2 ? 3 : 1][kGaTerms][64];
     __shared__ int wk[3 * kParts][64];
     const SplineSet& spl = *splp;   // (in global memory: a by-value copy would live in scratch)
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), k = wv / kParts, part = wv - k * kParts;
-    const int p = blockIdx.y;
+    const int p = blockIdx.y + (kPre && kParts == 1 ? bv_.pc0 : 0);
     const int n = blockIdx.x * 63 + lane, T = g.T;
     const bool act = lane < 63 && n < T;
     const Point& P = pts[p];
@@ -80,7 +82,19 @@ __global__ __launch_bounds__(192 * kParts) __attribute__((amdgpu_waves_per_eu(kG
     const bool up_sh = act && (n + 1 == T || g.hi[n] == g.lo[n + 1]);   // bin n's upper edge is lane + 1's
     int w = 0;
     LdsSink sk{&v[k][0][lane], &raw[kParts == 2 ? k : 0][0][lane]};
-    if (kPre) {
+    if (kPre && kParts == 1) {   // (scans: the batch blocks of k_ga_dilogs_batch, tables bv_.pc0 .. of this chunk)
+        if (act) {
+            GammaEdgePair ge;
+            AlphatEdgePair ae;
+            AlphatBinVals bv;
+            const int pl = p - bv_.pc0, U = bv_.U;
+            ga_pre_load_batch(bv_.gd + (size_t)(pl * 3 + k) * ga_gdep_doubles(T, U),
+                              bv_.sh + (size_t)(bv_.tb[pl] * 3 + k) * ga_shared_doubles(T, U), T, U, n, bv_.eu[2 * n],
+                              bv_.eu[2 * n + 1], ge, ae, bv);
+            if (gam) gamma_k<kRef, -1>(P, k, lo, hi, sk, w, &ge);
+            else alphat_k<kRef, -1>(P, spl, k, lo, hi, sk, w, &ae, &bv);
+        }
+    } else if (kPre) {
         if (act) {
             GammaEdgePair ge;
             AlphatEdgePair ae;
@@ -224,11 +238,83 @@ __global__ __launch_bounds__(64) void k_ga_dilogs(GridDev g, const Point* __rest
     if (nv == 2) o[T] = v[1];
 }
 
+// Scans in the reference order: the same dilogarithms per alpha batch (ga_batch_job, nusi_physics.hpp) -- grid
+// (ga_batch_blocks of the chunk's largest batch, the chunk's batches b0 .., 3 mass states).  The values that read
+// gr = Gamma_phi / m_phi, one per (table, distinct edge or bin), with the batch's tables on neighbouring lanes: their
+// arguments differ in gr only, so a wave's GSL calls take the same branches and nearly the same series lengths
+// (bins on the lanes: 64 different ones).  Every other value once per batch, where the per-table kernel evaluates it
+// once per table.  tb: the batch of each table of the chunk, for k_gamma_alphat<true, 1, true>.
+__global__ __launch_bounds__(64) void k_ga_dilogs_batch(GridDev g, const Point* __restrict__ pts,
+                                                        const int* __restrict__ batches, int b0, const double* __restrict__ ue,
+                                                        const int* __restrict__ ub, double* __restrict__ gd,
+                                                        double* __restrict__ sh, int* __restrict__ tb, int U, int pc0)
+{
+    const int lane = threadIdx.x, bi = blockIdx.y, k = blockIdx.z, T = g.T;
+    const int bw = batches[b0 + bi];
+    const int p0 = bw & 0xffffff, nb = (int)((unsigned)bw >> 24);
+    if (blockIdx.x == 0 && k == 0)
+        for (int q = lane; q < nb; q += 64) tb[p0 - pc0 + q] = bi;
+    int vk, item, q;
+    if (!ga_batch_job(blockIdx.x, lane, nb, T, U, &vk, &item, &q)) return;
+    const Point& P = pts[p0 + q];
+    if (!ga_batch_need(P, k, vk, item, g.lo, g.hi, ub)) return;   // (a resonant-only batch evaluates nothing)
+    const bool edge = ga_kind_edge(vk);
+    double v[2];
+    const int nv = ga_batch_value(P, k, vk, edge ? ue[item] : 0.0, edge ? 0.0 : g.lo[item], edge ? 0.0 : g.hi[item], v);
+    int st;
+    const size_t f = ga_batch_field(vk, item, T, U, &st);
+    double* o = vk < kGaGdepKinds ? gd + (size_t)((p0 + q - pc0) * 3 + k) * ga_gdep_doubles(T, U) + f
+                                  : sh + (size_t)(bi * 3 + k) * ga_shared_doubles(T, U) + f;
+    o[0] = v[0];
+    if (nv == 2) o[st] = v[1];
+}
+
 size_t gamma_alphat_pre_doubles(int T, int npts) { return (size_t)3 * kGaPreFields * T * npts; }
+size_t ga_batch_bytes(int T, int U, int ntab, int nbatch)
+{
+    return sizeof(double) * 3 * (ga_gdep_doubles(T, U) * ntab + ga_shared_doubles(T, U) * nbatch) + sizeof(int) * (size_t)ntab;
+}
+void ga_batch_edge_bins(int T, const std::vector<int>& eu, int U, std::vector<int>& ub)
+{
+    ub.assign(2 * (size_t)U, -1);
+    edge_bins(T, eu.data(), U, ub.data());
+}
+
+static thread_local const char* g_ga_kernel = "";
+const char* last_ga_kernel() { return g_ga_kernel; }
 
 hipError_t launch_gamma_alphat(const GridDev& g, const Point* pts, int npts, const SplineSet* spl, TablesDev t,
-                               int* warn, hipStream_t s, bool ref)
+                               int* warn, hipStream_t s, bool ref, const GaBatchDev* gb, const int* batches,
+                               const int* h_batches, int nbatches)
 {
+    if (ref && gb) {   // (scans, the host layer's choice: the batches' dilogarithms first, in chunks that fit gb->buf)
+        g_ga_kernel = "k_ga_dilogs_batch + k_gamma_alphat[pre]";
+        const int T = g.T, U = gb->U;
+        for (int b0 = 0; b0 < nbatches;) {
+            int b1 = b0, nt = 0, nbmax = 0;
+            while (b1 < nbatches) {
+                const int nb = (int)((unsigned)h_batches[b1] >> 24);
+                if (ga_batch_bytes(T, U, nt + nb, b1 - b0 + 1) > gb->bytes) break;
+                nt += nb;
+                nbmax = std::max(nbmax, nb);
+                ++b1;
+            }
+            if (b1 == b0) return hipErrorInvalidValue;   // (the block holds at least the largest batch: ga_batch_ensure)
+            const int pc0 = h_batches[b0] & 0xffffff;
+            double* gd = reinterpret_cast<double*>(gb->buf);
+            double* sh = gd + 3 * ga_gdep_doubles(T, U) * nt;
+            int* tb = reinterpret_cast<int*>(sh + 3 * ga_shared_doubles(T, U) * (b1 - b0));
+            hipLaunchKernelGGL(k_ga_dilogs_batch, dim3(ga_batch_blocks(nbmax, T, U), b1 - b0, 3), dim3(64), 0, s, g, pts,
+                               batches, b0, gb->ue, gb->ub, gd, sh, tb, U, pc0);
+            GaBatchView v;
+            v.gd = gd; v.sh = sh; v.tb = tb; v.eu = gb->eu; v.U = U; v.pc0 = pc0;
+            hipLaunchKernelGGL((k_gamma_alphat<true, 1, true>), dim3((T + 62) / 63, nt, 2), dim3(192), 0, s, g, pts, spl,
+                               t.G, t.At, warn, t.Wmin, nullptr, v);
+            b0 = b1;
+        }
+        return hipGetLastError();
+    }
+    g_ga_kernel = ref && t.Gpre ? "k_ga_dilogs + k_gamma_alphat[pre]" : "k_gamma_alphat";
     dim3 grid((g.T + 62) / 63, npts, 2);   // (63 bins per workgroup: the edge-shared lanes)
     if (ref && t.Gpre) {   // (calls of few tables, the host layer's choice: the dilogarithms one per work-item first)
         hipLaunchKernelGGL(k_ga_dilogs, dim3((g.T + 63) / 64, npts, 3 * kGaPreSlots), dim3(64), 0, s, g, pts, t.Gpre);
@@ -521,13 +607,8 @@ __global__ __launch_bounds__(256) void k_alpha_mcorner(const Point* __restrict__
 void mcorner_edges(int T, const double* lo, const double* hi, std::vector<int>& eu, std::vector<double>& ue)
 {
     eu.assign(2 * (size_t)T, 0);
-    ue.clear();
-    for (int b = 0; b < T; ++b) {
-        if (b == 0 || !(lo[b] == hi[b - 1])) ue.push_back(lo[b]);   // else the previous bin's upper edge
-        eu[2 * b] = (int)ue.size() - 1;
-        ue.push_back(hi[b]);
-        eu[2 * b + 1] = (int)ue.size() - 1;
-    }
+    ue.assign(2 * (size_t)T, 0.0);
+    ue.resize((size_t)edge_numbers(T, lo, hi, eu.data(), ue.data()));
 }
 
 

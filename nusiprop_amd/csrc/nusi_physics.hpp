@@ -551,35 +551,34 @@ NUSI_FN double alphat_entry(const Point& P, const SplineSet& spl, double Em, dou
 // Values no branch of the bin reads are evaluated too (and not read).  v[0], v[1] at field *f (v[1]: complex only);
 // returns the count.
 constexpr int kGaPreSlots = 22, kGaPreFields = 32;
-NUSI_FN int ga_pre_slot(const Point& P, int k, double Em, double Ep, int slot, double* v, int* f)
+// One edge value at energy E -- which: 0 ls, 1 l1s, 2 cz (Gamma) | 3 e78, 4 e51, 5 e1o, 6 e1p (alphaTilde) -- and one
+// bin value of [Em, Ep] -- b: 0 d26a, 1 d26b, 2 d43a, 3 d43b, 4 .. 7 c1 .. c4 -- with their arguments formed here
+// for every caller (ga_pre_slot, k_ga_dilogs_batch); v[0], v[1] (complex only), returns the count
+NUSI_FN int ga_edge_value(const Point& P, int k, double E, int which, double* v)
 {
-    if (slot < 6) {   // Gamma's edge values (reference order: no conj z value)
-        const int side = slot / 3, which = slot - 3 * side;
+    if (which < 3) {   // Gamma's edge values (reference order: no conj z value)
         GammaEdgeVals e{};
-        gamma_edge_vals<true>(P, k, side ? Ep : Em, which == 0 ? kGeLs : which == 1 ? kGeL1s : kGeCz, e);
-        *f = 4 * side + which;
+        gamma_edge_vals<true>(P, k, E, which == 0 ? kGeLs : which == 1 ? kGeL1s : kGeCz, e);
         if (which == 0) { v[0] = e.ls; return 1; }
         if (which == 1) { v[0] = e.l1s; return 1; }
         v[0] = e.cz.r; v[1] = e.cz.i;
         return 2;
     }
-    if (slot < 14) {   // alphaTilde's edge values
-        const int side = (slot - 6) / 4, which = slot - 6 - 4 * side;
-        AlphatEdgeVals e{};
-        alphat_edge_vals<true>(P, k, side ? Ep : Em, which == 0 ? kAe78 : which == 1 ? kAe51 : which == 2 ? kAe1o : kAe1p, e);
-        const int f0 = 8 + 6 * side;
-        if (which == 0) { *f = f0; v[0] = e.e78.r; v[1] = e.e78.i; return 2; }
-        if (which == 1) { *f = f0 + 2; v[0] = e.e51.r; v[1] = e.e51.i; return 2; }
-        *f = f0 + 2 + which;
-        v[0] = which == 2 ? e.e1o : e.e1p;
-        return 1;
-    }
+    const int a = which - 3;   // alphaTilde's edge values
+    AlphatEdgeVals e{};
+    alphat_edge_vals<true>(P, k, E, a == 0 ? kAe78 : a == 1 ? kAe51 : a == 2 ? kAe1o : kAe1p, e);
+    if (a == 0) { v[0] = e.e78.r; v[1] = e.e78.i; return 2; }
+    if (a == 1) { v[0] = e.e51.r; v[1] = e.e51.i; return 2; }
+    v[0] = a == 2 ? e.e1o : e.e1p;
+    return 1;
+}
+NUSI_FN int ga_bin_value(const Point& P, int k, double Em, double Ep, int b, double* v)
+{
     // alphaTilde's bin values: tm, tp, z2 .. z6 and the combination's arguments as alphat_k forms them
     const double mphi = P.mphi, Ga = P.Ga, m2 = mphi * mphi, gr = Ga / mphi, mk = P.mn[k];
     double tp = -2 * mk * Ep / m2, tm = -2 * mk * Em / m2;
     if (fabs(tm + 1) < 1e-7) tm += tm * 1e-6;
     if (fabs(tp + 1) < 1e-7) tp += tp * 1e-6;
-    const int b = slot - 14;
     if (b < 4) {
         const cd dt_m = C(2 + tm, -gr);
         cd z;
@@ -588,14 +587,28 @@ NUSI_FN int ga_pre_slot(const Point& P, int k, double Em, double Ep, int slot, d
         else if (b == 2) z = (1 + tm - tp) / dt_m;
         else z = 1 / dt_m;
         const cd d = cli2_t<true>(z);
-        *f = 20 + 2 * b;
         v[0] = d.r; v[1] = d.i;
         return 2;
     }
     const double x = b == 4 ? 1 + 1 / (-2 + tp) : b == 5 ? (-1 + tm) / (-2 + tp) : b == 6 ? 1 + (1 + tm - tp) / tp : 1 + 1 / tp;
-    *f = 28 + (b - 4);
     v[0] = li2_t<true>(x);
     return 1;
+}
+NUSI_FN int ga_pre_slot(const Point& P, int k, double Em, double Ep, int slot, double* v, int* f)
+{
+    if (slot < 6) {   // Gamma's edge values
+        const int side = slot / 3, which = slot - 3 * side;
+        *f = 4 * side + which;
+        return ga_edge_value(P, k, side ? Ep : Em, which, v);
+    }
+    if (slot < 14) {   // alphaTilde's edge values
+        const int side = (slot - 6) / 4, which = slot - 6 - 4 * side;
+        *f = 8 + 6 * side + (which == 0 ? 0 : which == 1 ? 2 : 2 + which);
+        return ga_edge_value(P, k, side ? Ep : Em, 3 + which, v);
+    }
+    const int b = slot - 14;
+    *f = b < 4 ? 20 + 2 * b : 28 + (b - 4);
+    return ga_bin_value(P, k, Em, Ep, b, v);
 }
 // the fields of (point, k, bin n) -> the pairs and bin values gamma_k / alphat_k take (fb: field 0 of (point, k),
 // fields T doubles apart)
@@ -609,6 +622,135 @@ NUSI_FN void ga_pre_load(const double* fb, int T, int n, GammaEdgePair& ge, Alph
     ae.hi.e78 = C(F(14), F(15)); ae.hi.e51 = C(F(16), F(17)); ae.hi.e1o = F(18); ae.hi.e1p = F(19);
     bv.d26a = C(F(20), F(21)); bv.d26b = C(F(22), F(23)); bv.d43a = C(F(24), F(25)); bv.d43b = C(F(26), F(27));
     bv.c1 = F(28); bv.c2 = F(29); bv.c3 = F(30); bv.c4 = F(31);
+}
+
+// Scans in the reference order (k_ga_dilogs_batch): the same values per batch -- the tables of one alpha batch share
+// m_phi, the masses and the flags, and s, t read nothing else of a point, so every value that does not read
+// gr = Gamma_phi / m_phi is one value for the whole batch.  Value kinds vk:
+//   0 cz, 1 e51 (per table and distinct edge), 2 d43a, 3 d43b (per table and bin)          -- read gr
+//   4 ls, 5 l1s, 6 e78, 7 e1o, 8 e1p (per batch and distinct edge), 9 d26a, 10 d26b, 11 .. 14 c1 .. c4 (per batch and bin)
+// over the U distinct edges of the table axis (mcorner_edges: an edge two bins share is evaluated once).  Two blocks:
+// kGaGdep(T, U) doubles per (table, k) and kGaShared(T, U) per (batch, k), each field a row of U or T doubles
+// (ga_batch_field: the offset of the value's first double, *stride to a complex value's second).
+// the distinct edges of a table axis (hi[b - 1] == lo[b] bitwise: one edge): eu[2 b + side] the edge number of bin
+// b's lower / upper edge, ue[u] its energy (room for 2 T); returns U.  ub[2 u], ub[2 u + 1]: the bin whose upper /
+// lower edge is u, -1 for none (an edge bounds at most one bin on each side).
+inline int edge_numbers(int T, const double* lo, const double* hi, int* eu, double* ue)
+{
+    int U = 0;
+    for (int b = 0; b < T; ++b) {
+        if (b == 0 || !(lo[b] == hi[b - 1])) ue[U++] = lo[b];   // else the previous bin's upper edge
+        eu[2 * b] = U - 1;
+        ue[U++] = hi[b];
+        eu[2 * b + 1] = U - 1;
+    }
+    return U;
+}
+inline void edge_bins(int T, const int* eu, int U, int* ub)
+{
+    for (int i = 0; i < 2 * U; ++i) ub[i] = -1;
+    for (int b = 0; b < T; ++b) {
+        ub[2 * eu[2 * b + 1]] = b;
+        ub[2 * eu[2 * b] + 1] = b;
+    }
+}
+constexpr int kGaKinds = 15, kGaGdepKinds = 4;
+NUSI_FN size_t ga_gdep_doubles(int T, int U) { return 4 * ((size_t)U + T); }
+NUSI_FN size_t ga_shared_doubles(int T, int U) { return 6 * (size_t)U + 8 * (size_t)T; }
+NUSI_FN bool ga_kind_edge(int vk) { return vk < 2 || (vk >= 4 && vk < 9); }
+// ga_edge_value's `which` / ga_bin_value's `b` of a kind
+NUSI_FN int ga_kind_sub(int vk)
+{
+    return vk == 0 ? 2 : vk == 1 ? 4 : vk == 2 ? 2 : vk == 3 ? 3 : vk == 4 ? 0 : vk == 5 ? 1 : vk == 6 ? 3 : vk == 7 ? 5
+           : vk == 8 ? 6 : vk == 9 ? 0 : vk == 10 ? 1 : vk - 7;
+}
+NUSI_FN size_t ga_batch_field(int vk, int item, int T, int U, int* stride)
+{
+    const size_t u = (size_t)U, t = (size_t)T;
+    *stride = ga_kind_edge(vk) ? U : T;
+    const size_t f0 = vk == 0 ? 0 : vk == 1 ? 2 * u : vk == 2 ? 4 * u : vk == 3 ? 4 * u + 2 * t        // the (table, k) block
+                      : vk < 6 ? (vk - 4) * u : vk == 6 ? 2 * u : vk == 7 ? 4 * u : vk == 8 ? 5 * u   // the (batch, k) block
+                      : vk == 9 ? 6 * u : vk == 10 ? 6 * u + 2 * t : 6 * u + (size_t)(vk - 7) * t;
+    return f0 + item;
+}
+// The producer's job map.  A batch of nb tables takes ga_batch_blocks workgroups of 64 jobs per mass state: the kinds
+// that read gr first, job j of a kind = item j / nb of table j % nb (the table index fastest, as k_alpha_mcorner
+// numbers its jobs: a wave holds the batch's tables at one or two neighbouring edges or bins, whose arguments differ
+// in gr only), then the shared kinds, one job per edge or bin.  false: the work-item has no job.
+NUSI_FN int ga_batch_blocks(int nb, int T, int U)
+{
+    return 2 * ((U * nb + 63) / 64) + 2 * ((T * nb + 63) / 64) + 5 * ((U + 63) / 64) + 6 * ((T + 63) / 64);
+}
+NUSI_FN bool ga_batch_job(int blk, int lane, int nb, int T, int U, int* vk, int* item, int* q)
+{
+    const int gU = (U * nb + 63) / 64, gT = (T * nb + 63) / 64, sU = (U + 63) / 64, sT = (T + 63) / 64;
+    int n, j;
+    if (blk < 2 * gU) { *vk = blk / gU; j = (blk - *vk * gU) * 64 + lane; n = U; }
+    else if ((blk -= 2 * gU) < 2 * gT) { const int c = blk / gT; *vk = 2 + c; j = (blk - c * gT) * 64 + lane; n = T; }
+    else if ((blk -= 2 * gT) < 5 * sU) { const int c = blk / sU; *vk = 4 + c; *item = (blk - c * sU) * 64 + lane; *q = 0; return *item < U; }
+    else if ((blk -= 5 * sU) < 6 * sT) { const int c = blk / sT; *vk = 9 + c; *item = (blk - c * sT) * 64 + lane; *q = 0; return *item < T; }
+    else return false;
+    *item = j / nb;
+    *q = j - *item * nb;
+    return *item < n;
+}
+// alphaTilde's bin values that alphat_k<true, -1> reads for bin (Em, Ep) (the Dirac s-t interference reads d51 and
+// d78 only, and has no t-u combination)
+constexpr unsigned kAbD26 = 1, kAbD43 = 2, kAbC = 4;
+NUSI_FN unsigned alphat_bin_need(const Point& P, int k, double Em, double Ep)
+{
+    if (!P.non_resonant || !P.majorana) return 0;
+    const double mphi = P.mphi, Ga = P.Ga, m2 = mphi * mphi, gr = Ga / mphi;
+    const double tp = alphat_t(P.mn[k], Ep, m2), tm = alphat_t(P.mn[k], Em, m2);
+    unsigned m = 0;
+    if (!(-tp < 1e-2 && -tm < 1e-2) && !(-tp > 1e2 && -tm > 1e2)) m |= kAbC;
+    if (!(-tp < 1e-5)) {
+        const cd dt_m = C(2 + tm, -gr);
+        if (dilogdiff_c_mid(C(1 / (1 + tm)), C(1 - tp / (1 + tm)))) m |= kAbD26;
+        if (dilogdiff_c_mid((1 + tm - tp) / dt_m, 1 / dt_m)) m |= kAbD43;
+    }
+    return m;
+}
+// Does any branch read the job's value?  An edge value: of the one or two bins the edge bounds (ub[2 u]: the bin
+// whose upper edge it is, ub[2 u + 1]: whose lower edge, -1: none).  For the shared kinds the answer is the same for
+// every table of the batch.  A value nobody needs is not written; the consumer loads its field and uses it nowhere.
+NUSI_FN bool ga_batch_need(const Point& P, int k, int vk, int item, const double* lo, const double* hi, const int* ub)
+{
+    if (!P.non_resonant) return false;
+    if (!ga_kind_edge(vk)) {
+        const unsigned m = alphat_bin_need(P, k, lo[item], hi[item]);
+        return (m & (vk == 2 || vk == 3 ? kAbD43 : vk == 9 || vk == 10 ? kAbD26 : kAbC)) != 0;
+    }
+    const bool gam = vk == 0 || vk == 4 || vk == 5;
+    const unsigned bit = vk == 0 ? kGeCz : vk == 4 ? kGeLs : vk == 5 ? kGeL1s : vk == 1 ? kAe51 : vk == 6 ? kAe78 : vk == 7 ? kAe1o : kAe1p;
+    unsigned m = 0;
+    for (int side = 0; side < 2; ++side) {
+        const int b = ub[2 * item + side];
+        if (b >= 0) m |= gam ? gamma_edge_need<-1>(P, k, lo[b], hi[b]) : alphat_edge_need<-1>(P, k, lo[b], hi[b]);
+    }
+    return (m & bit) != 0;
+}
+// one job's value into v (the count returned): E the edge's energy (edge kinds), [Em, Ep] the bin (bin kinds)
+NUSI_FN int ga_batch_value(const Point& P, int k, int vk, double E, double Em, double Ep, double* v)
+{
+    return ga_kind_edge(vk) ? ga_edge_value(P, k, E, ga_kind_sub(vk), v) : ga_bin_value(P, k, Em, Ep, ga_kind_sub(vk), v);
+}
+// the blocks of (table, k) gd and (batch, k) sh -> the pairs and bin values of bin n, whose edges are numbers ulo, uhi
+NUSI_FN void ga_pre_load_batch(const double* gd, const double* sh, int T, int U, int n, int ulo, int uhi, GammaEdgePair& ge,
+                               AlphatEdgePair& ae, AlphatBinVals& bv)
+{
+    auto R = [&](int vk, int item) { int st; return (vk < kGaGdepKinds ? gd : sh)[ga_batch_field(vk, item, T, U, &st)]; };
+    auto Z = [&](int vk, int item) {
+        int st;
+        const double* x = (vk < kGaGdepKinds ? gd : sh) + ga_batch_field(vk, item, T, U, &st);
+        return C(x[0], x[st]);
+    };
+    ge.lo.ls = R(4, ulo); ge.lo.l1s = R(5, ulo); ge.lo.cz = Z(0, ulo);
+    ge.hi.ls = R(4, uhi); ge.hi.l1s = R(5, uhi); ge.hi.cz = Z(0, uhi);
+    ae.lo.e78 = Z(6, ulo); ae.lo.e51 = Z(1, ulo); ae.lo.e1o = R(7, ulo); ae.lo.e1p = R(8, ulo);
+    ae.hi.e78 = Z(6, uhi); ae.hi.e51 = Z(1, uhi); ae.hi.e1o = R(7, uhi); ae.hi.e1p = R(8, uhi);
+    bv.d26a = Z(9, n); bv.d26b = Z(10, n); bv.d43a = Z(2, n); bv.d43b = Z(3, n);
+    bv.c1 = R(11, n); bv.c2 = R(12, n); bv.c3 = R(13, n); bv.c4 = R(14, n);
 }
 
 // ---------------------------------------------------------------------------

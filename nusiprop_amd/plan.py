@@ -128,7 +128,9 @@ class Plan:
         the opt-in scan mode sharing tables across m_phi on the r^(-o/2) lattice, o <= K; only tables with g <= 0.05
         share, the others are built directly), OPT_REFERENCE_ORDER (1, the default = the tables in the reference's own
         arithmetic: GSL's dilogarithm algorithms on the reference's arguments; 0 = the shared-algorithm order), OPT_REFO_CORNER_MB (the reference order's
-        member-corner block budget in MiB, 0 = automatic); include/nusi.h."""
+        member-corner block budget in MiB, 0 = automatic), OPT_GA_BATCH (the reference order's Gamma / alphaTilde path:
+        0 auto, 1 the per-table kernel, 2 the batch path whenever batches exist), OPT_GA_PRE_MB (the batch path's block
+        budget in MiB, 0 = 512; OPT_GA_PRE_KB: the same in KiB); include/nusi.h."""
         _lib.check(_lib.load().nusi_plan_set_option(self._h, int(option), int(value)))
 
     def profile_begin(self, max_calls):
@@ -156,6 +158,12 @@ class Plan:
         a, c = ctypes.c_char_p(), ctypes.c_char_p()
         _lib.check(_lib.load().nusi_plan_kernels(self._h, ctypes.byref(a), ctypes.byref(c)))
         return a.value.decode(), c.value.decode()
+
+    def ga_kernel(self):
+        """The Gamma / alphaTilde path of the last call, e.g. 'k_ga_dilogs_batch + k_gamma_alphat[pre]'."""
+        g = ctypes.c_char_p()
+        _lib.check(_lib.load().nusi_plan_ga_kernel(self._h, ctypes.byref(g)))
+        return g.value.decode()
 
     def tables(self, i):
         """Point i's Stage-A tables of the last call: Gamma[T], alphaTilde[T], alpha packed [T(T-1)/2]."""
