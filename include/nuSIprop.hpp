@@ -167,6 +167,14 @@ public:
         check(nusi_source_axis(h_, M, lo, hi, z));
     }
     void set_source(const double* S, const double* w = nullptr) { check(nusi_set_source(h_, S, w)); }
+    // The response matrix of this object's parameter point (include/nusi.h, nusi_response): G / G_fla [M][3][N_bins_E]
+    // (either may be null), G[n][k][b] the flux of mass state k in bin b per unit of S[n], for the redshift weight w
+    // (null = the star-formation rate); flux = norm * sum_n G[n] S[n].  The object's fluxes and source are untouched.
+    void response(double* G, double* G_fla = nullptr, const double* w = nullptr)
+    {
+        check(nusi_set_params(h_, mphi, g, mntot, si, norm));
+        check(nusi_response(h_, w, G, G_fla));
+    }
 
 private:
     nusi_handle* h_ = nullptr;

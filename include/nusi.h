@@ -118,6 +118,11 @@ int nusi_check_energy_conservation(nusi_handle *h, double *out);
  * spectrum's energy integral. */
 int nusi_source_axis(const nusi_handle *h, int *M, double *lo, double *hi, double *z);
 int nusi_set_source(nusi_handle *h, const double *S, const double *w);
+/* The response matrix of the object's parameter point (no reference
+ * counterpart): nusi_plan_response_host on the object's plan, G / G_fla
+ * [M][3][N] host arrays (either may be NULL), w [Nz] or NULL.  The object's
+ * fluxes, its source (nusi_set_source) and the plan's slots are not involved. */
+int nusi_response(nusi_handle *h, const double *w, double *G, double *G_fla);
 /* results of the last evolve(), row-major [k][b] (mass basis) / [f][b] (flavour) */
 int nusi_get_flux(const nusi_handle *h, double *out_3xN);      /* get_flux(i,j)     :359-381 */
 int nusi_get_flux_fla(const nusi_handle *h, double *out_3xN);  /* get_flux_fla(i,j) :383-405 */
@@ -181,7 +186,52 @@ int nusi_plan_set_source(nusi_plan *plan, int slot, const double *S /* [M] */, c
 int nusi_plan_evolve(nusi_plan *plan, const nusi_params *pts, int n, double *d_flux, double *d_flux_fla, void *stream);
 /* Same with host result buffers; synchronous. */
 int nusi_plan_evolve_host(nusi_plan *plan, const nusi_params *pts, int n, double *flux, double *flux_fla);
-/* Kernel times (ms) of the last nusi_plan_evolve*: [0] Gamma/alphaTilde
+/* Response matrices (no reference counterpart).  Every flux is linear in the
+ * source, and a separable source is S [M] on the source axis and w [Nz]
+ * (nusi_plan_set_source).  For point p (every field that enters its Stage-A
+ * tables; si, norm and source_model are ignored), redshift weights w (NULL =
+ * get_SFR) and source-axis bin n,
+ *     G[p][n][k][b]
+ * is the mass-basis flux nusi_plan_evolve gives a point whose tabulated slot
+ * holds S = e_n (the unit vector) with weights w and norm = 1, and
+ * G_fla[p][n][f][b] the same in the flavour basis: n-major arrays
+ * [p][n][3][N] of n * M * 3 * N doubles, so that for a spectrum S and norm c
+ *     flux = c * sum_n G[n] * S[n].
+ * From the cascade's direction, exactly: G[p][0] is all zero (bin 0 is never
+ * read) and G[p][n][.][b] = +0.0 for b >= n.
+ * nusi_plan_response evolves the n points' response matrices into the DEVICE
+ * arrays d_G / d_G_fla (either may be NULL); Stage A is nusi_plan_evolve's
+ * (deduplication, batches, every NUSI_OPT_*), and afterwards
+ * nusi_plan_tables, nusi_plan_warnings, nusi_plan_stage_ms and
+ * nusi_plan_kernels refer to this call.  The cascade is the impulse-source
+ * instance of the block-synchronous kernel (k_cascade_bs_impulse: 16 source
+ * bins of one table per workgroup), launched in chunks of whole tables under
+ * NUSI_OPT_RESPONSE_FIFO_KB; grids it does not fit, and plans set to
+ * NUSI_CASCADE_WAVEFRONT / REG / LDS, run the impulses through the scalar
+ * k_cascade.  n <= max_points bounds the tables of a call, not tables x M.
+ * nusi_plan_set_source and the plan's slots are not involved: a response
+ * neither reads nor changes them.  NUSI_EPARAM for a negative or non-finite
+ * weight.  nusi_plan_response_host: the same into host arrays, synchronous.
+ *
+ * nusi_plan_response_apply: Q spectra on ntab resident response matrices,
+ *     out[t][q][r] = scale[q] * acc,   acc = 0.0, and for n = 1 .. M-1
+ *     ascending  acc = acc + G[t][n][r] * S[q][n]
+ * (the product and the sum rounded separately, no fma; rows whose bin b >= n
+ * are skipped, which changes no bit of a G as above), r over the 3 N rows of
+ * G or of G_fla -- call it once for each array.  d_G [ntab][M][3][N] and
+ * d_out [ntab][Q][3][N] are DEVICE pointers; S [Q][M] and scale [Q] (NULL =
+ * 1) are host vectors and are copied.  NUSI_EPARAM for a negative or
+ * non-finite S (nusi_plan_set_source's rule) or a non-finite scale.  The call
+ * is ordered on `stream` (NULL = the plan's own, where a response with
+ * stream = NULL ran).  nusi_plan_response_apply_host: host G and out. */
+int nusi_plan_response(nusi_plan *plan, const nusi_params *pts, int n, const double *w /* [Nz] or NULL */,
+                       double *d_G, double *d_G_fla, void *stream);
+int nusi_plan_response_host(nusi_plan *plan, const nusi_params *pts, int n, const double *w, double *G, double *G_fla);
+int nusi_plan_response_apply(nusi_plan *plan, const double *d_G, int ntab, const double *S /* [Q][M] */, int Q,
+                             const double *scale /* [Q] or NULL */, double *d_out, void *stream);
+int nusi_plan_response_apply_host(nusi_plan *plan, const double *G, int ntab, const double *S, int Q,
+                                  const double *scale, double *out);
+/* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);
 /* Kernel-time accounting over many calls (bench): after profile_begin, each
@@ -310,6 +360,13 @@ int nusi_plan_set_cascade(nusi_plan *plan, int kind);
 #define NUSI_OPT_GA_BATCH 9
 #define NUSI_OPT_GA_PRE_MB 10
 #define NUSI_OPT_GA_PRE_KB 11
+/*   NUSI_OPT_RESPONSE_FIFO_KB  nusi_plan_response's impulse cascade hands its
+ *                          step passes on through a FIFO of 3 N 16 doubles
+ *                          per workgroup (2.5 MB per table at N_E = 300): at
+ *                          most this many KiB, the tables run in chunks that
+ *                          fit (at least one table); 0 = 1 GiB.  Any value
+ *                          gives the same bits. */
+#define NUSI_OPT_RESPONSE_FIFO_KB 12
 int nusi_plan_set_option(nusi_plan *plan, int option, int value);
 /* per-point NUSI_WARN_* bits of the last call */
 int nusi_plan_warnings(nusi_plan *plan, int *out, int n);

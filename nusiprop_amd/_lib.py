@@ -55,6 +55,8 @@ EXPORTS = [
     "nusi_plan_warnings", "nusi_plan_tables", "nusi_evolve_batch", "nusi_plan_set_cascade",
     "nusi_plan_kernels", "nusi_plan_ga_kernel", "nusi_plan_set_option",
     "nusi_plan_source_axis", "nusi_plan_set_source", "nusi_source_axis", "nusi_set_source",
+    "nusi_plan_response", "nusi_plan_response_host", "nusi_plan_response_apply", "nusi_plan_response_apply_host",
+    "nusi_response",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -64,6 +66,7 @@ OPT_REFERENCE_ORDER = 6
 OPT_CASCADE_SYNC = 7
 OPT_REFO_CORNER_MB = 8
 OPT_GA_BATCH, OPT_GA_PRE_MB, OPT_GA_PRE_KB = 9, 10, 11
+OPT_RESPONSE_FIFO_KB = 12
 
 _lib = None
 
@@ -118,6 +121,11 @@ def load():
         "nusi_plan_set_source": (i, [vp, i, dp, dp]),
         "nusi_source_axis": (i, [vp, ip, dp, dp, dp]),
         "nusi_set_source": (i, [vp, dp, dp]),
+        "nusi_plan_response": (i, [vp, pp, i, dp, vp, vp, vp]),
+        "nusi_plan_response_host": (i, [vp, pp, i, dp, dp, dp]),
+        "nusi_plan_response_apply": (i, [vp, vp, i, dp, i, dp, vp, vp]),
+        "nusi_plan_response_apply_host": (i, [vp, dp, i, dp, i, dp, dp]),
+        "nusi_response": (i, [vp, dp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

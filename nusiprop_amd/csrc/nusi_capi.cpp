@@ -4,6 +4,7 @@
 // mixing matrix, masses, normalisation; nuSIprop.hpp:102-171, 184-205) and
 // the energy-conservation diagnostic; the table build and the cascade run
 // on the GPU (nusi_kernels.hip).  There is no CPU fallback.
+#include <climits>
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -445,6 +446,19 @@ struct nusi_plan {
     double* d_slots = nullptr;      // tabulated sources (nusi_plan_set_source): [slot_cap][cascade_slot_doubles], S then w
     int slot_cap = 0;
     std::vector<unsigned char> slot_set;   // [slot_cap]: the slot holds a source
+    // nusi_plan_response (the impulse cascade) and nusi_plan_response_apply
+    int response_fifo_kb = 0;       // NUSI_OPT_RESPONSE_FIFO_KB: the impulse cascade's FIFO budget (0 = kResponseFifoBytes)
+    double* d_rw = nullptr;         // the call's redshift weights [Nz]
+    std::vector<double> h_rw;
+    double* d_rslots = nullptr;     // the scalar fallback's unit-vector slots [T + 1][cascade_slot_doubles] ...
+    std::vector<double> h_rslots;
+    nusi::Point* d_rpts = nullptr;  // ... its temporary point records of one chunk [kResponseChunk] ...
+    double* d_rscr = nullptr;       // ... and a chunk's output where the caller passed NULL [kResponseChunk][3 N]
+    double* d_app = nullptr;        // apply: the spectra S [Q][T + 1], then scale [Q]
+    size_t app_doubles = 0;
+    std::vector<double> h_app;
+    hipEvent_t ev_app = nullptr;    // end of the latest apply (the next one reuses d_app / h_app)
+    bool app_ran = false;
     std::vector<int> slot_of;       // table slot of each point of the last call
     int last_ntab = 0;
     int* d_warn = nullptr;
@@ -896,6 +910,12 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->d_smap);
     if (pl->h_smap) hipHostFree(pl->h_smap);
     hipFree(pl->d_fh);
+    if (pl->ev_app) hipEventDestroy(pl->ev_app);
+    hipFree(pl->d_rw);
+    hipFree(pl->d_rslots);
+    hipFree(pl->d_rpts);
+    hipFree(pl->d_rscr);
+    hipFree(pl->d_app);
     nusi::alpha_tiles_destroy(&pl->atiles);
     hipFree(pl->mc.buf);
     hipFree(pl->mc.eu);
@@ -1123,7 +1143,18 @@ int nusi_plan_set_source(nusi_plan* pl, int slot, const double* S, const double*
     return NUSI_OK;
 }
 
-int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flux, double* d_fla, void* stream)
+// nusi_plan_response's part of a call (plan_run): the redshift weights (validated; NULL = get_SFR)
+struct ResponseCall {
+    const double* w;
+};
+static int response_prepare(nusi_plan* pl, const ResponseCall& rc, int n, hipStream_t s);
+static int response_cascade(nusi_plan* pl, int n, bool all_nr, double* d_G, double* d_G_fla, hipStream_t s);
+
+// One call of a plan: Stage A for the points' distinct tables (deduplication, batches, every NUSI_OPT_*), then the
+// cascade -- the points' own sources into d_flux / d_fla (nusi_plan_evolve; rc == nullptr), or the impulse cascade
+// of every point's response matrix (nusi_plan_response; d_flux / d_fla are then G / G_fla and may stay NULL).
+static int plan_run(nusi_plan* pl, const nusi_params* pts, int n, double* d_flux, double* d_fla, void* stream,
+                    const ResponseCall* rc)
 {
     if (n < 1 || n > pl->max_points) return fail(NUSI_EPARAM, "number of points outside [1, max_points]");
     HIPCHECK(hipSetDevice(pl->device));
@@ -1134,7 +1165,13 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
         HIPCHECK(hipStreamWaitEvent(s, pl->ev_done, 0));     // so are d_pts, the tables and the warnings: one plan
     }                                                        // serialises its calls, whatever streams they use
     for (int i = 0; i < n; ++i) {
-        const int r = build_point(pl, pts[i], pl->h_pts[i]);
+        nusi_params q = pts[i];
+        if (rc) {   // a response ignores the point's source: si, norm and source_model (the table key reads none)
+            q.source_model = NUSI_SOURCE_POWER_LAW;
+            q.si = 2.0;
+            q.norm = 1.0;
+        }
+        const int r = build_point(pl, q, pl->h_pts[i]);
         if (r) return r;
     }
     // one Stage-A table per distinct (mphi, g, Gamma_phi, masses, |U|^2, flags): the tables do not
@@ -1195,7 +1232,7 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
         if (pl->slot_of[i] < nd) pl->h_pts[i].tslot = pl->slot_of[i] = perm[pl->slot_of[i]];
     const int cap = ab.cap, nbatch = ab.nbatch, nb_plain = ab.nb_plain;
     const size_t N3 = (size_t)3 * pl->grid.N;
-    if (!d_flux || !d_fla) {
+    if (!rc && (!d_flux || !d_fla)) {
         if (!pl->d_scratch) HIPCHECK(hipMalloc(&pl->d_scratch, sizeof(double) * 2 * N3 * pl->max_points));
         if (!d_flux) d_flux = pl->d_scratch;
         if (!d_fla) d_fla = pl->d_scratch + N3 * pl->max_points;
@@ -1218,7 +1255,9 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
     const bool bs = kind == NUSI_CASCADE_MFMA && nusi::cascade_bs_config(pl->gd, 1, force_passes) != 0;
     int ngb = 0, ngidx = 0;
     int bs_nwg[3] = {0, 0, 0};   // workgroups of P = 16, 2, 1 (their groups in h_gbgrp in that order)
-    if (bs) {
+    if (rc) {   // (the impulse cascade's own buffers; it groups source-axis bins, not points)
+        if (int r = response_prepare(pl, *rc, n, s)) return r;
+    } else if (bs) {
         const int rmax = force_passes ? 1 : pl->cascade_rhs == 0 ? 16 : pl->cascade_rhs;
         const bool g16 = rmax >= 3 && nusi::cascade_bs_config(pl->gd, 16, false) != 0;
         const bool g2 = rmax >= 2 && nusi::cascade_bs_config(pl->gd, 2, false) != 0;
@@ -1380,7 +1419,9 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
     if (bs && any_dsnb) HIPCHECK(nusi::launch_source_dsnb(pl->gd, pl->d_pts, n, pl->d_src, s));
     if (bs && any_tab) HIPCHECK(nusi::launch_source_tab(pl->gd, pl->d_pts, n, pl->d_slots, pl->d_src, s));
     const char* gb_name = nullptr;
-    if (bs) {
+    if (rc) {
+        if (int r = response_cascade(pl, n, all_nr, d_flux, d_fla, s)) return r;
+    } else if (bs) {
         const int Pk[3] = {16, 2, 1};
         static const char* const names[8] = {"", "k_cascade_bs_gamma", "k_cascade_bs_pairs", "k_cascade_bs_gamma + pairs",
                                              "k_cascade_bs", "k_cascade_bs_gamma + k_cascade_bs",
@@ -1413,6 +1454,203 @@ int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flu
     pl->last_n = n;
     pl->last_ntab = ntab;
     return NUSI_OK;
+}
+
+int nusi_plan_evolve(nusi_plan* pl, const nusi_params* pts, int n, double* d_flux, double* d_fla, void* stream)
+{
+    return plan_run(pl, pts, n, d_flux, d_fla, stream, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Response matrices (nusi_plan_response, nusi_plan_response_apply)
+// ---------------------------------------------------------------------------
+constexpr size_t kResponseFifoBytes = size_t(1) << 30;   // the impulse cascade's FIFO, at most (NUSI_OPT_RESPONSE_FIFO_KB = 0)
+constexpr int kResponseChunk = 4096;                     // columns per launch of the scalar fallback
+
+static bool response_impulse(const nusi_plan* pl)
+{
+    const int kind = pl->cascade_kind == NUSI_CASCADE_AUTO ? NUSI_CASCADE_MFMA : pl->cascade_kind;
+    return kind == NUSI_CASCADE_MFMA && nusi::cascade_impulse_fits(pl->gd);
+}
+// tables per launch of the impulse cascade: whole tables whose FIFOs fit the budget (at least one)
+static int response_chunk(const nusi_plan* pl, int n)
+{
+    const size_t per = sizeof(double) * nusi::cascade_impulse_scratch_doubles(pl->gd);
+    const size_t budget = pl->response_fifo_kb > 0 ? (size_t)pl->response_fifo_kb << 10 : kResponseFifoBytes;
+    return (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / per));
+}
+
+// Before the call's upload: the buffers of the response's cascade (allocations may synchronise) and its weights.
+static int response_prepare(nusi_plan* pl, const ResponseCall& rc, int n, hipStream_t s)
+{
+    const HostGrid& G = pl->grid;
+    const nusi::GridDev& g = pl->gd;
+    if ((long long)n * (G.T + 1) > (long long)INT_MAX) return fail(NUSI_EPARAM, "response: points x source-axis bins exceed 2^31 - 1");
+    pl->h_rw.assign(rc.w ? rc.w : G.sfr.data(), (rc.w ? rc.w : G.sfr.data()) + G.Nz);
+    if (response_impulse(pl)) {
+        if (!pl->d_rw) HIPCHECK(hipMalloc(&pl->d_rw, sizeof(double) * G.Nz));
+        if (g.Nz - 1 > 6) {   // (one pass of 6 steps hands nothing on)
+            const size_t fhd = nusi::cascade_impulse_scratch_doubles(g) * (size_t)response_chunk(pl, n);
+            if (fhd > pl->fh_doubles) {
+                hipFree(pl->d_fh);
+                pl->d_fh = nullptr;
+                pl->fh_doubles = 0;
+                HIPCHECK(hipMalloc(&pl->d_fh, sizeof(double) * fhd));
+                pl->fh_doubles = fhd;
+            }
+        }
+        HIPCHECK(hipMemcpyAsync(pl->d_rw, pl->h_rw.data(), sizeof(double) * G.Nz, hipMemcpyHostToDevice, s));
+        return NUSI_OK;
+    }
+    // the scalar fallback: slot n of a private slot array holds S = e_n and the weights
+    const size_t per = nusi::cascade_slot_doubles(g), M = (size_t)G.T + 1;
+    if (!pl->d_rslots) HIPCHECK(hipMalloc(&pl->d_rslots, sizeof(double) * per * M));
+    if (!pl->d_rpts) HIPCHECK(hipMalloc(&pl->d_rpts, sizeof(nusi::Point) * kResponseChunk));
+    if (!pl->d_rscr) HIPCHECK(hipMalloc(&pl->d_rscr, sizeof(double) * 3 * G.N * kResponseChunk));
+    pl->h_rslots.assign(per * M, 0.0);
+    for (size_t m = 0; m < M; ++m) {
+        pl->h_rslots[per * m + m] = 1.0;
+        memcpy(&pl->h_rslots[per * m + M], pl->h_rw.data(), sizeof(double) * G.Nz);
+    }
+    HIPCHECK(hipMemcpyAsync(pl->d_rslots, pl->h_rslots.data(), sizeof(double) * per * M, hipMemcpyHostToDevice, s));
+    return NUSI_OK;
+}
+
+// The cascade of a response call: G[p][n][3][N] / G_fla (either may be NULL) of the call's n points.
+static int response_cascade(nusi_plan* pl, int n, bool all_nr, double* d_G, double* d_Gf, hipStream_t s)
+{
+    const nusi::GridDev& g = pl->gd;
+    const size_t N3 = (size_t)3 * g.N, M = (size_t)g.T + 1;
+    if (response_impulse(pl)) {
+        // column 0 (bin 0 is never read): zeros; the kernel writes the columns 1 .. T
+        for (double* out : {d_G, d_Gf})
+            if (out) HIPCHECK(hipMemset2DAsync(out, sizeof(double) * M * N3, 0, sizeof(double) * N3, (size_t)n, s));
+        const int chunk = response_chunk(pl, n);
+        for (int p0 = 0; p0 < n; p0 += chunk)   // whole tables under the FIFO budget, one after the other on s
+            HIPCHECK(nusi::launch_cascade_impulse(g, pl->d_pts, p0, std::min(chunk, n - p0), pl->d_rw, pl->tabs, pl->d_fh,
+                                                  d_G, d_Gf, s, all_nr));
+        return NUSI_OK;
+    }
+    // the unchanged scalar k_cascade on temporary points: column c = p M + n is point p on the private slot n
+    // (norm = 1), a chunk of columns per launch; its outputs are contiguous in the n-major layout
+    std::vector<nusi::Point> tmp;
+    const size_t ncol = (size_t)n * M;
+    for (size_t c0 = 0; c0 < ncol; c0 += kResponseChunk) {
+        const size_t cnt = std::min<size_t>(kResponseChunk, ncol - c0);
+        tmp.resize(cnt);
+        for (size_t c = 0; c < cnt; ++c) {
+            const size_t p = (c0 + c) / M, m = (c0 + c) - p * M;
+            tmp[c] = pl->h_pts[p];
+            tmp[c].source = NUSI_SOURCE_TABULATED + (int)m;
+            tmp[c].norm = tmp[c].norm_total = 1.0;
+        }
+        HIPCHECK(hipMemcpyAsync(pl->d_rpts, tmp.data(), sizeof(nusi::Point) * cnt, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipStreamSynchronize(s));   // (tmp is reused; the slow path)
+        HIPCHECK(nusi::launch_cascade_exact(g, pl->d_rpts, (int)cnt, pl->tabs, pl->d_rslots, d_G ? d_G + c0 * N3 : pl->d_rscr,
+                                            d_Gf ? d_Gf + c0 * N3 : pl->d_rscr, s));
+    }
+    return NUSI_OK;
+}
+
+static int check_weights(const nusi_plan* pl, const double* w)
+{
+    if (w)
+        for (int i = 0; i < pl->grid.Nz; ++i)
+            if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(NUSI_EPARAM, "source redshift weight: an entry is negative or not finite");
+    return NUSI_OK;
+}
+
+int nusi_plan_response(nusi_plan* pl, const nusi_params* pts, int n, const double* w, double* d_G, double* d_G_fla,
+                       void* stream)
+{
+    if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
+    if (int r = check_weights(pl, w)) return r;
+    const ResponseCall rc{w};
+    return plan_run(pl, pts, n, d_G, d_G_fla, stream, &rc);
+}
+
+int nusi_plan_response_host(nusi_plan* pl, const nusi_params* pts, int n, const double* w, double* G, double* G_fla)
+{
+    if (!pl) {   // (no plan exists without a GPU: say so, as nusi_plan_create does)
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(NUSI_EHIP, "no HIP device available");
+        return fail(NUSI_EPARAM, "plan is NULL");
+    }
+    if (n < 1 || n > pl->max_points) return fail(NUSI_EPARAM, "number of points outside [1, max_points]");
+    HIPCHECK(hipSetDevice(pl->device));
+    const size_t nb = sizeof(double) * (size_t)n * (pl->grid.T + 1) * 3 * pl->grid.N;
+    double* d[2] = {nullptr, nullptr};
+    double* h[2] = {G, G_fla};
+    int r = NUSI_OK;
+    for (int k = 0; k < 2 && !r; ++k)
+        if (h[k] && hipMalloc(&d[k], nb) != hipSuccess) r = fail(NUSI_EHIP, "response: no device memory for the result");
+    if (!r) r = nusi_plan_response(pl, pts, n, w, d[0], d[1], nullptr);
+    if (!r && hipStreamSynchronize(pl->stream) != hipSuccess) r = fail(NUSI_EHIP, "response: the stream failed");
+    for (int k = 0; k < 2 && !r; ++k)
+        if (h[k] && hipMemcpy(h[k], d[k], nb, hipMemcpyDeviceToHost) != hipSuccess) r = fail(NUSI_EHIP, "response: copy to the host failed");
+    hipFree(d[0]);
+    hipFree(d[1]);
+    if (r) return r;
+    std::vector<int> wn(n);
+    r = nusi_plan_warnings(pl, wn.data(), n);
+    if (r) return r;
+    for (int v : wn)
+        if (v & nusi::kWarnSplineOOB) return fail(NUSI_EINTERP, "Error at interp: a phi-phi table lookup fell outside the node range");
+    return NUSI_OK;
+}
+
+int nusi_plan_response_apply(nusi_plan* pl, const double* d_G, int ntab, const double* S, int Q, const double* scale,
+                             double* d_out, void* stream)
+{
+    if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
+    if (!d_G || !d_out || !S) return fail(NUSI_EPARAM, "response apply: G, S and out must not be NULL");
+    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, "response apply: need ntab >= 1 and 1 <= Q <= 2^19");
+    const size_t M = (size_t)pl->grid.T + 1;
+    if ((long long)ntab * ((3 * pl->grid.N + 255) / 256) > (long long)INT_MAX) return fail(NUSI_EPARAM, "response apply: too many tables");
+    for (size_t e = 0; e < (size_t)Q * M; ++e)
+        if (!(S[e] >= 0.0) || !std::isfinite(S[e])) return fail(NUSI_EPARAM, "source spectrum: a bin integral is negative or not finite");
+    if (scale)
+        for (int q = 0; q < Q; ++q)
+            if (!std::isfinite(scale[q])) return fail(NUSI_EPARAM, "response apply: a scale is not finite");
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (!pl->ev_app) HIPCHECK(hipEventCreateWithFlags(&pl->ev_app, hipEventDisableTiming));
+    if (pl->app_ran) HIPCHECK(hipEventSynchronize(pl->ev_app));   // d_app / h_app are reused
+    const size_t need = (size_t)Q * M + (size_t)Q;
+    if (pl->app_doubles < need) {
+        hipFree(pl->d_app);
+        pl->d_app = nullptr;
+        pl->app_doubles = 0;
+        HIPCHECK(hipMalloc(&pl->d_app, sizeof(double) * need));
+        pl->app_doubles = need;
+    }
+    pl->h_app.assign(S, S + (size_t)Q * M);
+    if (scale) pl->h_app.insert(pl->h_app.end(), scale, scale + Q);
+    HIPCHECK(hipMemcpyAsync(pl->d_app, pl->h_app.data(), sizeof(double) * pl->h_app.size(), hipMemcpyHostToDevice, s));
+    HIPCHECK(nusi::launch_response_apply(pl->gd, d_G, ntab, pl->d_app, Q, scale ? pl->d_app + (size_t)Q * M : nullptr, d_out, s));
+    HIPCHECK(hipEventRecord(pl->ev_app, s));
+    pl->app_ran = true;
+    return NUSI_OK;
+}
+
+int nusi_plan_response_apply_host(nusi_plan* pl, const double* G, int ntab, const double* S, int Q, const double* scale,
+                                  double* out)
+{
+    if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
+    if (!G || !out || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response apply: G and out must not be NULL, ntab and Q >= 1");
+    HIPCHECK(hipSetDevice(pl->device));
+    const size_t N3 = (size_t)3 * pl->grid.N, gb = sizeof(double) * (size_t)ntab * (pl->grid.T + 1) * N3;
+    const size_t ob = sizeof(double) * (size_t)ntab * Q * N3;
+    double *dG = nullptr, *dO = nullptr;
+    int r = NUSI_OK;
+    if (hipMalloc(&dG, gb) != hipSuccess || hipMalloc(&dO, ob) != hipSuccess) r = fail(NUSI_EHIP, "response apply: no device memory");
+    if (!r && hipMemcpy(dG, G, gb, hipMemcpyHostToDevice) != hipSuccess) r = fail(NUSI_EHIP, "response apply: copy to the device failed");
+    if (!r) r = nusi_plan_response_apply(pl, dG, ntab, S, Q, scale, dO, nullptr);
+    if (!r && hipStreamSynchronize(pl->stream) != hipSuccess) r = fail(NUSI_EHIP, "response apply: the stream failed");
+    if (!r && hipMemcpy(out, dO, ob, hipMemcpyDeviceToHost) != hipSuccess) r = fail(NUSI_EHIP, "response apply: copy to the host failed");
+    hipFree(dG);
+    hipFree(dO);
+    return r;
 }
 
 int nusi_plan_profile_begin(nusi_plan* pl, int max_calls)
@@ -1506,6 +1744,10 @@ int nusi_plan_set_option(nusi_plan* pl, int option, int value)
     case NUSI_OPT_GA_PRE_KB:
         if (value < 0 || value > (1 << 30)) return fail(NUSI_EPARAM, "NUSI_OPT_GA_PRE_KB outside [0, 2^30]");
         pl->ga_pre_kb = value;
+        return NUSI_OK;
+    case NUSI_OPT_RESPONSE_FIFO_KB:
+        if (value < 0 || value > (1 << 30)) return fail(NUSI_EPARAM, "NUSI_OPT_RESPONSE_FIFO_KB outside [0, 2^30]");
+        pl->response_fifo_kb = value;
         return NUSI_OK;
     case NUSI_OPT_REFERENCE_ORDER:
         if (value < 0 || value > 1) return fail(NUSI_EPARAM, "NUSI_OPT_REFERENCE_ORDER outside [0, 1]");
@@ -1823,6 +2065,14 @@ int nusi_evolve(nusi_handle* h)
     r = nusi_plan_warnings(h->plan, &w, 1);
     h->warn = w & (NUSI_WARN_GAMMA | NUSI_WARN_ALPHATILDE | NUSI_WARN_ALPHA);
     return r;
+}
+
+// The response matrix of the object's parameter point (nusi_plan_response_host on its plan): the object's fluxes,
+// source and slot 0 are untouched.
+int nusi_response(nusi_handle* h, const double* w, double* G, double* G_fla)
+{
+    if (!h) return fail(NUSI_EPARAM, "object is NULL");
+    return nusi_plan_response_host(h->plan, &h->p, 1, w, G, G_fla);
 }
 
 int nusi_check_energy_conservation(nusi_handle* h, double* out)

@@ -129,6 +129,20 @@ size_t cascade_bs_scratch_doubles(const GridDev& g, int P);
 hipError_t launch_cascade_bs(const GridDev& g, const Point* pts, int P, const int* gidx, const int2* grp, int nwg,
                              TablesDev t, double* fh, double* flux, double* flux_fla, hipStream_t s, bool all_nr,
                              bool force_passes);
+// The impulse cascade k_cascade_bs_impulse (nusi_plan_response): the response matrix G[p][n][3][N] of the points
+// pts[p0 .. p0 + npts) -- column n the fluxes of a unit source in source-axis bin n (S = e_n, norm = 1, redshift
+// weights w [Nz], device) -- written at G / G_fla + ((p (T + 1) + n) 3 N) for n = 1 .. T (column 0 is the caller's
+// memset; either output may be nullptr).  cascade_impulse_groups workgroups per point, 16 bins each; fh: a FIFO of
+// cascade_impulse_scratch_doubles per point of the launch (step passes).  cascade_impulse_fits: the grid fits.
+bool cascade_impulse_fits(const GridDev& g);
+int cascade_impulse_groups(const GridDev& g);
+size_t cascade_impulse_scratch_doubles(const GridDev& g);
+hipError_t launch_cascade_impulse(const GridDev& g, const Point* pts, int p0, int npts, const double* w, TablesDev t,
+                                  double* fh, double* G, double* G_fla, hipStream_t s, bool all_nr);
+// k_response_apply: out[t][q][r] = scale[q] sum_n G[t][n][r] S[q][n] (n ascending from 1, no fma) over the 3 N rows
+// of ntab resident response matrices; S [Q][T + 1], scale [Q] (or nullptr), G and out in device memory
+hipError_t launch_response_apply(const GridDev& g, const double* G, int ntab, const double* S, int Q, const double* scale,
+                                 double* out, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

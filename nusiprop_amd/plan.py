@@ -115,6 +115,74 @@ class Plan:
                                                 ctypes.c_void_p(d_fla_ptr),
                                                 ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
+    # --- response matrices (include/nusi.h "Response matrices") ---
+    def _weights(self, z_weight):
+        from . import sources
+        if z_weight is None:
+            return None
+        return sources.weight_vector(z_weight, self.source_axis()[2])
+
+    def response(self, points, z_weight=None):
+        """The response matrices of the points: host arrays (G, G_fla) of shape (n, M, 3, N), G[p, n, k, b] the flux of
+        mass state k in bin b per unit of the source-axis bin integral S[n] (redshift weights z_weight: W(z_i) [Nz],
+        a callable of z, or None for the star-formation rate).  The points' si, norm and source_model are ignored, and
+        no source slot is read or changed.  flux = norm * sum_n G[p, n] S[n] (response.apply_host, apply_response)."""
+        arr = points if isinstance(points, ctypes.Array) else self.params_array(points)
+        n, M = len(arr), self.T + 1
+        G, Gf = np.zeros((n, M, 3, self.N)), np.zeros((n, M, 3, self.N))
+        w = self._weights(z_weight)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_host(self._h, arr, n, w.ctypes.data_as(dp) if w is not None else None,
+                                                       G.ctypes.data_as(dp), Gf.ctypes.data_as(dp)))
+        return G, Gf
+
+    def response_device(self, arr, d_G_ptr, d_G_fla_ptr, z_weight=None, stream_ptr=None):
+        """Asynchronous response into device buffers of n * M * 3 * N doubles (raw pointers; either may be 0 / None)."""
+        w = self._weights(z_weight)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response(self._h, arr, len(arr), w.ctypes.data_as(dp) if w is not None else None,
+                                                  ctypes.c_void_p(d_G_ptr) if d_G_ptr else None,
+                                                  ctypes.c_void_p(d_G_fla_ptr) if d_G_fla_ptr else None,
+                                                  ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def _spectra(self, spectra, scale):
+        from . import sources
+        lo, hi, _ = self.source_axis()
+        if callable(spectra) or (isinstance(spectra, np.ndarray) and spectra.ndim == 1):
+            spectra = [spectra]
+        S = np.ascontiguousarray([sources.spectrum_vector(sp, lo, hi) for sp in spectra], dtype=np.float64)
+        sc = None
+        if scale is not None:
+            sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (len(S),)))
+        return S, sc
+
+    def apply_response(self, G, spectra, scale=None):
+        """Q spectra on the response matrices G (ntab, M, 3, N) -- G or G_fla of ``response`` -- on the GPU:
+        out[t, q] = scale[q] * sum_n G[t, n] S[q, n], shape (ntab, Q, 3, N), bit for bit response.apply_host.
+        spectra: a sequence of bin-integral vectors [M] or callables dN/dE(E) (sources.spectrum_vector); scale: None,
+        a number or one per spectrum."""
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if G.ndim != 4 or G.shape[1:] != (self.T + 1, 3, self.N):
+            raise ValueError("apply_response: G must have shape (ntab, %d, 3, %d), got %s" % (self.T + 1, self.N, G.shape))
+        S, sc = self._spectra(spectra, scale)
+        out = np.zeros((G.shape[0], len(S), 3, self.N))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_apply_host(self._h, G.ctypes.data_as(dp), G.shape[0], S.ctypes.data_as(dp),
+                                                             len(S), sc.ctypes.data_as(dp) if sc is not None else None,
+                                                             out.ctypes.data_as(dp)))
+        return out
+
+    def apply_response_device(self, d_G_ptr, ntab, spectra, d_out_ptr, scale=None, stream_ptr=None):
+        """Asynchronous apply on device-resident response matrices: d_G [ntab][M][3][N], d_out [ntab][Q][3][N] (raw
+        pointers); the spectra and scales are host data and are copied.  Returns Q."""
+        S, sc = self._spectra(spectra, scale)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_apply(self._h, ctypes.c_void_p(d_G_ptr), int(ntab), S.ctypes.data_as(dp),
+                                                        len(S), sc.ctypes.data_as(dp) if sc is not None else None,
+                                                        ctypes.c_void_p(d_out_ptr),
+                                                        ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+        return len(S)
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since
@@ -130,7 +198,8 @@ class Plan:
         arithmetic: GSL's dilogarithm algorithms on the reference's arguments; 0 = the shared-algorithm order), OPT_REFO_CORNER_MB (the reference order's
         member-corner block budget in MiB, 0 = automatic), OPT_GA_BATCH (the reference order's Gamma / alphaTilde path:
         0 auto, 1 the per-table kernel, 2 the batch path whenever batches exist), OPT_GA_PRE_MB (the batch path's block
-        budget in MiB, 0 = 512; OPT_GA_PRE_KB: the same in KiB); include/nusi.h."""
+        budget in MiB, 0 = 512; OPT_GA_PRE_KB: the same in KiB), OPT_RESPONSE_FIFO_KB (the response's impulse
+        cascade: its step-pass FIFO budget in KiB, 0 = 1 GiB; the tables run in chunks that fit); include/nusi.h."""
         _lib.check(_lib.load().nusi_plan_set_option(self._h, int(option), int(value)))
 
     def profile_begin(self, max_calls):

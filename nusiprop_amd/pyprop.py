@@ -143,6 +143,22 @@ class pyprop:  # noqa: N801  (name of the reference class)
             _lib.check(L.nusi_set_source(self._h, S.ctypes.data_as(dp), w.ctypes.data_as(dp) if w is not None else None))
         self.evolved = False
 
+    def response(self, z_weight=None):
+        """Extension (no reference counterpart): the response matrices (G, G_fla) of this object's parameter point,
+        shape (M, 3, N) -- the flux per unit of each source-axis bin integral (Plan.response; z_weight = W(z_i), a
+        callable of z, or None for the star-formation rate).  The object's fluxes, source and evolved flag are
+        untouched; ``response.apply_host(G, S, norm)`` gives the flux of any spectrum S."""
+        from . import sources
+        L = _lib.load()
+        dp = ctypes.POINTER(ctypes.c_double)
+        _, _, z = self.source_axis()
+        w = sources.weight_vector(z_weight, z)
+        M, N = self._n() + len(z) - 1, self._n()
+        G, Gf = np.zeros((M, 3, N)), np.zeros((M, 3, N))
+        _lib.check(L.nusi_response(self._h, w.ctypes.data_as(dp) if w is not None else None, G.ctypes.data_as(dp),
+                                   Gf.ctypes.data_as(dp)))
+        return G, Gf
+
     def kernels(self):
         """Extension (no reference counterpart): names of the alpha-table and cascade kernels the last
         evolve() launched, e.g. ('k_alpha_batch', 'k_cascade_bs')."""
