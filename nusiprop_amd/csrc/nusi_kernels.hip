@@ -1206,6 +1206,29 @@ __global__ __launch_bounds__(256) void k_debug_div_forced(const double* __restri
     fast[i] = 1;
 }
 
+// Test only (tests/test_atan2_range_vote_gpu.py): nusi_libm.hpp's atan2 on arrays of operands -- element i is lane
+// i % 64 of wave i / 64.  ai, aw, af: atan2_i, atan2_w, atan2_full of (y, x); pi, pw: the path the element's call took
+// in atan2_i and in atan2_w -- 0 the first-range vote's short body, 1 the select path, 2 fdlibm's branches --, set
+// inside the code that ran by the flagged instances atan2_vote_t<.., true> (the library's own instances carry no flag:
+// the flagged call's result is compared with theirs here, and 8 is added to the path where the bits differ).  atan2_w's
+// outputs mean something only for waves whose lanes are all within its caller's bounds
+__global__ __launch_bounds__(256) void k_debug_atan2(const double* __restrict__ y, const double* __restrict__ x, int n,
+                                                     double* __restrict__ ai, double* __restrict__ aw,
+                                                     double* __restrict__ af, int* __restrict__ pi, int* __restrict__ pw)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double b = y[i], a = x[i];
+    const double vi = nm::atan2_i(b, a), vw = nm::atan2_w(b, a);
+    int qi = -1, qw = -1;
+    const double fi = nm::atan2_vote_t<false, true>(b, a, &qi), fw = nm::atan2_vote_t<true, true>(b, a, &qw);
+    ai[i] = vi;
+    aw[i] = vw;
+    af[i] = nm::atan2_full(b, a);
+    pi[i] = qi + (nm::bits(fi) != nm::bits(vi) ? 8 : 0);
+    pw[i] = qw + (nm::bits(fw) != nm::bits(vw) ? 8 : 0);
+}
+
 }  // namespace nusi
 
 // Test only, not declared in nusi.h: host arrays of n operands through k_debug_div_shared (forced = 0) or
@@ -1251,6 +1274,35 @@ static int debug_div(int forced, const double* a0, const double* a1, const doubl
     double* const out[5] = {q0, q1, s, p0, p1};
     for (int j = 0; ok && j < 5; ++j) ok = hipMemcpy(out[j], d + (3 + j) * (size_t)n, nb, hipMemcpyDeviceToHost) == hipSuccess;
     ok = ok && hipMemcpy(fast, f, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
+    hipFree(d);
+    hipFree(f);
+    return ok ? 0 : -5;
+}
+
+// Test only, not declared in nusi.h: host arrays of n operand pairs through k_debug_atan2 on the current device
+extern "C" int nusi_debug_atan2(const double* y, const double* x, int n, double* ai, double* aw, double* af, int* pi,
+                                int* pw)
+{
+    if (n <= 0) return -1;
+    const size_t N = (size_t)n, nb = sizeof(double) * N, ni = sizeof(int) * N;
+    double* d = nullptr;
+    int* f = nullptr;
+    if (hipMalloc(&d, 5 * nb) != hipSuccess) return -2;
+    if (hipMalloc(&f, 2 * ni) != hipSuccess) {
+        hipFree(d);
+        return -2;
+    }
+    bool ok = hipMemcpy(d, y, nb, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d + N, x, nb, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(nusi::k_debug_atan2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d, d + N, n, d + 2 * N,
+                           d + 3 * N, d + 4 * N, f, f + N);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    }
+    double* const out[3] = {ai, aw, af};
+    for (int j = 0; ok && j < 3; ++j) ok = hipMemcpy(out[j], d + (2 + j) * N, nb, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(pi, f, ni, hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(pw, f + N, ni, hipMemcpyDeviceToHost) == hipSuccess;
     hipFree(d);
     hipFree(f);
     return ok ? 0 : -5;

@@ -308,7 +308,6 @@ NUSI_FN double atan2_sel_t(double y, double x)
     const double zz = at - pi_lo;
     return m == 0 ? at : m == 1 ? -at : m == 2 ? pi - zz : zz - pi;
 }
-NUSI_FN double atan2_sel(double y, double x) { return atan2_sel_t<false>(y, x); }
 NUSI_FN bool wave_all_l(bool p)
 {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -317,26 +316,78 @@ NUSI_FN bool wave_all_l(bool p)
     return p;
 #endif
 }
-// the rare waves' fdlibm atan2 as a call: inlined at every atan2 site it was most of k_alpha_mcorner's code (~1 700
-// of its 8 600 instructions per site, against an instruction cache shared by two CUs)
-NUSI_LM double atan2_rare(double y, double x) { return atan2_full(y, x); }
-NUSI_FN double atan2_i(double y, double x)
-{
-    if (wave_all_l(atan2_plain(y, x))) return atan2_sel(y, x);
-    return atan2_rare(y, x);
-}
-// atan2_i for a caller that bounds its operands (the member-corner kernel's chain inside the member window,
+// atan2_w: atan2_i for a caller that bounds its operands (the member-corner kernel's chain inside the member window,
 // nusi_gsl.hpp): every active lane's x and y finite with modulus at most 2^500, y nonzero and at least 2^-500, x
 // at least 2^-500 or 0.  The vote for the common path is then three compares on two products: |y| <= 2^59 |x| and
 // |x| <= 2^59 |y| put the exponents at most 59 apart, so atan2_plain's k = (iy - ix) >> 20, which is that difference
 // or one less, is within +-60 (and x = 0 fails the first); x != 1.  Its divisions take the short sequence: the
 // quotient's operands are nonzero, at least 2^-500 and their exponents 59 apart at most
-NUSI_FN double atan2_w(double y, double x)
+NUSI_FN bool atan2_w_plain(double y, double x)
 {
     const double ax = fabs(x), ay = fabs(y);
-    if (wave_all_l(ay <= ax * 0x1p59 && ax <= ay * 0x1p59 && x != 1.0)) return atan2_sel_t<true>(y, x);
-    return atan2_rare(y, x);
+    return ay <= ax * 0x1p59 && ax <= ay * 0x1p59 && x != 1.0;
 }
+template <bool kW>
+NUSI_FN bool atan2_common(double y, double x) { return kW ? atan2_w_plain(y, x) : atan2_plain(y, x); }
+// s_atan.c's first range of its argument t = |y / x|: t < 0.4375 (id = -1, no argument reduction)
+NUSI_FN bool atan_first_range(double t) { return hiw(t) < 0x3fdc0000; }
+// The path a call took, for the test-only instances (kPath; tests/hostcheck_atan2, k_debug_atan2): written where the
+// path is taken, so the flag is what ran.  The library's instances (kPath = false) carry no flag
+enum { kAtan2First = 0, kAtan2Select = 1, kAtan2Full = 2 };
+// what a wave runs that fails one of atan2_vote_t's two votes: the select path under the common path's vote, else
+// fdlibm's branches -- atan2 as it was before the first-range vote
+template <bool kW, bool kPath>
+NUSI_FN double atan2_slow_body(double y, double x, int* path)
+{
+    if (wave_all_l(atan2_common<kW>(y, x))) {
+        if (kPath) *path = kAtan2Select;
+        return atan2_sel_t<kW>(y, x);
+    }
+    if (kPath) *path = kAtan2Full;
+    return atan2_full(y, x);
+}
+// ... as one call: a site keeps only the short first-range body inline.  (Inlined at every atan2 site, fdlibm's
+// branches alone were ~1 700 instructions per site of k_alpha_mcorner's code, against an instruction cache shared by
+// two CUs; with the select path inline beside the short body the kernel had 42 SGPR lane spills instead of 18)
+template <bool kW>
+NUSI_LM double atan2_slow(double y, double x) { return atan2_slow_body<kW, false>(y, x, nullptr); }
+// A second wave vote, after the common path's quotient: every active lane's t is in s_atan.c's first range, t <
+// 0.4375, as in nearly every wave of the alpha kernels.  Such a wave needs none of the select path's
+// four select chains, candidate numerators and denominators, second division and atanhi / atanlo form.  The bits are
+// the select path's: in that range num = t and den = 1.0, and t / 1.0 is t exactly (by the division and by the short
+// sequence alike), so xr = t; num, den, ahi and alo have no other use there, and at = xr - xr (s1 + s2), the |t| <
+// 2^-29 select and the octant are the select path's own operations on the same operands -- what s_atan.c computes for
+// id = -1.  Both votes are wave-uniform (scalar branches; no exec mask is kept per lane); on the host each is the
+// call's own predicate.  A wave that fails either calls atan2_slow, which takes it from the operands again
+template <bool kW, bool kPath = false>
+NUSI_FN double atan2_vote_t(double y, double x, int* path = nullptr)
+{
+    constexpr double pi = 3.1415926535897931160E+00, pi_lo = 1.2246467991473531772E-16;
+    constexpr double aT[11] = {3.33333333333329318027e-01,  -1.99999999998764832476e-01, 1.42857142725034663711e-01,
+                               -1.11111104054623557880e-01, 9.09088713343650656196e-02,  -7.69187620504482999495e-02,
+                               6.66107313738753120669e-02,  -5.83357013379057348645e-02, 4.97687799461593236017e-02,
+                               -3.65315727442169155270e-02, 1.62858201153657823623e-02};
+    if (wave_all_l(atan2_common<kW>(y, x))) {
+        const double t = fabs(div_v(kW, y, x));
+        if (wave_all_l(atan_first_range(t))) {
+            if (kPath) *path = kAtan2First;
+            const double xr = t;
+            const double z = xr * xr;
+            const double w = z * z;
+            const double s1 = z * (aT[0] + w * (aT[2] + w * (aT[4] + w * (aT[6] + w * (aT[8] + w * aT[10])))));
+            const double s2 = w * (aT[1] + w * (aT[3] + w * (aT[5] + w * (aT[7] + w * aT[9]))));
+            double at = xr - xr * (s1 + s2);
+            if (hiw(t) < 0x3e200000) at = t;   // |t| < 2^-29 (a select)
+            const int m = ((hiw(y) >> 31) & 1) | ((hiw(x) >> 30) & 2);   // 2 sign(x) + sign(y)
+            const double zz = at - pi_lo;
+            return m == 0 ? at : m == 1 ? -at : m == 2 ? pi - zz : zz - pi;
+        }
+    }
+    if (kPath) return atan2_slow_body<kW, true>(y, x, path);
+    return atan2_slow<kW>(y, x);
+}
+NUSI_FN double atan2_i(double y, double x) { return atan2_vote_t<false>(y, x); }
+NUSI_FN double atan2_w(double y, double x) { return atan2_vote_t<true>(y, x); }
 
 // Out-of-line entry points (see NUSI_LM); the *_i bodies above are inlined where a caller wants
 // them inline (the polylogarithms, which are themselves out of line).
