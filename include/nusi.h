@@ -231,6 +231,57 @@ int nusi_plan_response_apply(nusi_plan *plan, const double *d_G, int ntab, const
                              const double *scale /* [Q] or NULL */, double *d_out, void *stream);
 int nusi_plan_response_apply_host(nusi_plan *plan, const double *G, int ntab, const double *S, int Q,
                                   const double *scale, double *out);
+/* The detector of a plan (no reference counterpart): folding fluxes and response matrices into expected event counts
+ * per reconstructed-energy bin, on the device.
+ * nusi_plan_set_detector registers D [C][3][N] and a background B [C] (NULL = 0): D[c][f][b] is the expected number
+ * of events in reconstructed bin c per unit of flux_fla[f][b] as the library returns it -- the bin average dPhi/dE
+ * (nuSIprop.hpp:328-336) -- so the true-energy bin width, effective area, exposure and migration are all inside D.
+ * Ordering and copying are nusi_plan_set_source's: the call waits for the plan's latest call, copies synchronously
+ * (the caller may free its arrays), and later calls see the new detector.  D == NULL (with any C) clears it.
+ * NUSI_EPARAM for C outside 1 .. NUSI_DETECTOR_BINS_MAX or a negative or non-finite entry of D or B (everything
+ * below relies on every summed term being non-negative); the calls below return NUSI_ESTATE while no detector is set.
+ * A call that fails (a refused parameter, no device memory) leaves the plan with the detector it had.  The detector
+ * calls of a plan may be issued on different streams: each is ordered after the plan's earlier detector calls,
+ * wherever they ran.
+ * nusi_plan_detector_bins: C, 0 = none.
+ *
+ * The fold (k_detector_fold, one batched fp64 GEMM on the matrix cores), r over the 3 N entries of a row:
+ *     nusi_plan_response_fold   R[t][n][c] = sum_r G_fla[t][n][r] D[c][r]            (no background)
+ *     nusi_plan_fold_flux       mu[p][c]   = sum_r flux_fla[p][r] D[c][r] + B[c]
+ * d_G_fla [ntab][M][3][N] is a response matrix of nusi_plan_response (its entries of bins b >= n are +0.0 and are NOT
+ * read), d_flux_fla [n][3][N] an ordinary evolve output; d_R [ntab][M][C] and d_mu [n][C] are DEVICE pointers.
+ * Unlike the apply, the fold has NO defined summation order -- the matrix core owns it.  The contract is a bound:
+ * every term is non-negative, and a sum of K products in any order, fused or not, carries at most K roundings per
+ * term, so
+ *     |computed - exact| <= gamma_K * exact,   gamma_K = K u / (1 - K u),  u = 2^-53,  K = 3 N
+ * (one more rounding for the background), provided no non-zero product is subnormal; where every product is zero
+ * the result is +0.0.  A table's or a row tile's result does not depend on the call's other rows.
+ *
+ * nusi_plan_response_events (k_detector_events): Q spectra on ntab folded matrices, in a defined order:
+ *     acc = 0.0, and for n = 1 .. M-1 ascending  acc = acc + R[t][n][c] * S[q][n]
+ *     mu[t][q][c] = scale[q] * acc + B[c]
+ * (every product and sum rounded separately, no fma), and with data [C]
+ *     nll[t][q] = sum over c ascending from 0.0 of term_c,  term_c = mu_c - data_c * log(mu_c),
+ *     term_c = mu_c where data_c == 0 (the log is not evaluated)
+ * -- the Poisson negative log-likelihood without its data-only constant; +inf where data_c > 0 and mu_c == 0; log is
+ * the library's own (nusi_libm.hpp nm::log, the oracle's ora_log).  S [Q][M], scale [Q] (NULL = 1) and data [C] are
+ * host vectors and are copied; d_mu [ntab][Q][C] and d_nll [ntab][Q] are DEVICE pointers, either may be NULL but
+ * not both, and d_nll needs data.  NUSI_EPARAM for a negative or non-finite S, scale or data.  The calls are
+ * ordered on `stream` (NULL = the plan's own).  The _host forms take host arrays and are synchronous. */
+#define NUSI_DETECTOR_BINS_MAX 64
+int nusi_plan_set_detector(nusi_plan *plan, int C, const double *D /* [C][3][N] */, const double *B /* [C] or NULL */);
+int nusi_plan_detector_bins(const nusi_plan *plan);
+int nusi_plan_fold_flux(nusi_plan *plan, const double *d_flux_fla /* [n][3][N] */, int n, double *d_mu /* [n][C] */,
+                        void *stream);
+int nusi_plan_fold_flux_host(nusi_plan *plan, const double *flux_fla, int n, double *mu);
+int nusi_plan_response_fold(nusi_plan *plan, const double *d_G_fla /* [ntab][M][3][N] */, int ntab,
+                            double *d_R /* [ntab][M][C] */, void *stream);
+int nusi_plan_response_fold_host(nusi_plan *plan, const double *G_fla, int ntab, double *R);
+int nusi_plan_response_events(nusi_plan *plan, const double *d_R, int ntab, const double *S /* [Q][M] */, int Q,
+                              const double *scale /* [Q] or NULL */, const double *data /* [C] or NULL */,
+                              double *d_mu /* [ntab][Q][C] or NULL */, double *d_nll /* [ntab][Q] or NULL */, void *stream);
+int nusi_plan_response_events_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *scale,
+                                   const double *data, double *mu, double *nll);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);

@@ -6,9 +6,9 @@ libnusi.so), with the reference's Python surface (``pyprop``) on top.
 """
 from ._lib import (NusiError, NusiParams, SOURCE_DSNB, SOURCE_POWER_LAW, SOURCE_TABULATED, WARN_ALPHA,  # noqa: F401
                    WARN_ALPHATILDE, WARN_GAMMA, make_params, load)
-from . import response, sources  # noqa: F401
+from . import detector, response, sources  # noqa: F401
 from .plan import Plan, unpack_alpha  # noqa: F401
 from .pyprop import pyprop  # noqa: F401
 
-__all__ = ["pyprop", "Plan", "unpack_alpha", "NusiError", "NusiParams", "make_params", "load", "sources", "response",
+__all__ = ["pyprop", "Plan", "unpack_alpha", "NusiError", "NusiParams", "make_params", "load", "sources", "response", "detector",
            "SOURCE_DSNB", "SOURCE_POWER_LAW", "SOURCE_TABULATED"]

@@ -22,6 +22,7 @@ SOURCE_DSNB = 0
 SOURCE_POWER_LAW = 1
 SOURCE_TABULATED = 2        # + slot: a user-tabulated source of the plan (Plan.set_source, nusiprop_amd.sources)
 SOURCE_SLOTS_MAX = 65536
+DETECTOR_BINS_MAX = 64      # reconstructed bins of a plan's detector (Plan.set_detector, nusiprop_amd.detector)
 
 WARN_GAMMA = 1
 WARN_ALPHATILDE = 2
@@ -57,6 +58,9 @@ EXPORTS = [
     "nusi_plan_source_axis", "nusi_plan_set_source", "nusi_source_axis", "nusi_set_source",
     "nusi_plan_response", "nusi_plan_response_host", "nusi_plan_response_apply", "nusi_plan_response_apply_host",
     "nusi_response",
+    "nusi_plan_set_detector", "nusi_plan_detector_bins", "nusi_plan_fold_flux", "nusi_plan_fold_flux_host",
+    "nusi_plan_response_fold", "nusi_plan_response_fold_host", "nusi_plan_response_events",
+    "nusi_plan_response_events_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -126,6 +130,14 @@ def load():
         "nusi_plan_response_apply": (i, [vp, vp, i, dp, i, dp, vp, vp]),
         "nusi_plan_response_apply_host": (i, [vp, dp, i, dp, i, dp, dp]),
         "nusi_response": (i, [vp, dp, dp, dp]),
+        "nusi_plan_set_detector": (i, [vp, i, dp, dp]),
+        "nusi_plan_detector_bins": (i, [vp]),
+        "nusi_plan_fold_flux": (i, [vp, vp, i, vp, vp]),
+        "nusi_plan_fold_flux_host": (i, [vp, dp, i, dp]),
+        "nusi_plan_response_fold": (i, [vp, vp, i, vp, vp]),
+        "nusi_plan_response_fold_host": (i, [vp, dp, i, dp]),
+        "nusi_plan_response_events": (i, [vp, vp, i, dp, i, dp, dp, vp, vp, vp]),
+        "nusi_plan_response_events_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

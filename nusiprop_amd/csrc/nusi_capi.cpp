@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <tuple>
 #include <array>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -459,6 +460,14 @@ struct nusi_plan {
     std::vector<double> h_app;
     hipEvent_t ev_app = nullptr;    // end of the latest apply (the next one reuses d_app / h_app)
     bool app_ran = false;
+    // the detector (nusi_plan_set_detector) and its calls (fold, events)
+    int det_C = 0;                  // reconstructed bins; 0 = no detector
+    double* d_det = nullptr;        // Dt [3 N][detector_ld(C)] (K-major, zero-padded columns), then the background [C]
+    double* d_evt = nullptr;        // events: the spectra S [Q][T + 1], then scale [Q], then data [C]
+    size_t evt_doubles = 0;
+    std::vector<double> h_evt;
+    hipEvent_t ev_det = nullptr;    // end of the latest fold / events call (set_detector and the next events wait for it)
+    bool det_ran = false;
     std::vector<int> slot_of;       // table slot of each point of the last call
     int last_ntab = 0;
     int* d_warn = nullptr;
@@ -916,6 +925,9 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->d_rpts);
     hipFree(pl->d_rscr);
     hipFree(pl->d_app);
+    if (pl->ev_det) hipEventDestroy(pl->ev_det);
+    hipFree(pl->d_det);
+    hipFree(pl->d_evt);
     nusi::alpha_tiles_destroy(&pl->atiles);
     hipFree(pl->mc.buf);
     hipFree(pl->mc.eu);
@@ -1651,6 +1663,205 @@ int nusi_plan_response_apply_host(nusi_plan* pl, const double* G, int ntab, cons
     hipFree(dG);
     hipFree(dO);
     return r;
+}
+
+// ---------------------------------------------------------------------------
+// The detector of a plan: nusi_plan_set_detector, the folds and the expected counts (nusi_detector.hip)
+static int no_plan()   // (no plan exists without a GPU: say so, as nusi_plan_create does)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(NUSI_EHIP, "no HIP device available");
+    return fail(NUSI_EPARAM, "plan is NULL");
+}
+// The detector calls of a plan may run on different streams, and ONE event, ev_det, stands for the end of all of them:
+// each call first makes its stream wait for the event as it stands (the earlier calls, wherever they ran) and records
+// it anew after its kernel, so whoever waits for ev_det -- set_detector before it frees d_det, the next events call
+// before it overwrites d_evt -- waits for every earlier detector call.
+static int detector_chain(nusi_plan* pl, hipStream_t s)
+{
+    if (pl->det_ran) HIPCHECK(hipStreamWaitEvent(s, pl->ev_det, 0));
+    return NUSI_OK;
+}
+static int detector_mark(nusi_plan* pl, hipStream_t s)   // the end of a call that read the detector
+{
+    if (!pl->ev_det) HIPCHECK(hipEventCreateWithFlags(&pl->ev_det, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(pl->ev_det, s));
+    pl->det_ran = true;
+    return NUSI_OK;
+}
+static int detector_fold(nusi_plan* pl, const double* d_X, int ntab, int rows, bool tri, double* d_out, void* stream, const char* what)
+{
+    if (!pl->det_C) return fail(NUSI_ESTATE, std::string(what) + ": the plan has no detector (nusi_plan_set_detector)");
+    if (!d_X || !d_out) return fail(NUSI_EPARAM, std::string(what) + ": the input and the output must not be NULL");
+    if (ntab < 1 || rows < 1) return fail(NUSI_EPARAM, std::string(what) + ": need at least one row");
+    if ((long long)ntab * ((rows + 15) / 16) > (long long)INT_MAX) return fail(NUSI_EPARAM, std::string(what) + ": too many rows");
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    const int C = pl->det_C;
+    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
+    if (int r = detector_chain(pl, s)) return r;
+    HIPCHECK(nusi::launch_detector_fold(pl->gd, d_X, ntab, rows, tri, pl->d_det, C, tri ? nullptr : bg, d_out, s));
+    return detector_mark(pl, s);
+}
+// host arrays through a device call: in [nin] -> out [nout] doubles
+static int detector_host(nusi_plan* pl, const double* in, size_t nin, double* out, size_t nout, const char* what,
+                  const std::function<int(const double*, double*)>& call)
+{
+    HIPCHECK(hipSetDevice(pl->device));
+    double *dI = nullptr, *dO = nullptr;
+    int r = NUSI_OK;
+    if (hipMalloc(&dI, sizeof(double) * nin) != hipSuccess || hipMalloc(&dO, sizeof(double) * nout) != hipSuccess)
+        r = fail(NUSI_EHIP, std::string(what) + ": no device memory");
+    if (!r && hipMemcpy(dI, in, sizeof(double) * nin, hipMemcpyHostToDevice) != hipSuccess)
+        r = fail(NUSI_EHIP, std::string(what) + ": copy to the device failed");
+    if (!r) r = call(dI, dO);
+    if (!r && hipStreamSynchronize(pl->stream) != hipSuccess) r = fail(NUSI_EHIP, std::string(what) + ": the stream failed");
+    if (!r && hipMemcpy(out, dO, sizeof(double) * nout, hipMemcpyDeviceToHost) != hipSuccess)
+        r = fail(NUSI_EHIP, std::string(what) + ": copy to the host failed");
+    hipFree(dI);
+    hipFree(dO);
+    return r;
+}
+
+int nusi_plan_set_detector(nusi_plan* pl, int C, const double* D, const double* B)
+{
+    if (!pl) return no_plan();
+    const bool clear = !D;   // (C = 0 comes with D = NULL; a D with C = 0 is refused below)
+    if (D) {
+        if (C < 1 || C > NUSI_DETECTOR_BINS_MAX) return fail(NUSI_EPARAM, "detector: C outside 1 .. NUSI_DETECTOR_BINS_MAX");
+        const size_t R3 = (size_t)3 * pl->grid.N;
+        for (size_t e = 0; e < (size_t)C * R3; ++e)
+            if (!(D[e] >= 0.0) || !std::isfinite(D[e])) return fail(NUSI_EPARAM, "detector: an entry of D is negative or not finite");
+        if (B)
+            for (int c = 0; c < C; ++c)
+                if (!(B[c] >= 0.0) || !std::isfinite(B[c])) return fail(NUSI_EPARAM, "detector: a background is negative or not finite");
+    }
+    HIPCHECK(hipSetDevice(pl->device));
+    // the new detector first, in a block of its own: a failure below leaves the plan with the detector it had
+    double* d_new = nullptr;
+    if (!clear) {
+        const size_t R3 = (size_t)3 * pl->grid.N;
+        const int ld = nusi::detector_ld(C);
+        std::vector<double> v(R3 * ld + (size_t)C, 0.0);
+        for (int c = 0; c < C; ++c)
+            for (size_t r = 0; r < R3; ++r) v[r * ld + c] = D[(size_t)c * R3 + r];
+        if (B) memcpy(v.data() + R3 * ld, B, sizeof(double) * C);
+        HIPCHECK(hipMalloc(&d_new, sizeof(double) * v.size()));
+        const hipError_t e = hipMemcpy(d_new, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(d_new);
+            HIPCHECK(e);
+        }
+    }
+    // ordered with the plan's calls (nusi_plan_set_source's rule): the earlier ones, on whatever stream they ran,
+    // finish with the old detector (ev_det covers every detector call: detector_chain) before it is freed
+    hipError_t e = pl->ran ? hipEventSynchronize(pl->ev_done) : hipSuccess;
+    if (e == hipSuccess && pl->det_ran) e = hipEventSynchronize(pl->ev_det);
+    if (e != hipSuccess) {
+        hipFree(d_new);
+        HIPCHECK(e);
+    }
+    hipFree(pl->d_det);
+    pl->d_det = d_new;
+    pl->det_C = clear ? 0 : C;
+    return NUSI_OK;
+}
+
+int nusi_plan_detector_bins(const nusi_plan* pl) { return pl ? pl->det_C : 0; }
+
+int nusi_plan_fold_flux(nusi_plan* pl, const double* d_flux_fla, int n, double* d_mu, void* stream)
+{
+    if (!pl) return no_plan();
+    return detector_fold(pl, d_flux_fla, 1, n, false, d_mu, stream, "fold flux");
+}
+
+int nusi_plan_response_fold(nusi_plan* pl, const double* d_G_fla, int ntab, double* d_R, void* stream)
+{
+    if (!pl) return no_plan();
+    return detector_fold(pl, d_G_fla, ntab, pl->grid.T + 1, true, d_R, stream, "response fold");
+}
+
+int nusi_plan_fold_flux_host(nusi_plan* pl, const double* flux_fla, int n, double* mu)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "fold flux: the plan has no detector (nusi_plan_set_detector)");
+    if (!flux_fla || !mu || n < 1) return fail(NUSI_EPARAM, "fold flux: the input and the output must not be NULL, n >= 1");
+    return detector_host(pl, flux_fla, (size_t)n * 3 * pl->grid.N, mu, (size_t)n * pl->det_C, "fold flux",
+                         [&](const double* dI, double* dO) { return nusi_plan_fold_flux(pl, dI, n, dO, nullptr); });
+}
+
+int nusi_plan_response_fold_host(nusi_plan* pl, const double* G_fla, int ntab, double* R)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response fold: the plan has no detector (nusi_plan_set_detector)");
+    if (!G_fla || !R || ntab < 1) return fail(NUSI_EPARAM, "response fold: the input and the output must not be NULL, ntab >= 1");
+    const size_t M = (size_t)pl->grid.T + 1;
+    return detector_host(pl, G_fla, (size_t)ntab * M * 3 * pl->grid.N, R, (size_t)ntab * M * pl->det_C, "response fold",
+                         [&](const double* dI, double* dO) { return nusi_plan_response_fold(pl, dI, ntab, dO, nullptr); });
+}
+
+int nusi_plan_response_events(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* scale,
+                              const double* data, double* d_mu, double* d_nll, void* stream)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response events: the plan has no detector (nusi_plan_set_detector)");
+    if (!d_R || !S) return fail(NUSI_EPARAM, "response events: R and S must not be NULL");
+    if (!d_mu && !d_nll) return fail(NUSI_EPARAM, "response events: mu and nll are both NULL");
+    if (d_nll && !data) return fail(NUSI_EPARAM, "response events: nll needs data");
+    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, "response events: need ntab >= 1 and 1 <= Q <= 2^19");
+    const size_t M = (size_t)pl->grid.T + 1;
+    const int C = pl->det_C;
+    for (size_t e = 0; e < (size_t)Q * M; ++e)
+        if (!(S[e] >= 0.0) || !std::isfinite(S[e])) return fail(NUSI_EPARAM, "source spectrum: a bin integral is negative or not finite");
+    if (scale)
+        for (int q = 0; q < Q; ++q)
+            if (!(scale[q] >= 0.0) || !std::isfinite(scale[q])) return fail(NUSI_EPARAM, "response events: a scale is negative or not finite");
+    if (data)
+        for (int c = 0; c < C; ++c)
+            if (!(data[c] >= 0.0) || !std::isfinite(data[c])) return fail(NUSI_EPARAM, "response events: a datum is negative or not finite");
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (pl->det_ran) HIPCHECK(hipEventSynchronize(pl->ev_det));   // d_evt / h_evt are reused (every earlier detector
+                                                                  // call has finished: detector_chain)
+    const size_t need = (size_t)Q * M + (size_t)Q + (size_t)C;
+    if (pl->evt_doubles < need) {
+        hipFree(pl->d_evt);
+        pl->d_evt = nullptr;
+        pl->evt_doubles = 0;
+        HIPCHECK(hipMalloc(&pl->d_evt, sizeof(double) * need));
+        pl->evt_doubles = need;
+    }
+    pl->h_evt.assign(S, S + (size_t)Q * M);
+    pl->h_evt.resize(need, 0.0);
+    if (scale) memcpy(pl->h_evt.data() + (size_t)Q * M, scale, sizeof(double) * Q);
+    if (data) memcpy(pl->h_evt.data() + (size_t)Q * M + Q, data, sizeof(double) * C);
+    HIPCHECK(hipMemcpyAsync(pl->d_evt, pl->h_evt.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
+    const double* d_sc = pl->d_evt + (size_t)Q * M;
+    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
+    HIPCHECK(nusi::launch_detector_events(pl->gd, d_R, ntab, pl->d_evt, Q, scale ? d_sc : nullptr, d_sc + Q, bg, C, d_mu,
+                                          d_nll, s));
+    return detector_mark(pl, s);
+}
+
+int nusi_plan_response_events_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* scale,
+                                   const double* data, double* mu, double* nll)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response events: the plan has no detector (nusi_plan_set_detector)");
+    if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response events: R must not be NULL, ntab and Q >= 1");
+    if (!mu && !nll) return fail(NUSI_EPARAM, "response events: mu and nll are both NULL");
+    const size_t M = (size_t)pl->grid.T + 1, C = (size_t)pl->det_C, nmu = (size_t)ntab * Q * C, nn = (size_t)ntab * Q;
+    // one output block: mu [ntab][Q][C], then nll [ntab][Q]
+    std::vector<double> o(nmu + nn);
+    const int r = detector_host(pl, R, (size_t)ntab * M * C, o.data(), o.size(), "response events",
+                                [&](const double* dI, double* dO) {
+                                    return nusi_plan_response_events(pl, dI, ntab, S, Q, scale, data, mu ? dO : nullptr,
+                                                                     nll ? dO + nmu : nullptr, nullptr);
+                                });
+    if (r) return r;
+    if (mu) memcpy(mu, o.data(), sizeof(double) * nmu);
+    if (nll) memcpy(nll, o.data() + nmu, sizeof(double) * nn);
+    return NUSI_OK;
 }
 
 int nusi_plan_profile_begin(nusi_plan* pl, int max_calls)

@@ -1,0 +1,225 @@
+// nuSIprop MI355X -- folding fluxes and response matrices with a detector (nusi_plan_set_detector; no reference
+// counterpart: the reference stops at get_flux_fla).
+//
+//   k_detector_fold<CT>   rows [.][3 N] times the detector matrix D [3 N][C] on the fp64 matrix cores
+//                         (nusi_plan_fold_flux, nusi_plan_response_fold); CT = ceil(C / 16) column tiles
+//   k_detector_events     spectra on folded response matrices R [t][M][C]: expected counts per reconstructed bin
+//                         and the Poisson statistic (nusi_plan_response_events), in a defined order
+#include <hip/hip_runtime.h>
+
+#include "nusi_internal.hpp"
+#include "nusi_libm.hpp"
+
+namespace nusi {
+
+typedef double det_f64x4 __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------------------
+// k_detector_fold: out[t][n][c] = sum_{r < 3 N} X[t][n][r] D[c][r] (+ bg[c]), a batched fp64 GEMM
+// (rows x 3 N) . (3 N x C) on v_mfma_f64_16x16x4_f64.
+//
+// One workgroup (4 waves) takes 16 rows n0 .. n0 + 15 of one table and every column.  K = the 3 N entries of a row
+// runs in chunks of kFoldKC staged through LDS: rows are 3 N doubles apart, so the loads go along a row (each wave
+// instruction reads 512 contiguous bytes), eight per thread, issued a chunk ahead of the MFMAs that consume them.
+// The four waves split a chunk's K quads (wave w takes quads w, w + 4, ..), each holding a full 16 x 16 CT
+// accumulator; the partial sums meet in LDS and wave 0 adds them in wave order.  The detector is read from the
+// plan's K-major copy Dt [3 N][16 CT] (zero-padded columns) straight from L2: lane l's B operand of column tile ct
+// is Dt[k = l >> 4][16 ct + (l & 15)], 128 contiguous bytes per K.
+//
+// Operand maps (as in nusi_cascade_bs_body.inc): A[row = l & 15][k = l >> 4], B[k = l >> 4][col = l & 15],
+// C/D element e of lane l = [row = (l >> 4) + 4 e][col = l & 15].
+//
+// tri (response rows): G[n][.][b] = +0.0 for b >= n, so the tile reads only the bins b < nb = min(N, n0 + 16) of
+// each flavour; K then runs over the compacted index kk = f nb + b.  A K remainder is zero-filled on the A side
+// (the B side reads a clamped, finite entry), so it adds +0.0.  Every term is non-negative: the sum is at most
+// gamma_{3 N} from exact in any order, and +0.0 where every product is zero.
+// ---------------------------------------------------------------------------
+constexpr int kFoldThreads = 256, kFoldKC = 128, kFoldLd = kFoldKC + 2, kFoldRows = 16;
+
+template <int CT>
+__global__ __launch_bounds__(kFoldThreads) void k_detector_fold(const double* __restrict__ X, const double* __restrict__ Dt,
+                                                                const double* __restrict__ bg, double* __restrict__ out,
+                                                                int rows, int N, int C, int ntile, int tri)
+{
+    constexpr int kStage = kFoldRows * kFoldLd, kRed = 3 * CT * 256, kLds = kStage > kRed ? kStage : kRed;
+    constexpr int Cp = 16 * CT;
+    __shared__ double sh[kLds];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = (int)blockIdx.x / ntile, n0 = ((int)blockIdx.x - t * ntile) * kFoldRows;
+    const int nb = (tri && n0 + kFoldRows < N) ? n0 + kFoldRows : N;
+    const int K = 3 * nb, R3 = 3 * N, nch = (K + kFoldKC - 1) / kFoldKC;
+    const int skip = N - nb;
+    auto rmap = [&](int kk) { return kk + ((kk >= nb) + (kk >= 2 * nb)) * skip; };   // compacted K -> entry of the row
+    const double* __restrict__ Xt = X + ((size_t)t * rows + n0) * R3;
+    const int kl = tid & (kFoldKC - 1), rp = tid >> 7;
+    const int rlast = rows - 1 - n0;   // last valid row of the tile (>= 0)
+    auto load = [&](int ch, double (&v)[8]) {
+        const int kk = ch * kFoldKC + kl;
+        const bool ok = kk < K;
+        const int r = rmap(ok ? kk : K - 1);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int row = rp + 2 * j;
+            const double x = Xt[(size_t)(row < rlast ? row : rlast) * R3 + r];
+            v[j] = (ok && row <= rlast) ? x : 0.0;
+        }
+    };
+    det_f64x4 acc[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) acc[ct] = det_f64x4{0.0, 0.0, 0.0, 0.0};
+    double v[8];
+    load(0, v);
+#pragma unroll 1
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();   // the previous chunk's MFMAs have read sh
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sh[(rp + 2 * j) * kFoldLd + kl] = v[j];
+        __syncthreads();
+        if (ch + 1 < nch) load(ch + 1, v);
+        const int kc0 = ch * kFoldKC;
+#pragma unroll
+        for (int i = 0; i < kFoldKC / 16; ++i) {
+            const int kq = wave + 4 * i;
+            if (kc0 + 4 * kq < K) {   // (uniform per wave)
+                const int kk = kc0 + 4 * kq + (lane >> 4);
+                const double a = sh[(lane & 15) * kFoldLd + 4 * kq + (lane >> 4)];
+                const double* __restrict__ Dr = Dt + (size_t)rmap(kk < K ? kk : K - 1) * Cp + (lane & 15);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+                    acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Dr[16 * ct], acc[ct], 0, 0, 0);
+            }
+        }
+    }
+    __syncthreads();
+    if (wave > 0)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sh[((wave - 1) * CT + ct) * 256 + e * 64 + lane] = acc[ct][e];
+    __syncthreads();
+    if (wave == 0)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                double s = acc[ct][e];
+#pragma unroll
+                for (int w = 0; w < 3; ++w) s = s + sh[(w * CT + ct) * 256 + e * 64 + lane];
+                const int row = n0 + (lane >> 4) + 4 * e, col = 16 * ct + (lane & 15);
+                if (row < rows && col < C) out[((size_t)t * rows + row) * C + col] = bg ? s + bg[col] : s;
+            }
+}
+
+int detector_ld(int C) { return 16 * ((C + 15) / 16); }
+
+hipError_t launch_detector_fold(const GridDev& g, const double* X, int ntab, int rows, bool tri, const double* Dt, int C,
+                                const double* bg, double* out, hipStream_t s)
+{
+    if (ntab <= 0 || rows <= 0) return hipSuccess;
+    const int ntile = (rows + kFoldRows - 1) / kFoldRows;
+    const dim3 grid((unsigned)ntab * ntile), block(kFoldThreads);
+    switch ((C + 15) / 16) {
+    case 1: hipLaunchKernelGGL((k_detector_fold<1>), grid, block, 0, s, X, Dt, bg, out, rows, g.N, C, ntile, (int)tri); break;
+    case 2: hipLaunchKernelGGL((k_detector_fold<2>), grid, block, 0, s, X, Dt, bg, out, rows, g.N, C, ntile, (int)tri); break;
+    case 3: hipLaunchKernelGGL((k_detector_fold<3>), grid, block, 0, s, X, Dt, bg, out, rows, g.N, C, ntile, (int)tri); break;
+    case 4: hipLaunchKernelGGL((k_detector_fold<4>), grid, block, 0, s, X, Dt, bg, out, rows, g.N, C, ntile, (int)tri); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_detector_events: spectra on folded response matrices (nusi_plan_response_events), in a defined order:
+//     acc = 0.0;  for n = 1 .. M-1 ascending: acc = acc + R[t][n][c] * S[q][n];  mu = scale[q] * acc + bg[c]
+// (every product and sum rounded separately: -ffp-contract=off, and the pragma below), and with data
+//     nll[t][q] = sum over c ascending from 0.0 of  mu_c - data_c * log(mu_c)   (mu_c where data_c == 0),
+// log = nm::log's body.  Lanes sit on (c, a group of kEvQ spectra): R[t] (M C doubles) is re-read from L2 with c on
+// neighbouring lanes, each value serving kEvQ accumulators.  The statistic's c-sum is serial in one lane per (t, q),
+// over the block's mu in LDS.
+// ---------------------------------------------------------------------------
+constexpr int kEvThreads = 256, kEvQ = 4, kEvLds = 1536;
+// the block's mu in LDS: QB rows of C | 1 doubles, QB = (kEvThreads >> ceil(log2 C)) kEvQ; the largest over
+// C = 1 .. NUSI_DETECTOR_BINS_MAX is at C = 2 (512 x 3)
+constexpr int ev_lds_doubles(int C)
+{
+    int lg = 0;
+    while ((1 << lg) < C) ++lg;
+    return (kEvThreads >> lg) * kEvQ * (C | 1);
+}
+constexpr int ev_lds_max()
+{
+    int m = 0;
+    for (int C = 1; C <= NUSI_DETECTOR_BINS_MAX; ++C) m = ev_lds_doubles(C) > m ? ev_lds_doubles(C) : m;
+    return m;
+}
+static_assert(ev_lds_max() <= kEvLds, "k_detector_events: the block's mu does not fit smu[]");
+static_assert((kEvThreads >> 6) >= 1 && NUSI_DETECTOR_BINS_MAX <= 64, "k_detector_events: a block holds at least one group of 64 lanes on c");
+
+__global__ __launch_bounds__(kEvThreads) void k_detector_events(const double* __restrict__ R, const double* __restrict__ S,
+                                                                const double* __restrict__ scale,
+                                                                const double* __restrict__ data,
+                                                                const double* __restrict__ bg, double* __restrict__ mu,
+                                                                double* __restrict__ nll, int M, int C, int lgC, int Q)
+{
+#pragma clang fp contract(off)
+    __shared__ double smu[kEvLds];
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = (kEvThreads >> lgC) * kEvQ, qb0 = (int)blockIdx.y * QB, q0 = qb0 + grp * kEvQ;
+    const int cc = c < C ? c : C - 1, Cs = C | 1;
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* Sq[kEvQ];
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) Sq[j] = S + (size_t)(q0 + j < Q ? q0 + j : Q - 1) * M;
+    double acc[kEvQ];
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) acc[j] = 0.0;
+#pragma unroll 4
+    for (int n = 1; n < M; ++n) {
+        const double rv = Rt[(size_t)n * C];
+#pragma unroll
+        for (int j = 0; j < kEvQ; ++j) acc[j] = acc[j] + rv * Sq[j][n];
+    }
+    const double b = bg[cc];
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) {
+        const int q = q0 + j;
+        const double sa = (scale ? scale[q < Q ? q : Q - 1] : 1.0) * acc[j];
+        const double m = sa + b;
+        if (c < C) {
+            smu[(grp * kEvQ + j) * Cs + c] = m;
+            if (mu && q < Q) mu[((size_t)t * Q + q) * C + c] = m;
+        }
+    }
+    if (!nll) return;   // (uniform)
+    __syncthreads();
+    // (a block owns QB spectra -- 1024 at C = 1, 512 at C = 2 -- on kEvThreads threads: a strided loop)
+    for (int i = tid; i < QB && qb0 + i < Q; i += kEvThreads) {
+        const int q = qb0 + i;
+        double s = 0.0;
+        for (int k = 0; k < C; ++k) {
+            const double m = smu[i * Cs + k], d = data[k];
+            double term = m;
+            if (d != 0.0) {
+                const double p = d * nm::log_i(m);
+                term = m - p;
+            }
+            s = s + term;
+        }
+        nll[(size_t)t * Q + q] = s;
+    }
+}
+
+hipError_t launch_detector_events(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* scale,
+                                  const double* data, const double* bg, int C, double* mu, double* nll, hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0) return hipSuccess;
+    int lg = 0;
+    while ((1 << lg) < C) ++lg;
+    const int QB = (kEvThreads >> lg) * kEvQ;
+    hipLaunchKernelGGL(k_detector_events, dim3((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), dim3(kEvThreads), 0, s, R, S,
+                       scale, data, bg, mu, nll, g.T + 1, C, lg, Q);
+    return hipGetLastError();
+}
+
+}  // namespace nusi

@@ -143,6 +143,17 @@ hipError_t launch_cascade_impulse(const GridDev& g, const Point* pts, int p0, in
 // of ntab resident response matrices; S [Q][T + 1], scale [Q] (or nullptr), G and out in device memory
 hipError_t launch_response_apply(const GridDev& g, const double* G, int ntab, const double* S, int Q, const double* scale,
                                  double* out, hipStream_t s);
+// The detector of a plan (nusi_detector.hip).  k_detector_fold: out[t][n][c] = sum_r X[t][n][r] D[c][r] (+ bg[c] where
+// bg != nullptr) over the 3 N entries of ntab x rows rows, on the fp64 matrix cores; Dt is the plan's K-major copy of
+// D, [3 N][detector_ld(C)] with zero-padded columns; tri: X is a response matrix (rows = T + 1), whose entries of
+// bins b >= n are +0.0 and are not read.  k_detector_events: mu[t][q][c] = scale[q] (sum_n R[t][n][c] S[q][n]) + bg[c]
+// (n ascending from 1, no fma) and nll[t][q] = sum_c mu - data log mu; S [Q][T + 1], scale [Q] (or nullptr), data [C]
+// (with nll), bg [C], all in device memory; mu or nll may be nullptr.
+int detector_ld(int C);
+hipError_t launch_detector_fold(const GridDev& g, const double* X, int ntab, int rows, bool tri, const double* Dt, int C,
+                                const double* bg, double* out, hipStream_t s);
+hipError_t launch_detector_events(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* scale,
+                                  const double* data, const double* bg, int C, double* mu, double* nll, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

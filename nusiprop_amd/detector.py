@@ -1,0 +1,122 @@
+"""Folding fluxes with a detector on the CPU (numpy only): the yardstick of the plan's detector calls and the user's
+host path.
+
+A fit compares binned event counts, not fluxes.  The detector of a plan is one matrix, D[c][f][b] = the expected
+number of events in reconstructed-energy bin c per unit of flux_fla[f][b] (include/nusi.h), and the reduction is linear,
+so it commutes with the response apply: D . (G_fla . S) = (D . G_fla) . S.  Folding a response matrix once gives
+R[n][c], M x C doubles, and every spectrum is then a C-vector of expected counts::
+
+    D = detector.matrix(lo[:N], hi[:N], aeff, migration, exposure)       # (C, 3, N)
+    plan.set_detector(D, background=b)
+    R = plan.fold_response(G_fla)                                       # (ntab, M, C); fold_host on the CPU
+    mu, nll = plan.events(R, spectra, scale=1e-8, data=counts)          # events_host + poisson_host on the CPU
+
+``fold_host`` has no defined summation order (neither has the GPU's, which runs on the matrix cores): with every term
+non-negative, either is within gamma_K = K u / (1 - K u), K = 3 N, u = 2^-53, of the exact sum.  ``events_host`` and
+``poisson_host`` are the sums nusi_plan_response_events defines, in its order, so mu agrees bit for bit and nll to the
+last bits of the log.
+"""
+import numpy as np
+
+BINS_MAX = 64       # NUSI_DETECTOR_BINS_MAX
+
+
+def gamma(K):
+    """gamma_K = K u / (1 - K u), u = 2^-53: the relative error bound of a sum of K non-negative products."""
+    u = 2.0 ** -53
+    return K * u / (1.0 - K * u)
+
+
+def fold_host(rows, D):
+    """out[..., c] = sum_{f, b} rows[..., f, b] * D[c, f, b].  rows: (..., 3, N) -- flux_fla (n, 3, N) or G_fla
+    (ntab, M, 3, N); D: (C, 3, N).  No background, no defined order (a matrix product)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    D = np.asarray(D, dtype=np.float64)
+    if D.ndim != 3 or rows.ndim < 2 or rows.shape[-2:] != D.shape[1:]:
+        raise ValueError("fold_host: rows (.., 3, N) and D (C, 3, N) do not match: %s, %s" % (rows.shape, D.shape))
+    K = D.shape[1] * D.shape[2]
+    out = rows.reshape(-1, K) @ D.reshape(D.shape[0], K).T
+    return out.reshape(rows.shape[:-2] + (D.shape[0],))
+
+
+def events_host(R, S, scale=None, background=None):
+    """mu[..., q, c] = scale[q] * acc + background[c], acc = sum_{n=1}^{M-1} R[..., n, c] * S[q, n] in ascending n
+    (each product rounded, then the sum: response.apply_host's loop).
+
+    R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  scale: None (= 1), a number or (Q,).  background: None (= 0),
+    a number or (C,)."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    one_tab, one_q = R.ndim == 2, S.ndim == 1
+    Rt = R[None] if one_tab else R
+    Sq = S[None] if one_q else S
+    if Rt.ndim != 3 or Sq.ndim != 2 or Rt.shape[1] != Sq.shape[1]:
+        raise ValueError("events_host: R (.., M, C) and S (.., M) do not match: %s, %s" % (R.shape, S.shape))
+    ntab, M, C = Rt.shape
+    Q = Sq.shape[0]
+    acc = np.zeros((ntab, Q, C))
+    for n in range(1, M):
+        term = Rt[:, None, n] * Sq[None, :, n, None]      # rounded products ...
+        acc = acc + term                                  # ... then the rounded sum
+    sc = np.ones(Q) if scale is None else np.broadcast_to(np.asarray(scale, dtype=np.float64), (Q,))
+    bg = np.zeros(C) if background is None else np.broadcast_to(np.asarray(background, dtype=np.float64), (C,))
+    mu = sc[None, :, None] * acc                          # two roundings: the scale ...
+    mu = mu + bg[None, None, :]                           # ... and the background
+    if one_q:
+        mu = mu[:, 0]
+    if one_tab:
+        mu = mu[0]
+    return mu
+
+
+def poisson_host(mu, data, log=np.log):
+    """nll[...] = sum over c ascending, from 0.0, of mu_c - data_c * log(mu_c) -- mu_c where data_c == 0 (the log is
+    not evaluated) -- each operation rounded: the Poisson negative log-likelihood without its data-only constant.
+    +inf where data_c > 0 and mu_c == 0.  mu: (..., C); data: (C,); log: a scalar function of a float."""
+    mu = np.asarray(mu, dtype=np.float64)
+    data = np.asarray(data, dtype=np.float64)
+    if data.ndim != 1 or mu.ndim < 1 or mu.shape[-1] != data.shape[0]:
+        raise ValueError("poisson_host: mu (.., C) and data (C,) do not match: %s, %s" % (mu.shape, data.shape))
+    flat = mu.reshape(-1, data.shape[0])
+    out = np.zeros(flat.shape[0])
+    for i in range(flat.shape[0]):
+        s = 0.0
+        for c in range(data.shape[0]):
+            m, d = float(flat[i, c]), float(data[c])
+            if d == 0.0:
+                term = m
+            elif m == 0.0:
+                term = float("inf")
+            else:
+                term = m - d * float(log(m))
+            s = s + term
+        out[i] = s
+    return out.reshape(mu.shape[:-1])
+
+
+def matrix(lo, hi, aeff, migration=None, exposure=1.0):
+    """D[c, f, b] = exposure * (hi_b - lo_b) * aeff[f][b] * migration[c][b], shape (C, 3, N).
+
+    lo, hi: the true-energy bin edges [N] (Plan.source_axis()[:2], first N entries); aeff: (3, N) or (N,) (one for
+    all flavours), or a callable of (f, E) evaluated at the bins' geometric centres; migration: (C, N), the
+    probability of a true-energy bin b event landing in reconstructed bin c (None = the identity, C = N);
+    exposure: a number.  ValueError above detector.BINS_MAX reconstructed bins or for a negative or non-finite entry."""
+    lo = np.asarray(lo, dtype=np.float64)
+    hi = np.asarray(hi, dtype=np.float64)
+    if lo.ndim != 1 or lo.shape != hi.shape:
+        raise ValueError("matrix: lo and hi must be vectors of one length")
+    N = lo.shape[0]
+    if callable(aeff):
+        E = np.sqrt(lo * hi)
+        A = np.array([[float(aeff(f, float(e))) for e in E] for f in range(3)])
+    else:
+        A = np.broadcast_to(np.asarray(aeff, dtype=np.float64), (3, N))
+    mig = np.eye(N) if migration is None else np.asarray(migration, dtype=np.float64)
+    if mig.ndim != 2 or mig.shape[1] != N:
+        raise ValueError("matrix: migration must have shape (C, %d), got %s" % (N, mig.shape))
+    if not 1 <= mig.shape[0] <= BINS_MAX:
+        raise ValueError("matrix: %d reconstructed bins, the detector holds 1 .. %d" % (mig.shape[0], BINS_MAX))
+    D = (float(exposure) * (hi - lo))[None, None, :] * A[None, :, :] * mig[:, None, :]
+    if not np.all(np.isfinite(D)) or np.any(D < 0):
+        raise ValueError("matrix: an entry is negative or not finite")
+    return np.ascontiguousarray(D)

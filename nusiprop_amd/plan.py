@@ -183,6 +183,109 @@ class Plan:
                                                         ctypes.c_void_p(stream_ptr) if stream_ptr else None))
         return len(S)
 
+    # --- the detector (include/nusi.h "The detector of a plan") ---
+    def set_detector(self, D, background=None):
+        """Register the detector: D (C, 3, N), D[c, f, b] = expected events in reconstructed bin c per unit of
+        flux_fla[f, b] (detector.matrix builds one from bin widths, effective areas, a migration matrix and an exposure),
+        and a background expectation per bin (C,), None = 0.  C <= 64; every entry finite and >= 0.  None clears the
+        detector.  Later calls see the new detector, earlier results are untouched."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        L = _lib.load()
+        if D is None:
+            _lib.check(L.nusi_plan_set_detector(self._h, 0, None, None))
+            return
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if D.ndim != 3 or D.shape[1:] != (3, self.N):
+            raise ValueError("set_detector: D must have shape (C, 3, %d), got %s" % (self.N, D.shape))
+        B = None
+        if background is not None:
+            B = np.ascontiguousarray(np.broadcast_to(np.asarray(background, dtype=np.float64), (D.shape[0],)))
+        _lib.check(L.nusi_plan_set_detector(self._h, D.shape[0], D.ctypes.data_as(dp),
+                                            B.ctypes.data_as(dp) if B is not None else None))
+
+    def detector_bins(self):
+        """C, the detector's reconstructed bins; 0 = no detector."""
+        return int(_lib.load().nusi_plan_detector_bins(self._h))
+
+    def fold_flux(self, flux_fla):
+        """Expected counts of flavour fluxes (n, 3, N) -- evolve's second output -- on the GPU:
+        mu[p, c] = sum_{f, b} flux_fla[p, f, b] D[c, f, b] + background[c], shape (n, C); within gamma_{3N} of exact
+        (detector.fold_host; no defined summation order)."""
+        F = np.ascontiguousarray(flux_fla, dtype=np.float64)
+        if F.ndim != 3 or F.shape[1:] != (3, self.N):
+            raise ValueError("fold_flux: flux_fla must have shape (n, 3, %d), got %s" % (self.N, F.shape))
+        mu = np.zeros((F.shape[0], self.detector_bins()))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_fold_flux_host(self._h, F.ctypes.data_as(dp), F.shape[0], mu.ctypes.data_as(dp)))
+        return mu
+
+    def fold_flux_device(self, d_flux_fla_ptr, n, d_mu_ptr, stream_ptr=None):
+        """Asynchronous fold of device-resident flavour fluxes [n][3][N] into d_mu [n][C] (raw pointers)."""
+        _lib.check(_lib.load().nusi_plan_fold_flux(self._h, ctypes.c_void_p(d_flux_fla_ptr), int(n),
+                                                   ctypes.c_void_p(d_mu_ptr),
+                                                   ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def fold_response(self, G_fla):
+        """Fold response matrices G_fla (ntab, M, 3, N) of ``response`` with the detector on the GPU:
+        R[t, n, c] = sum_{f, b} G_fla[t, n, f, b] D[c, f, b] (no background), shape (ntab, M, C).  The entries of bins
+        b >= n -- exact zeros of a response matrix -- are not read."""
+        G = np.ascontiguousarray(G_fla, dtype=np.float64)
+        if G.ndim != 4 or G.shape[1:] != (self.T + 1, 3, self.N):
+            raise ValueError("fold_response: G_fla must have shape (ntab, %d, 3, %d), got %s" % (self.T + 1, self.N, G.shape))
+        R = np.zeros((G.shape[0], self.T + 1, self.detector_bins()))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_fold_host(self._h, G.ctypes.data_as(dp), G.shape[0], R.ctypes.data_as(dp)))
+        return R
+
+    def fold_response_device(self, d_G_fla_ptr, ntab, d_R_ptr, stream_ptr=None):
+        """Asynchronous fold of device-resident response matrices [ntab][M][3][N] into d_R [ntab][M][C] (raw pointers)."""
+        _lib.check(_lib.load().nusi_plan_response_fold(self._h, ctypes.c_void_p(d_G_fla_ptr), int(ntab),
+                                                       ctypes.c_void_p(d_R_ptr),
+                                                       ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def _data(self, data):
+        if data is None:
+            return None
+        d = np.ascontiguousarray(data, dtype=np.float64)
+        if d.shape != (self.detector_bins(),):
+            raise ValueError("events: data must have shape (%d,), got %s" % (self.detector_bins(), d.shape))
+        return d
+
+    def events(self, R, spectra, scale=None, data=None):
+        """Expected counts of Q spectra on folded response matrices R (ntab, M, C) on the GPU:
+        mu[t, q, c] = scale[q] * sum_n R[t, n, c] S[q, n] + background[c], shape (ntab, Q, C), bit for bit
+        detector.events_host.  With data (C,) also nll[t, q] = sum_c mu - data log mu (detector.poisson_host, the
+        Poisson negative log-likelihood without its data-only constant): returns (mu, nll).  spectra and scale as for
+        apply_response (scale >= 0 here)."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        C = self.detector_bins()
+        if C and (R.ndim != 3 or R.shape[1:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("events: R must have shape (ntab, %d, %d), got %s" % (self.T + 1, C, R.shape))
+        S, sc = self._spectra(spectra, scale)
+        d = self._data(data)
+        mu = np.zeros((R.shape[0], len(S), C))
+        nll = np.zeros((R.shape[0], len(S))) if d is not None else None
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_events_host(
+            self._h, R.ctypes.data_as(dp), R.shape[0], S.ctypes.data_as(dp), len(S),
+            sc.ctypes.data_as(dp) if sc is not None else None, d.ctypes.data_as(dp) if d is not None else None,
+            mu.ctypes.data_as(dp), nll.ctypes.data_as(dp) if nll is not None else None))
+        return mu if d is None else (mu, nll)
+
+    def events_device(self, d_R_ptr, ntab, spectra, d_mu_ptr, d_nll_ptr=None, scale=None, data=None, stream_ptr=None):
+        """Asynchronous events on device-resident folded matrices: d_R [ntab][M][C], d_mu [ntab][Q][C] and d_nll
+        [ntab][Q] (raw pointers; either output may be 0 / None, d_nll needs data); the spectra, scales and data are
+        host data and are copied.  Returns Q."""
+        S, sc = self._spectra(spectra, scale)
+        d = self._data(data)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_events(
+            self._h, ctypes.c_void_p(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S),
+            sc.ctypes.data_as(dp) if sc is not None else None, d.ctypes.data_as(dp) if d is not None else None,
+            ctypes.c_void_p(d_mu_ptr) if d_mu_ptr else None, ctypes.c_void_p(d_nll_ptr) if d_nll_ptr else None,
+            ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+        return len(S)
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since
