@@ -576,7 +576,7 @@ constexpr int kMcJobs = 1024;   // jobs (corner x point) per k_alpha_mcorner wor
 __global__ __launch_bounds__(256) void k_alpha_mcorner(const Point* __restrict__ pts, const int* __restrict__ batches,
                                                        MCornerDev mc, int pc0, int jobs)
 {
-    __shared__ double v[2 * kMcJobs];   // [q][cl][Dcr, Dci]
+    __shared__ __attribute__((aligned(16))) double v[2 * kMcJobs];   // [q][cl][Dcr, Dci]
     __shared__ double cst[2][kMcJobs];           // S', t of corner c0 + cl (shared by the batch's tables)
     const int bw = batches[blockIdx.y], k = blockIdx.z, tid = threadIdx.x;
     const int p0 = bw & 0xffffff, nb = (int)((unsigned)bw >> 24);
@@ -597,10 +597,24 @@ __global__ __launch_bounds__(256) void k_alpha_mcorner(const Point* __restrict__
         v[2 * (q * cb + cl) + 1] = Dc.i;
     }
     __syncthreads();
-    double* const o = mc.buf + (size_t)(p0 - pc0) * 6 * mc.NC + (size_t)k * 2 * nb * mc.NC;
-    for (int e = tid; e < 2 * nj; e += 256) {   // runs of 2 cb doubles per table q
-        const int q = e / (2 * cb), r = e - q * 2 * cb;
-        if (c0 + r / 2 < mc.NC) o[((size_t)q * mc.NC + c0) * 2 + r] = v[e];
+    // Runs of cb (Dcr, Dci) pairs per table q, a pair (16 bytes, aligned in v and in the block) per store.  Pair e = tid
+    // + 256 i is corner r = e % cb of table q = e / cb: divided once, then stepped by 256 = dq cb + dr -- the division
+    // and the 64-bit index product per 8-byte store were ~35 VALU instructions an iteration, 70 per GSL call in a
+    // kernel bound by VALU issue.  (A call of 256 jobs per workgroup, a single propagation, stores
+    // once per work-item; the former loop kept for such calls measured the same there, so there is one form.)
+    double* const ob = mc.buf + (size_t)(p0 - pc0) * 6 * mc.NC + (size_t)k * 2 * nb * mc.NC;
+    double2* const o = reinterpret_cast<double2*>(ob) + c0;
+    const double2* const v2 = reinterpret_cast<const double2*>(v);
+    const int nr = mc.NC - c0 < cb ? (int)(mc.NC - c0) : cb;   // the corners of this workgroup inside the axis
+    const int dq = 256 / cb, dr = 256 - dq * cb;
+    int q = tid / cb, r = tid - q * cb;
+    size_t off = (size_t)q * mc.NC + r;
+    const size_t doff = (size_t)dq * mc.NC + dr, woff = (size_t)(mc.NC - cb);
+    for (int e = tid; e < nj; e += 256) {
+        if (r < nr) o[off] = v2[e];
+        r += dr;
+        off += doff;
+        if (r >= cb) { r -= cb; off += woff; }
     }
 }
 
