@@ -282,6 +282,45 @@ int nusi_plan_response_events(nusi_plan *plan, const double *d_R, int ntab, cons
                               double *d_mu /* [ntab][Q][C] or NULL */, double *d_nll /* [ntab][Q] or NULL */, void *stream);
 int nusi_plan_response_events_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *scale,
                                    const double *data, double *mu, double *nll);
+/* nusi_plan_response_profile (k_detector_profile): the Poisson statistic of nusi_plan_response_events PROFILED over
+ * the flux normalisation -- for every table t and spectrum q the a >= 0 that minimises -ln L(a s + B | data), found
+ * by Newton's iteration on the derivative g(a) = sum_c s_c - sum_c data_c s_c / (a s_c + B_c), which is increasing
+ * and concave in a, from a start left of the root.  Every step is +, *, / and comparisons on IEEE doubles, each
+ * rounded separately (no fma), in a defined order, so ahat, mu and status are defined to the bit:
+ *   s_c      the events call's accumulator: acc = 0.0, acc = acc + R[t][n][c] * S[q][n], n = 1 .. M-1 ascending
+ *   tree(x)  x over c padded to P = 2^ceil(log2 C) entries with +0.0, then the vector replaced by the sums of its
+ *            adjacent pairs (0+1, 2+3, ..) until one value is left
+ *   active   bin c with data_c > 0 and s_c > 0; an inactive bin adds exactly 0.0 to S2 and S3 and is never divided
+ *   S1 = tree(s); if S1 == 0 or no bin is active: ahat = 0, NUSI_FIT_FLAT, no step
+ *   start    a = max(0, max over active c of (data_c / S1 - B_c / s_c))
+ *   step     den_c = a s_c + B_c (two roundings), u_c = s_c / den_c, r_c = data_c u_c, h_c = r_c u_c;
+ *            S2 = tree(r), S3 = tree(h), g = S1 - S2;  g >= 0: stop (NUSI_FIT_BOUNDARY if a == 0);
+ *            a_new = a + (S2 - S1) / S3;  a_new <= a: stop;  else a = a_new
+ *   at most NUSI_FIT_ITER_MAX steps, then NUSI_FIT_NOT_CONVERGED with the last a
+ *   mu[t][q][c] = ahat s_c + B_c (two roundings) and nll[t][q] the events call's statistic of that mu (+inf, and
+ *   NUSI_FIT_INFINITE, where data_c > 0 = mu_c: a bin with data, no signal and no background -- it does not enter
+ *   the iteration)
+ *   status[t][q] = the number of steps taken (low 8 bits, NUSI_FIT_STEPS_MASK) | the flags
+ * provided no non-zero product is subnormal and none overflows.  In exact arithmetic on those doubles
+ * |g(ahat)| <= (2 ceil(log2 C) + 18) u (S1 + S2), u = 2^-53, wherever ahat > 0 and the iteration converged
+ * (DESIGN.md sec. 4).  S [Q][M] and data [C] are host vectors and are copied (validation, copying and stream ordering
+ * as for nusi_plan_response_events; there is no scale: it is what is fitted); d_ahat [ntab][Q], d_nll [ntab][Q],
+ * d_mu [ntab][Q][C] (doubles) and d_status [ntab][Q] (ints) are DEVICE pointers, all but d_ahat may be NULL.
+ * NUSI_ESTATE without a detector, NUSI_EPARAM for data == NULL, d_ahat == NULL or a negative or non-finite S or
+ * data.  The _host form takes host arrays and is synchronous. */
+#define NUSI_FIT_ITER_MAX 64
+#define NUSI_FIT_STEPS_MASK 0xff
+#define NUSI_FIT_FLAT 0x100
+#define NUSI_FIT_BOUNDARY 0x200
+#define NUSI_FIT_NOT_CONVERGED 0x400
+#define NUSI_FIT_INFINITE 0x800
+int nusi_plan_response_profile(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab,
+                               const double *S /* [Q][M] */, int Q, const double *data /* [C] */,
+                               double *d_ahat /* [ntab][Q] */, double *d_nll /* [ntab][Q] or NULL */,
+                               double *d_mu /* [ntab][Q][C] or NULL */, int *d_status /* [ntab][Q] or NULL */,
+                               void *stream);
+int nusi_plan_response_profile_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
+                                    double *ahat, double *nll, double *mu, int *status);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);

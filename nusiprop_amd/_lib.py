@@ -23,6 +23,10 @@ SOURCE_POWER_LAW = 1
 SOURCE_TABULATED = 2        # + slot: a user-tabulated source of the plan (Plan.set_source, nusiprop_amd.sources)
 SOURCE_SLOTS_MAX = 65536
 DETECTOR_BINS_MAX = 64      # reconstructed bins of a plan's detector (Plan.set_detector, nusiprop_amd.detector)
+# the status word of Plan.profile (NUSI_FIT_*): the step count in the low 8 bits, flags above
+FIT_ITER_MAX = 64
+FIT_STEPS_MASK = 0xFF
+FIT_FLAT, FIT_BOUNDARY, FIT_NOT_CONVERGED, FIT_INFINITE = 0x100, 0x200, 0x400, 0x800
 
 WARN_GAMMA = 1
 WARN_ALPHATILDE = 2
@@ -60,7 +64,7 @@ EXPORTS = [
     "nusi_response",
     "nusi_plan_set_detector", "nusi_plan_detector_bins", "nusi_plan_fold_flux", "nusi_plan_fold_flux_host",
     "nusi_plan_response_fold", "nusi_plan_response_fold_host", "nusi_plan_response_events",
-    "nusi_plan_response_events_host",
+    "nusi_plan_response_events_host", "nusi_plan_response_profile", "nusi_plan_response_profile_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -138,6 +142,8 @@ def load():
         "nusi_plan_response_fold_host": (i, [vp, dp, i, dp]),
         "nusi_plan_response_events": (i, [vp, vp, i, dp, i, dp, dp, vp, vp, vp]),
         "nusi_plan_response_events_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp]),
+        "nusi_plan_response_profile": (i, [vp, vp, i, dp, i, dp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_profile_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, ip]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

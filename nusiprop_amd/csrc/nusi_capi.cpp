@@ -1800,27 +1800,28 @@ int nusi_plan_response_fold_host(nusi_plan* pl, const double* G_fla, int ntab, d
                          [&](const double* dI, double* dO) { return nusi_plan_response_fold(pl, dI, ntab, dO, nullptr); });
 }
 
-int nusi_plan_response_events(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* scale,
-                              const double* data, double* d_mu, double* d_nll, void* stream)
+// The argument checks of the events and the profile call (what: the call's name in the messages), and the staging of
+// their host vectors: S [Q][M], scale [Q] (or zeros) and data [C] (or zeros) into the plan's d_evt, in that order, on s.
+static int events_check(const nusi_plan* pl, const char* what, const double* d_R, int ntab, const double* S, int Q,
+                        const double* scale, const double* data)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response events: the plan has no detector (nusi_plan_set_detector)");
-    if (!d_R || !S) return fail(NUSI_EPARAM, "response events: R and S must not be NULL");
-    if (!d_mu && !d_nll) return fail(NUSI_EPARAM, "response events: mu and nll are both NULL");
-    if (d_nll && !data) return fail(NUSI_EPARAM, "response events: nll needs data");
-    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, "response events: need ntab >= 1 and 1 <= Q <= 2^19");
+    if (!d_R || !S) return fail(NUSI_EPARAM, std::string(what) + ": R and S must not be NULL");
+    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, std::string(what) + ": need ntab >= 1 and 1 <= Q <= 2^19");
     const size_t M = (size_t)pl->grid.T + 1;
-    const int C = pl->det_C;
     for (size_t e = 0; e < (size_t)Q * M; ++e)
         if (!(S[e] >= 0.0) || !std::isfinite(S[e])) return fail(NUSI_EPARAM, "source spectrum: a bin integral is negative or not finite");
     if (scale)
         for (int q = 0; q < Q; ++q)
-            if (!(scale[q] >= 0.0) || !std::isfinite(scale[q])) return fail(NUSI_EPARAM, "response events: a scale is negative or not finite");
+            if (!(scale[q] >= 0.0) || !std::isfinite(scale[q])) return fail(NUSI_EPARAM, std::string(what) + ": a scale is negative or not finite");
     if (data)
-        for (int c = 0; c < C; ++c)
-            if (!(data[c] >= 0.0) || !std::isfinite(data[c])) return fail(NUSI_EPARAM, "response events: a datum is negative or not finite");
-    HIPCHECK(hipSetDevice(pl->device));
-    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+        for (int c = 0; c < pl->det_C; ++c)
+            if (!(data[c] >= 0.0) || !std::isfinite(data[c])) return fail(NUSI_EPARAM, std::string(what) + ": a datum is negative or not finite");
+    return NUSI_OK;
+}
+static int events_stage(nusi_plan* pl, const double* S, int Q, const double* scale, const double* data, hipStream_t s)
+{
+    const size_t M = (size_t)pl->grid.T + 1;
+    const int C = pl->det_C;
     if (pl->det_ran) HIPCHECK(hipEventSynchronize(pl->ev_det));   // d_evt / h_evt are reused (every earlier detector
                                                                   // call has finished: detector_chain)
     const size_t need = (size_t)Q * M + (size_t)Q + (size_t)C;
@@ -1836,6 +1837,22 @@ int nusi_plan_response_events(nusi_plan* pl, const double* d_R, int ntab, const 
     if (scale) memcpy(pl->h_evt.data() + (size_t)Q * M, scale, sizeof(double) * Q);
     if (data) memcpy(pl->h_evt.data() + (size_t)Q * M + Q, data, sizeof(double) * C);
     HIPCHECK(hipMemcpyAsync(pl->d_evt, pl->h_evt.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
+    return NUSI_OK;
+}
+
+int nusi_plan_response_events(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* scale,
+                              const double* data, double* d_mu, double* d_nll, void* stream)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response events: the plan has no detector (nusi_plan_set_detector)");
+    if (!d_mu && !d_nll) return fail(NUSI_EPARAM, "response events: mu and nll are both NULL");
+    if (d_nll && !data) return fail(NUSI_EPARAM, "response events: nll needs data");
+    if (int r = events_check(pl, "response events", d_R, ntab, S, Q, scale, data)) return r;
+    const size_t M = (size_t)pl->grid.T + 1;
+    const int C = pl->det_C;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (int r = events_stage(pl, S, Q, scale, data, s)) return r;
     const double* d_sc = pl->d_evt + (size_t)Q * M;
     const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
     HIPCHECK(nusi::launch_detector_events(pl->gd, d_R, ntab, pl->d_evt, Q, scale ? d_sc : nullptr, d_sc + Q, bg, C, d_mu,
@@ -1861,6 +1878,48 @@ int nusi_plan_response_events_host(nusi_plan* pl, const double* R, int ntab, con
     if (r) return r;
     if (mu) memcpy(mu, o.data(), sizeof(double) * nmu);
     if (nll) memcpy(nll, o.data() + nmu, sizeof(double) * nn);
+    return NUSI_OK;
+}
+
+int nusi_plan_response_profile(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data,
+                               double* d_ahat, double* d_nll, double* d_mu, int* d_status, void* stream)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response profile: the plan has no detector (nusi_plan_set_detector)");
+    if (!data || !d_ahat) return fail(NUSI_EPARAM, "response profile: data and ahat must not be NULL");
+    if (int r = events_check(pl, "response profile", d_R, ntab, S, Q, nullptr, data)) return r;
+    const size_t M = (size_t)pl->grid.T + 1;
+    const int C = pl->det_C;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (int r = events_stage(pl, S, Q, nullptr, data, s)) return r;
+    const double* d_data = pl->d_evt + (size_t)Q * M + Q;
+    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
+    HIPCHECK(nusi::launch_detector_profile(pl->gd, d_R, ntab, pl->d_evt, Q, d_data, bg, C, d_ahat, d_nll, d_mu, d_status, s));
+    return detector_mark(pl, s);
+}
+
+int nusi_plan_response_profile_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
+                                    double* ahat, double* nll, double* mu, int* status)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response profile: the plan has no detector (nusi_plan_set_detector)");
+    if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response profile: R must not be NULL, ntab and Q >= 1");
+    if (!data || !ahat) return fail(NUSI_EPARAM, "response profile: data and ahat must not be NULL");
+    const size_t M = (size_t)pl->grid.T + 1, C = (size_t)pl->det_C, nmu = (size_t)ntab * Q * C, nn = (size_t)ntab * Q;
+    // one output block: ahat [ntab][Q], nll [ntab][Q], mu [ntab][Q][C], then status [ntab][Q] (ints)
+    std::vector<double> o(2 * nn + nmu + (nn + 1) / 2);
+    const int r = detector_host(pl, R, (size_t)ntab * M * C, o.data(), o.size(), "response profile",
+                                [&](const double* dI, double* dO) {
+                                    return nusi_plan_response_profile(pl, dI, ntab, S, Q, data, dO, nll ? dO + nn : nullptr,
+                                                                      mu ? dO + 2 * nn : nullptr,
+                                                                      status ? (int*)(dO + 2 * nn + nmu) : nullptr, nullptr);
+                                });
+    if (r) return r;
+    memcpy(ahat, o.data(), sizeof(double) * nn);
+    if (nll) memcpy(nll, o.data() + nn, sizeof(double) * nn);
+    if (mu) memcpy(mu, o.data() + 2 * nn, sizeof(double) * nmu);
+    if (status) memcpy(status, o.data() + 2 * nn + nmu, sizeof(int) * nn);
     return NUSI_OK;
 }
 

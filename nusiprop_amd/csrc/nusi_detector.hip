@@ -5,6 +5,8 @@
 //                         (nusi_plan_fold_flux, nusi_plan_response_fold); CT = ceil(C / 16) column tiles
 //   k_detector_events     spectra on folded response matrices R [t][M][C]: expected counts per reconstructed bin
 //                         and the Poisson statistic (nusi_plan_response_events), in a defined order
+//   k_detector_profile    that statistic profiled over the flux normalisation: Newton's iteration per (t, q), its
+//                         sums over the bins as butterflies inside a wave (nusi_plan_response_profile)
 #include <hip/hip_runtime.h>
 
 #include "nusi_internal.hpp"
@@ -219,6 +221,191 @@ hipError_t launch_detector_events(const GridDev& g, const double* R, int ntab, c
     const int QB = (kEvThreads >> lg) * kEvQ;
     hipLaunchKernelGGL(k_detector_events, dim3((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), dim3(kEvThreads), 0, s, R, S,
                        scale, data, bg, mu, nll, g.T + 1, C, lg, Q);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_detector_profile: the statistic profiled over the flux normalisation (nusi_plan_response_profile): per (t, q) the
+// a >= 0 minimising -ln L(a s + B | data), by the iteration include/nusi.h defines.  The front half and the statistic
+// are k_detector_events' (the same text, kept apart so that kernel's code does not move): lanes on (c, a group of kEvQ
+// spectra), four accumulators s_c per lane.  The P = 2^lgC lanes of a group lie inside one wave (P <= 64, groups
+// aligned), so the sums over c are xor-butterflies over those lanes: stage k adds the partner across 2^k lanes, which
+// is the tree of adjacent pairs, and every lane ends with the same bits (a + b = b + a).  Strides 1 and 2 are DPP
+// quad permutations; 4 and 8 are the row's half mirror and mirror (the lanes of a quad, or of eight, already hold one
+// value, so lane 7 - i, or 15 - i, stands for lane i ^ 4, or i ^ 8); 16 is ds_swizzle, 32 a bpermute.  No LDS
+// round trip and no barrier inside the iteration.  The iterate a is uniform over a group's lanes by construction;
+// the four chains of a lane run interleaved (the fp64 divisions of one behind the others); a chain that has stopped
+// keeps its a, and the wave leaves the loop when no chain of any of its groups runs, so the butterflies always run
+// with full exec.  Padding lanes (c >= C) carry s = data = B = 0 and are inactive bins.
+// ---------------------------------------------------------------------------
+template <int CTRL>
+__device__ __forceinline__ double det_dpp(double x)
+{
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double det_swizzle16(double x)   // lane i ^ 16: bit mode, and 0x1f, or 0, xor 0x10
+{
+    const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(x), 0x401f);
+    const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(x), 0x401f);
+    return __hiloint2double(hi, lo);
+}
+// v[k] = op over the 2^lgC lanes of the group, for NV values at once (lgC is uniform)
+template <int NV, class Op>
+__device__ __forceinline__ void det_butterfly(double (&v)[NV], int lgC, Op op)
+{
+    if (lgC > 0)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = op(v[k], det_dpp<0xb1>(v[k]));    // quad_perm [1, 0, 3, 2]
+    if (lgC > 1)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = op(v[k], det_dpp<0x4e>(v[k]));    // quad_perm [2, 3, 0, 1]
+    if (lgC > 2)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = op(v[k], det_dpp<0x141>(v[k]));   // row_half_mirror
+    if (lgC > 3)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = op(v[k], det_dpp<0x140>(v[k]));   // row_mirror
+    if (lgC > 4)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = op(v[k], det_swizzle16(v[k]));
+    if (lgC > 5)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = op(v[k], __shfl_xor(v[k], 32));
+}
+
+__global__ __launch_bounds__(kEvThreads) void k_detector_profile(const double* __restrict__ R, const double* __restrict__ S,
+                                                                 const double* __restrict__ data,
+                                                                 const double* __restrict__ bg, double* __restrict__ ahat,
+                                                                 double* __restrict__ nll, double* __restrict__ mu,
+                                                                 int* __restrict__ status, int M, int C, int lgC, int Q)
+{
+#pragma clang fp contract(off)
+    __shared__ double smu[kEvLds];
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = (kEvThreads >> lgC) * kEvQ, qb0 = (int)blockIdx.y * QB, q0 = qb0 + grp * kEvQ;
+    const int cc = c < C ? c : C - 1, Cs = C | 1;
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* Sq[kEvQ];
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) Sq[j] = S + (size_t)(q0 + j < Q ? q0 + j : Q - 1) * M;
+    double s[kEvQ];
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) s[j] = 0.0;
+#pragma unroll 4
+    for (int n = 1; n < M; ++n) {
+        const double rv = Rt[(size_t)n * C];
+#pragma unroll
+        for (int j = 0; j < kEvQ; ++j) s[j] = s[j] + rv * Sq[j][n];
+    }
+    const bool in = c < C;
+    const double b = in ? bg[cc] : 0.0, d = in ? data[cc] : 0.0;
+    // the group's lanes in a ballot
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto max = [](double x, double y) { return y > x ? y : x; };
+    double S1[kEvQ], a[kEvQ];
+    bool act[kEvQ], run[kEvQ];
+    int st[kEvQ];
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) {
+        if (!in) s[j] = 0.0;
+        S1[j] = s[j];
+        act[j] = d > 0.0 && s[j] > 0.0;
+    }
+    det_butterfly(S1, lgC, add);
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) {
+        run[j] = S1[j] != 0.0 && (__ballot(act[j]) & gmask) != 0;
+        st[j] = run[j] ? 0 : NUSI_FIT_FLAT;
+        const double x0 = d / S1[j], x1 = b / s[j];
+        a[j] = act[j] ? x0 - x1 : 0.0;
+    }
+    det_butterfly(a, lgC, max);
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) a[j] = (run[j] && a[j] > 0.0) ? a[j] : 0.0;
+    // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
+    while (__any(run[0] || run[1] || run[2] || run[3])) {
+        double v[2 * kEvQ];
+#pragma unroll
+        for (int j = 0; j < kEvQ; ++j) {
+            double den = a[j] * s[j];
+            den = den + b;
+            const double q = s[j] / den;
+            const double u = act[j] ? q : 0.0;
+            const double r = d * u;
+            v[j] = r;
+            v[kEvQ + j] = r * u;
+        }
+        det_butterfly(v, lgC, add);
+#pragma unroll
+        for (int j = 0; j < kEvQ; ++j) {
+            const double S2 = v[j], S3 = v[kEvQ + j];
+            const double g = S1[j] - S2;
+            const double dn = S2 - S1[j];
+            const double an = a[j] + dn / S3;
+            if (run[j]) {
+                ++st[j];
+                if (!(g < 0.0)) {
+                    run[j] = false;
+                    if (a[j] == 0.0) st[j] |= NUSI_FIT_BOUNDARY;
+                } else if (!(an > a[j])) {
+                    run[j] = false;
+                } else {
+                    a[j] = an;
+                    if ((st[j] & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
+                        run[j] = false;
+                        st[j] |= NUSI_FIT_NOT_CONVERGED;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kEvQ; ++j) {
+        const int q = q0 + j;
+        double m = a[j] * s[j];
+        m = m + b;
+        if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st[j] |= NUSI_FIT_INFINITE;
+        if (in) {
+            smu[(grp * kEvQ + j) * Cs + c] = m;
+            if (mu && q < Q) mu[((size_t)t * Q + q) * C + c] = m;
+        }
+        if (c == 0 && q < Q) {
+            ahat[(size_t)t * Q + q] = a[j];
+            if (status) status[(size_t)t * Q + q] = st[j];
+        }
+    }
+    if (!nll) return;   // (uniform)
+    __syncthreads();
+    for (int i = tid; i < QB && qb0 + i < Q; i += kEvThreads) {
+        const int q = qb0 + i;
+        double sum = 0.0;
+        for (int k = 0; k < C; ++k) {
+            const double m = smu[i * Cs + k], dk = data[k];
+            double term = m;
+            if (dk != 0.0) {
+                const double p = dk * nm::log_i(m);
+                term = m - p;
+            }
+            sum = sum + term;
+        }
+        nll[(size_t)t * Q + q] = sum;
+    }
+}
+
+hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                                   const double* bg, int C, double* ahat, double* nll, double* mu, int* status,
+                                   hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0) return hipSuccess;
+    int lg = 0;
+    while ((1 << lg) < C) ++lg;
+    const int QB = (kEvThreads >> lg) * kEvQ;
+    hipLaunchKernelGGL(k_detector_profile, dim3((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), dim3(kEvThreads), 0, s, R, S,
+                       data, bg, ahat, nll, mu, status, g.T + 1, C, lg, Q);
     return hipGetLastError();
 }
 

@@ -154,6 +154,11 @@ hipError_t launch_detector_fold(const GridDev& g, const double* X, int ntab, int
                                 const double* bg, double* out, hipStream_t s);
 hipError_t launch_detector_events(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* scale,
                                   const double* data, const double* bg, int C, double* mu, double* nll, hipStream_t s);
+// k_detector_profile: per (t, q) the a >= 0 minimising the statistic of a s + bg (include/nusi.h); ahat, nll [ntab][Q],
+// mu [ntab][Q][C], status [ntab][Q] in device memory, all but ahat may be nullptr
+hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                                   const double* bg, int C, double* ahat, double* nll, double* mu, int* status,
+                                   hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

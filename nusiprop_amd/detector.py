@@ -10,15 +10,21 @@ R[n][c], M x C doubles, and every spectrum is then a C-vector of expected counts
     plan.set_detector(D, background=b)
     R = plan.fold_response(G_fla)                                       # (ntab, M, C); fold_host on the CPU
     mu, nll = plan.events(R, spectra, scale=1e-8, data=counts)          # events_host + poisson_host on the CPU
+    ahat, nll_hat, _, st = plan.profile(R, spectra, data=counts)        # profile_host on the CPU: min over the scale
 
 ``fold_host`` has no defined summation order (neither has the GPU's, which runs on the matrix cores): with every term
 non-negative, either is within gamma_K = K u / (1 - K u), K = 3 N, u = 2^-53, of the exact sum.  ``events_host`` and
 ``poisson_host`` are the sums nusi_plan_response_events defines, in its order, so mu agrees bit for bit and nll to the
-last bits of the log.
+last bits of the log.  ``profile_host`` is the iteration nusi_plan_response_profile defines, operation for operation
+(``tree`` is its sum over the bins), so ahat, mu and the status word agree bit for bit as well.
 """
 import numpy as np
 
 BINS_MAX = 64       # NUSI_DETECTOR_BINS_MAX
+# the profile's status word (include/nusi.h NUSI_FIT_*): the step count in the low 8 bits, flags above
+FIT_ITER_MAX = 64
+FIT_STEPS_MASK = 0xFF
+FIT_FLAT, FIT_BOUNDARY, FIT_NOT_CONVERGED, FIT_INFINITE = 0x100, 0x200, 0x400, 0x800
 
 
 def gamma(K):
@@ -92,6 +98,81 @@ def poisson_host(mu, data, log=np.log):
             s = s + term
         out[i] = s
     return out.reshape(mu.shape[:-1])
+
+
+def tree(x):
+    """The pairwise sum over the last axis that a butterfly over neighbouring lanes computes: pad to P = 2^ceil(log2 C)
+    entries with +0.0, then replace the vector by the sums of adjacent pairs (0+1, 2+3, ..) until one value is left."""
+    x = np.asarray(x, dtype=np.float64)
+    C = x.shape[-1]
+    P = 1
+    while P < C:
+        P *= 2
+    v = np.zeros(x.shape[:-1] + (P,))
+    v[..., :C] = x
+    while v.shape[-1] > 1:
+        v = v[..., 0::2] + v[..., 1::2]
+    return v[..., 0]
+
+
+def profile_host(R, S, data, background=None, log=np.log):
+    """The Poisson statistic profiled over the flux normalisation: for every table and spectrum the a >= 0 that
+    minimises -ln L(a s + B | data), s_c = sum_n R[..., n, c] S[q, n] (events_host's accumulator), by the iteration
+    nusi_plan_response_profile defines (include/nusi.h) -- the same operations in the same order, so ahat, mu and
+    status agree with the GPU bit for bit and nll to the last bits of the log.
+
+    R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  data: (C,).  background: None (= 0), a number or (C,).
+    Returns (ahat, nll, mu, status): ahat, nll and status (int32: the step count in the low 8 bits, FIT_* flags above)
+    of shape (ntab, Q), mu = ahat s + B of shape (ntab, Q, C); the squeezed axes of events_host are squeezed here."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    data = np.asarray(data, dtype=np.float64)
+    one_tab, one_q = R.ndim == 2, S.ndim == 1
+    s = events_host(R[None] if one_tab else R, S[None] if one_q else S)           # 1.0 * acc + 0.0: acc itself
+    C = s.shape[-1]
+    if data.shape != (C,):
+        raise ValueError("profile_host: data must have shape (%d,), got %s" % (C, data.shape))
+    if not np.all(np.isfinite(data)) or np.any(data < 0):
+        raise ValueError("profile_host: a datum is negative or not finite")
+    B = np.zeros(C) if background is None else np.broadcast_to(np.asarray(background, dtype=np.float64), (C,))
+    d = np.broadcast_to(data, s.shape)
+    act = (d > 0) & (s > 0)
+    S1 = tree(s)
+    flat = (S1 == 0) | ~act.any(axis=-1)
+    flags = np.where(flat, FIT_FLAT, 0).astype(np.int32)
+    steps = np.zeros(S1.shape, dtype=np.int32)
+    with np.errstate(all="ignore"):
+        x = np.where(act, d / S1[..., None] - B / s, 0.0)
+        a = np.where(flat, 0.0, np.maximum(0.0, x.max(axis=-1)))
+        run = ~flat
+        for it in range(FIT_ITER_MAX):
+            if not run.any():
+                break
+            den = a[..., None] * s                         # two roundings
+            den = den + B
+            u = np.where(act, s / den, 0.0)                # inactive bins: exactly 0.0 in both sums, never divided
+            r = d * u
+            h = r * u
+            S2, S3 = tree(r), tree(h)
+            steps[run] += 1
+            g = S1 - S2
+            stop = run & ~(g < 0)
+            flags[stop & (a == 0)] |= FIT_BOUNDARY
+            run = run & ~stop
+            an = a + (S2 - S1) / S3
+            run = run & (an > a)
+            a = np.where(run, an, a)
+        flags[run] |= FIT_NOT_CONVERGED
+    mu = a[..., None] * s
+    mu = mu + B
+    flags[np.any((d > 0) & (mu == 0), axis=-1)] |= FIT_INFINITE
+    nll = poisson_host(mu, data, log=log)
+    status = steps | flags
+    if one_q:
+        a, nll, mu, status = a[:, 0], nll[:, 0], mu[:, 0], status[:, 0]
+    if one_tab:
+        a, nll, mu, status = a[0], nll[0], mu[0], status[0]
+    return a, nll, mu, status
 
 
 def matrix(lo, hi, aeff, migration=None, exposure=1.0):

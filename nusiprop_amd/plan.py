@@ -286,6 +286,46 @@ class Plan:
             ctypes.c_void_p(stream_ptr) if stream_ptr else None))
         return len(S)
 
+    def profile(self, R, spectra, data):
+        """The statistic of ``events`` profiled over the flux normalisation, on the GPU: for every table and spectrum
+        the a >= 0 that minimises -ln L(a s + background | data), s the expected signal counts of the spectrum at
+        scale 1.  Returns (ahat, nll, mu, status): ahat, nll and status of shape (ntab, Q), mu = ahat s + background of
+        shape (ntab, Q, C); status holds the Newton steps taken in its low 8 bits and the _lib.FIT_* flags above
+        (FIT_FLAT: no signal or no data in any signal bin, ahat = 0; FIT_BOUNDARY: the minimum is at a = 0;
+        FIT_NOT_CONVERGED; FIT_INFINITE: a bin with data has neither signal nor background, nll = +inf).  ahat, mu and
+        status equal detector.profile_host bit for bit.  There is no scale: it is what is fitted."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        C = self.detector_bins()
+        if C and (R.ndim != 3 or R.shape[1:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("profile: R must have shape (ntab, %d, %d), got %s" % (self.T + 1, C, R.shape))
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
+        ntab, Q = R.shape[0], len(S)
+        ahat, nll, mu = np.zeros((ntab, Q)), np.zeros((ntab, Q)), np.zeros((ntab, Q, C))
+        status = np.zeros((ntab, Q), dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_profile_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp) if d is not None else None,
+            ahat.ctypes.data_as(dp), nll.ctypes.data_as(dp), mu.ctypes.data_as(dp),
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return ahat, nll, mu, status
+
+    def profile_device(self, d_R_ptr, ntab, spectra, data, d_ahat_ptr, d_nll_ptr=None, d_mu_ptr=None, d_status_ptr=None,
+                       stream_ptr=None):
+        """Asynchronous profile on device-resident folded matrices: d_R [ntab][M][C], d_ahat and d_nll [ntab][Q],
+        d_mu [ntab][Q][C] (doubles) and d_status [ntab][Q] (ints) are raw pointers, every output but d_ahat may be
+        0 / None; the spectra and data are host data and are copied.  Returns Q."""
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_response_profile(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None,
+            vp(d_ahat_ptr) if d_ahat_ptr else None, vp(d_nll_ptr) if d_nll_ptr else None,
+            vp(d_mu_ptr) if d_mu_ptr else None, vp(d_status_ptr) if d_status_ptr else None,
+            vp(stream_ptr) if stream_ptr else None))
+        return len(S)
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since

@@ -7,6 +7,8 @@ measurement.
   fold     nusi_plan_response_fold of the n resident G_fla at C = 16, 32 and 64: ms and GB/s against the bytes of G_fla
            the kernel reads (the bins b < n0 + 16 of each 16-row tile) and against all of G_fla
   events   nusi_plan_response_events of Q = 1000 spectra on the n folded matrices (C = 32), mu only and mu + nll
+  profile  nusi_plan_response_profile at the same shape, every output: its ratio to the events' mu + nll line (the same
+           bytes and the same front half) and the mean Newton step count from the status words
   apply    nusi_plan_response_apply at Q = 8 in the same session: it reads the same bytes of G_fla in one accumulator
            chunk, so it is the fold's yardstick
 
@@ -34,6 +36,7 @@ def hip():
     vp = ctypes.c_void_p
     H.hipMalloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t]
     H.hipFree.argtypes = [vp]
+    H.hipMemcpy.argtypes = [vp, vp, ctypes.c_size_t, ctypes.c_int]
     return H
 
 
@@ -91,6 +94,19 @@ def main():
             plan._h, dR, n, S.ctypes.data_as(dp), Q, sc.ctypes.data_as(dp), dat, dMu, nll, None)))
         print(json.dumps({"what": "events", "tables": n, "C": C, "Q": Q, "outputs": label, "ms": t, "ms_min": tmin}),
               flush=True)
+    t_events = t
+    dAhat, dSt = ctypes.c_void_p(), ctypes.c_void_p()
+    assert H.hipMalloc(ctypes.byref(dAhat), n * Q * 8) == 0 and H.hipMalloc(ctypes.byref(dSt), n * Q * 4) == 0
+    t, tmin = timed(H, a.reps, lambda: nu._lib.check(L.nusi_plan_response_profile(
+        plan._h, dR, n, S.ctypes.data_as(dp), Q, data.ctypes.data_as(dp), dAhat, dNll, dMu, dSt, None)))
+    st = np.zeros(n * Q, dtype=np.int32)
+    assert H.hipMemcpy(st.ctypes.data, dSt, st.nbytes, 2) == 0
+    steps = st & nu._lib.FIT_STEPS_MASK
+    print(json.dumps({"what": "profile", "tables": n, "C": C, "Q": Q, "outputs": "ahat+nll+mu+status", "ms": t, "ms_min": tmin,
+                      "ratio_to_events_mu_nll": t / t_events, "steps_mean": float(steps.mean()), "steps_max": int(steps.max()),
+                      "flagged": int(np.count_nonzero(st & ~nu._lib.FIT_STEPS_MASK))}), flush=True)
+    for d in (dAhat, dSt):
+        H.hipFree(d)
     S8 = S[:8]
     t, tmin = timed(H, a.reps, lambda: plan.apply_response_device(dGf.value, n, S8, dO.value))
     print(json.dumps({"what": "apply", "tables": n, "Q": 8, "ms": t, "ms_min": tmin, "GBps_of_G": nbytes / t * 1e-6}),
