@@ -321,6 +321,75 @@ int nusi_plan_response_profile(nusi_plan *plan, const double *d_R /* [ntab][M][C
                                void *stream);
 int nusi_plan_response_profile_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
                                     double *ahat, double *nll, double *mu, int *status);
+/* Floating background templates (k_detector_fit): the statistic minimised over the signal's scale AND the
+ * normalisations of K <= NUSI_FIT_TEMPLATES_MAX background templates T_j [C] >= 0 of the plan's detector, each under an
+ * optional Gaussian prior (mean m_j >= 0, width sigma_j > 0; sigma_j = +inf, or prior_sigma == NULL, = none):
+ *     mu_c(theta) = theta_0 s_c + sum_j theta_j T_j[c] + B_c,   theta >= 0,   j = 1 .. K
+ *     f(theta)    = sum_c (mu_c - data_c log mu_c) + sum_j w_j (theta_j - m_j)^2 / 2,   w_j = 1 / (sigma_j sigma_j)
+ * B stays the fixed part; the signal has no prior (w_0 = m_0 = 0 below; m_j = 0 where w_j = 0).
+ * nusi_plan_set_templates copies T [K][C] and the priors (ordering and copying as nusi_plan_set_detector).  It needs
+ * a detector (NUSI_ESTATE); K = 0 or T == NULL clears the templates; NUSI_EPARAM for K outside 0 ..
+ * NUSI_FIT_TEMPLATES_MAX, a negative or non-finite entry of T or prior_mean, a template of zeros, sigma <= 0 or NaN.
+ * Setting a detector (or clearing it) clears the templates.  nusi_plan_templates: K, 0 = none.
+ *
+ * nusi_plan_response_fit: theta_hat = argmin f for every table t and spectrum q, by a damped Newton iteration on the
+ * bound-constrained convex problem.  Every operation is +, -, *, / or a comparison on IEEE doubles, each rounded
+ * separately (no fma), in a defined order, so theta, mu and status are defined to the bit (detector.fit_host is the
+ * same text in numpy); only nll passes through the log.  With X_0 = s (the profile's accumulator), X_j = T_j, n = 1 + K,
+ * tree() the profile's sum over the bins, kappa = 2 (ceil(log2 C) + K) + 18 and u = 2^-53:
+ *   S1_j = tree(X_j).  Component j is live when S1_j > 0 -- and, for the signal, some bin has data_c > 0 and s_c > 0;
+ *            a signal that is not live keeps theta_0 = 0 (NUSI_FIT_FLAT) and the fit goes on over the templates
+ *   active   bin c with data_c > 0 and (B_c > 0 or X_jc > 0 for a live j); inactive bins add exactly 0.0 to every sum
+ *            below and are never divided.  dmin = min(1, the smallest active datum)
+ *   start    theta_j = tree(data over the active bins) / (n_live * S1_j) for the live j, 0 for the others
+ *   eval(x)  den_c = x_0 X_0c, den_c = den_c + x_j X_jc (j ascending), den_c = den_c + B_c;  bad = an active den_c is
+ *            not > 0;  w_c = data_c / den_c, r_c = w_c / den_c;  S2_j = tree(X_jc w_c),
+ *            H_jk = tree((X_jc r_c) X_kc) + (j == k ? w_j : 0) for j <= k,  g_j = (S1_j - S2_j) + w_j (x_j - m_j)
+ *   The iteration holds theta, a direction p and a step length t.  First eval(start): bad = stop with
+ *   NUSI_FIT_NOT_CONVERGED, else it is theta.  Then, with g, H and S2 of theta's eval:
+ *   free     the live j with theta_j > 0 or g_j < 0
+ *   stop     when every free j has |g_j| <= kappa u scale_j,  scale_j = (S1_j + S2_j) + w_j (theta_j + m_j)
+ *   caps     the step before changed no theta_j, or NUSI_FIT_ITER_MAX steps are taken: NUSI_FIT_NOT_CONVERGED, stop
+ *   solve    F = free.  p = -H^-1 g on F (the other j: p_j = 0) by L D L^T in ascending order:
+ *            c_ij = H_ij - sum_{k<j} c_ik L_jk, L_ij = c_ij / D_j, D_i = H_ii - sum_{k<i} c_ik L_ik; y_i = -g_i -
+ *            sum_{k<i} L_ik y_k; p_i = y_i / D_i - sum_{k>i} L_ki p_k (i descending; every sum subtracts k ascending).
+ *            A j in F with theta_j == 0 and p_j < 0 leaves F (all such at once) and the solve is repeated.
+ *            A D_i not > 0, or acc = sum_{j in F} g_j p_j (from 0.0, ascending) not < 0: NUSI_FIT_SINGULAR, stop
+ *   length   ratio_j = theta_j / -p_j for the j in F with p_j < 0;  t = min(1, the ratios);  clipped = t < 1;
+ *            quad = not clipped and -acc <= dmin / 16;  the candidate is x_j = theta_j + t p_j, and exactly 0 for
+ *            the j whose ratio_j == t when clipped
+ *   trial    eval(x);  slope = sum_j p_j g_j(x) (from 0.0, ascending).  The candidate is accepted when it is not bad
+ *            and (quad or slope is not > 0): theta = x, one step counted, and on with `free`.  Otherwise t = t / 2,
+ *            x_j = theta_j + t p_j and the trial is repeated; after NUSI_FIT_TRIALS_MAX halvings of one step:
+ *            NUSI_FIT_NOT_CONVERGED, stop with theta
+ *   mu[t][q][c] = den_c(theta_hat); nll[t][q] = the events call's statistic of that mu, then for j = 1 .. K ascending
+ *   with w_j > 0: nll = nll + ((0.5 w_j) (theta_j - m_j)) (theta_j - m_j)
+ *   status[t][q] = the steps taken (low 8 bits) | NUSI_FIT_FLAT | NUSI_FIT_BOUNDARY (a live signal with theta_0 == 0)
+ *            | NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR | NUSI_FIT_INFINITE (data_c > 0 = mu_c, nll = +inf; such a bin
+ *            is inactive) | NUSI_FIT_ZERO << j for every component j with theta_j == 0 | the halvings of all steps,
+ *            saturating at NUSI_FIT_TRIALS_MASK, << NUSI_FIT_TRIALS_SHIFT
+ * provided no non-zero product is subnormal and none overflows.  f / dmin is self-concordant, so the halving ends and
+ * the iteration converges; where it stopped by `stop`, in exact arithmetic on those doubles
+ * |g_j(theta_hat)| <= (kappa + ceil(log2 C) + 2 K + 9) u scale_j for the free j, and g_j >= -that for the others.
+ * S, data and the outputs are as for nusi_plan_response_profile; d_theta [ntab][Q][1 + K] must not be NULL.
+ * NUSI_ESTATE without a detector or without templates (that case is nusi_plan_response_profile). */
+enum {   /* (the fit's own constants; the status word's NUSI_FIT_* macros above are shared with the profile) */
+    NUSI_FIT_TEMPLATES_MAX = 3,
+    NUSI_FIT_TRIALS_MAX = 64,
+    NUSI_FIT_SINGULAR = 0x1000,
+    NUSI_FIT_ZERO = 0x10000,
+    NUSI_FIT_TRIALS_SHIFT = 24,
+    NUSI_FIT_TRIALS_MASK = 0x7f
+};
+int nusi_plan_set_templates(nusi_plan *plan, int K, const double *T /* [K][C] */, const double *prior_mean /* [K] or NULL */,
+                            const double *prior_sigma /* [K] or NULL */);
+int nusi_plan_templates(const nusi_plan *plan);
+int nusi_plan_response_fit(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab, const double *S /* [Q][M] */,
+                           int Q, const double *data /* [C] */, double *d_theta /* [ntab][Q][1 + K] */,
+                           double *d_nll /* [ntab][Q] or NULL */, double *d_mu /* [ntab][Q][C] or NULL */,
+                           int *d_status /* [ntab][Q] or NULL */, void *stream);
+int nusi_plan_response_fit_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
+                                double *theta, double *nll, double *mu, int *status);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);

@@ -27,6 +27,10 @@ DETECTOR_BINS_MAX = 64      # reconstructed bins of a plan's detector (Plan.set_
 FIT_ITER_MAX = 64
 FIT_STEPS_MASK = 0xFF
 FIT_FLAT, FIT_BOUNDARY, FIT_NOT_CONVERGED, FIT_INFINITE = 0x100, 0x200, 0x400, 0x800
+# ... and of Plan.fit: a singular Newton system, FIT_ZERO << j for a component that ends at zero, the halvings from bit 24
+FIT_TEMPLATES_MAX = 3
+FIT_TRIALS_MAX = 64
+FIT_SINGULAR, FIT_ZERO, FIT_TRIALS_SHIFT, FIT_TRIALS_MASK = 0x1000, 0x10000, 24, 0x7F
 
 WARN_GAMMA = 1
 WARN_ALPHATILDE = 2
@@ -65,6 +69,7 @@ EXPORTS = [
     "nusi_plan_set_detector", "nusi_plan_detector_bins", "nusi_plan_fold_flux", "nusi_plan_fold_flux_host",
     "nusi_plan_response_fold", "nusi_plan_response_fold_host", "nusi_plan_response_events",
     "nusi_plan_response_events_host", "nusi_plan_response_profile", "nusi_plan_response_profile_host",
+    "nusi_plan_set_templates", "nusi_plan_templates", "nusi_plan_response_fit", "nusi_plan_response_fit_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -144,6 +149,10 @@ def load():
         "nusi_plan_response_events_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp]),
         "nusi_plan_response_profile": (i, [vp, vp, i, dp, i, dp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_profile_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, ip]),
+        "nusi_plan_set_templates": (i, [vp, i, dp, dp, dp]),
+        "nusi_plan_templates": (i, [vp]),
+        "nusi_plan_response_fit": (i, [vp, vp, i, dp, i, dp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_fit_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, ip]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -463,6 +463,9 @@ struct nusi_plan {
     // the detector (nusi_plan_set_detector) and its calls (fold, events)
     int det_C = 0;                  // reconstructed bins; 0 = no detector
     double* d_det = nullptr;        // Dt [3 N][detector_ld(C)] (K-major, zero-padded columns), then the background [C]
+    int fit_K = 0;                  // background templates of the fit (nusi_plan_set_templates); 0 = none
+    double* d_tpl = nullptr;        // T [K][C]
+    double fit_m[NUSI_FIT_TEMPLATES_MAX] = {}, fit_w[NUSI_FIT_TEMPLATES_MAX] = {};   // the priors: means, 1 / sigma^2 (0 = none)
     double* d_evt = nullptr;        // events: the spectra S [Q][T + 1], then scale [Q], then data [C]
     size_t evt_doubles = 0;
     std::vector<double> h_evt;
@@ -927,6 +930,7 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->d_app);
     if (pl->ev_det) hipEventDestroy(pl->ev_det);
     hipFree(pl->d_det);
+    hipFree(pl->d_tpl);
     hipFree(pl->d_evt);
     nusi::alpha_tiles_destroy(&pl->atiles);
     hipFree(pl->mc.buf);
@@ -1764,6 +1768,9 @@ int nusi_plan_set_detector(nusi_plan* pl, int C, const double* D, const double* 
     hipFree(pl->d_det);
     pl->d_det = d_new;
     pl->det_C = clear ? 0 : C;
+    hipFree(pl->d_tpl);   // the templates belong to the detector they were set for
+    pl->d_tpl = nullptr;
+    pl->fit_K = 0;
     return NUSI_OK;
 }
 
@@ -1920,6 +1927,108 @@ int nusi_plan_response_profile_host(nusi_plan* pl, const double* R, int ntab, co
     if (nll) memcpy(nll, o.data() + nn, sizeof(double) * nn);
     if (mu) memcpy(mu, o.data() + 2 * nn, sizeof(double) * nmu);
     if (status) memcpy(status, o.data() + 2 * nn + nmu, sizeof(int) * nn);
+    return NUSI_OK;
+}
+
+// The fit's background templates (nusi_plan_set_templates) and the fit (nusi_detector.hip k_detector_fit)
+int nusi_plan_set_templates(nusi_plan* pl, int K, const double* T, const double* prior_mean, const double* prior_sigma)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "templates: the plan has no detector (nusi_plan_set_detector)");
+    const bool clear = !T || K == 0;
+    const int C = pl->det_C;
+    double m[NUSI_FIT_TEMPLATES_MAX] = {}, w[NUSI_FIT_TEMPLATES_MAX] = {};
+    if (!clear) {
+        if (K < 0 || K > NUSI_FIT_TEMPLATES_MAX) return fail(NUSI_EPARAM, "templates: K outside 0 .. NUSI_FIT_TEMPLATES_MAX");
+        for (int j = 0; j < K; ++j) {
+            bool some = false;
+            for (int c = 0; c < C; ++c) {
+                const double x = T[(size_t)j * C + c];
+                if (!(x >= 0.0) || !std::isfinite(x)) return fail(NUSI_EPARAM, "templates: an entry is negative or not finite");
+                some = some || x > 0.0;
+            }
+            if (!some) return fail(NUSI_EPARAM, "templates: a template of zeros");
+            if (prior_mean && (!(prior_mean[j] >= 0.0) || !std::isfinite(prior_mean[j])))
+                return fail(NUSI_EPARAM, "templates: a prior mean is negative or not finite");
+            if (prior_sigma) {
+                const double sg = prior_sigma[j];
+                if (!(sg > 0.0)) return fail(NUSI_EPARAM, "templates: a prior width is not > 0");
+                w[j] = 1.0 / (sg * sg);
+                m[j] = (w[j] > 0.0 && prior_mean) ? prior_mean[j] : 0.0;
+            }
+        }
+    } else if (K < 0 || K > NUSI_FIT_TEMPLATES_MAX) {
+        return fail(NUSI_EPARAM, "templates: K outside 0 .. NUSI_FIT_TEMPLATES_MAX");
+    }
+    HIPCHECK(hipSetDevice(pl->device));
+    double* d_new = nullptr;
+    if (!clear) {
+        HIPCHECK(hipMalloc(&d_new, sizeof(double) * (size_t)K * C));
+        const hipError_t e = hipMemcpy(d_new, T, sizeof(double) * (size_t)K * C, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            hipFree(d_new);
+            HIPCHECK(e);
+        }
+    }
+    // (ev_det covers every earlier detector call, the fits among them: nusi_plan_set_detector's rule)
+    const hipError_t e = pl->det_ran ? hipEventSynchronize(pl->ev_det) : hipSuccess;
+    if (e != hipSuccess) {
+        hipFree(d_new);
+        HIPCHECK(e);
+    }
+    hipFree(pl->d_tpl);
+    pl->d_tpl = d_new;
+    pl->fit_K = clear ? 0 : K;
+    memcpy(pl->fit_m, m, sizeof(m));
+    memcpy(pl->fit_w, w, sizeof(w));
+    return NUSI_OK;
+}
+
+int nusi_plan_templates(const nusi_plan* pl) { return pl ? pl->fit_K : 0; }
+
+int nusi_plan_response_fit(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data,
+                           double* d_theta, double* d_nll, double* d_mu, int* d_status, void* stream)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response fit: the plan has no detector (nusi_plan_set_detector)");
+    if (!pl->fit_K) return fail(NUSI_ESTATE, "response fit: the plan has no templates (nusi_plan_set_templates; without them: nusi_plan_response_profile)");
+    if (!data || !d_theta) return fail(NUSI_EPARAM, "response fit: data and theta must not be NULL");
+    if (int r = events_check(pl, "response fit", d_R, ntab, S, Q, nullptr, data)) return r;
+    const size_t M = (size_t)pl->grid.T + 1;
+    const int C = pl->det_C;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (int r = events_stage(pl, S, Q, nullptr, data, s)) return r;
+    const double* d_data = pl->d_evt + (size_t)Q * M + Q;
+    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
+    HIPCHECK(nusi::launch_detector_fit(pl->gd, d_R, ntab, pl->d_evt, Q, d_data, bg, C, pl->fit_K, pl->d_tpl, pl->fit_m,
+                                       pl->fit_w, d_theta, d_nll, d_mu, d_status, s));
+    return detector_mark(pl, s);
+}
+
+int nusi_plan_response_fit_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
+                                double* theta, double* nll, double* mu, int* status)
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, "response fit: the plan has no detector (nusi_plan_set_detector)");
+    if (!pl->fit_K) return fail(NUSI_ESTATE, "response fit: the plan has no templates (nusi_plan_set_templates; without them: nusi_plan_response_profile)");
+    if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response fit: R must not be NULL, ntab and Q >= 1");
+    if (!data || !theta) return fail(NUSI_EPARAM, "response fit: data and theta must not be NULL");
+    const size_t M = (size_t)pl->grid.T + 1, C = (size_t)pl->det_C, nmu = (size_t)ntab * Q * C, nn = (size_t)ntab * Q;
+    const size_t nth = nn * (size_t)(1 + pl->fit_K);
+    // one output block: theta [ntab][Q][1 + K], nll [ntab][Q], mu [ntab][Q][C], then status [ntab][Q] (ints)
+    std::vector<double> o(nth + nn + nmu + (nn + 1) / 2);
+    const int r = detector_host(pl, R, (size_t)ntab * M * C, o.data(), o.size(), "response fit",
+                                [&](const double* dI, double* dO) {
+                                    return nusi_plan_response_fit(pl, dI, ntab, S, Q, data, dO, nll ? dO + nth : nullptr,
+                                                                  mu ? dO + nth + nn : nullptr,
+                                                                  status ? (int*)(dO + nth + nn + nmu) : nullptr, nullptr);
+                                });
+    if (r) return r;
+    memcpy(theta, o.data(), sizeof(double) * nth);
+    if (nll) memcpy(nll, o.data() + nth, sizeof(double) * nn);
+    if (mu) memcpy(mu, o.data() + nth + nn, sizeof(double) * nmu);
+    if (status) memcpy(status, o.data() + nth + nn + nmu, sizeof(int) * nn);
     return NUSI_OK;
 }
 

@@ -7,6 +7,8 @@
 //                         and the Poisson statistic (nusi_plan_response_events), in a defined order
 //   k_detector_profile    that statistic profiled over the flux normalisation: Newton's iteration per (t, q), its
 //                         sums over the bins as butterflies inside a wave (nusi_plan_response_profile)
+//   k_detector_fit<NC>    that statistic minimised over NC = 1 + K normalisations, the signal's and K background
+//                         templates' under Gaussian priors: a damped Newton iteration per (t, q) (nusi_plan_response_fit)
 #include <hip/hip_runtime.h>
 
 #include "nusi_internal.hpp"
@@ -406,6 +408,340 @@ hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, 
     const int QB = (kEvThreads >> lg) * kEvQ;
     hipLaunchKernelGGL(k_detector_profile, dim3((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), dim3(kEvThreads), 0, s, R, S,
                        data, bg, ahat, nll, mu, status, g.T + 1, C, lg, Q);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_detector_fit<NC>: the statistic minimised over NC = 1 + K non-negative normalisations at once -- the signal's and
+// those of K background templates under Gaussian priors (nusi_plan_response_fit), by the damped Newton iteration
+// include/nusi.h defines.  Lanes sit on (c, ONE spectrum): a chain holds NC iterates, NC candidates and NC directions
+// and a round's NC + NC (NC + 1) / 2 sums, which does not fit several times into 128 registers.  The front half is the
+// events kernel's with one accumulator.  A round evaluates the gradient's and the Hessian's sums over the bins at the
+// chain's evaluation point -- the start, or a candidate theta + t p -- in ONE det_butterfly over the group's lanes;
+// everything after it (accepting the candidate, the free set, the stop, the L D L^T solve, the step length) uses only
+// those sums and values uniform over the group, so every lane of a group does it redundantly and theta stays uniform
+// by construction.  Groups stop after different numbers of rounds: a stopped chain keeps its theta and skips the
+// logic, the wave leaves the loop when none of its chains runs, and the butterfly always runs with full exec.  The
+// priors (pm, pw: NC entries, the signal's zeros in front) are uniform over the grid and live in scalar registers.
+// LDS: per spectrum of the block its mu and theta_1 .. theta_K, for the statistic and its penalties.
+// ---------------------------------------------------------------------------
+constexpr int fit_row(int C, int NC) { return (C + NC - 1) | 1; }
+constexpr int fit_lds_doubles(int C, int NC)
+{
+    int lg = 0;
+    while ((1 << lg) < C) ++lg;
+    return (kEvThreads >> lg) * fit_row(C, NC);
+}
+constexpr int fit_lds_max(int NC)
+{
+    int m = 0;
+    for (int C = 1; C <= NUSI_DETECTOR_BINS_MAX; ++C) m = fit_lds_doubles(C, NC) > m ? fit_lds_doubles(C, NC) : m;
+    return m;
+}
+
+struct FitPrior {
+    double m[NUSI_FIT_TEMPLATES_MAX + 1], w[NUSI_FIT_TEMPLATES_MAX + 1];
+};
+
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) void k_detector_fit(const double* __restrict__ R, const double* __restrict__ S,
+                                                             const double* __restrict__ data,
+                                                             const double* __restrict__ bg, const double* __restrict__ T,
+                                                             const FitPrior pr, const double ku,
+                                                             double* __restrict__ theta, double* __restrict__ nll,
+                                                             double* __restrict__ mu, int* __restrict__ status, int M,
+                                                             int C, int lgC, int Q)
+{
+#pragma clang fp contract(off)
+    constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
+    __shared__ double smu[fit_lds_max(NC)];
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, qb0 = (int)blockIdx.y * QB, q = qb0 + grp;
+    const int cc = c < C ? c : C - 1, RS = fit_row(C, NC);
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)(q < Q ? q : Q - 1) * M;
+    const bool in = c < C;
+    double X[NC];
+    {
+        double s0 = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
+        X[0] = in ? s0 : 0.0;
+    }
+#pragma unroll
+    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
+    const double b = in ? bg[cc] : 0.0, d = in ? data[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+
+    double S1[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) S1[j] = X[j];
+    det_butterfly(S1, lgC, add);
+    bool live[NC];
+    live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
+    bool sup = b > 0.0;
+    int nl = 0;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        if (j > 0) live[j] = S1[j] > 0.0;
+        sup = sup || (live[j] && X[j] > 0.0);
+        nl += live[j] ? 1 : 0;
+    }
+    const bool act = d > 0.0 && sup;
+    double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
+    det_butterfly(dsum, lgC, add);
+    det_butterfly(dmin, lgC, min);
+    const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+    double th[NC], the[NC], p[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        const double x = D0 / ((double)nl * S1[j]);
+        th[j] = live[j] ? x : 0.0;
+        the[j] = th[j];
+        p[j] = 0.0;
+    }
+    double tt = 1.0;
+    int st = 0, steps = 0, halv = 0, trials = 0;
+    bool run = true, first = true, quad = false;
+    // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
+    while (__any(run)) {
+        double v[NS];
+        double den = the[0] * X[0];
+#pragma unroll
+        for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
+        den = den + b;
+        const double wq0 = d / den;
+        const double wq = act ? wq0 : 0.0;
+        const double r0 = wq / den;
+        const double r = act ? r0 : 0.0;
+        {
+            int i = NC;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                v[j] = X[j] * wq;
+                const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
+#pragma unroll
+                for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
+            }
+        }
+        det_butterfly(v, lgC, add);
+        const bool bad = any(act && !(den > 0.0));
+        if (run) {
+            double g[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
+            bool ok, changed = true;
+            if (first) {
+                ok = !bad;
+                if (!ok) {
+                    run = false;
+                    st |= NUSI_FIT_NOT_CONVERGED;
+                }
+            } else {
+                double slope = 0.0;
+#pragma unroll
+                for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
+                ok = !bad && (quad || !(slope > 0.0));
+                if (!ok) {
+                    if (trials == NUSI_FIT_TRIALS_MAX) {
+                        run = false;
+                        st |= NUSI_FIT_NOT_CONVERGED;
+                    } else {
+                        ++trials;
+                        ++halv;
+                        tt = tt * 0.5;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
+                    }
+                } else {
+                    changed = false;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
+                    ++steps;
+                }
+            }
+            if (ok) {
+                bool fs[NC], conv = true;
+#pragma unroll
+                for (int j = 0; j < NC; ++j) {
+                    th[j] = the[j];
+                    fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
+                    const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
+                    const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                    if (fs[j] && !(ag <= ku * scale)) conv = false;
+                }
+                if (conv) {
+                    run = false;
+                } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
+                    run = false;
+                    st |= NUSI_FIT_NOT_CONVERGED;
+                } else {
+                    first = false;
+                    // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
+                    // a component at zero that the direction pushes below leaves fs and the solve is repeated
+                    bool sing = false;
+#pragma unroll 1
+                    for (int rep = 0; rep <= NC; ++rep) {
+                        double Lm[NC][NC], Dg[NC], y[NC];
+                        sing = false;
+                        int i0 = NC;
+                        double a[NC][NC];
+#pragma unroll
+                        for (int j = 0; j < NC; ++j)
+#pragma unroll
+                            for (int k = j; k < NC; ++k) {
+                                const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
+                                a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
+                            }
+#pragma unroll
+                        for (int i = 0; i < NC; ++i) {
+                            double cw[NC];
+#pragma unroll
+                            for (int j = 0; j < i; ++j) {
+                                double x = a[i][j];
+#pragma unroll
+                                for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                cw[j] = x;
+                                Lm[i][j] = x / Dg[j];
+                            }
+                            double x = a[i][i];
+#pragma unroll
+                            for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                            if (!(x > 0.0)) sing = true;
+                            Dg[i] = x;
+                        }
+#pragma unroll
+                        for (int i = 0; i < NC; ++i) {
+                            double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                            for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                            y[i] = x;
+                        }
+#pragma unroll
+                        for (int i = NC - 1; i >= 0; --i) {
+                            double x = y[i] / Dg[i];
+#pragma unroll
+                            for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
+                            p[i] = x;
+                        }
+                        if (sing) break;
+                        bool rm = false;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j)
+                            if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
+                                fs[j] = false;
+                                rm = true;
+                            }
+                        if (!rm) break;
+                    }
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j)
+                        if (fs[j]) acc = acc + g[j] * p[j];
+                    if (sing || !(acc < 0.0)) {
+                        run = false;
+                        st |= NUSI_FIT_SINGULAR;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) p[j] = 0.0;
+                    } else {
+                        double ratio[NC];
+                        tt = 1.0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) {
+                            const double x = th[j] / -p[j];
+                            ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
+                            if (ratio[j] < tt) tt = ratio[j];
+                        }
+                        const bool clipped = tt < 1.0;
+                        quad = !clipped && -acc <= dq;
+                        trials = 0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) {
+                            const double x = th[j] + tt * p[j];
+                            the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    double m = th[0] * X[0];
+#pragma unroll
+    for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
+    m = m + b;
+    if (!live[0])
+        st |= NUSI_FIT_FLAT;
+    else if (th[0] == 0.0)
+        st |= NUSI_FIT_BOUNDARY;
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+        if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
+    if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
+    st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+    if (in) {
+        smu[grp * RS + c] = m;
+        if (mu && q < Q) mu[((size_t)t * Q + q) * C + c] = m;
+    }
+    if (c == 0) {
+#pragma unroll
+        for (int j = 1; j < NC; ++j) smu[grp * RS + C + j - 1] = th[j];
+        if (q < Q) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j) theta[((size_t)t * Q + q) * NC + j] = th[j];
+            if (status) status[(size_t)t * Q + q] = st;
+        }
+    }
+    if (!nll) return;   // (uniform)
+    __syncthreads();
+    // (a block owns QB <= kEvThreads spectra)
+    if (tid < QB && qb0 + tid < Q) {
+        double sum = 0.0;
+        for (int k = 0; k < C; ++k) {
+            const double mk = smu[tid * RS + k], dk = data[k];
+            double term = mk;
+            if (dk != 0.0) {
+                const double pl = dk * nm::log_i(mk);
+                term = mk - pl;
+            }
+            sum = sum + term;
+        }
+#pragma unroll
+        for (int j = 1; j < NC; ++j)
+            if (pr.w[j] > 0.0) {
+                const double dl = smu[tid * RS + C + j - 1] - pr.m[j];
+                const double pen = ((0.5 * pr.w[j]) * dl) * dl;
+                sum = sum + pen;
+            }
+        nll[(size_t)t * Q + qb0 + tid] = sum;
+    }
+}
+
+hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                               const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
+                               double* theta, double* nll, double* mu, int* status, hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0) return hipSuccess;
+    int lg = 0;
+    while ((1 << lg) < C) ++lg;
+    const int QB = kEvThreads >> lg;
+    FitPrior pr;
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
+        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
+        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
+    }
+    const double ku = (double)(2 * (lg + K) + 18) * 0x1p-53;   // kappa(C, K) u (include/nusi.h)
+    const dim3 grid((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), block(kEvThreads);
+    const int M = g.T + 1;
+    switch (K) {
+    case 1: hipLaunchKernelGGL((k_detector_fit<2>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, lg, Q); break;
+    case 2: hipLaunchKernelGGL((k_detector_fit<3>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, lg, Q); break;
+    case 3: hipLaunchKernelGGL((k_detector_fit<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, lg, Q); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -159,6 +159,12 @@ hipError_t launch_detector_events(const GridDev& g, const double* R, int ntab, c
 hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
                                    const double* bg, int C, double* ahat, double* nll, double* mu, int* status,
                                    hipStream_t s);
+// k_detector_fit: per (t, q) the theta >= 0 [1 + K] minimising the statistic of theta_0 s + sum_j theta_j T_j + bg with
+// the priors' penalties (include/nusi.h); T [K][C] in device memory, pm and pw [K] the priors' means and weights on
+// the host; theta [ntab][Q][1 + K], nll, mu, status as the profile's, all but theta may be nullptr
+hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                               const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
+                               double* theta, double* nll, double* mu, int* status, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

@@ -16,7 +16,11 @@ R[n][c], M x C doubles, and every spectrum is then a C-vector of expected counts
 non-negative, either is within gamma_K = K u / (1 - K u), K = 3 N, u = 2^-53, of the exact sum.  ``events_host`` and
 ``poisson_host`` are the sums nusi_plan_response_events defines, in its order, so mu agrees bit for bit and nll to the
 last bits of the log.  ``profile_host`` is the iteration nusi_plan_response_profile defines, operation for operation
-(``tree`` is its sum over the bins), so ahat, mu and the status word agree bit for bit as well.
+(``tree`` is its sum over the bins), so ahat, mu and the status word agree bit for bit as well.  ``fit_host`` is the
+same for nusi_plan_response_fit, the fit that floats K background templates with the signal::
+
+    plan.set_templates(T, prior=(mean, sigma))                           # (K, C), K <= FIT_TEMPLATES_MAX
+    theta, nll, mu, st = plan.fit(R, spectra, data=counts)              # fit_host on the CPU: theta (ntab, Q, 1 + K)
 """
 import numpy as np
 
@@ -25,6 +29,13 @@ BINS_MAX = 64       # NUSI_DETECTOR_BINS_MAX
 FIT_ITER_MAX = 64
 FIT_STEPS_MASK = 0xFF
 FIT_FLAT, FIT_BOUNDARY, FIT_NOT_CONVERGED, FIT_INFINITE = 0x100, 0x200, 0x400, 0x800
+# the fit with floating templates (nusi_plan_response_fit) adds: a singular Newton system, one bit per component that ends
+# at zero (FIT_ZERO << j) and the halvings of all its steps (saturating at FIT_TRIALS_MASK) from bit FIT_TRIALS_SHIFT
+FIT_TEMPLATES_MAX = 3
+FIT_TRIALS_MAX = 64
+FIT_SINGULAR = 0x1000
+FIT_ZERO = 0x10000
+FIT_TRIALS_SHIFT, FIT_TRIALS_MASK = 24, 0x7F
 
 
 def gamma(K):
@@ -173,6 +184,244 @@ def profile_host(R, S, data, background=None, log=np.log):
     if one_tab:
         a, nll, mu, status = a[0], nll[0], mu[0], status[0]
     return a, nll, mu, status
+
+
+def fit_kappa(C, K):
+    """kappa(C, K) = 2 (ceil(log2 C) + K) + 18: the stop of nusi_plan_response_fit, |g_j| <= kappa u scale_j on the
+    computed gradient (include/nusi.h; derived in DESIGN.md sec. 4, "The fit with floating templates")."""
+    L = 0
+    while (1 << L) < C:
+        L += 1
+    return 2 * (L + K) + 18
+
+
+def K_fit(C, K):
+    """The bound on the EXACT residual of a converged fit, in units of u scale_j: the stop's kappa plus the rounding of
+    the computed gradient, ceil(log2 C) + 2 K + 8, plus one for the computed scale."""
+    L = 0
+    while (1 << L) < C:
+        L += 1
+    return fit_kappa(C, K) + L + 2 * K + 9
+
+
+def _prior(K, prior):
+    """(mean [1 + K], weight [1 + K]) with the signal's zeros in front: w_j = 1 / (sigma_j sigma_j), 0 = no prior."""
+    m, w = np.zeros(1 + K), np.zeros(1 + K)
+    if prior is not None:
+        mean, sigma = prior
+        sigma = np.broadcast_to(np.asarray(np.inf if sigma is None else sigma, dtype=np.float64), (K,))
+        mean = np.broadcast_to(np.asarray(0.0 if mean is None else mean, dtype=np.float64), (K,))
+        if np.any(np.isnan(sigma)) or np.any(sigma <= 0) or not np.all(np.isfinite(mean)) or np.any(mean < 0):
+            raise ValueError("fit: a prior needs a finite mean >= 0 and a width > 0")
+        with np.errstate(all="ignore"):
+            w[1:] = 1.0 / (sigma * sigma)
+        m[1:] = np.where(w[1:] > 0, mean, 0.0)
+    return m, w
+
+
+def _templates(templates, C):
+    T = np.asarray(templates, dtype=np.float64)
+    if T.ndim == 1:
+        T = T[None]
+    if T.ndim != 2 or T.shape[1] != C or not 1 <= T.shape[0] <= FIT_TEMPLATES_MAX:
+        raise ValueError("fit: templates must have shape (K, %d), K = 1 .. %d, got %s" % (C, FIT_TEMPLATES_MAX, T.shape))
+    if not np.all(np.isfinite(T)) or np.any(T < 0) or np.any(T.max(axis=1) == 0):
+        raise ValueError("fit: a template entry is negative or not finite, or a template is all zeros")
+    return T
+
+
+def _fit_solve(A, g, fs, n):
+    """p = -A^-1 g on the components of the set fs (the others: an identity row and p = 0), by L D L^T in ascending
+    order.  Returns (p, singular)."""
+    a = [[(A[max(i, j)][min(i, j)] if (fs[i] and fs[j]) else (1.0 if i == j else 0.0)) for j in range(n)] for i in range(n)]
+    rhs = [(-g[i] if fs[i] else 0.0) for i in range(n)]
+    Lm = [[0.0] * n for _ in range(n)]
+    Dg = [0.0] * n
+    for i in range(n):
+        c = [0.0] * n
+        for j in range(i):
+            v = a[i][j]
+            for k in range(j):
+                v = v - c[k] * Lm[j][k]
+            c[j] = v
+            Lm[i][j] = v / Dg[j]
+        dd = a[i][i]
+        for k in range(i):
+            dd = dd - c[k] * Lm[i][k]
+        if not dd > 0.0:
+            return None, True
+        Dg[i] = dd
+    y = [0.0] * n
+    for i in range(n):
+        v = rhs[i]
+        for k in range(i):
+            v = v - Lm[i][k] * y[k]
+        y[i] = v
+    p = [0.0] * n
+    for i in range(n - 1, -1, -1):
+        v = y[i] / Dg[i]
+        for k in range(i + 1, n):
+            v = v - Lm[k][i] * p[k]
+        p[i] = v
+    return p, False
+
+
+def _fit_one(X, B, d, m, w, ku):
+    """One fit of nusi_plan_response_fit: X (1 + K, C) the signal and the templates, B, d (C,), m, w (1 + K,) the
+    priors' means and weights (0 in front), ku = kappa u.  Returns (theta list, status)."""
+    n, C = X.shape
+    S1 = [float(v) for v in tree(X)]
+    live = [S1[0] > 0.0 and bool(np.any((d > 0) & (X[0] > 0)))] + [S1[j] > 0.0 for j in range(1, n)]
+    sup = B > 0
+    for j in range(n):
+        if live[j]:
+            sup = sup | (X[j] > 0)
+    act = (d > 0) & sup
+    D0 = float(tree(np.where(act, d, 0.0)))
+    dmin = min(1.0, float(np.min(np.where(act, d, 1.0))))
+    nl = float(sum(live))
+    m = [float(v) for v in m]
+    w = [float(v) for v in w]
+    th = [(D0 / (nl * S1[j]) if live[j] else 0.0) for j in range(n)]
+    the = list(th)
+    XX = [(j, k) for j in range(n) for k in range(j, n)]
+    JJ, KK = [j for j, _ in XX], [k for _, k in XX]
+    flags, steps, halv = 0, 0, 0
+    first, p, t, quad, trials = True, [0.0] * n, 1.0, False, 0
+    while True:
+        den = the[0] * X[0]
+        for j in range(1, n):
+            den = den + the[j] * X[j]
+        den = den + B
+        bad = bool(np.any(act & ~(den > 0)))
+        wq = np.where(act, d / den, 0.0)
+        r = np.where(act, wq / den, 0.0)
+        xr = X * r
+        sums = tree(np.concatenate([X * wq, xr[JJ] * X[KK]]))
+        S2 = [float(v) for v in sums[:n]]
+        g = [(S1[j] - S2[j]) + w[j] * (the[j] - m[j]) for j in range(n)]
+        changed = True
+        if first:
+            if bad:
+                flags |= FIT_NOT_CONVERGED
+                break
+        else:
+            slope = 0.0
+            for j in range(n):
+                slope = slope + p[j] * g[j]
+            if bad or not (quad or not slope > 0.0):
+                if trials == FIT_TRIALS_MAX:
+                    flags |= FIT_NOT_CONVERGED
+                    break
+                trials += 1
+                halv += 1
+                t = t * 0.5
+                the = [th[j] + t * p[j] for j in range(n)]
+                continue
+            changed = any(the[j] != th[j] for j in range(n))
+            steps += 1
+        th = list(the)
+        free = [live[j] and (th[j] > 0.0 or g[j] < 0.0) for j in range(n)]
+        if all(abs(g[j]) <= ku * ((S1[j] + S2[j]) + w[j] * (th[j] + m[j])) for j in range(n) if free[j]):
+            break
+        if (not first and not changed) or steps == FIT_ITER_MAX:
+            flags |= FIT_NOT_CONVERGED
+            break
+        first = False
+        A = [[0.0] * n for _ in range(n)]
+        for i, (j, k) in enumerate(XX):
+            A[k][j] = float(sums[n + i]) + (w[j] if j == k else 0.0)
+        fs = list(free)
+        while True:
+            p, sing = _fit_solve(A, g, fs, n)
+            if sing:
+                break
+            rm = [fs[j] and th[j] == 0.0 and p[j] < 0.0 for j in range(n)]
+            if not any(rm):
+                break
+            fs = [fs[j] and not rm[j] for j in range(n)]
+        acc = 0.0
+        if not sing:
+            for j in range(n):
+                if fs[j]:
+                    acc = acc + g[j] * p[j]
+        if sing or not acc < 0.0:
+            flags |= FIT_SINGULAR
+            break
+        ratio = [(th[j] / -p[j] if (fs[j] and p[j] < 0.0) else 1.0) for j in range(n)]
+        t = 1.0
+        for j in range(n):
+            if ratio[j] < t:
+                t = ratio[j]
+        clipped = t < 1.0
+        quad = (not clipped) and -acc <= 0.0625 * dmin
+        trials = 0
+        the = [(0.0 if (clipped and fs[j] and p[j] < 0.0 and ratio[j] == t) else th[j] + t * p[j]) for j in range(n)]
+    if not live[0]:
+        flags |= FIT_FLAT
+    elif th[0] == 0.0:
+        flags |= FIT_BOUNDARY
+    for j in range(n):
+        if th[j] == 0.0:
+            flags |= FIT_ZERO << j
+    return th, steps | flags | (min(halv, FIT_TRIALS_MASK) << FIT_TRIALS_SHIFT)
+
+
+def fit_host(R, S, data, templates, prior=None, background=None, log=np.log):
+    """The Poisson statistic minimised over the signal's scale AND the normalisations of K background templates, by the
+    iteration nusi_plan_response_fit defines (include/nusi.h), operation for operation: theta, mu and status agree with
+    the GPU bit for bit and nll to the last bits of the log.
+
+        mu_c(theta) = theta_0 s_c + sum_j theta_j T_j[c] + B_c,  theta >= 0
+        f(theta)    = sum_c (mu_c - data_c log mu_c) + sum_j w_j (theta_j - m_j)^2 / 2,  w_j = 1 / (sigma_j sigma_j)
+
+    R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  data: (C,).  templates: (K, C), K = 1 .. FIT_TEMPLATES_MAX, entries
+    >= 0, none all zeros.  prior: None or (mean (K,), sigma (K,)), sigma = inf: no prior on that template.  background:
+    the fixed part B, None (= 0), a number or (C,).  Returns (theta (ntab, Q, 1 + K), nll (ntab, Q), mu (ntab, Q, C),
+    status (ntab, Q) int32): the Newton steps in the low 8 bits, the FIT_* flags, FIT_ZERO << j for every component
+    that ends at zero and the halvings of all steps (saturating) from bit FIT_TRIALS_SHIFT; the axes events_host
+    squeezes are squeezed here."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    data = np.asarray(data, dtype=np.float64)
+    one_tab, one_q = R.ndim == 2, S.ndim == 1
+    s = events_host(R[None] if one_tab else R, S[None] if one_q else S)
+    ntab, Q, C = s.shape
+    if data.shape != (C,):
+        raise ValueError("fit_host: data must have shape (%d,), got %s" % (C, data.shape))
+    if not np.all(np.isfinite(data)) or np.any(data < 0):
+        raise ValueError("fit_host: a datum is negative or not finite")
+    T = _templates(templates, C)
+    K = T.shape[0]
+    m, w = _prior(K, prior)
+    B = np.zeros(C) if background is None else np.array(np.broadcast_to(np.asarray(background, dtype=np.float64), (C,)))
+    ku = fit_kappa(C, K) * 2.0 ** -53
+    theta = np.zeros((ntab, Q, 1 + K))
+    status = np.zeros((ntab, Q), dtype=np.int32)
+    mu = np.zeros((ntab, Q, C))
+    X = np.zeros((1 + K, C))
+    X[1:] = T
+    with np.errstate(all="ignore"):
+        for t in range(ntab):
+            for q in range(Q):
+                X[0] = s[t, q]
+                th, st = _fit_one(X, B, data, m, w, ku)
+                theta[t, q], status[t, q] = th, st
+                den = th[0] * X[0]
+                for j in range(1, 1 + K):
+                    den = den + th[j] * X[j]
+                mu[t, q] = den + B
+    status[np.any((data > 0) & (mu == 0), axis=-1)] |= FIT_INFINITE
+    nll = poisson_host(mu, data, log=log)
+    for j in range(1, 1 + K):                                  # the penalties, ascending j, each operation rounded
+        if w[j] > 0:
+            dl = theta[..., j] - m[j]
+            nll = nll + ((0.5 * w[j]) * dl) * dl
+    if one_q:
+        theta, nll, mu, status = theta[:, 0], nll[:, 0], mu[:, 0], status[:, 0]
+    if one_tab:
+        theta, nll, mu, status = theta[0], nll[0], mu[0], status[0]
+    return theta, nll, mu, status
 
 
 def matrix(lo, hi, aeff, migration=None, exposure=1.0):

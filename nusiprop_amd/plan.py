@@ -326,6 +326,78 @@ class Plan:
             vp(stream_ptr) if stream_ptr else None))
         return len(S)
 
+    def set_templates(self, templates, prior=None):
+        """Register K <= 3 background templates (K, C) of the detector -- expected counts per reconstructed bin at
+        normalisation 1, entries finite and >= 0, none all zeros -- whose normalisations ``fit`` floats with the
+        signal's.  prior: None or (mean (K,), sigma (K,)), a Gaussian constraint per template (mean >= 0, sigma > 0,
+        sigma = inf: none).  None clears the templates; so does set_detector."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        L = _lib.load()
+        if templates is None:
+            _lib.check(L.nusi_plan_set_templates(self._h, 0, None, None, None))
+            return
+        T = np.ascontiguousarray(templates, dtype=np.float64)
+        if T.ndim == 1:
+            T = T[None]
+        C = self.detector_bins()
+        if C and (T.ndim != 2 or T.shape[1] != C):           # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("set_templates: templates must have shape (K, %d), got %s" % (C, T.shape))
+        K = T.shape[0]
+        mean = sigma = None
+        if prior is not None:
+            mean, sigma = prior
+            if mean is not None:
+                mean = np.ascontiguousarray(np.broadcast_to(np.asarray(mean, dtype=np.float64), (K,)))
+            if sigma is not None:
+                sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (K,)))
+        _lib.check(L.nusi_plan_set_templates(self._h, K, T.ctypes.data_as(dp),
+                                             mean.ctypes.data_as(dp) if mean is not None else None,
+                                             sigma.ctypes.data_as(dp) if sigma is not None else None))
+
+    def templates(self):
+        """K, the number of background templates; 0 = none."""
+        return int(_lib.load().nusi_plan_templates(self._h))
+
+    def fit(self, R, spectra, data):
+        """The statistic of ``events`` minimised over the signal's scale and the templates' normalisations at once, on
+        the GPU: theta >= 0 minimising sum_c (mu_c - data_c log mu_c) + sum_j (theta_j - mean_j)^2 / (2 sigma_j^2),
+        mu = theta_0 s + sum_j theta_j T_j + background.  Returns (theta (ntab, Q, 1 + K), nll (ntab, Q),
+        mu (ntab, Q, C), status (ntab, Q) int32): the Newton steps in the low 8 bits, the _lib.FIT_* flags (FIT_FLAT:
+        no signal, the templates are still fitted; FIT_BOUNDARY: theta_0 = 0; FIT_NOT_CONVERGED; FIT_SINGULAR: the
+        data do not determine the components; FIT_INFINITE), FIT_ZERO << j for a component that ends at zero and the
+        halvings from bit FIT_TRIALS_SHIFT.  theta, mu and status equal detector.fit_host bit for bit."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        C, K = self.detector_bins(), self.templates()
+        if C and (R.ndim != 3 or R.shape[1:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("fit: R must have shape (ntab, %d, %d), got %s" % (self.T + 1, C, R.shape))
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
+        ntab, Q = R.shape[0], len(S)
+        theta, nll, mu = np.zeros((ntab, Q, 1 + K)), np.zeros((ntab, Q)), np.zeros((ntab, Q, C))
+        status = np.zeros((ntab, Q), dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_fit_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp) if d is not None else None,
+            theta.ctypes.data_as(dp), nll.ctypes.data_as(dp), mu.ctypes.data_as(dp),
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return theta, nll, mu, status
+
+    def fit_device(self, d_R_ptr, ntab, spectra, data, d_theta_ptr, d_nll_ptr=None, d_mu_ptr=None, d_status_ptr=None,
+                   stream_ptr=None):
+        """Asynchronous fit on device-resident folded matrices: d_R [ntab][M][C], d_theta [ntab][Q][1 + K], d_nll
+        [ntab][Q], d_mu [ntab][Q][C] (doubles) and d_status [ntab][Q] (ints) are raw pointers, every output but
+        d_theta may be 0 / None; the spectra and data are host data and are copied.  Returns Q."""
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_response_fit(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None,
+            vp(d_theta_ptr) if d_theta_ptr else None, vp(d_nll_ptr) if d_nll_ptr else None,
+            vp(d_mu_ptr) if d_mu_ptr else None, vp(d_status_ptr) if d_status_ptr else None,
+            vp(stream_ptr) if stream_ptr else None))
+        return len(S)
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since
