@@ -1693,18 +1693,24 @@ static int detector_mark(nusi_plan* pl, hipStream_t s)   // the end of a call th
     pl->det_ran = true;
     return NUSI_OK;
 }
+static int detector_plan(const nusi_plan* pl, const char* what)   // a plan, and one with a detector
+{
+    if (!pl) return no_plan();
+    if (!pl->det_C) return fail(NUSI_ESTATE, std::string(what) + ": the plan has no detector (nusi_plan_set_detector)");
+    return NUSI_OK;
+}
+// the background of the plan's detector: d_det is Dt [3 N][ld], then bg [C]
+static const double* detector_bg(const nusi_plan* pl) { return pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(pl->det_C); }
 static int detector_fold(nusi_plan* pl, const double* d_X, int ntab, int rows, bool tri, double* d_out, void* stream, const char* what)
 {
-    if (!pl->det_C) return fail(NUSI_ESTATE, std::string(what) + ": the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, what)) return r;
     if (!d_X || !d_out) return fail(NUSI_EPARAM, std::string(what) + ": the input and the output must not be NULL");
     if (ntab < 1 || rows < 1) return fail(NUSI_EPARAM, std::string(what) + ": need at least one row");
     if ((long long)ntab * ((rows + 15) / 16) > (long long)INT_MAX) return fail(NUSI_EPARAM, std::string(what) + ": too many rows");
     HIPCHECK(hipSetDevice(pl->device));
     hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-    const int C = pl->det_C;
-    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
     if (int r = detector_chain(pl, s)) return r;
-    HIPCHECK(nusi::launch_detector_fold(pl->gd, d_X, ntab, rows, tri, pl->d_det, C, tri ? nullptr : bg, d_out, s));
+    HIPCHECK(nusi::launch_detector_fold(pl->gd, d_X, ntab, rows, tri, pl->d_det, pl->det_C, tri ? nullptr : detector_bg(pl), d_out, s));
     return detector_mark(pl, s);
 }
 // host arrays through a device call: in [nin] -> out [nout] doubles
@@ -1724,6 +1730,29 @@ static int detector_host(nusi_plan* pl, const double* in, size_t nin, double* ou
         r = fail(NUSI_EHIP, std::string(what) + ": copy to the host failed");
     hipFree(dI);
     hipFree(dO);
+    return r;
+}
+// The events, the profile and the fit call on host arrays: R [ntab][M][C] through detector_host into one block of the
+// output segments in their order, each on a multiple of 8 bytes; the call gets their device addresses (NULL where the
+// host pointer is NULL) and the segments asked for are copied back.
+struct HostSeg {
+    void* host;
+    size_t count, size;   // elements, bytes per element
+};
+static int events_host(nusi_plan* pl, const double* R, int ntab, const std::vector<HostSeg>& segs, const char* what,
+                       const std::function<int(const double*, void* const*)>& call)
+{
+    std::vector<size_t> off(1, 0);
+    for (const HostSeg& g : segs) off.push_back(off.back() + (g.count * g.size + 7) / 8);
+    std::vector<double> o(off.back());
+    const int r = detector_host(pl, R, (size_t)ntab * (pl->grid.T + 1) * pl->det_C, o.data(), o.size(), what,
+                                [&](const double* dI, double* dO) {
+                                    std::vector<void*> d;
+                                    for (const HostSeg& g : segs) d.push_back(g.host ? dO + off[d.size()] : nullptr);
+                                    return call(dI, d.data());
+                                });
+    for (size_t k = 0; k < segs.size() && !r; ++k)
+        if (segs[k].host) memcpy(segs[k].host, o.data() + off[k], segs[k].count * segs[k].size);
     return r;
 }
 
@@ -1790,8 +1819,7 @@ int nusi_plan_response_fold(nusi_plan* pl, const double* d_G_fla, int ntab, doub
 
 int nusi_plan_fold_flux_host(nusi_plan* pl, const double* flux_fla, int n, double* mu)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "fold flux: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "fold flux")) return r;
     if (!flux_fla || !mu || n < 1) return fail(NUSI_EPARAM, "fold flux: the input and the output must not be NULL, n >= 1");
     return detector_host(pl, flux_fla, (size_t)n * 3 * pl->grid.N, mu, (size_t)n * pl->det_C, "fold flux",
                          [&](const double* dI, double* dO) { return nusi_plan_fold_flux(pl, dI, n, dO, nullptr); });
@@ -1799,8 +1827,7 @@ int nusi_plan_fold_flux_host(nusi_plan* pl, const double* flux_fla, int n, doubl
 
 int nusi_plan_response_fold_host(nusi_plan* pl, const double* G_fla, int ntab, double* R)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response fold: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "response fold")) return r;
     if (!G_fla || !R || ntab < 1) return fail(NUSI_EPARAM, "response fold: the input and the output must not be NULL, ntab >= 1");
     const size_t M = (size_t)pl->grid.T + 1;
     return detector_host(pl, G_fla, (size_t)ntab * M * 3 * pl->grid.N, R, (size_t)ntab * M * pl->det_C, "response fold",
@@ -1846,95 +1873,83 @@ static int events_stage(nusi_plan* pl, const double* S, int Q, const double* sca
     HIPCHECK(hipMemcpyAsync(pl->d_evt, pl->h_evt.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
     return NUSI_OK;
 }
+// What the events, the profile and the fit call share after their own checks: events_check, the device and the stream,
+// events_stage; gives the stream and the staged vectors (scale: NULL without one) with the detector's background.
+// The call launches on a.s and ends with detector_mark.
+struct EventsArgs {
+    hipStream_t s;
+    const double *S, *scale, *data, *bg;
+};
+static int events_begin(nusi_plan* pl, const char* what, const double* d_R, int ntab, const double* S, int Q,
+                        const double* scale, const double* data, void* stream, EventsArgs& a)
+{
+    if (int r = events_check(pl, what, d_R, ntab, S, Q, scale, data)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    a.s = stream ? (hipStream_t)stream : pl->stream;
+    if (int r = events_stage(pl, S, Q, scale, data, a.s)) return r;
+    const double* d_sc = pl->d_evt + (size_t)Q * ((size_t)pl->grid.T + 1);
+    a.S = pl->d_evt;
+    a.scale = scale ? d_sc : nullptr;
+    a.data = d_sc + Q;
+    a.bg = detector_bg(pl);
+    return NUSI_OK;
+}
 
 int nusi_plan_response_events(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* scale,
                               const double* data, double* d_mu, double* d_nll, void* stream)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response events: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "response events")) return r;
     if (!d_mu && !d_nll) return fail(NUSI_EPARAM, "response events: mu and nll are both NULL");
     if (d_nll && !data) return fail(NUSI_EPARAM, "response events: nll needs data");
-    if (int r = events_check(pl, "response events", d_R, ntab, S, Q, scale, data)) return r;
-    const size_t M = (size_t)pl->grid.T + 1;
-    const int C = pl->det_C;
-    HIPCHECK(hipSetDevice(pl->device));
-    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-    if (int r = events_stage(pl, S, Q, scale, data, s)) return r;
-    const double* d_sc = pl->d_evt + (size_t)Q * M;
-    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
-    HIPCHECK(nusi::launch_detector_events(pl->gd, d_R, ntab, pl->d_evt, Q, scale ? d_sc : nullptr, d_sc + Q, bg, C, d_mu,
-                                          d_nll, s));
-    return detector_mark(pl, s);
+    EventsArgs a;
+    if (int r = events_begin(pl, "response events", d_R, ntab, S, Q, scale, data, stream, a)) return r;
+    HIPCHECK(nusi::launch_detector_events(pl->gd, d_R, ntab, a.S, Q, a.scale, a.data, a.bg, pl->det_C, d_mu, d_nll, a.s));
+    return detector_mark(pl, a.s);
 }
 
 int nusi_plan_response_events_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* scale,
                                    const double* data, double* mu, double* nll)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response events: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "response events")) return r;
     if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response events: R must not be NULL, ntab and Q >= 1");
     if (!mu && !nll) return fail(NUSI_EPARAM, "response events: mu and nll are both NULL");
-    const size_t M = (size_t)pl->grid.T + 1, C = (size_t)pl->det_C, nmu = (size_t)ntab * Q * C, nn = (size_t)ntab * Q;
-    // one output block: mu [ntab][Q][C], then nll [ntab][Q]
-    std::vector<double> o(nmu + nn);
-    const int r = detector_host(pl, R, (size_t)ntab * M * C, o.data(), o.size(), "response events",
-                                [&](const double* dI, double* dO) {
-                                    return nusi_plan_response_events(pl, dI, ntab, S, Q, scale, data, mu ? dO : nullptr,
-                                                                     nll ? dO + nmu : nullptr, nullptr);
-                                });
-    if (r) return r;
-    if (mu) memcpy(mu, o.data(), sizeof(double) * nmu);
-    if (nll) memcpy(nll, o.data() + nmu, sizeof(double) * nn);
-    return NUSI_OK;
+    const size_t nn = (size_t)ntab * Q, nmu = nn * pl->det_C;
+    return events_host(pl, R, ntab, {{mu, nmu, sizeof(double)}, {nll, nn, sizeof(double)}}, "response events",
+                       [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_events(pl, dI, ntab, S, Q, scale, data, (double*)d[0], (double*)d[1], nullptr);
+                       });
 }
 
 int nusi_plan_response_profile(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data,
                                double* d_ahat, double* d_nll, double* d_mu, int* d_status, void* stream)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response profile: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "response profile")) return r;
     if (!data || !d_ahat) return fail(NUSI_EPARAM, "response profile: data and ahat must not be NULL");
-    if (int r = events_check(pl, "response profile", d_R, ntab, S, Q, nullptr, data)) return r;
-    const size_t M = (size_t)pl->grid.T + 1;
-    const int C = pl->det_C;
-    HIPCHECK(hipSetDevice(pl->device));
-    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-    if (int r = events_stage(pl, S, Q, nullptr, data, s)) return r;
-    const double* d_data = pl->d_evt + (size_t)Q * M + Q;
-    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
-    HIPCHECK(nusi::launch_detector_profile(pl->gd, d_R, ntab, pl->d_evt, Q, d_data, bg, C, d_ahat, d_nll, d_mu, d_status, s));
-    return detector_mark(pl, s);
+    EventsArgs a;
+    if (int r = events_begin(pl, "response profile", d_R, ntab, S, Q, nullptr, data, stream, a)) return r;
+    HIPCHECK(nusi::launch_detector_profile(pl->gd, d_R, ntab, a.S, Q, a.data, a.bg, pl->det_C, d_ahat, d_nll, d_mu, d_status, a.s));
+    return detector_mark(pl, a.s);
 }
 
 int nusi_plan_response_profile_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
                                     double* ahat, double* nll, double* mu, int* status)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response profile: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "response profile")) return r;
     if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response profile: R must not be NULL, ntab and Q >= 1");
     if (!data || !ahat) return fail(NUSI_EPARAM, "response profile: data and ahat must not be NULL");
-    const size_t M = (size_t)pl->grid.T + 1, C = (size_t)pl->det_C, nmu = (size_t)ntab * Q * C, nn = (size_t)ntab * Q;
-    // one output block: ahat [ntab][Q], nll [ntab][Q], mu [ntab][Q][C], then status [ntab][Q] (ints)
-    std::vector<double> o(2 * nn + nmu + (nn + 1) / 2);
-    const int r = detector_host(pl, R, (size_t)ntab * M * C, o.data(), o.size(), "response profile",
-                                [&](const double* dI, double* dO) {
-                                    return nusi_plan_response_profile(pl, dI, ntab, S, Q, data, dO, nll ? dO + nn : nullptr,
-                                                                      mu ? dO + 2 * nn : nullptr,
-                                                                      status ? (int*)(dO + 2 * nn + nmu) : nullptr, nullptr);
-                                });
-    if (r) return r;
-    memcpy(ahat, o.data(), sizeof(double) * nn);
-    if (nll) memcpy(nll, o.data() + nn, sizeof(double) * nn);
-    if (mu) memcpy(mu, o.data() + 2 * nn, sizeof(double) * nmu);
-    if (status) memcpy(status, o.data() + 2 * nn + nmu, sizeof(int) * nn);
-    return NUSI_OK;
+    const size_t nn = (size_t)ntab * Q, nmu = nn * pl->det_C;
+    return events_host(pl, R, ntab,
+                       {{ahat, nn, sizeof(double)}, {nll, nn, sizeof(double)}, {mu, nmu, sizeof(double)}, {status, nn, sizeof(int)}},
+                       "response profile", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_profile(pl, dI, ntab, S, Q, data, (double*)d[0], (double*)d[1], (double*)d[2],
+                                                             (int*)d[3], nullptr);
+                       });
 }
 
 // The fit's background templates (nusi_plan_set_templates) and the fit (nusi_detector.hip k_detector_fit)
 int nusi_plan_set_templates(nusi_plan* pl, int K, const double* T, const double* prior_mean, const double* prior_sigma)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "templates: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "templates")) return r;
     const bool clear = !T || K == 0;
     const int C = pl->det_C;
     double m[NUSI_FIT_TEMPLATES_MAX] = {}, w[NUSI_FIT_TEMPLATES_MAX] = {};
@@ -1989,47 +2004,30 @@ int nusi_plan_templates(const nusi_plan* pl) { return pl ? pl->fit_K : 0; }
 int nusi_plan_response_fit(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data,
                            double* d_theta, double* d_nll, double* d_mu, int* d_status, void* stream)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response fit: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "response fit")) return r;
     if (!pl->fit_K) return fail(NUSI_ESTATE, "response fit: the plan has no templates (nusi_plan_set_templates; without them: nusi_plan_response_profile)");
     if (!data || !d_theta) return fail(NUSI_EPARAM, "response fit: data and theta must not be NULL");
-    if (int r = events_check(pl, "response fit", d_R, ntab, S, Q, nullptr, data)) return r;
-    const size_t M = (size_t)pl->grid.T + 1;
-    const int C = pl->det_C;
-    HIPCHECK(hipSetDevice(pl->device));
-    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-    if (int r = events_stage(pl, S, Q, nullptr, data, s)) return r;
-    const double* d_data = pl->d_evt + (size_t)Q * M + Q;
-    const double* bg = pl->d_det + (size_t)3 * pl->grid.N * nusi::detector_ld(C);
-    HIPCHECK(nusi::launch_detector_fit(pl->gd, d_R, ntab, pl->d_evt, Q, d_data, bg, C, pl->fit_K, pl->d_tpl, pl->fit_m,
-                                       pl->fit_w, d_theta, d_nll, d_mu, d_status, s));
-    return detector_mark(pl, s);
+    EventsArgs a;
+    if (int r = events_begin(pl, "response fit", d_R, ntab, S, Q, nullptr, data, stream, a)) return r;
+    HIPCHECK(nusi::launch_detector_fit(pl->gd, d_R, ntab, a.S, Q, a.data, a.bg, pl->det_C, pl->fit_K, pl->d_tpl, pl->fit_m,
+                                       pl->fit_w, d_theta, d_nll, d_mu, d_status, a.s));
+    return detector_mark(pl, a.s);
 }
 
 int nusi_plan_response_fit_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
                                 double* theta, double* nll, double* mu, int* status)
 {
-    if (!pl) return no_plan();
-    if (!pl->det_C) return fail(NUSI_ESTATE, "response fit: the plan has no detector (nusi_plan_set_detector)");
+    if (int r = detector_plan(pl, "response fit")) return r;
     if (!pl->fit_K) return fail(NUSI_ESTATE, "response fit: the plan has no templates (nusi_plan_set_templates; without them: nusi_plan_response_profile)");
     if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response fit: R must not be NULL, ntab and Q >= 1");
     if (!data || !theta) return fail(NUSI_EPARAM, "response fit: data and theta must not be NULL");
-    const size_t M = (size_t)pl->grid.T + 1, C = (size_t)pl->det_C, nmu = (size_t)ntab * Q * C, nn = (size_t)ntab * Q;
-    const size_t nth = nn * (size_t)(1 + pl->fit_K);
-    // one output block: theta [ntab][Q][1 + K], nll [ntab][Q], mu [ntab][Q][C], then status [ntab][Q] (ints)
-    std::vector<double> o(nth + nn + nmu + (nn + 1) / 2);
-    const int r = detector_host(pl, R, (size_t)ntab * M * C, o.data(), o.size(), "response fit",
-                                [&](const double* dI, double* dO) {
-                                    return nusi_plan_response_fit(pl, dI, ntab, S, Q, data, dO, nll ? dO + nth : nullptr,
-                                                                  mu ? dO + nth + nn : nullptr,
-                                                                  status ? (int*)(dO + nth + nn + nmu) : nullptr, nullptr);
-                                });
-    if (r) return r;
-    memcpy(theta, o.data(), sizeof(double) * nth);
-    if (nll) memcpy(nll, o.data() + nth, sizeof(double) * nn);
-    if (mu) memcpy(mu, o.data() + nth + nn, sizeof(double) * nmu);
-    if (status) memcpy(status, o.data() + nth + nn + nmu, sizeof(int) * nn);
-    return NUSI_OK;
+    const size_t nn = (size_t)ntab * Q, nmu = nn * pl->det_C, nth = nn * (1 + pl->fit_K);
+    return events_host(pl, R, ntab,
+                       {{theta, nth, sizeof(double)}, {nll, nn, sizeof(double)}, {mu, nmu, sizeof(double)}, {status, nn, sizeof(int)}},
+                       "response fit", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_fit(pl, dI, ntab, S, Q, data, (double*)d[0], (double*)d[1], (double*)d[2],
+                                                         (int*)d[3], nullptr);
+                       });
 }
 
 int nusi_plan_profile_begin(nusi_plan* pl, int max_calls)

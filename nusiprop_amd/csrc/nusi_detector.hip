@@ -133,23 +133,80 @@ hipError_t launch_detector_fold(const GridDev& g, const double* X, int ntab, int
 }
 
 // ---------------------------------------------------------------------------
-// k_detector_events: spectra on folded response matrices (nusi_plan_response_events), in a defined order:
-//     acc = 0.0;  for n = 1 .. M-1 ascending: acc = acc + R[t][n][c] * S[q][n];  mu = scale[q] * acc + bg[c]
-// (every product and sum rounded separately: -ffp-contract=off, and the pragma below), and with data
-//     nll[t][q] = sum over c ascending from 0.0 of  mu_c - data_c * log(mu_c)   (mu_c where data_c == 0),
-// log = nm::log's body.  Lanes sit on (c, a group of kEvQ spectra): R[t] (M C doubles) is re-read from L2 with c on
-// neighbouring lanes, each value serving kEvQ accumulators.  The statistic's c-sum is serial in one lane per (t, q),
-// over the block's mu in LDS.
+// The event-side kernels (k_detector_events, _profile, _fit<NC>): a block of kEvThreads lanes takes one table t.  Its
+// lanes sit on (c, group): c = the low lgC = ceil(log2 C) bits of the thread index (padding lanes c >= C read bin
+// C - 1 and store nothing), a group = per spectra (kEvQ, or the fit's one), so a block owns QB = det_qb(lgC, per)
+// spectra and the grid is (tables, ceil(Q / QB)): DetGeom.  The 2^lgC lanes of a group lie inside one wave (C <= 64,
+// groups aligned).  The events and the profile kernel call det_front and det_poisson; k_detector_fit writes both out
+// with one accumulator, because through the helpers k_detector_fit<4> measured 0.4 % slower.
 // ---------------------------------------------------------------------------
 constexpr int kEvThreads = 256, kEvQ = 4, kEvLds = 1536;
-// the block's mu in LDS: QB rows of C | 1 doubles, QB = (kEvThreads >> ceil(log2 C)) kEvQ; the largest over
-// C = 1 .. NUSI_DETECTOR_BINS_MAX is at C = 2 (512 x 3)
-constexpr int ev_lds_doubles(int C)
+static_assert((kEvThreads >> 6) >= 1 && NUSI_DETECTOR_BINS_MAX <= 64, "event kernels: a block holds at least one group of 64 lanes on c");
+
+constexpr int ceil_log2(int C)
 {
     int lg = 0;
     while ((1 << lg) < C) ++lg;
-    return (kEvThreads >> lg) * kEvQ * (C | 1);
+    return lg;
 }
+constexpr int det_qb(int lgC, int per) { return (kEvThreads >> lgC) * per; }
+
+struct DetGeom {
+    int lg, QB;
+    dim3 grid;
+    DetGeom(int C, int per, int ntab, int Q) : lg(ceil_log2(C)), QB(det_qb(lg, per)), grid((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)) {}
+};
+
+// The front half, in the order include/nusi.h defines:
+//     acc = 0.0;  for n = 1 .. M-1 ascending: acc = acc + R[t][n][c] * S[q][n]
+// (every product and sum rounded separately: -ffp-contract=off, and the pragma below) for the NQ spectra q0 .. of a
+// lane (spectra past Q - 1 read spectrum Q - 1).  R[t] (M C doubles) is re-read from L2 with c on neighbouring
+// lanes, each value serving NQ accumulators.
+template <int NQ>
+__device__ __forceinline__ void det_front(const double* __restrict__ R, const double* __restrict__ S, int t, int M, int C,
+                                          int cc, int q0, int Q, double (&acc)[NQ])
+{
+#pragma clang fp contract(off)
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* Sq[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) Sq[j] = S + (size_t)(q0 + j < Q ? q0 + j : Q - 1) * M;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) acc[j] = 0.0;
+#pragma unroll 4
+    for (int n = 1; n < M; ++n) {
+        const double rv = Rt[(size_t)n * C];
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) acc[j] = acc[j] + rv * Sq[j][n];
+    }
+}
+
+// The statistic of one spectrum, in the order include/nusi.h defines:
+//     sum over c ascending from 0.0 of  mu_c - data_c * log(mu_c)   (mu_c where data_c == 0),  log = nm::log's body,
+// serial in one lane over the spectrum's row of the block's mu in LDS.
+__device__ __forceinline__ double det_poisson(const double* row, const double* __restrict__ data, int C)
+{
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int k = 0; k < C; ++k) {
+        const double m = row[k], d = data[k];
+        double term = m;
+        if (d != 0.0) {
+            const double p = d * nm::log_i(m);
+            term = m - p;
+        }
+        s = s + term;
+    }
+    return s;
+}
+
+// ---------------------------------------------------------------------------
+// k_detector_events: spectra on folded response matrices (nusi_plan_response_events):
+//     mu = scale[q] * acc + bg[c],  acc = det_front's,  and with data  nll[t][q] = det_poisson(mu).
+// The block's mu in LDS: QB rows of C | 1 doubles; the largest over C = 1 .. NUSI_DETECTOR_BINS_MAX is at C = 2
+// (512 x 3).
+// ---------------------------------------------------------------------------
+constexpr int ev_lds_doubles(int C) { return det_qb(ceil_log2(C), kEvQ) * (C | 1); }
 constexpr int ev_lds_max()
 {
     int m = 0;
@@ -157,7 +214,6 @@ constexpr int ev_lds_max()
     return m;
 }
 static_assert(ev_lds_max() <= kEvLds, "k_detector_events: the block's mu does not fit smu[]");
-static_assert((kEvThreads >> 6) >= 1 && NUSI_DETECTOR_BINS_MAX <= 64, "k_detector_events: a block holds at least one group of 64 lanes on c");
 
 __global__ __launch_bounds__(kEvThreads) void k_detector_events(const double* __restrict__ R, const double* __restrict__ S,
                                                                 const double* __restrict__ scale,
@@ -169,21 +225,10 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_events(const double* __
     __shared__ double smu[kEvLds];
     const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
     const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
-    const int QB = (kEvThreads >> lgC) * kEvQ, qb0 = (int)blockIdx.y * QB, q0 = qb0 + grp * kEvQ;
+    const int QB = det_qb(lgC, kEvQ), qb0 = (int)blockIdx.y * QB, q0 = qb0 + grp * kEvQ;
     const int cc = c < C ? c : C - 1, Cs = C | 1;
-    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
-    const double* Sq[kEvQ];
-#pragma unroll
-    for (int j = 0; j < kEvQ; ++j) Sq[j] = S + (size_t)(q0 + j < Q ? q0 + j : Q - 1) * M;
     double acc[kEvQ];
-#pragma unroll
-    for (int j = 0; j < kEvQ; ++j) acc[j] = 0.0;
-#pragma unroll 4
-    for (int n = 1; n < M; ++n) {
-        const double rv = Rt[(size_t)n * C];
-#pragma unroll
-        for (int j = 0; j < kEvQ; ++j) acc[j] = acc[j] + rv * Sq[j][n];
-    }
+    det_front(R, S, t, M, C, cc, q0, Q, acc);
     const double b = bg[cc];
 #pragma unroll
     for (int j = 0; j < kEvQ; ++j) {
@@ -200,17 +245,7 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_events(const double* __
     // (a block owns QB spectra -- 1024 at C = 1, 512 at C = 2 -- on kEvThreads threads: a strided loop)
     for (int i = tid; i < QB && qb0 + i < Q; i += kEvThreads) {
         const int q = qb0 + i;
-        double s = 0.0;
-        for (int k = 0; k < C; ++k) {
-            const double m = smu[i * Cs + k], d = data[k];
-            double term = m;
-            if (d != 0.0) {
-                const double p = d * nm::log_i(m);
-                term = m - p;
-            }
-            s = s + term;
-        }
-        nll[(size_t)t * Q + q] = s;
+        nll[(size_t)t * Q + q] = det_poisson(smu + i * Cs, data, C);
     }
 }
 
@@ -218,27 +253,22 @@ hipError_t launch_detector_events(const GridDev& g, const double* R, int ntab, c
                                   const double* data, const double* bg, int C, double* mu, double* nll, hipStream_t s)
 {
     if (ntab <= 0 || Q <= 0) return hipSuccess;
-    int lg = 0;
-    while ((1 << lg) < C) ++lg;
-    const int QB = (kEvThreads >> lg) * kEvQ;
-    hipLaunchKernelGGL(k_detector_events, dim3((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), dim3(kEvThreads), 0, s, R, S,
-                       scale, data, bg, mu, nll, g.T + 1, C, lg, Q);
+    const DetGeom ge(C, kEvQ, ntab, Q);
+    hipLaunchKernelGGL(k_detector_events, ge.grid, dim3(kEvThreads), 0, s, R, S, scale, data, bg, mu, nll, g.T + 1, C, ge.lg, Q);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
 // k_detector_profile: the statistic profiled over the flux normalisation (nusi_plan_response_profile): per (t, q) the
-// a >= 0 minimising -ln L(a s + B | data), by the iteration include/nusi.h defines.  The front half and the statistic
-// are k_detector_events' (the same text, kept apart so that kernel's code does not move): lanes on (c, a group of kEvQ
-// spectra), four accumulators s_c per lane.  The P = 2^lgC lanes of a group lie inside one wave (P <= 64, groups
-// aligned), so the sums over c are xor-butterflies over those lanes: stage k adds the partner across 2^k lanes, which
-// is the tree of adjacent pairs, and every lane ends with the same bits (a + b = b + a).  Strides 1 and 2 are DPP
-// quad permutations; 4 and 8 are the row's half mirror and mirror (the lanes of a quad, or of eight, already hold one
-// value, so lane 7 - i, or 15 - i, stands for lane i ^ 4, or i ^ 8); 16 is ds_swizzle, 32 a bpermute.  No LDS
-// round trip and no barrier inside the iteration.  The iterate a is uniform over a group's lanes by construction;
-// the four chains of a lane run interleaved (the fp64 divisions of one behind the others); a chain that has stopped
-// keeps its a, and the wave leaves the loop when no chain of any of its groups runs, so the butterflies always run
-// with full exec.  Padding lanes (c >= C) carry s = data = B = 0 and are inactive bins.
+// a >= 0 minimising -ln L(a s + B | data), by the iteration include/nusi.h defines, on k_detector_events' block shape:
+// four accumulators s_c per lane.  The sums over c are xor-butterflies over a group's lanes: stage k adds the partner
+// across 2^k lanes, which is the tree of adjacent pairs, and every lane ends with the same bits (a + b = b + a).
+// Strides 1 and 2 are DPP quad permutations; 4 and 8 are the row's half mirror and mirror (the lanes of a quad, or of
+// eight, already hold one value, so lane 7 - i, or 15 - i, stands for lane i ^ 4, or i ^ 8); 16 is ds_swizzle, 32 a
+// bpermute.  No LDS round trip and no barrier inside the iteration.  The iterate a is uniform over a group's lanes by
+// construction; the four chains of a lane run interleaved (the fp64 divisions of one behind the others); a chain that
+// has stopped keeps its a, and the wave leaves the loop when no chain of any of its groups runs, so the butterflies
+// always run with full exec.  Padding lanes (c >= C) carry s = data = B = 0 and are inactive bins.
 // ---------------------------------------------------------------------------
 template <int CTRL>
 __device__ __forceinline__ double det_dpp(double x)
@@ -287,24 +317,13 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_profile(const double* _
     __shared__ double smu[kEvLds];
     const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
     const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
-    const int QB = (kEvThreads >> lgC) * kEvQ, qb0 = (int)blockIdx.y * QB, q0 = qb0 + grp * kEvQ;
+    const int QB = det_qb(lgC, kEvQ), qb0 = (int)blockIdx.y * QB, q0 = qb0 + grp * kEvQ;
     const int cc = c < C ? c : C - 1, Cs = C | 1;
-    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
-    const double* Sq[kEvQ];
-#pragma unroll
-    for (int j = 0; j < kEvQ; ++j) Sq[j] = S + (size_t)(q0 + j < Q ? q0 + j : Q - 1) * M;
     double s[kEvQ];
-#pragma unroll
-    for (int j = 0; j < kEvQ; ++j) s[j] = 0.0;
-#pragma unroll 4
-    for (int n = 1; n < M; ++n) {
-        const double rv = Rt[(size_t)n * C];
-#pragma unroll
-        for (int j = 0; j < kEvQ; ++j) s[j] = s[j] + rv * Sq[j][n];
-    }
+    det_front(R, S, t, M, C, cc, q0, Q, s);
     const bool in = c < C;
     const double b = in ? bg[cc] : 0.0, d = in ? data[cc] : 0.0;
-    // the group's lanes in a ballot
+    // the group's lanes in a ballot (written out here and in k_detector_fit: a shared helper moved both kernels' code)
     const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
     auto add = [](double x, double y) { return x + y; };
     auto max = [](double x, double y) { return y > x ? y : x; };
@@ -384,17 +403,7 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_profile(const double* _
     __syncthreads();
     for (int i = tid; i < QB && qb0 + i < Q; i += kEvThreads) {
         const int q = qb0 + i;
-        double sum = 0.0;
-        for (int k = 0; k < C; ++k) {
-            const double m = smu[i * Cs + k], dk = data[k];
-            double term = m;
-            if (dk != 0.0) {
-                const double p = dk * nm::log_i(m);
-                term = m - p;
-            }
-            sum = sum + term;
-        }
-        nll[(size_t)t * Q + q] = sum;
+        nll[(size_t)t * Q + q] = det_poisson(smu + i * Cs, data, C);
     }
 }
 
@@ -403,11 +412,9 @@ hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, 
                                    hipStream_t s)
 {
     if (ntab <= 0 || Q <= 0) return hipSuccess;
-    int lg = 0;
-    while ((1 << lg) < C) ++lg;
-    const int QB = (kEvThreads >> lg) * kEvQ;
-    hipLaunchKernelGGL(k_detector_profile, dim3((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), dim3(kEvThreads), 0, s, R, S,
-                       data, bg, ahat, nll, mu, status, g.T + 1, C, lg, Q);
+    const DetGeom ge(C, kEvQ, ntab, Q);
+    hipLaunchKernelGGL(k_detector_profile, ge.grid, dim3(kEvThreads), 0, s, R, S, data, bg, ahat, nll, mu, status, g.T + 1, C,
+                       ge.lg, Q);
     return hipGetLastError();
 }
 
@@ -415,9 +422,9 @@ hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, 
 // k_detector_fit<NC>: the statistic minimised over NC = 1 + K non-negative normalisations at once -- the signal's and
 // those of K background templates under Gaussian priors (nusi_plan_response_fit), by the damped Newton iteration
 // include/nusi.h defines.  Lanes sit on (c, ONE spectrum): a chain holds NC iterates, NC candidates and NC directions
-// and a round's NC + NC (NC + 1) / 2 sums, which does not fit several times into 128 registers.  The front half is the
-// events kernel's with one accumulator.  A round evaluates the gradient's and the Hessian's sums over the bins at the
-// chain's evaluation point -- the start, or a candidate theta + t p -- in ONE det_butterfly over the group's lanes;
+// and a round's NC + NC (NC + 1) / 2 sums, which does not fit several times into 128 registers.  A round evaluates the
+// gradient's and the Hessian's sums over the bins at the chain's evaluation point -- the start, or a candidate
+// theta + t p -- in ONE det_butterfly over the group's lanes;
 // everything after it (accepting the candidate, the free set, the stop, the L D L^T solve, the step length) uses only
 // those sums and values uniform over the group, so every lane of a group does it redundantly and theta stays uniform
 // by construction.  Groups stop after different numbers of rounds: a stopped chain keeps its theta and skips the
@@ -426,12 +433,7 @@ hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, 
 // LDS: per spectrum of the block its mu and theta_1 .. theta_K, for the statistic and its penalties.
 // ---------------------------------------------------------------------------
 constexpr int fit_row(int C, int NC) { return (C + NC - 1) | 1; }
-constexpr int fit_lds_doubles(int C, int NC)
-{
-    int lg = 0;
-    while ((1 << lg) < C) ++lg;
-    return (kEvThreads >> lg) * fit_row(C, NC);
-}
+constexpr int fit_lds_doubles(int C, int NC) { return det_qb(ceil_log2(C), 1) * fit_row(C, NC); }
 constexpr int fit_lds_max(int NC)
 {
     int m = 0;
@@ -725,21 +727,19 @@ hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, cons
                                double* theta, double* nll, double* mu, int* status, hipStream_t s)
 {
     if (ntab <= 0 || Q <= 0) return hipSuccess;
-    int lg = 0;
-    while ((1 << lg) < C) ++lg;
-    const int QB = kEvThreads >> lg;
+    const DetGeom ge(C, 1, ntab, Q);
     FitPrior pr;
     for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
         pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
         pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
     }
-    const double ku = (double)(2 * (lg + K) + 18) * 0x1p-53;   // kappa(C, K) u (include/nusi.h)
-    const dim3 grid((unsigned)ntab, (unsigned)((Q + QB - 1) / QB)), block(kEvThreads);
+    const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;   // kappa(C, K) u (include/nusi.h)
+    const dim3 grid = ge.grid, block(kEvThreads);
     const int M = g.T + 1;
     switch (K) {
-    case 1: hipLaunchKernelGGL((k_detector_fit<2>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, lg, Q); break;
-    case 2: hipLaunchKernelGGL((k_detector_fit<3>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, lg, Q); break;
-    case 3: hipLaunchKernelGGL((k_detector_fit<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, lg, Q); break;
+    case 1: hipLaunchKernelGGL((k_detector_fit<2>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
+    case 2: hipLaunchKernelGGL((k_detector_fit<3>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
+    case 3: hipLaunchKernelGGL((k_detector_fit<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

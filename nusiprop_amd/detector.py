@@ -44,6 +44,22 @@ def gamma(K):
     return K * u / (1.0 - K * u)
 
 
+def _ceil_log2(C):
+    L = 0
+    while (1 << L) < C:
+        L += 1
+    return L
+
+
+def _squeeze(one_tab, one_q, *arrays):
+    """The arrays (ntab, Q, ..) without the axes that a single table (R of two axes) or spectrum (S of one) added."""
+    if one_q:
+        arrays = [a[:, 0] for a in arrays]
+    if one_tab:
+        arrays = [a[0] for a in arrays]
+    return tuple(arrays)
+
+
 def fold_host(rows, D):
     """out[..., c] = sum_{f, b} rows[..., f, b] * D[c, f, b].  rows: (..., 3, N) -- flux_fla (n, 3, N) or G_fla
     (ntab, M, 3, N); D: (C, 3, N).  No background, no defined order (a matrix product)."""
@@ -79,11 +95,7 @@ def events_host(R, S, scale=None, background=None):
     bg = np.zeros(C) if background is None else np.broadcast_to(np.asarray(background, dtype=np.float64), (C,))
     mu = sc[None, :, None] * acc                          # two roundings: the scale ...
     mu = mu + bg[None, None, :]                           # ... and the background
-    if one_q:
-        mu = mu[:, 0]
-    if one_tab:
-        mu = mu[0]
-    return mu
+    return _squeeze(one_tab, one_q, mu)[0]
 
 
 def poisson_host(mu, data, log=np.log):
@@ -116,14 +128,27 @@ def tree(x):
     entries with +0.0, then replace the vector by the sums of adjacent pairs (0+1, 2+3, ..) until one value is left."""
     x = np.asarray(x, dtype=np.float64)
     C = x.shape[-1]
-    P = 1
-    while P < C:
-        P *= 2
-    v = np.zeros(x.shape[:-1] + (P,))
+    v = np.zeros(x.shape[:-1] + (1 << _ceil_log2(C),))
     v[..., :C] = x
     while v.shape[-1] > 1:
         v = v[..., 0::2] + v[..., 1::2]
     return v[..., 0]
+
+
+def _signal(who, R, S, data):
+    """The front of profile_host and fit_host: (s (ntab, Q, C) = events_host's accumulator, the checked data (C,),
+    one_tab, one_q)."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    data = np.asarray(data, dtype=np.float64)
+    one_tab, one_q = R.ndim == 2, S.ndim == 1
+    s = events_host(R[None] if one_tab else R, S[None] if one_q else S)           # 1.0 * acc + 0.0: acc itself
+    C = s.shape[-1]
+    if data.shape != (C,):
+        raise ValueError("%s: data must have shape (%d,), got %s" % (who, C, data.shape))
+    if not np.all(np.isfinite(data)) or np.any(data < 0):
+        raise ValueError("%s: a datum is negative or not finite" % who)
+    return s, data, one_tab, one_q
 
 
 def profile_host(R, S, data, background=None, log=np.log):
@@ -135,16 +160,8 @@ def profile_host(R, S, data, background=None, log=np.log):
     R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  data: (C,).  background: None (= 0), a number or (C,).
     Returns (ahat, nll, mu, status): ahat, nll and status (int32: the step count in the low 8 bits, FIT_* flags above)
     of shape (ntab, Q), mu = ahat s + B of shape (ntab, Q, C); the squeezed axes of events_host are squeezed here."""
-    R = np.asarray(R, dtype=np.float64)
-    S = np.asarray(S, dtype=np.float64)
-    data = np.asarray(data, dtype=np.float64)
-    one_tab, one_q = R.ndim == 2, S.ndim == 1
-    s = events_host(R[None] if one_tab else R, S[None] if one_q else S)           # 1.0 * acc + 0.0: acc itself
+    s, data, one_tab, one_q = _signal("profile_host", R, S, data)
     C = s.shape[-1]
-    if data.shape != (C,):
-        raise ValueError("profile_host: data must have shape (%d,), got %s" % (C, data.shape))
-    if not np.all(np.isfinite(data)) or np.any(data < 0):
-        raise ValueError("profile_host: a datum is negative or not finite")
     B = np.zeros(C) if background is None else np.broadcast_to(np.asarray(background, dtype=np.float64), (C,))
     d = np.broadcast_to(data, s.shape)
     act = (d > 0) & (s > 0)
@@ -178,30 +195,19 @@ def profile_host(R, S, data, background=None, log=np.log):
     mu = mu + B
     flags[np.any((d > 0) & (mu == 0), axis=-1)] |= FIT_INFINITE
     nll = poisson_host(mu, data, log=log)
-    status = steps | flags
-    if one_q:
-        a, nll, mu, status = a[:, 0], nll[:, 0], mu[:, 0], status[:, 0]
-    if one_tab:
-        a, nll, mu, status = a[0], nll[0], mu[0], status[0]
-    return a, nll, mu, status
+    return _squeeze(one_tab, one_q, a, nll, mu, steps | flags)
 
 
 def fit_kappa(C, K):
     """kappa(C, K) = 2 (ceil(log2 C) + K) + 18: the stop of nusi_plan_response_fit, |g_j| <= kappa u scale_j on the
     computed gradient (include/nusi.h; derived in DESIGN.md sec. 4, "The fit with floating templates")."""
-    L = 0
-    while (1 << L) < C:
-        L += 1
-    return 2 * (L + K) + 18
+    return 2 * (_ceil_log2(C) + K) + 18
 
 
 def K_fit(C, K):
     """The bound on the EXACT residual of a converged fit, in units of u scale_j: the stop's kappa plus the rounding of
     the computed gradient, ceil(log2 C) + 2 K + 8, plus one for the computed scale."""
-    L = 0
-    while (1 << L) < C:
-        L += 1
-    return fit_kappa(C, K) + L + 2 * K + 9
+    return fit_kappa(C, K) + _ceil_log2(C) + 2 * K + 9
 
 
 def _prior(K, prior):
@@ -381,16 +387,8 @@ def fit_host(R, S, data, templates, prior=None, background=None, log=np.log):
     status (ntab, Q) int32): the Newton steps in the low 8 bits, the FIT_* flags, FIT_ZERO << j for every component
     that ends at zero and the halvings of all steps (saturating) from bit FIT_TRIALS_SHIFT; the axes events_host
     squeezes are squeezed here."""
-    R = np.asarray(R, dtype=np.float64)
-    S = np.asarray(S, dtype=np.float64)
-    data = np.asarray(data, dtype=np.float64)
-    one_tab, one_q = R.ndim == 2, S.ndim == 1
-    s = events_host(R[None] if one_tab else R, S[None] if one_q else S)
+    s, data, one_tab, one_q = _signal("fit_host", R, S, data)
     ntab, Q, C = s.shape
-    if data.shape != (C,):
-        raise ValueError("fit_host: data must have shape (%d,), got %s" % (C, data.shape))
-    if not np.all(np.isfinite(data)) or np.any(data < 0):
-        raise ValueError("fit_host: a datum is negative or not finite")
     T = _templates(templates, C)
     K = T.shape[0]
     m, w = _prior(K, prior)
@@ -417,11 +415,7 @@ def fit_host(R, S, data, templates, prior=None, background=None, log=np.log):
         if w[j] > 0:
             dl = theta[..., j] - m[j]
             nll = nll + ((0.5 * w[j]) * dl) * dl
-    if one_q:
-        theta, nll, mu, status = theta[:, 0], nll[:, 0], mu[:, 0], status[:, 0]
-    if one_tab:
-        theta, nll, mu, status = theta[0], nll[0], mu[0], status[0]
-    return theta, nll, mu, status
+    return _squeeze(one_tab, one_q, theta, nll, mu, status)
 
 
 def matrix(lo, hi, aeff, migration=None, exposure=1.0):

@@ -243,6 +243,14 @@ class Plan:
                                                        ctypes.c_void_p(d_R_ptr),
                                                        ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
+    def _folded(self, R, who):
+        """(R as a contiguous (ntab, M, C) array, C) for the call ``who``."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        C = self.detector_bins()
+        if C and (R.ndim != 3 or R.shape[1:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("%s: R must have shape (ntab, %d, %d), got %s" % (who, self.T + 1, C, R.shape))
+        return R, C
+
     def _data(self, data):
         if data is None:
             return None
@@ -257,10 +265,7 @@ class Plan:
         detector.events_host.  With data (C,) also nll[t, q] = sum_c mu - data log mu (detector.poisson_host, the
         Poisson negative log-likelihood without its data-only constant): returns (mu, nll).  spectra and scale as for
         apply_response (scale >= 0 here)."""
-        R = np.ascontiguousarray(R, dtype=np.float64)
-        C = self.detector_bins()
-        if C and (R.ndim != 3 or R.shape[1:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
-            raise ValueError("events: R must have shape (ntab, %d, %d), got %s" % (self.T + 1, C, R.shape))
+        R, C = self._folded(R, "events")
         S, sc = self._spectra(spectra, scale)
         d = self._data(data)
         mu = np.zeros((R.shape[0], len(S), C))
@@ -286,6 +291,35 @@ class Plan:
             ctypes.c_void_p(stream_ptr) if stream_ptr else None))
         return len(S)
 
+    def _minimise(self, who, R, spectra, data, width):
+        """profile and fit: (the fitted normalisations (ntab, Q) + width, nll, mu, status) of the library's host form."""
+        R, C = self._folded(R, who)
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
+        ntab, Q = R.shape[0], len(S)
+        first, nll, mu = np.zeros((ntab, Q) + width), np.zeros((ntab, Q)), np.zeros((ntab, Q, C))
+        status = np.zeros((ntab, Q), dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(getattr(_lib.load(), "nusi_plan_response_%s_host" % who)(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp) if d is not None else None,
+            first.ctypes.data_as(dp), nll.ctypes.data_as(dp), mu.ctypes.data_as(dp),
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return first, nll, mu, status
+
+    def _minimise_device(self, who, d_R_ptr, ntab, spectra, data, d_first_ptr, d_nll_ptr, d_mu_ptr, d_status_ptr,
+                         stream_ptr):
+        """profile_device and fit_device: the library's device form on raw pointers.  Returns Q."""
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(getattr(_lib.load(), "nusi_plan_response_" + who)(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None,
+            vp(d_first_ptr) if d_first_ptr else None, vp(d_nll_ptr) if d_nll_ptr else None,
+            vp(d_mu_ptr) if d_mu_ptr else None, vp(d_status_ptr) if d_status_ptr else None,
+            vp(stream_ptr) if stream_ptr else None))
+        return len(S)
+
     def profile(self, R, spectra, data):
         """The statistic of ``events`` profiled over the flux normalisation, on the GPU: for every table and spectrum
         the a >= 0 that minimises -ln L(a s + background | data), s the expected signal counts of the spectrum at
@@ -294,37 +328,15 @@ class Plan:
         (FIT_FLAT: no signal or no data in any signal bin, ahat = 0; FIT_BOUNDARY: the minimum is at a = 0;
         FIT_NOT_CONVERGED; FIT_INFINITE: a bin with data has neither signal nor background, nll = +inf).  ahat, mu and
         status equal detector.profile_host bit for bit.  There is no scale: it is what is fitted."""
-        R = np.ascontiguousarray(R, dtype=np.float64)
-        C = self.detector_bins()
-        if C and (R.ndim != 3 or R.shape[1:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
-            raise ValueError("profile: R must have shape (ntab, %d, %d), got %s" % (self.T + 1, C, R.shape))
-        S, _ = self._spectra(spectra, None)
-        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
-        ntab, Q = R.shape[0], len(S)
-        ahat, nll, mu = np.zeros((ntab, Q)), np.zeros((ntab, Q)), np.zeros((ntab, Q, C))
-        status = np.zeros((ntab, Q), dtype=np.int32)
-        dp = ctypes.POINTER(ctypes.c_double)
-        _lib.check(_lib.load().nusi_plan_response_profile_host(
-            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp) if d is not None else None,
-            ahat.ctypes.data_as(dp), nll.ctypes.data_as(dp), mu.ctypes.data_as(dp),
-            status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
-        return ahat, nll, mu, status
+        return self._minimise("profile", R, spectra, data, ())
 
     def profile_device(self, d_R_ptr, ntab, spectra, data, d_ahat_ptr, d_nll_ptr=None, d_mu_ptr=None, d_status_ptr=None,
                        stream_ptr=None):
         """Asynchronous profile on device-resident folded matrices: d_R [ntab][M][C], d_ahat and d_nll [ntab][Q],
         d_mu [ntab][Q][C] (doubles) and d_status [ntab][Q] (ints) are raw pointers, every output but d_ahat may be
         0 / None; the spectra and data are host data and are copied.  Returns Q."""
-        S, _ = self._spectra(spectra, None)
-        d = self._data(data)
-        dp = ctypes.POINTER(ctypes.c_double)
-        vp = ctypes.c_void_p
-        _lib.check(_lib.load().nusi_plan_response_profile(
-            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None,
-            vp(d_ahat_ptr) if d_ahat_ptr else None, vp(d_nll_ptr) if d_nll_ptr else None,
-            vp(d_mu_ptr) if d_mu_ptr else None, vp(d_status_ptr) if d_status_ptr else None,
-            vp(stream_ptr) if stream_ptr else None))
-        return len(S)
+        return self._minimise_device("profile", d_R_ptr, ntab, spectra, data, d_ahat_ptr, d_nll_ptr, d_mu_ptr,
+                                     d_status_ptr, stream_ptr)
 
     def set_templates(self, templates, prior=None):
         """Register K <= 3 background templates (K, C) of the detector -- expected counts per reconstructed bin at
@@ -366,37 +378,15 @@ class Plan:
         no signal, the templates are still fitted; FIT_BOUNDARY: theta_0 = 0; FIT_NOT_CONVERGED; FIT_SINGULAR: the
         data do not determine the components; FIT_INFINITE), FIT_ZERO << j for a component that ends at zero and the
         halvings from bit FIT_TRIALS_SHIFT.  theta, mu and status equal detector.fit_host bit for bit."""
-        R = np.ascontiguousarray(R, dtype=np.float64)
-        C, K = self.detector_bins(), self.templates()
-        if C and (R.ndim != 3 or R.shape[1:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
-            raise ValueError("fit: R must have shape (ntab, %d, %d), got %s" % (self.T + 1, C, R.shape))
-        S, _ = self._spectra(spectra, None)
-        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
-        ntab, Q = R.shape[0], len(S)
-        theta, nll, mu = np.zeros((ntab, Q, 1 + K)), np.zeros((ntab, Q)), np.zeros((ntab, Q, C))
-        status = np.zeros((ntab, Q), dtype=np.int32)
-        dp = ctypes.POINTER(ctypes.c_double)
-        _lib.check(_lib.load().nusi_plan_response_fit_host(
-            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp) if d is not None else None,
-            theta.ctypes.data_as(dp), nll.ctypes.data_as(dp), mu.ctypes.data_as(dp),
-            status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
-        return theta, nll, mu, status
+        return self._minimise("fit", R, spectra, data, (1 + self.templates(),))
 
     def fit_device(self, d_R_ptr, ntab, spectra, data, d_theta_ptr, d_nll_ptr=None, d_mu_ptr=None, d_status_ptr=None,
                    stream_ptr=None):
         """Asynchronous fit on device-resident folded matrices: d_R [ntab][M][C], d_theta [ntab][Q][1 + K], d_nll
         [ntab][Q], d_mu [ntab][Q][C] (doubles) and d_status [ntab][Q] (ints) are raw pointers, every output but
         d_theta may be 0 / None; the spectra and data are host data and are copied.  Returns Q."""
-        S, _ = self._spectra(spectra, None)
-        d = self._data(data)
-        dp = ctypes.POINTER(ctypes.c_double)
-        vp = ctypes.c_void_p
-        _lib.check(_lib.load().nusi_plan_response_fit(
-            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None,
-            vp(d_theta_ptr) if d_theta_ptr else None, vp(d_nll_ptr) if d_nll_ptr else None,
-            vp(d_mu_ptr) if d_mu_ptr else None, vp(d_status_ptr) if d_status_ptr else None,
-            vp(stream_ptr) if stream_ptr else None))
-        return len(S)
+        return self._minimise_device("fit", d_R_ptr, ntab, spectra, data, d_theta_ptr, d_nll_ptr, d_mu_ptr, d_status_ptr,
+                                     stream_ptr)
 
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push

@@ -3,14 +3,15 @@
 
     scripts/dev_isa_diff.py <rev-a> <rev-b> [--rename OLD=NEW ...] [--jobs N]
 
-For nusi_kernels.hip and nusi_cascade.hip: both revisions are exported with `git archive` (a <rev> that names
-a directory is taken as a source tree as it stands, e.g. `.` for uncommitted work), the device side is compiled
+For nusi_kernels.hip, nusi_cascade.hip and nusi_detector.hip: both revisions are exported with `git archive` (a <rev>
+that names a directory is taken as a source tree as it stands, e.g. `.` for uncommitted work), the device side is compiled
 with the Makefile's own command for that file plus `--cuda-device-only -S`, the text is split per symbol, and
 three lists are printed: symbols only in A, only in B, and symbols whose text differs (with a unified diff).
 Normalised before comparing: local label numbers (.LBB<n>_, .Ltmp<n>, .Lfunc_end<n>), comments, and the
 --rename mapping (re.sub on A's text; mangled names hold no regex metacharacter but '.' and '$').  Assembly
 text, not the linked code object: there the pc-relative literals to out-of-line callees shift whenever any
-function moves.  Exit status 1 if anything differs.
+function moves.  After the lists, every kernel's instruction lines, SGPRs, VGPRs, scratch and LDS bytes in A and B
+(the compiler's "Kernel info" comments).  Exit status 1 if anything differs.
 """
 import argparse
 import concurrent.futures
@@ -24,10 +25,11 @@ import tarfile
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ("nusi_kernels.hip", "nusi_cascade.hip")
+FILES = ("nusi_kernels.hip", "nusi_cascade.hip", "nusi_detector.hip")
 TYPE = re.compile(r"^\s*\.type\s+([^\s,]+),@(function|object)")
 LABEL = re.compile(r"\.(LBB|Ltmp|Lfunc_end|Lfunc_begin)\d+")
 # directives that open the *next* symbol and so trail the previous symbol's chunk
+INFO = re.compile(r"^; (TotalNumSgprs|NumVgprs|ScratchSize|LDSByteSize): (\d+)")
 PREAMBLE = re.compile(r"^\s*\.(text|section|protected|globl|weak|hidden|p2align)\b")
 
 
@@ -78,6 +80,24 @@ def split(path, rename):
     return syms
 
 
+def kernel_info(path):
+    """{kernel: {figure: value}} from the "Kernel info" comment block that follows each kernel's text."""
+    info, name = {}, None
+    for line in open(path):
+        m = TYPE.match(line)
+        if m:
+            name = m.group(1)
+        m = INFO.match(line)
+        if m and name:
+            info.setdefault(name, {})[m.group(1)] = int(m.group(2))
+    return info
+
+
+def ninstr(lines):
+    """The instruction lines of a symbol's chunk: neither directives nor labels."""
+    return sum(1 for l in lines if not l.lstrip().startswith(".") and not l.endswith(":"))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("rev_a")
@@ -105,6 +125,12 @@ def main():
                     print("   " + s)
             for s in diff:
                 sys.stdout.writelines(l + "\n" for l in difflib.unified_diff(A[s], B[s], "a/" + s, "b/" + s, lineterm="", n=1))
+            KA, KB = kernel_info(asm[0, f].result()), kernel_info(asm[1, f].result())
+            print("-- kernels: instruction lines, SGPRs, VGPRs, scratch, LDS bytes (A -> B)")
+            for s in KA:
+                if s in KB and s in A and s in B and "LDSByteSize" in KA[s]:   # (out-of-line functions have none)
+                    print("   %s  %d -> %d" % (s, ninstr(A[s]), ninstr(B[s])) + "".join(
+                        ", %d -> %d" % (KA[s][k], KB[s][k]) for k in ("TotalNumSgprs", "NumVgprs", "ScratchSize", "LDSByteSize")))
             differs = differs or len(A) != len(B) or bool(diff) or set(A) != set(B)
     return 1 if differs else 0
 
