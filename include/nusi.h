@@ -390,6 +390,35 @@ int nusi_plan_response_fit(nusi_plan *plan, const double *d_R /* [ntab][M][C] */
                            int *d_status /* [ntab][Q] or NULL */, void *stream);
 int nusi_plan_response_fit_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
                                 double *theta, double *nll, double *mu, int *status);
+/* nusi_plan_response_ensemble (k_ensemble_profile, k_ensemble_fit, k_ensemble_best): P data sets data[p][C] -- an
+ * ensemble of pseudo-experiments -- against every table and spectrum in ONE call, and of each (p, t) only the BEST
+ * spectrum's record.  The front half s[t][q][c] = sum_n R[t][n][c] S[q][n] does not depend on the data: it is computed
+ * once and the P fits run on it.
+ *
+ * The selection rule.  For a data set p and a table t, the record of spectrum q is exactly what
+ * nusi_plan_response_fit gives for (t, q) against data[p] -- theta [1 + K], status, nll -- or, on a plan without
+ * templates (K = nusi_plan_templates(plan) = 0), what nusi_plan_response_profile gives: ahat (theta has width 1), status,
+ * nll.  The same iteration, the same operations in the same order: the bits of those calls.  The best record is the
+ * minimum under the key
+ *     (isnan(nll), nll, q)   compared lexicographically, nll as numbers:
+ * a NaN loses to everything, +inf included; equal nll resolve to the lowest q.  The key is a total order on the
+ * spectra, so the result does not depend on how the reduction is arranged (NUSI_OPT_ENSEMBLE_QSLICES, _PSLICES:
+ * the same bits for every value).  If every nll is +inf (NUSI_FIT_INFINITE) the record is that of q = 0.
+ *
+ * d_q[p][t] = that q, d_nll[p][t], d_theta[p][t][1 + K], d_status[p][t]: device memory; d_theta and d_status may be
+ * NULL.  S [Q][M] and data [P][C] are host arrays and are copied (entries finite and >= 0); the device generates no
+ * random numbers, pseudo-data are the caller's.  Asynchronous and ordered with the plan's other detector calls like
+ * nusi_plan_response_fit.  NUSI_ESTATE without a detector; NUSI_EPARAM for a NULL d_R, S, data, d_q or d_nll, P outside
+ * 1 .. NUSI_ENSEMBLE_DATASETS_MAX, ntab < 1, Q outside 1 .. 2^19, P ntab >= 2^31, or a negative or non-finite entry of
+ * S or data; a refused call changes nothing.  _host: R and the outputs in host memory, synchronous. */
+#define NUSI_ENSEMBLE_DATASETS_MAX 65536
+int nusi_plan_response_ensemble(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab,
+                                const double *S /* [Q][M] */, int Q, const double *data /* [P][C] */, int P,
+                                int *d_q /* [P][ntab] */, double *d_nll /* [P][ntab] */,
+                                double *d_theta /* [P][ntab][1 + K] or NULL */, int *d_status /* [P][ntab] or NULL */,
+                                void *stream);
+int nusi_plan_response_ensemble_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q,
+                                     const double *data, int P, int *q, double *nll, double *theta, int *status);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);
@@ -526,6 +555,17 @@ int nusi_plan_set_cascade(nusi_plan *plan, int kind);
  *                          fit (at least one table); 0 = 1 GiB.  Any value
  *                          gives the same bits. */
 #define NUSI_OPT_RESPONSE_FIFO_KB 12
+/*   NUSI_OPT_ENSEMBLE_QSLICES, NUSI_OPT_ENSEMBLE_PSLICES  the grid of
+ *                          nusi_plan_response_ensemble is (tables, q-slices,
+ *                          p-slices): a block takes the spectrum blocks of its
+ *                          q-slice and the data sets of its p-slice.  0 =
+ *                          automatic (the grid fills the card, the q-slices'
+ *                          records stay within 256 MiB of scratch); n >= 1 =
+ *                          exactly min(n, what there is to split) (tests: every
+ *                          path at small shapes).  Any value gives the same
+ *                          bits. */
+#define NUSI_OPT_ENSEMBLE_QSLICES 13
+#define NUSI_OPT_ENSEMBLE_PSLICES 14
 int nusi_plan_set_option(nusi_plan *plan, int option, int value);
 /* per-point NUSI_WARN_* bits of the last call */
 int nusi_plan_warnings(nusi_plan *plan, int *out, int n);

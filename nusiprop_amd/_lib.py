@@ -70,6 +70,7 @@ EXPORTS = [
     "nusi_plan_response_fold", "nusi_plan_response_fold_host", "nusi_plan_response_events",
     "nusi_plan_response_events_host", "nusi_plan_response_profile", "nusi_plan_response_profile_host",
     "nusi_plan_set_templates", "nusi_plan_templates", "nusi_plan_response_fit", "nusi_plan_response_fit_host",
+    "nusi_plan_response_ensemble", "nusi_plan_response_ensemble_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -80,6 +81,8 @@ OPT_CASCADE_SYNC = 7
 OPT_REFO_CORNER_MB = 8
 OPT_GA_BATCH, OPT_GA_PRE_MB, OPT_GA_PRE_KB = 9, 10, 11
 OPT_RESPONSE_FIFO_KB = 12
+OPT_ENSEMBLE_QSLICES, OPT_ENSEMBLE_PSLICES = 13, 14    # Plan.ensemble's grid (tables, q-slices, p-slices); 0 = automatic
+ENSEMBLE_DATASETS_MAX = 65536
 
 _lib = None
 
@@ -153,6 +156,8 @@ def load():
         "nusi_plan_templates": (i, [vp]),
         "nusi_plan_response_fit": (i, [vp, vp, i, dp, i, dp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_fit_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, ip]),
+        "nusi_plan_response_ensemble": (i, [vp, vp, i, dp, i, dp, i, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_ensemble_host": (i, [vp, dp, i, dp, i, dp, i, ip, dp, dp, ip]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

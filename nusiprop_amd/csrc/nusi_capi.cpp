@@ -466,8 +466,12 @@ struct nusi_plan {
     int fit_K = 0;                  // background templates of the fit (nusi_plan_set_templates); 0 = none
     double* d_tpl = nullptr;        // T [K][C]
     double fit_m[NUSI_FIT_TEMPLATES_MAX] = {}, fit_w[NUSI_FIT_TEMPLATES_MAX] = {};   // the priors: means, 1 / sigma^2 (0 = none)
-    double* d_evt = nullptr;        // events: the spectra S [Q][T + 1], then scale [Q], then data [C]
+    double* d_evt = nullptr;        // events: the spectra S [Q][T + 1], then scale [Q], then data [C] (the ensemble: [P][C])
     size_t evt_doubles = 0;
+    int ens_qslices = 0;            // NUSI_OPT_ENSEMBLE_QSLICES, NUSI_OPT_ENSEMBLE_PSLICES: 0 = automatic
+    int ens_pslices = 0;
+    void* d_ens = nullptr;          // the ensemble's q-slice records [qslices][P][ntab] (at most kEnsScratchBytes when
+    size_t ens_bytes = 0;           // the slices are automatic)
     std::vector<double> h_evt;
     hipEvent_t ev_det = nullptr;    // end of the latest fold / events call (set_detector and the next events wait for it)
     bool det_ran = false;
@@ -932,6 +936,7 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->d_det);
     hipFree(pl->d_tpl);
     hipFree(pl->d_evt);
+    hipFree(pl->d_ens);
     nusi::alpha_tiles_destroy(&pl->atiles);
     hipFree(pl->mc.buf);
     hipFree(pl->mc.eu);
@@ -1835,9 +1840,10 @@ int nusi_plan_response_fold_host(nusi_plan* pl, const double* G_fla, int ntab, d
 }
 
 // The argument checks of the events and the profile call (what: the call's name in the messages), and the staging of
-// their host vectors: S [Q][M], scale [Q] (or zeros) and data [C] (or zeros) into the plan's d_evt, in that order, on s.
+// their host vectors: S [Q][M], scale [Q] (or zeros) and data [P][C] (or zeros; P = 1 for every call but the ensemble)
+// into the plan's d_evt, in that order, on s.
 static int events_check(const nusi_plan* pl, const char* what, const double* d_R, int ntab, const double* S, int Q,
-                        const double* scale, const double* data)
+                        const double* scale, const double* data, int P)
 {
     if (!d_R || !S) return fail(NUSI_EPARAM, std::string(what) + ": R and S must not be NULL");
     if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, std::string(what) + ": need ntab >= 1 and 1 <= Q <= 2^19");
@@ -1848,17 +1854,17 @@ static int events_check(const nusi_plan* pl, const char* what, const double* d_R
         for (int q = 0; q < Q; ++q)
             if (!(scale[q] >= 0.0) || !std::isfinite(scale[q])) return fail(NUSI_EPARAM, std::string(what) + ": a scale is negative or not finite");
     if (data)
-        for (int c = 0; c < pl->det_C; ++c)
+        for (size_t c = 0; c < (size_t)P * pl->det_C; ++c)
             if (!(data[c] >= 0.0) || !std::isfinite(data[c])) return fail(NUSI_EPARAM, std::string(what) + ": a datum is negative or not finite");
     return NUSI_OK;
 }
-static int events_stage(nusi_plan* pl, const double* S, int Q, const double* scale, const double* data, hipStream_t s)
+static int events_stage(nusi_plan* pl, const double* S, int Q, const double* scale, const double* data, int P, hipStream_t s)
 {
     const size_t M = (size_t)pl->grid.T + 1;
     const int C = pl->det_C;
     if (pl->det_ran) HIPCHECK(hipEventSynchronize(pl->ev_det));   // d_evt / h_evt are reused (every earlier detector
                                                                   // call has finished: detector_chain)
-    const size_t need = (size_t)Q * M + (size_t)Q + (size_t)C;
+    const size_t need = (size_t)Q * M + (size_t)Q + (size_t)P * C;
     if (pl->evt_doubles < need) {
         hipFree(pl->d_evt);
         pl->d_evt = nullptr;
@@ -1869,7 +1875,7 @@ static int events_stage(nusi_plan* pl, const double* S, int Q, const double* sca
     pl->h_evt.assign(S, S + (size_t)Q * M);
     pl->h_evt.resize(need, 0.0);
     if (scale) memcpy(pl->h_evt.data() + (size_t)Q * M, scale, sizeof(double) * Q);
-    if (data) memcpy(pl->h_evt.data() + (size_t)Q * M + Q, data, sizeof(double) * C);
+    if (data) memcpy(pl->h_evt.data() + (size_t)Q * M + Q, data, sizeof(double) * P * C);
     HIPCHECK(hipMemcpyAsync(pl->d_evt, pl->h_evt.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
     return NUSI_OK;
 }
@@ -1881,12 +1887,12 @@ struct EventsArgs {
     const double *S, *scale, *data, *bg;
 };
 static int events_begin(nusi_plan* pl, const char* what, const double* d_R, int ntab, const double* S, int Q,
-                        const double* scale, const double* data, void* stream, EventsArgs& a)
+                        const double* scale, const double* data, int P, void* stream, EventsArgs& a)
 {
-    if (int r = events_check(pl, what, d_R, ntab, S, Q, scale, data)) return r;
+    if (int r = events_check(pl, what, d_R, ntab, S, Q, scale, data, P)) return r;
     HIPCHECK(hipSetDevice(pl->device));
     a.s = stream ? (hipStream_t)stream : pl->stream;
-    if (int r = events_stage(pl, S, Q, scale, data, a.s)) return r;
+    if (int r = events_stage(pl, S, Q, scale, data, P, a.s)) return r;
     const double* d_sc = pl->d_evt + (size_t)Q * ((size_t)pl->grid.T + 1);
     a.S = pl->d_evt;
     a.scale = scale ? d_sc : nullptr;
@@ -1902,7 +1908,7 @@ int nusi_plan_response_events(nusi_plan* pl, const double* d_R, int ntab, const 
     if (!d_mu && !d_nll) return fail(NUSI_EPARAM, "response events: mu and nll are both NULL");
     if (d_nll && !data) return fail(NUSI_EPARAM, "response events: nll needs data");
     EventsArgs a;
-    if (int r = events_begin(pl, "response events", d_R, ntab, S, Q, scale, data, stream, a)) return r;
+    if (int r = events_begin(pl, "response events", d_R, ntab, S, Q, scale, data, 1, stream, a)) return r;
     HIPCHECK(nusi::launch_detector_events(pl->gd, d_R, ntab, a.S, Q, a.scale, a.data, a.bg, pl->det_C, d_mu, d_nll, a.s));
     return detector_mark(pl, a.s);
 }
@@ -1926,7 +1932,7 @@ int nusi_plan_response_profile(nusi_plan* pl, const double* d_R, int ntab, const
     if (int r = detector_plan(pl, "response profile")) return r;
     if (!data || !d_ahat) return fail(NUSI_EPARAM, "response profile: data and ahat must not be NULL");
     EventsArgs a;
-    if (int r = events_begin(pl, "response profile", d_R, ntab, S, Q, nullptr, data, stream, a)) return r;
+    if (int r = events_begin(pl, "response profile", d_R, ntab, S, Q, nullptr, data, 1, stream, a)) return r;
     HIPCHECK(nusi::launch_detector_profile(pl->gd, d_R, ntab, a.S, Q, a.data, a.bg, pl->det_C, d_ahat, d_nll, d_mu, d_status, a.s));
     return detector_mark(pl, a.s);
 }
@@ -2008,7 +2014,7 @@ int nusi_plan_response_fit(nusi_plan* pl, const double* d_R, int ntab, const dou
     if (!pl->fit_K) return fail(NUSI_ESTATE, "response fit: the plan has no templates (nusi_plan_set_templates; without them: nusi_plan_response_profile)");
     if (!data || !d_theta) return fail(NUSI_EPARAM, "response fit: data and theta must not be NULL");
     EventsArgs a;
-    if (int r = events_begin(pl, "response fit", d_R, ntab, S, Q, nullptr, data, stream, a)) return r;
+    if (int r = events_begin(pl, "response fit", d_R, ntab, S, Q, nullptr, data, 1, stream, a)) return r;
     HIPCHECK(nusi::launch_detector_fit(pl->gd, d_R, ntab, a.S, Q, a.data, a.bg, pl->det_C, pl->fit_K, pl->d_tpl, pl->fit_m,
                                        pl->fit_w, d_theta, d_nll, d_mu, d_status, a.s));
     return detector_mark(pl, a.s);
@@ -2027,6 +2033,80 @@ int nusi_plan_response_fit_host(nusi_plan* pl, const double* R, int ntab, const 
                        "response fit", [&](const double* dI, void* const* d) {
                            return nusi_plan_response_fit(pl, dI, ntab, S, Q, data, (double*)d[0], (double*)d[1], (double*)d[2],
                                                          (int*)d[3], nullptr);
+                       });
+}
+
+// The ensemble (nusi_detector.hip k_ensemble_profile / k_ensemble_fit / k_ensemble_best).  The grid is (tables,
+// q-slices, p-slices).  Automatic slices: the grid should hold kEnsBlocksPerCU blocks per compute unit, several rounds
+// of what is resident at once, so that the last round's tail is short (measured: DESIGN.md sec. 4).  Spectrum blocks
+// are split first -- a q-slice repeats no work, it costs P ntab records of scratch and the merge -- as far as the
+// spectrum blocks and kEnsScratchBytes of scratch allow; the data sets are split only where that leaves the grid short,
+// and into slices of at least kEnsSliceDatasets, since every p-slice repeats the front half.  An option > 0 holds
+// instead, capped only by what there is to split.
+constexpr size_t kEnsScratchBytes = size_t(256) << 20;
+constexpr int kEnsBlocksPerCU = 32, kEnsSliceDatasets = 16;
+static int ensemble_slices(nusi_plan* pl, int ntab, int Q, int P, int& qs, int& ps)
+{
+    const int nqb = nusi::ensemble_blocks(pl->det_C, pl->fit_K, Q);
+    int ncu = 0;
+    HIPCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device));
+    const long long want = (long long)kEnsBlocksPerCU * (ncu > 0 ? ncu : 1);
+    if (pl->ens_qslices > 0) {
+        qs = std::min(pl->ens_qslices, nqb);
+    } else {
+        const size_t per = (size_t)P * ntab * nusi::ensemble_record_bytes(pl->fit_K);
+        const long long fit = (long long)(kEnsScratchBytes / per);
+        qs = (int)std::min<long long>(std::min<long long>(nqb, 65535), (want + ntab - 1) / ntab);
+        if (qs > fit) qs = fit > 1 ? (int)fit : 1;
+    }
+    if (pl->ens_pslices > 0) {
+        ps = std::min(pl->ens_pslices, P);
+    } else {
+        const long long have = (long long)ntab * qs;
+        ps = (int)std::min<long long>(std::max(P / kEnsSliceDatasets, 1), (want + have - 1) / have);
+    }
+    return NUSI_OK;
+}
+
+int nusi_plan_response_ensemble(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data, int P,
+                                int* d_q, double* d_nll, double* d_theta, int* d_status, void* stream)
+{
+    if (int r = detector_plan(pl, "response ensemble")) return r;
+    if (!data || !d_q || !d_nll) return fail(NUSI_EPARAM, "response ensemble: data, q and nll must not be NULL");
+    if (P < 1 || P > NUSI_ENSEMBLE_DATASETS_MAX) return fail(NUSI_EPARAM, "response ensemble: P outside 1 .. NUSI_ENSEMBLE_DATASETS_MAX");
+    if ((long long)ntab * P > (long long)INT_MAX) return fail(NUSI_EPARAM, "response ensemble: too many records (P ntab >= 2^31)");
+    EventsArgs a;
+    if (int r = events_begin(pl, "response ensemble", d_R, ntab, S, Q, nullptr, data, P, stream, a)) return r;
+    int qs = 1, ps = 1;
+    if (int r = ensemble_slices(pl, ntab, Q, P, qs, ps)) return r;
+    if (qs > 1) {   // (every earlier detector call has finished: events_stage)
+        const size_t need = (size_t)qs * P * ntab * nusi::ensemble_record_bytes(pl->fit_K);
+        if (pl->ens_bytes < need) {
+            hipFree(pl->d_ens);
+            pl->d_ens = nullptr;
+            pl->ens_bytes = 0;
+            HIPCHECK(hipMalloc(&pl->d_ens, need));
+            pl->ens_bytes = need;
+        }
+    }
+    HIPCHECK(nusi::launch_detector_ensemble(pl->gd, d_R, ntab, a.S, Q, a.data, P, a.bg, pl->det_C, pl->fit_K, pl->d_tpl,
+                                            pl->fit_m, pl->fit_w, qs, ps, pl->d_ens, d_q, d_nll, d_theta, d_status, a.s));
+    return detector_mark(pl, a.s);
+}
+
+int nusi_plan_response_ensemble_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
+                                     int P, int* q, double* nll, double* theta, int* status)
+{
+    if (int r = detector_plan(pl, "response ensemble")) return r;
+    if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response ensemble: R must not be NULL, ntab and Q >= 1");
+    if (!data || !q || !nll) return fail(NUSI_EPARAM, "response ensemble: data, q and nll must not be NULL");
+    if (P < 1 || P > NUSI_ENSEMBLE_DATASETS_MAX) return fail(NUSI_EPARAM, "response ensemble: P outside 1 .. NUSI_ENSEMBLE_DATASETS_MAX");
+    const size_t nn = (size_t)P * ntab, nth = nn * (1 + pl->fit_K);
+    return events_host(pl, R, ntab,
+                       {{q, nn, sizeof(int)}, {nll, nn, sizeof(double)}, {theta, nth, sizeof(double)}, {status, nn, sizeof(int)}},
+                       "response ensemble", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_ensemble(pl, dI, ntab, S, Q, data, P, (int*)d[0], (double*)d[1],
+                                                              (double*)d[2], (int*)d[3], nullptr);
                        });
 }
 
@@ -2125,6 +2205,14 @@ int nusi_plan_set_option(nusi_plan* pl, int option, int value)
     case NUSI_OPT_RESPONSE_FIFO_KB:
         if (value < 0 || value > (1 << 30)) return fail(NUSI_EPARAM, "NUSI_OPT_RESPONSE_FIFO_KB outside [0, 2^30]");
         pl->response_fifo_kb = value;
+        return NUSI_OK;
+    case NUSI_OPT_ENSEMBLE_QSLICES:
+        if (value < 0 || value > 65535) return fail(NUSI_EPARAM, "NUSI_OPT_ENSEMBLE_QSLICES outside [0, 65535]");
+        pl->ens_qslices = value;
+        return NUSI_OK;
+    case NUSI_OPT_ENSEMBLE_PSLICES:
+        if (value < 0 || value > 65535) return fail(NUSI_EPARAM, "NUSI_OPT_ENSEMBLE_PSLICES outside [0, 65535]");
+        pl->ens_pslices = value;
         return NUSI_OK;
     case NUSI_OPT_REFERENCE_ORDER:
         if (value < 0 || value > 1) return fail(NUSI_EPARAM, "NUSI_OPT_REFERENCE_ORDER outside [0, 1]");

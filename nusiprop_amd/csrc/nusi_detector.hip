@@ -9,6 +9,9 @@
 //                         sums over the bins as butterflies inside a wave (nusi_plan_response_profile)
 //   k_detector_fit<NC>    that statistic minimised over NC = 1 + K normalisations, the signal's and K background
 //                         templates' under Gaussian priors: a damped Newton iteration per (t, q) (nusi_plan_response_fit)
+//   k_ensemble_profile, k_ensemble_fit<NC>, k_ensemble_best
+//                         those two iterations for P data sets on one front half, and per (data set, table) the best
+//                         spectrum's record only (nusi_plan_response_ensemble)
 #include <hip/hip_runtime.h>
 
 #include "nusi_internal.hpp"
@@ -742,6 +745,628 @@ hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, cons
     case 3: hipLaunchKernelGGL((k_detector_fit<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The ensemble kernels (nusi_plan_response_ensemble): P data sets data[p][C] against every table and spectrum, and of
+// each (p, t) only the BEST spectrum's record (q, nll, theta, status) under the key include/nusi.h defines,
+// (isnan(nll), nll, q) compared lexicographically.  k_ensemble_profile runs k_detector_profile's iteration (no
+// templates, theta = ahat), k_ensemble_fit<NC> k_detector_fit<NC>'s, on those kernels' block shapes; their bodies are
+// COPIED here, operation for operation, and not shared: moving the existing kernels' bodies into helpers moved their
+// code objects and their timing, and they keep theirs.  det_front, det_poisson and det_butterfly are
+// the existing helpers, called as they are.
+//
+// Grid (tables, q-slices, p-slices).  A block walks the spectrum blocks qb of its q-slice and, per spectrum block, the
+// data sets of its p-slice: the front half s = sum_n R S, the sums S1 and the templates' liveness do not depend on the
+// data and are computed once per spectrum block and kept in registers; per data set only d, act, live[0], sup, D0,
+// dmin, the start and the iteration run.
+//
+// Per data set: the lanes write their spectrum's row -- the statistic's terms mu_c - data_c log(mu_c) [C], each formed
+// on its bin's own lane (the same operations as the serial loops of det_poisson and k_detector_fit, so the same bits;
+// one log per lane instead of C in a row on one lane of eight), theta [W], the status word (as a double: exact) --
+// to LDS, ONE barrier, the terms' sum in the defined serial order by one lane per spectrum, a reduction under the key
+// over each wave (xor shuffles) and lane 0 of each wave writes its wave's record to LDS.  Rows and wave records are
+// double-buffered on the data set's parity: the wave records of data set i are merged by thread 0 after the barrier of
+// data set i + 1 (after the last: one more barrier), which makes them visible and is passed by every lane only after it
+// has read its rows of data set i; buffer i & 1 is next written for data set i + 2, behind that barrier.  Thread 0
+// merges into the running record of (p, t) in global memory, which no other block and no other thread touches: for the
+// q-slice's first spectrum block it writes, afterwards it reads, compares and writes.  No atomics.  With one q-slice
+// the running records are the call's outputs; with more they are the plan's scratch [q-slice][P][ntab] and
+// k_ensemble_best merges the slices.  The key is a total order on the (distinct) q, so every tree gives the same record.
+//
+// LDS: 2 det_qb(lgC, per) rows of ens_row(C, W) = (C + W + 1) | 1 doubles, sized for the largest C, and EnsWin<W>:
+// 8 (2 ens_rows_max(per, W) + 8 (W + 2)) bytes.
+// ---------------------------------------------------------------------------
+struct EnsOut {
+    int* q;          // records [slice][P][ntab]; theta [..][W]
+    double* nll;
+    double* theta;   // (theta, status: NULL = not wanted; never NULL in the scratch)
+    int* status;
+    size_t slice;    // records per q-slice; 0: one q-slice, the records are the call's outputs
+};
+
+constexpr int kEnsWaves = kEvThreads >> 6;
+constexpr int ens_row(int C, int W) { return (C + W + 1) | 1; }
+constexpr int ens_rows_max(int per, int W)
+{
+    int m = 0;
+    for (int C = 1; C <= NUSI_DETECTOR_BINS_MAX; ++C) {
+        const int n = det_qb(ceil_log2(C), per) * ens_row(C, W);
+        m = n > m ? n : m;
+    }
+    return m;
+}
+
+template <int W>
+struct EnsWin {   // the waves' records of a data set, double-buffered
+    double nll[2][kEnsWaves], th[2][kEnsWaves][W];
+    int q[2][kEnsWaves], st[2][kEnsWaves];
+};
+
+// is record a better than record b?  (isnan(nll), nll, q) ascending; a wave without a spectrum carries (NaN, INT_MAX)
+__device__ __forceinline__ bool ens_better(double an, int aq, double bn, int bq)
+{
+    const bool na = an != an, nb = bn != bn;
+    if (na != nb) return nb;
+    if (!na && an != bn) return an < bn;
+    return aq < bq;
+}
+
+// the wave's best (nll, q) on every lane; then lane 0 writes the wave's record from the winner's row
+template <int W>
+__device__ __forceinline__ void ens_wave_record(double n, int q, EnsWin<W>& win, int buf, int wave, const double* rows,
+                                                int RS, int C, int qb0)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const double on = __shfl_xor(n, m);
+        const int oq = __shfl_xor(q, m);
+        if (ens_better(on, oq, n, q)) {
+            n = on;
+            q = oq;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        win.nll[buf][wave] = n;
+        win.q[buf][wave] = q;
+        if (q != INT_MAX) {
+            const double* row = rows + (size_t)(q - qb0) * RS + C;
+#pragma unroll
+            for (int j = 0; j < W; ++j) win.th[buf][wave][j] = row[j];
+            win.st[buf][wave] = (int)row[W];
+        }
+    }
+}
+
+// thread 0: the nw wave records of buffer buf into the running record r (fresh: the record holds nothing yet)
+template <int W>
+__device__ __forceinline__ void ens_commit(const EnsWin<W>& win, int buf, int nw, const EnsOut& o, size_t r, bool fresh)
+{
+    int k = 0;
+    for (int i = 1; i < nw; ++i)
+        if (ens_better(win.nll[buf][i], win.q[buf][i], win.nll[buf][k], win.q[buf][k])) k = i;
+    if (!fresh && !ens_better(win.nll[buf][k], win.q[buf][k], o.nll[r], o.q[r])) return;
+    o.nll[r] = win.nll[buf][k];
+    o.q[r] = win.q[buf][k];
+    if (o.theta)
+#pragma unroll
+        for (int j = 0; j < W; ++j) o.theta[r * W + j] = win.th[buf][k][j];
+    if (o.status) o.status[r] = win.st[buf][k];
+}
+
+// a block's share of n items among the nparts blocks along one grid axis: [lo, hi), balanced, never empty for
+// nparts <= n
+__device__ __forceinline__ void ens_share(int n, int part, int nparts, int& lo, int& hi)
+{
+    lo = (int)((long long)n * part / nparts);
+    hi = (int)((long long)n * (part + 1) / nparts);
+}
+
+__global__ __launch_bounds__(kEvThreads) void k_ensemble_profile(const double* __restrict__ R, const double* __restrict__ S,
+                                                                 const double* __restrict__ data,
+                                                                 const double* __restrict__ bg, const EnsOut o, int M, int C,
+                                                                 int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    constexpr int kRows = ens_rows_max(kEvQ, 1);
+    __shared__ double srow[2 * kRows];
+    __shared__ EnsWin<1> win;
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x, ntab = (int)gridDim.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = det_qb(lgC, kEvQ), nqb = (Q + QB - 1) / QB;
+    const int cc = c < C ? c : C - 1, RS = ens_row(C, 1);
+    const int nw = QB < kEvThreads ? (QB + 63) >> 6 : kEnsWaves;   // the waves that hold a spectrum's statistic
+    int b0, b1, p0, p1;
+    ens_share(nqb, (int)blockIdx.y, (int)gridDim.y, b0, b1);
+    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
+    const bool in = c < C;
+    const double b = in ? bg[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto max = [](double x, double y) { return y > x ? y : x; };
+    int it = 0;
+    size_t rprev = 0;
+    bool fprev = false;
+    for (int qb = b0; qb < b1; ++qb) {
+        const int qb0 = qb * QB, q0 = qb0 + grp * kEvQ;
+        double s[kEvQ], S1[kEvQ];
+        det_front(R, S, t, M, C, cc, q0, Q, s);
+#pragma unroll
+        for (int j = 0; j < kEvQ; ++j) {
+            if (!in) s[j] = 0.0;
+            S1[j] = s[j];
+        }
+        det_butterfly(S1, lgC, add);
+        for (int p = p0; p < p1; ++p, ++it) {
+            const double* __restrict__ dat = data + (size_t)p * C;
+            const double d = in ? dat[cc] : 0.0;
+            // --- k_detector_profile's iteration, copied ---
+            double a[kEvQ];
+            bool act[kEvQ], run[kEvQ];
+            int st[kEvQ];
+#pragma unroll
+            for (int j = 0; j < kEvQ; ++j) {
+                act[j] = d > 0.0 && s[j] > 0.0;
+                run[j] = S1[j] != 0.0 && (__ballot(act[j]) & gmask) != 0;
+                st[j] = run[j] ? 0 : NUSI_FIT_FLAT;
+                const double x0 = d / S1[j], x1 = b / s[j];
+                a[j] = act[j] ? x0 - x1 : 0.0;
+            }
+            det_butterfly(a, lgC, max);
+#pragma unroll
+            for (int j = 0; j < kEvQ; ++j) a[j] = (run[j] && a[j] > 0.0) ? a[j] : 0.0;
+            // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
+            while (__any(run[0] || run[1] || run[2] || run[3])) {
+                double v[2 * kEvQ];
+#pragma unroll
+                for (int j = 0; j < kEvQ; ++j) {
+                    double den = a[j] * s[j];
+                    den = den + b;
+                    const double q = s[j] / den;
+                    const double u = act[j] ? q : 0.0;
+                    const double r = d * u;
+                    v[j] = r;
+                    v[kEvQ + j] = r * u;
+                }
+                det_butterfly(v, lgC, add);
+#pragma unroll
+                for (int j = 0; j < kEvQ; ++j) {
+                    const double S2 = v[j], S3 = v[kEvQ + j];
+                    const double g = S1[j] - S2;
+                    const double dn = S2 - S1[j];
+                    const double an = a[j] + dn / S3;
+                    if (run[j]) {
+                        ++st[j];
+                        if (!(g < 0.0)) {
+                            run[j] = false;
+                            if (a[j] == 0.0) st[j] |= NUSI_FIT_BOUNDARY;
+                        } else if (!(an > a[j])) {
+                            run[j] = false;
+                        } else {
+                            a[j] = an;
+                            if ((st[j] & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
+                                run[j] = false;
+                                st[j] |= NUSI_FIT_NOT_CONVERGED;
+                            }
+                        }
+                    }
+                }
+            }
+            const int buf = it & 1;
+            double* rows = srow + buf * kRows;
+#pragma unroll
+            for (int j = 0; j < kEvQ; ++j) {
+                double m = a[j] * s[j];
+                m = m + b;
+                if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st[j] |= NUSI_FIT_INFINITE;
+                double term = m;   // det_poisson's term of (spectrum, c), on the bin's own lane
+                if (d != 0.0) {
+                    const double pl = d * nm::log_i(m);
+                    term = m - pl;
+                }
+                double* row = rows + (grp * kEvQ + j) * RS;
+                if (in) row[c] = term;
+                if (c == 0) {
+                    row[C] = a[j];
+                    row[C + 1] = (double)st[j];
+                }
+            }
+            // --- the statistic and the block's best record ---
+            __syncthreads();
+            if (it > 0 && tid == 0) ens_commit(win, buf ^ 1, nw, o, rprev, fprev);
+            rprev = (size_t)blockIdx.y * o.slice + (size_t)p * ntab + t;
+            fprev = qb == b0;
+            if ((tid >> 6) < nw) {
+                double bn = __builtin_nan("");
+                int bq = INT_MAX;
+                // (a block owns QB spectra -- 1024 at C = 1 -- on kEvThreads threads: ascending i, so ascending q)
+                for (int i = tid; i < QB && qb0 + i < Q; i += kEvThreads) {
+                    double n = 0.0;   // det_poisson's sum: the terms ascending in c, from 0.0
+                    for (int k = 0; k < C; ++k) n = n + rows[i * RS + k];
+                    if (ens_better(n, qb0 + i, bn, bq)) {
+                        bn = n;
+                        bq = qb0 + i;
+                    }
+                }
+                ens_wave_record(bn, bq, win, buf, tid >> 6, rows, RS, C, qb0);
+            }
+        }
+    }
+    __syncthreads();
+    if (it > 0 && tid == 0) ens_commit(win, (it - 1) & 1, nw, o, rprev, fprev);
+}
+
+// Registers: the loop over the data sets keeps more alive around the iteration than k_detector_fit does (the row
+// pointers, the lane's place, what the compiler hoists out of the loop), so the allocator is told the aim: four waves
+// per SIMD (128 registers) for NC = 2 and 3.  NC = 4 -- k_detector_fit<4> itself stands at 127 -- does not get there
+// without scratch (14 registers spilled); it is held to three waves (168) instead and takes 164, no scratch.
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) __attribute__((amdgpu_waves_per_eu(NC == 4 ? 3 : 4))) void k_ensemble_fit(const double* __restrict__ R, const double* __restrict__ S,
+                                                             const double* __restrict__ data,
+                                                             const double* __restrict__ bg, const double* __restrict__ T,
+                                                             const FitPrior pr, const double ku, const EnsOut o, int M,
+                                                             int C, int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
+    constexpr int kRows = ens_rows_max(1, NC);
+    __shared__ double srow[2 * kRows];
+    __shared__ EnsWin<NC> win;
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x, ntab = (int)gridDim.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, nqb = (Q + QB - 1) / QB;
+    const int cc = c < C ? c : C - 1, RS = ens_row(C, NC);
+    const int nw = (QB + 63) >> 6;   // the waves that hold a spectrum's statistic
+    int b0, b1, p0, p1;
+    ens_share(nqb, (int)blockIdx.y, (int)gridDim.y, b0, b1);
+    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const bool in = c < C;
+    double X[NC];
+#pragma unroll
+    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
+    const double b = in ? bg[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+    int it = 0;
+    size_t rprev = 0;
+    bool fprev = false;
+    for (int qb = b0; qb < b1; ++qb) {
+        const int qb0 = qb * QB, q = qb0 + grp;
+        const double* __restrict__ Sq = S + (size_t)(q < Q ? q : Q - 1) * M;
+        {
+            double s0 = 0.0;
+#pragma unroll 4
+            for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
+            X[0] = in ? s0 : 0.0;
+        }
+        double S1[NC];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) S1[j] = X[j];
+        det_butterfly(S1, lgC, add);
+        for (int pi = p0; pi < p1; ++pi, ++it) {
+            const double* __restrict__ dat = data + (size_t)pi * C;
+            const double d = in ? dat[cc] : 0.0;
+            // --- k_detector_fit's iteration, copied ---
+            bool live[NC];
+            live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
+            bool sup = b > 0.0;
+            int nl = 0;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                if (j > 0) live[j] = S1[j] > 0.0;
+                sup = sup || (live[j] && X[j] > 0.0);
+                nl += live[j] ? 1 : 0;
+            }
+            const bool act = d > 0.0 && sup;
+            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
+            det_butterfly(dsum, lgC, add);
+            det_butterfly(dmin, lgC, min);
+            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+            double th[NC], the[NC], p[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const double x = D0 / ((double)nl * S1[j]);
+                th[j] = live[j] ? x : 0.0;
+                the[j] = th[j];
+                p[j] = 0.0;
+            }
+            double tt = 1.0;
+            int st = 0, steps = 0, halv = 0, trials = 0;
+            bool run = true, first = true, quad = false;
+            // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
+            while (__any(run)) {
+                double v[NS];
+                double den = the[0] * X[0];
+#pragma unroll
+                for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
+                den = den + b;
+                const double wq0 = d / den;
+                const double wq = act ? wq0 : 0.0;
+                const double r0 = wq / den;
+                const double r = act ? r0 : 0.0;
+                {
+                    int i = NC;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) {
+                        v[j] = X[j] * wq;
+                        const double xr = X[j] * r;
+#pragma unroll
+                        for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
+                    }
+                }
+                det_butterfly(v, lgC, add);
+                const bool bad = any(act && !(den > 0.0));
+                if (run) {
+                    double g[NC];
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
+                    bool ok, changed = true;
+                    if (first) {
+                        ok = !bad;
+                        if (!ok) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        }
+                    } else {
+                        double slope = 0.0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
+                        ok = !bad && (quad || !(slope > 0.0));
+                        if (!ok) {
+                            if (trials == NUSI_FIT_TRIALS_MAX) {
+                                run = false;
+                                st |= NUSI_FIT_NOT_CONVERGED;
+                            } else {
+                                ++trials;
+                                ++halv;
+                                tt = tt * 0.5;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
+                            }
+                        } else {
+                            changed = false;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
+                            ++steps;
+                        }
+                    }
+                    if (ok) {
+                        bool fs[NC], conv = true;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) {
+                            th[j] = the[j];
+                            fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
+                            const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
+                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                            if (fs[j] && !(ag <= ku * scale)) conv = false;
+                        }
+                        if (conv) {
+                            run = false;
+                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        } else {
+                            first = false;
+                            bool sing = false;
+#pragma unroll 1
+                            for (int rep = 0; rep <= NC; ++rep) {
+                                double Lm[NC][NC], Dg[NC], y[NC];
+                                sing = false;
+                                int i0 = NC;
+                                double a[NC][NC];
+#pragma unroll
+                                for (int j = 0; j < NC; ++j)
+#pragma unroll
+                                    for (int k = j; k < NC; ++k) {
+                                        const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
+                                        a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
+                                    }
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) {
+                                    double cw[NC];
+#pragma unroll
+                                    for (int j = 0; j < i; ++j) {
+                                        double x = a[i][j];
+#pragma unroll
+                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                        cw[j] = x;
+                                        Lm[i][j] = x / Dg[j];
+                                    }
+                                    double x = a[i][i];
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                                    if (!(x > 0.0)) sing = true;
+                                    Dg[i] = x;
+                                }
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) {
+                                    double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                                    y[i] = x;
+                                }
+#pragma unroll
+                                for (int i = NC - 1; i >= 0; --i) {
+                                    double x = y[i] / Dg[i];
+#pragma unroll
+                                    for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
+                                    p[i] = x;
+                                }
+                                if (sing) break;
+                                bool rm = false;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j)
+                                    if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
+                                        fs[j] = false;
+                                        rm = true;
+                                    }
+                                if (!rm) break;
+                            }
+                            double acc = 0.0;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j)
+                                if (fs[j]) acc = acc + g[j] * p[j];
+                            if (sing || !(acc < 0.0)) {
+                                run = false;
+                                st |= NUSI_FIT_SINGULAR;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) p[j] = 0.0;
+                            } else {
+                                double ratio[NC];
+                                tt = 1.0;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) {
+                                    const double x = th[j] / -p[j];
+                                    ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
+                                    if (ratio[j] < tt) tt = ratio[j];
+                                }
+                                const bool clipped = tt < 1.0;
+                                quad = !clipped && -acc <= dq;
+                                trials = 0;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) {
+                                    const double x = th[j] + tt * p[j];
+                                    the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            double m = th[0] * X[0];
+#pragma unroll
+            for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
+            m = m + b;
+            if (!live[0])
+                st |= NUSI_FIT_FLAT;
+            else if (th[0] == 0.0)
+                st |= NUSI_FIT_BOUNDARY;
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+                if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
+            if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
+            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+            const int buf = it & 1;
+            double* rows = srow + buf * kRows;
+            double term = m;   // the statistic's term of (spectrum, c), on the bin's own lane
+            if (d != 0.0) {
+                const double pl = d * nm::log_i(m);
+                term = m - pl;
+            }
+            if (in) rows[grp * RS + c] = term;
+            if (c == 0) {
+#pragma unroll
+                for (int j = 0; j < NC; ++j) rows[grp * RS + C + j] = th[j];
+                rows[grp * RS + C + NC] = (double)st;
+            }
+            // --- the statistic and the block's best record ---
+            __syncthreads();
+            if (it > 0 && tid == 0) ens_commit(win, buf ^ 1, nw, o, rprev, fprev);
+            rprev = (size_t)blockIdx.y * o.slice + (size_t)pi * ntab + t;
+            fprev = qb == b0;
+            if ((tid >> 6) < nw) {
+                double sum = __builtin_nan("");
+                int bq = INT_MAX;
+                // (a block owns QB <= kEvThreads spectra)
+                if (tid < QB && qb0 + tid < Q) {
+                    bq = qb0 + tid;
+                    sum = 0.0;   // k_detector_fit's sum: the terms ascending in c, from 0.0, then the penalties
+                    for (int k = 0; k < C; ++k) sum = sum + rows[tid * RS + k];
+#pragma unroll
+                    for (int j = 1; j < NC; ++j)
+                        if (pr.w[j] > 0.0) {
+                            const double dl = rows[tid * RS + C + j] - pr.m[j];
+                            const double pen = ((0.5 * pr.w[j]) * dl) * dl;
+                            sum = sum + pen;
+                        }
+                }
+                ens_wave_record(sum, bq, win, buf, tid >> 6, rows, RS, C, qb0);
+            }
+        }
+    }
+    __syncthreads();
+    if (it > 0 && tid == 0) ens_commit(win, (it - 1) & 1, nw, o, rprev, fprev);
+}
+
+// The q-slices' records [nslice][n] (n = P ntab) into the call's outputs, one thread per (p, t), slices ascending.
+__global__ __launch_bounds__(kEvThreads) void k_ensemble_best(const EnsOut in, int nslice, size_t n, int W, const EnsOut o)
+{
+    const size_t r = (size_t)blockIdx.x * kEvThreads + threadIdx.x;
+    if (r >= n) return;
+    int k = 0;
+    double bn = in.nll[r];
+    int bq = in.q[r];
+    for (int i = 1; i < nslice; ++i) {
+        const double x = in.nll[(size_t)i * n + r];
+        const int xq = in.q[(size_t)i * n + r];
+        if (ens_better(x, xq, bn, bq)) {
+            bn = x;
+            bq = xq;
+            k = i;
+        }
+    }
+    const size_t src = (size_t)k * n + r;
+    o.nll[r] = bn;
+    o.q[r] = bq;
+    if (o.theta)
+        for (int j = 0; j < W; ++j) o.theta[r * W + j] = in.theta[src * W + j];
+    if (o.status) o.status[r] = in.status[src];
+}
+
+size_t ensemble_record_bytes(int K) { return sizeof(double) * (2 + K) + 2 * sizeof(int); }
+
+int ensemble_blocks(int C, int K, int Q)
+{
+    const DetGeom ge(C, K ? 1 : kEvQ, 1, Q);
+    return (int)ge.grid.y;
+}
+
+hipError_t launch_detector_ensemble(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                                    int P, const double* bg, int C, int K, const double* T, const double* pm,
+                                    const double* pw, int qslices, int pslices, void* scratch, int* oq, double* onll,
+                                    double* otheta, int* ostatus, hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0 || P <= 0) return hipSuccess;
+    const DetGeom ge(C, K ? 1 : kEvQ, ntab, Q);
+    if (qslices < 1 || qslices > (int)ge.grid.y || pslices < 1 || pslices > P || (qslices > 1 && !scratch))
+        return hipErrorInvalidValue;
+    const int W = 1 + K, M = g.T + 1;
+    const size_t n = (size_t)P * ntab;
+    const EnsOut out{oq, onll, otheta, ostatus, 0};
+    EnsOut rec = out;
+    if (qslices > 1) {   // the scratch: nll, theta, q, status, each [qslices][n]
+        const size_t ns = (size_t)qslices * n;
+        rec.nll = (double*)scratch;
+        rec.theta = rec.nll + ns;
+        rec.q = (int*)(rec.theta + ns * W);
+        rec.status = rec.q + ns;
+        rec.slice = n;
+    }
+    const dim3 grid((unsigned)ntab, (unsigned)qslices, (unsigned)pslices), block(kEvThreads);
+    if (K == 0) {
+        hipLaunchKernelGGL(k_ensemble_profile, grid, block, 0, s, R, S, data, bg, rec, M, C, ge.lg, Q, P);
+    } else {
+        FitPrior pr;
+        for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
+            pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
+            pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
+        }
+        const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;   // kappa(C, K) u (include/nusi.h)
+        switch (K) {
+        case 1: hipLaunchKernelGGL((k_ensemble_fit<2>), grid, block, 0, s, R, S, data, bg, T, pr, ku, rec, M, C, ge.lg, Q, P); break;
+        case 2: hipLaunchKernelGGL((k_ensemble_fit<3>), grid, block, 0, s, R, S, data, bg, T, pr, ku, rec, M, C, ge.lg, Q, P); break;
+        case 3: hipLaunchKernelGGL((k_ensemble_fit<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, rec, M, C, ge.lg, Q, P); break;
+        default: return hipErrorInvalidValue;
+        }
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || qslices == 1) return e;
+    const size_t nblk = (n + kEvThreads - 1) / kEvThreads;
+    hipLaunchKernelGGL(k_ensemble_best, dim3((unsigned)nblk), block, 0, s, rec, qslices, n, W, out);
     return hipGetLastError();
 }
 

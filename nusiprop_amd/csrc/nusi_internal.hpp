@@ -165,6 +165,17 @@ hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, 
 hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
                                const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
                                double* theta, double* nll, double* mu, int* status, hipStream_t s);
+// k_ensemble_profile (K = 0) / k_ensemble_fit<1 + K>: P data sets data [P][C] (device memory), per (p, t) the best
+// spectrum's record under the key of include/nusi.h: q, nll, status [P][ntab], theta [P][ntab][1 + K] in device memory,
+// theta and status may be nullptr.  Grid (ntab, qslices, pslices): 1 <= qslices <= ensemble_blocks(C, K, Q) (the
+// spectrum blocks per table), 1 <= pslices <= P.  With qslices > 1 the slices' records go to scratch --
+// qslices P ntab ensemble_record_bytes(K) bytes of device memory -- and k_ensemble_best merges them.
+size_t ensemble_record_bytes(int K);
+int ensemble_blocks(int C, int K, int Q);
+hipError_t launch_detector_ensemble(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                                    int P, const double* bg, int C, int K, const double* T, const double* pm,
+                                    const double* pw, int qslices, int pslices, void* scratch, int* oq, double* onll,
+                                    double* otheta, int* ostatus, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

@@ -21,6 +21,12 @@ same for nusi_plan_response_fit, the fit that floats K background templates with
 
     plan.set_templates(T, prior=(mean, sigma))                           # (K, C), K <= FIT_TEMPLATES_MAX
     theta, nll, mu, st = plan.fit(R, spectra, data=counts)              # fit_host on the CPU: theta (ntab, Q, 1 + K)
+
+``ensemble_host`` loops either over P data sets and keeps, per data set and table, the best spectrum's record under
+``argbest``'s key (isnan(nll), nll, q) -- nusi_plan_response_ensemble's selection rule; ``pseudo_data`` draws the toys::
+
+    toys = detector.pseudo_data(mu[0, 0], 1000, np.random.default_rng(1))   # (P, C) Poisson counts
+    q, nll, theta, st = plan.ensemble(R, spectra, toys)                  # ensemble_host on the CPU: (P, ntab) records
 """
 import numpy as np
 
@@ -416,6 +422,73 @@ def fit_host(R, S, data, templates, prior=None, background=None, log=np.log):
             dl = theta[..., j] - m[j]
             nll = nll + ((0.5 * w[j]) * dl) * dl
     return _squeeze(one_tab, one_q, theta, nll, mu, status)
+
+
+def argbest(nll, axis=-1):
+    """The selection rule of nusi_plan_response_ensemble (include/nusi.h): along ``axis`` the index of the minimum under
+    the key (isnan(nll), nll, index), compared lexicographically -- a NaN loses to everything, +inf included, and equal
+    values resolve to the lowest index (all +inf, or all NaN: index 0).  The key is a total order, so any reduction
+    tree gives the same index."""
+    x = np.asarray(nll, dtype=np.float64)
+    if x.ndim == 0 or x.shape[axis] == 0:
+        raise ValueError("argbest: nothing to choose from along axis %d of shape %s" % (axis, x.shape))
+    nan = np.isnan(x)
+    filled = np.where(nan, np.inf, x)
+    k = np.argmin(filled, axis=axis)                               # (ties: the first occurrence)
+    least = np.take_along_axis(filled, np.expand_dims(k, axis), axis).squeeze(axis)
+    # the least is +inf: every non-NaN entry is +inf and the first of THEM wins, not a NaN filled in before it
+    return np.where(least == np.inf, np.argmax(~nan, axis=axis), k)
+
+
+def ensemble_host(R, S, datasets, templates=None, prior=None, background=None, log=np.log):
+    """nusi_plan_response_ensemble on the CPU: for every data set p and table t the best spectrum's record.  A loop of
+    fit_host (with templates) or profile_host (without: theta has width 1 and holds ahat) over the data sets, reduced
+    over the spectra with argbest.
+
+    R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  datasets: (C,) or (P, C), entries finite and >= 0.  templates,
+    prior, background, log: as for fit_host.  Returns (q (P, ntab) int32, nll (P, ntab), theta (P, ntab, 1 + K),
+    status (P, ntab) int32); no axis is squeezed."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    data = np.asarray(datasets, dtype=np.float64)
+    if R.ndim == 2:
+        R = R[None]
+    if S.ndim == 1:
+        S = S[None]
+    if data.ndim == 1:
+        data = data[None]
+    if R.ndim != 3 or S.ndim != 2 or R.shape[1] != S.shape[1]:
+        raise ValueError("ensemble_host: R (.., M, C) and S (.., M) do not match: %s, %s" % (R.shape, S.shape))
+    ntab, C = R.shape[0], R.shape[2]
+    if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] != C:
+        raise ValueError("ensemble_host: datasets must have shape (P, %d), P >= 1, got %s" % (C, data.shape))
+    if not np.all(np.isfinite(data)) or np.any(data < 0):
+        raise ValueError("ensemble_host: a datum is negative or not finite")
+    K = 0 if templates is None else _templates(templates, C).shape[0]
+    P = data.shape[0]
+    q = np.zeros((P, ntab), dtype=np.int32)
+    nll, theta, status = np.zeros((P, ntab)), np.zeros((P, ntab, 1 + K)), np.zeros((P, ntab), dtype=np.int32)
+    rows = np.arange(ntab)
+    for p in range(P):
+        if K:
+            th, n, _, st = fit_host(R, S, data[p], templates, prior=prior, background=background, log=log)
+        else:
+            a, n, _, st = profile_host(R, S, data[p], background=background, log=log)
+            th = a[..., None]
+        best = argbest(n, axis=-1)
+        q[p], nll[p], theta[p], status[p] = best, n[rows, best], th[rows, best], st[rows, best]
+    return q, nll, theta, status
+
+
+def pseudo_data(mu, P, rng):
+    """P Poisson pseudo-experiments around the expected counts mu (C,): counts (P, C) as float64, drawn from ``rng``, a
+    numpy.random.Generator (the device generates no random numbers: toys are host data)."""
+    mu = np.asarray(mu, dtype=np.float64)
+    if mu.ndim != 1 or not np.all(np.isfinite(mu)) or np.any(mu < 0):
+        raise ValueError("pseudo_data: mu must be a vector of finite expectations >= 0")
+    if int(P) < 1:
+        raise ValueError("pseudo_data: P must be >= 1")
+    return np.ascontiguousarray(rng.poisson(mu, size=(int(P), mu.shape[0])), dtype=np.float64)
 
 
 def matrix(lo, hi, aeff, migration=None, exposure=1.0):

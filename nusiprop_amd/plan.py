@@ -388,6 +388,52 @@ class Plan:
         return self._minimise_device("fit", d_R_ptr, ntab, spectra, data, d_theta_ptr, d_nll_ptr, d_mu_ptr, d_status_ptr,
                                      stream_ptr)
 
+    def _datasets(self, datasets):
+        d = np.ascontiguousarray(datasets, dtype=np.float64)
+        if d.ndim == 1:
+            d = d[None]
+        C = self.detector_bins()
+        if C and (d.ndim != 2 or d.shape[0] < 1 or d.shape[1] != C):   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("ensemble: datasets must have shape (P, %d), P >= 1, got %s" % (C, d.shape))
+        return d
+
+    def ensemble(self, R, spectra, datasets):
+        """P data sets -- an ensemble of pseudo-experiments, datasets (P, C) -- against every table and spectrum in one
+        call on the GPU, and of each (p, t) only the best spectrum's record: the signal counts of (t, q) are computed
+        once and the P fits run on them.  The record of a spectrum is what ``fit`` gives for it against datasets[p]
+        (``profile`` on a plan without templates, K = 0: theta is ahat), bit for bit; the best is the minimum under the
+        key (isnan(nll), nll, q) -- detector.argbest: a NaN loses to everything, ties go to the lowest q.  Returns
+        (q (P, ntab) int32, nll (P, ntab), theta (P, ntab, 1 + K), status (P, ntab) int32), the same as
+        detector.ensemble_host up to the last bits of nll's log.  The device draws no random numbers: the toys are host
+        data (detector.pseudo_data)."""
+        R, C = self._folded(R, "ensemble")
+        S, _ = self._spectra(spectra, None)
+        d = self._datasets(datasets)
+        ntab, P, W = R.shape[0], d.shape[0], 1 + self.templates()
+        q, status = np.zeros((P, ntab), dtype=np.int32), np.zeros((P, ntab), dtype=np.int32)
+        nll, theta = np.zeros((P, ntab)), np.zeros((P, ntab, W))
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        _lib.check(_lib.load().nusi_plan_response_ensemble_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp), P,
+            q.ctypes.data_as(ip), nll.ctypes.data_as(dp), theta.ctypes.data_as(dp), status.ctypes.data_as(ip)))
+        return q, nll, theta, status
+
+    def ensemble_device(self, d_R_ptr, ntab, spectra, datasets, d_q_ptr, d_nll_ptr, d_theta_ptr=None, d_status_ptr=None,
+                        stream_ptr=None):
+        """Asynchronous ensemble on device-resident folded matrices: d_R [ntab][M][C], d_q and d_status [P][ntab]
+        (ints), d_nll [P][ntab] and d_theta [P][ntab][1 + K] (doubles) are raw pointers, d_theta and d_status may be
+        0 / None; the spectra and the data sets are host data and are copied.  Returns (Q, P)."""
+        S, _ = self._spectra(spectra, None)
+        d = self._datasets(datasets) if datasets is not None else None
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_response_ensemble(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None,
+            d.shape[0] if d is not None else 0, vp(d_q_ptr) if d_q_ptr else None, vp(d_nll_ptr) if d_nll_ptr else None,
+            vp(d_theta_ptr) if d_theta_ptr else None, vp(d_status_ptr) if d_status_ptr else None,
+            vp(stream_ptr) if stream_ptr else None))
+        return len(S), (d.shape[0] if d is not None else 0)
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since
@@ -404,7 +450,9 @@ class Plan:
         member-corner block budget in MiB, 0 = automatic), OPT_GA_BATCH (the reference order's Gamma / alphaTilde path:
         0 auto, 1 the per-table kernel, 2 the batch path whenever batches exist), OPT_GA_PRE_MB (the batch path's block
         budget in MiB, 0 = 512; OPT_GA_PRE_KB: the same in KiB), OPT_RESPONSE_FIFO_KB (the response's impulse
-        cascade: its step-pass FIFO budget in KiB, 0 = 1 GiB; the tables run in chunks that fit); include/nusi.h."""
+        cascade: its step-pass FIFO budget in KiB, 0 = 1 GiB; the tables run in chunks that fit), OPT_ENSEMBLE_QSLICES
+        and OPT_ENSEMBLE_PSLICES (``ensemble``'s grid is (tables, q-slices, p-slices): 0 = automatic, n >= 1 = exactly
+        min(n, what there is to split); any value gives the same bits); include/nusi.h."""
         _lib.check(_lib.load().nusi_plan_set_option(self._h, int(option), int(value)))
 
     def profile_begin(self, max_calls):
