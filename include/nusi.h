@@ -390,6 +390,112 @@ int nusi_plan_response_fit(nusi_plan *plan, const double *d_R /* [ntab][M][C] */
                            int *d_status /* [ntab][Q] or NULL */, void *stream);
 int nusi_plan_response_fit_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
                                 double *theta, double *nll, double *mu, int *status);
+/* nusi_plan_response_fit_fixed (k_conditional_fit): the CONDITIONAL fit -- the fit above with the signal's scale HELD at
+ * a given a = scale[q] >= 0 and only the K templates floating: theta_1 .. theta_K >= 0 minimising f(a, .) for every table
+ * t and spectrum q.  At a = 0 it is the background-only fit; at any a it is the inner problem of the statistic
+ * q(a) = 2 (min_theta f(a, theta) - min f).  It is nusi_plan_response_fit's iteration on the components j = 1 .. K alone,
+ * every operation and its order as defined there, with these differences and nothing else (X_0 = s, X_j = T_j, tree(),
+ * u and the priors as there):
+ *   S1_j     = tree(X_j) for j = 1 .. K only; component j is live when S1_j > 0.  The signal is not a component: it is
+ *            neither live nor free, has no gradient, no row of H and no direction
+ *   active   bin c with data_c > 0 and (B_c > 0, or X_jc > 0 for a live j >= 1, or (a > 0 and s_c > 0)): the held signal
+ *            supports a bin.  dmin as there
+ *   start    theta_j = tree(data over the active bins) / (n_live * S1_j) for the live j >= 1, n_live counting them; 0 for
+ *            the others
+ *   eval(x)  den_c = a X_0c, den_c = den_c + x_j X_jc (j = 1 .. K ascending), den_c = den_c + B_c -- the fit's den at
+ *            x_0 = a, so the conditional mu at some theta has the bits the fit's mu has at (a, theta); bad, w_c, r_c as
+ *            there;  S2_j, H_jk and g_j for j, k = 1 .. K only
+ *   free, stop, caps, solve, length, trial: as there over j = 1 .. K (slope and acc sum over j = 1 .. K ascending), with
+ *            the same kappa = 2 (ceil(log2 C) + K) + 18: den has as many terms as the fit's, so the computed gradient
+ *            carries the same roundings, and the floor sum_k H_jk theta_k <= scale_j holds for any subset of components
+ *            
+ *   theta[t][q][0] = a, copied; theta[t][q][j] = theta_j.  mu = den(theta_hat); nll as there (the statistic of mu, then
+ *            the penalties j = 1 .. K ascending)
+ *   status[t][q] = the steps taken (low 8 bits) | NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR | NUSI_FIT_INFINITE |
+ *            NUSI_FIT_ZERO << j for every j >= 1 with theta_j == 0 | the halvings as there.  Component 0 never sets
+ *            NUSI_FIT_ZERO (a = 0 is an input, not an outcome); NUSI_FIT_FLAT and NUSI_FIT_BOUNDARY do not apply and are
+ *            never set
+ * (detector.fit_fixed_host is the same text in numpy).  Where it stopped by `stop` the fit's bound on the exact
+ * gradient holds for j >= 1 with the fit's constant.  scale [Q] is a host vector and is copied, like S and data; the
+ * outputs are as for nusi_plan_response_fit.  NUSI_ESTATE without a detector or without templates (that case is
+ * nusi_plan_response_events: nothing floats); NUSI_EPARAM as for the fit, and for scale == NULL or a scale that is
+ * negative or not finite. */
+int nusi_plan_response_fit_fixed(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab,
+                                 const double *S /* [Q][M] */, int Q, const double *scale /* [Q] */,
+                                 const double *data /* [C] */, double *d_theta /* [ntab][Q][1 + K] */,
+                                 double *d_nll /* [ntab][Q] or NULL */, double *d_mu /* [ntab][Q][C] or NULL */,
+                                 int *d_status /* [ntab][Q] or NULL */, void *stream);
+int nusi_plan_response_fit_fixed_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q,
+                                      const double *scale, const double *data, double *theta, double *nll, double *mu,
+                                      int *status);
+/* nusi_plan_response_limit (k_interval): profile-likelihood limits on the signal's scale.  With
+ *     lambda(a) = min_theta f(a, theta) - min f      (q(a) = 2 lambda(a))
+ * it returns, for every table t and spectrum q, the best fit and the roots a_lo < theta_hat_0 < a_hi of
+ * lambda(a) = delta / 2 -- delta = 2.706 for a one-sided 95 % limit, 1 for a 68 % interval -- on the sides `which` asks
+ * for (NUSI_LIMIT_LOWER | NUSI_LIMIT_UPPER).  lambda is convex in a (a partial minimum of a convex f), so Newton's iteration
+ * in a converges monotonically from the side where lambda > delta / 2 and reaches that side in one step from the other;
+ * its derivative is g_0 = S1_0 - S2_0 at the conditional optimum (the envelope theorem).  K = nusi_plan_templates(plan)
+ * may be 0.  Every operation but the log is +, -, *, /, a comparison, frexp or ldexp on IEEE doubles, each rounded
+ * separately, in a defined order (detector.limit_host is the same text in numpy); the log decides only through
+ * lambda's last bits.  With X, tree(), u, the priors and kappa as for nusi_plan_response_fit, hd = 0.5 delta:
+ *   best fit  the record of nusi_plan_response_fit (K = 0: of nusi_plan_response_profile, theta_hat = (ahat)), the same
+ *            operations in the same order: theta_hat, nll_hat, status[t][q][0] and mu_hat = its mu have those calls' bits
+ *   no fit   status[0] has NUSI_FIT_NOT_CONVERGED or NUSI_FIT_SINGULAR: both limits NaN, NUSI_LIMIT_NO_FIT, no step
+ *   no signal  S1_0 = tree(s) == 0: a_hi = +inf (NUSI_LIMIT_UNBOUNDED), a_lo = 0 (NUSI_LIMIT_UNBOUNDED | _AT_ZERO), no step
+ *   lact     bin c with data_c > 0 and mu_hat_c > 0 (a bin of NUSI_FIT_INFINITE is not: its mu is 0 at every a)
+ *   step0    w_c = data_c / mu_hat_c, r_c = w_c / mu_hat_c on lact bins, 0 elsewhere; S3 = tree((s_c r_c) s_c);
+ *            S3 > 0: step0 = 2^ceil(e / 2), delta / S3 = f 2^e with f in [1/2, 1) (frexp) -- the quadratic model's
+ *            distance sqrt(delta / S3) rounded up to a power of two;  else step0 = hd / S1_0
+ *   start    upper: a = theta_hat_0 + step0.  lower: theta_hat_0 == 0: a_lo = 0, NUSI_LIMIT_AT_ZERO, no step; else
+ *            a = theta_hat_0 - step0, and 0.5 theta_hat_0 if that is not > 0.  theta = (theta_hat_1 .. theta_hat_K)
+ *   zero_ok  no bin has data_c > 0, s_c > 0, B_c == 0 and no live template with T_jc > 0: such a bin's only support
+ *            is the signal, lambda(0) = +inf, and the lower search never evaluates a = 0
+ *   An outer step at a:
+ *   inner    the iteration of nusi_plan_response_fit_fixed at the held a, every rule of its text, started from theta
+ *            instead of its `start`; if that first eval is bad, from its `start` after all.  Each eval also forms
+ *            S2_0 = tree(s_c w_c), the last of the round's sums.  NUSI_FIT_NOT_CONVERGED or _SINGULAR of it:
+ *            NUSI_LIMIT_NOT_CONVERGED, stop.  Else theta = its result, one outer step counted, its Newton steps added
+ *            to the side's inner count; S2_0 is that of the last accepted eval.  K = 0: the one eval, no step
+ *   lambda   mu_c = den_c(a, theta) in the fit's order; dmu_c = mu_c - mu_hat_c; on lact bins ratio_c = mu_c /
+ *            mu_hat_c, l_c = log(ratio_c) (-inf where ratio_c is not > 0), p_c = data_c l_c, term_c = dmu_c - p_c,
+ *            mag_c = |dmu_c| + |p_c|; elsewhere term_c = dmu_c, mag_c = |dmu_c|;  lam = tree(term), mag = tree(mag);
+ *            then for j = 1 .. K ascending with w_j > 0: d_j = theta_j - theta_hat_j, s_j = (theta_j - m_j) +
+ *            (theta_hat_j - m_j), pd_j = ((0.5 w_j) d_j) s_j, lam = lam + pd_j, mag = mag + |pd_j|
+ *   h = lam - hd;  eps = (kappa_lambda u) (mag + hd), kappa_lambda = 2 (ceil(log2 C) + K) + 14;  g_0 = S1_0 - S2_0
+ *   at zero  (lower, a == 0)  h not > 0: a_lo = 0, NUSI_LIMIT_AT_ZERO, stop; else, unless the cap is reached, zero is
+ *            done, seen = false, a = 0.5 a_prev and on with the next outer step (no Newton step from zero: lambda is
+ *            log-steep there)
+ *   stop     |h| <= eps, or seen and h not > 0 (the monotone phase has met the noise of h): stop, converged
+ *   seen = h > 0
+ *   caps     NUSI_LIMIT_ITER_MAX outer steps taken, or g_0 not > 0 (upper; not < 0, lower): NUSI_LIMIT_NOT_CONVERGED, stop
+ *   step     a_new = a - h / g_0.  lower and a_new not > 0: seen = false, and a_new = 0 with a_prev = a if zero_ok and
+ *            zero is not done, else a_new = 0.5 a.  a_new not < +inf: NUSI_LIMIT_NOT_CONVERGED, stop.  a_new == a: stop,
+ *            converged.  Else a = a_new
+ *   The side's result is the last a.  Its word status[t][q][1] (lower), [2] (upper) = the outer steps (low 8 bits,
+ *   NUSI_LIMIT_STEPS_MASK) | the NUSI_LIMIT_* flags | the inner count, saturating at NUSI_LIMIT_INNER_MASK, <<
+ *   NUSI_LIMIT_INNER_SHIFT.  A side not asked for: NaN and a word of 0, and its pointer may be NULL.
+ * S, data and the ordering as for nusi_plan_response_fit; d_lo, d_hi, d_nll_hat [ntab][Q], d_theta_hat [ntab][Q][1 + K]
+ * (doubles) and d_status [ntab][Q][3] (ints) are DEVICE pointers; any may be NULL but the result of a side asked for.
+ * NUSI_ESTATE without a detector; NUSI_EPARAM as for the fit, and for a delta that is not finite or not > 0, `which`
+ * outside 1 .. 3, or a NULL result of a side asked for.  The _host form takes host arrays and is synchronous. */
+#define NUSI_LIMIT_LOWER 1
+#define NUSI_LIMIT_UPPER 2
+#define NUSI_LIMIT_ITER_MAX 64
+#define NUSI_LIMIT_STEPS_MASK 0xff
+#define NUSI_LIMIT_AT_ZERO 0x100
+#define NUSI_LIMIT_UNBOUNDED 0x200
+#define NUSI_LIMIT_NO_FIT 0x400
+#define NUSI_LIMIT_NOT_CONVERGED 0x800
+#define NUSI_LIMIT_INNER_SHIFT 16
+#define NUSI_LIMIT_INNER_MASK 0x7fff
+int nusi_plan_response_limit(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab, const double *S /* [Q][M] */,
+                             int Q, const double *data /* [C] */, double delta, int which,
+                             double *d_lo /* [ntab][Q] */, double *d_hi /* [ntab][Q] */,
+                             double *d_theta_hat /* [ntab][Q][1 + K] or NULL */, double *d_nll_hat /* [ntab][Q] or NULL */,
+                             int *d_status /* [ntab][Q][3] or NULL */, void *stream);
+int nusi_plan_response_limit_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
+                                  double delta, int which, double *lo, double *hi, double *theta_hat, double *nll_hat,
+                                  int *status);
 /* nusi_plan_response_ensemble (k_ensemble_profile, k_ensemble_fit, k_ensemble_best): P data sets data[p][C] -- an
  * ensemble of pseudo-experiments -- against every table and spectrum in ONE call, and of each (p, t) only the BEST
  * spectrum's record.  The front half s[t][q][c] = sum_n R[t][n][c] S[q][n] does not depend on the data: it is computed

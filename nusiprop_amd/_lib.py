@@ -31,6 +31,13 @@ FIT_FLAT, FIT_BOUNDARY, FIT_NOT_CONVERGED, FIT_INFINITE = 0x100, 0x200, 0x400, 0
 FIT_TEMPLATES_MAX = 3
 FIT_TRIALS_MAX = 64
 FIT_SINGULAR, FIT_ZERO, FIT_TRIALS_SHIFT, FIT_TRIALS_MASK = 0x1000, 0x10000, 24, 0x7F
+# Plan.limit (NUSI_LIMIT_*): the sides, the outer cap, and a side's status word: the outer steps in the low 8 bits, the flags,
+# the inner Newton steps (saturating) from bit 16
+LIMIT_LOWER, LIMIT_UPPER = 1, 2
+LIMIT_ITER_MAX = 64
+LIMIT_STEPS_MASK = 0xFF
+LIMIT_AT_ZERO, LIMIT_UNBOUNDED, LIMIT_NO_FIT, LIMIT_NOT_CONVERGED = 0x100, 0x200, 0x400, 0x800
+LIMIT_INNER_SHIFT, LIMIT_INNER_MASK = 16, 0x7FFF
 
 WARN_GAMMA = 1
 WARN_ALPHATILDE = 2
@@ -70,6 +77,8 @@ EXPORTS = [
     "nusi_plan_response_fold", "nusi_plan_response_fold_host", "nusi_plan_response_events",
     "nusi_plan_response_events_host", "nusi_plan_response_profile", "nusi_plan_response_profile_host",
     "nusi_plan_set_templates", "nusi_plan_templates", "nusi_plan_response_fit", "nusi_plan_response_fit_host",
+    "nusi_plan_response_fit_fixed", "nusi_plan_response_fit_fixed_host",
+    "nusi_plan_response_limit", "nusi_plan_response_limit_host",
     "nusi_plan_response_ensemble", "nusi_plan_response_ensemble_host",
 ]
 
@@ -156,6 +165,10 @@ def load():
         "nusi_plan_templates": (i, [vp]),
         "nusi_plan_response_fit": (i, [vp, vp, i, dp, i, dp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_fit_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, ip]),
+        "nusi_plan_response_fit_fixed": (i, [vp, vp, i, dp, i, dp, dp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_fit_fixed_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, dp, ip]),
+        "nusi_plan_response_limit": (i, [vp, vp, i, dp, i, dp, d, i, vp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_limit_host": (i, [vp, dp, i, dp, i, dp, d, i, dp, dp, dp, dp, ip]),
         "nusi_plan_response_ensemble": (i, [vp, vp, i, dp, i, dp, i, vp, vp, vp, vp, vp]),
         "nusi_plan_response_ensemble_host": (i, [vp, dp, i, dp, i, dp, i, ip, dp, dp, ip]),
     }

@@ -2110,6 +2110,82 @@ int nusi_plan_response_ensemble_host(nusi_plan* pl, const double* R, int ntab, c
                        });
 }
 
+// The conditional fit (nusi_detector.hip k_conditional_fit): the fit's templates with the signal's scale held.  The
+// scales ride in the slot events_stage has for the events call's.
+static int fit_fixed_plan(const nusi_plan* pl)
+{
+    if (int r = detector_plan(pl, "response fit_fixed")) return r;
+    if (!pl->fit_K) return fail(NUSI_ESTATE, "response fit_fixed: the plan has no templates (nusi_plan_set_templates; without them: nusi_plan_response_events)");
+    return NUSI_OK;
+}
+
+int nusi_plan_response_fit_fixed(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* scale,
+                                 const double* data, double* d_theta, double* d_nll, double* d_mu, int* d_status, void* stream)
+{
+    if (int r = fit_fixed_plan(pl)) return r;
+    if (!scale || !data || !d_theta) return fail(NUSI_EPARAM, "response fit_fixed: scale, data and theta must not be NULL");
+    EventsArgs a;
+    if (int r = events_begin(pl, "response fit_fixed", d_R, ntab, S, Q, scale, data, 1, stream, a)) return r;
+    HIPCHECK(nusi::launch_conditional_fit(pl->gd, d_R, ntab, a.S, Q, a.scale, a.data, a.bg, pl->det_C, pl->fit_K, pl->d_tpl,
+                                          pl->fit_m, pl->fit_w, d_theta, d_nll, d_mu, d_status, a.s));
+    return detector_mark(pl, a.s);
+}
+
+int nusi_plan_response_fit_fixed_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* scale,
+                                      const double* data, double* theta, double* nll, double* mu, int* status)
+{
+    if (int r = fit_fixed_plan(pl)) return r;
+    if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response fit_fixed: R must not be NULL, ntab and Q >= 1");
+    if (!scale || !data || !theta) return fail(NUSI_EPARAM, "response fit_fixed: scale, data and theta must not be NULL");
+    const size_t nn = (size_t)ntab * Q, nmu = nn * pl->det_C, nth = nn * (1 + pl->fit_K);
+    return events_host(pl, R, ntab,
+                       {{theta, nth, sizeof(double)}, {nll, nn, sizeof(double)}, {mu, nmu, sizeof(double)}, {status, nn, sizeof(int)}},
+                       "response fit_fixed", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_fit_fixed(pl, dI, ntab, S, Q, scale, data, (double*)d[0], (double*)d[1],
+                                                               (double*)d[2], (int*)d[3], nullptr);
+                       });
+}
+
+// The limits on the signal's scale (nusi_detector.hip k_interval): with or without templates.
+static int limit_check(const nusi_plan* pl, const double* data, double delta, int which, const void* lo, const void* hi)
+{
+    if (int r = detector_plan(pl, "response limit")) return r;
+    if (!data) return fail(NUSI_EPARAM, "response limit: data must not be NULL");
+    if (!std::isfinite(delta) || !(delta > 0.0)) return fail(NUSI_EPARAM, "response limit: delta must be finite and > 0");
+    if (which < 1 || which > 3) return fail(NUSI_EPARAM, "response limit: which outside NUSI_LIMIT_LOWER | NUSI_LIMIT_UPPER");
+    if (((which & NUSI_LIMIT_LOWER) && !lo) || ((which & NUSI_LIMIT_UPPER) && !hi))
+        return fail(NUSI_EPARAM, "response limit: the output of a side asked for is NULL");
+    return NUSI_OK;
+}
+
+int nusi_plan_response_limit(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data,
+                             double delta, int which, double* d_lo, double* d_hi, double* d_theta_hat, double* d_nll_hat,
+                             int* d_status, void* stream)
+{
+    if (int r = limit_check(pl, data, delta, which, d_lo, d_hi)) return r;
+    EventsArgs a;
+    if (int r = events_begin(pl, "response limit", d_R, ntab, S, Q, nullptr, data, 1, stream, a)) return r;
+    HIPCHECK(nusi::launch_detector_limit(pl->gd, d_R, ntab, a.S, Q, a.data, a.bg, pl->det_C, pl->fit_K, pl->d_tpl, pl->fit_m,
+                                         pl->fit_w, delta, which, d_lo, d_hi, d_theta_hat, d_nll_hat, d_status, a.s));
+    return detector_mark(pl, a.s);
+}
+
+int nusi_plan_response_limit_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
+                                  double delta, int which, double* lo, double* hi, double* theta_hat, double* nll_hat,
+                                  int* status)
+{
+    if (int r = limit_check(pl, data, delta, which, lo, hi)) return r;
+    if (!R || ntab < 1 || Q < 1) return fail(NUSI_EPARAM, "response limit: R must not be NULL, ntab and Q >= 1");
+    const size_t nn = (size_t)ntab * Q, nth = nn * (1 + pl->fit_K);
+    return events_host(pl, R, ntab,
+                       {{lo, nn, sizeof(double)}, {hi, nn, sizeof(double)}, {theta_hat, nth, sizeof(double)},
+                        {nll_hat, nn, sizeof(double)}, {status, 3 * nn, sizeof(int)}},
+                       "response limit", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_limit(pl, dI, ntab, S, Q, data, delta, which, (double*)d[0], (double*)d[1],
+                                                           (double*)d[2], (double*)d[3], (int*)d[4], nullptr);
+                       });
+}
+
 int nusi_plan_profile_begin(nusi_plan* pl, int max_calls)
 {
     HIPCHECK(hipSetDevice(pl->device));

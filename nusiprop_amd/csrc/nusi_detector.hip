@@ -1370,4 +1370,1051 @@ hipError_t launch_detector_ensemble(const GridDev& g, const double* R, int ntab,
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// k_conditional_fit<NC>: the statistic minimised over the NC = K templates' normalisations with the signal's scale HELD
+// at a given a[q] >= 0 (nusi_plan_response_fit_fixed): the background-only fit at a = 0, and the inner problem of the
+// statistic q(a) = 2 (min_theta f(a, theta) - min f) at any a.  It is k_detector_fit's damped Newton iteration on the
+// components 1 .. K alone, on that kernel's block shape -- lanes on (c, ONE spectrum), a round's NC + NC (NC + 1) / 2
+// sums in one det_butterfly, the logic after it redundant on a group's lanes, full exec in every butterfly -- with the
+// signal's term a s_c held in den: den_c = a s_c, + theta_j T_jc (j ascending), + B_c, the fit's order, so the
+// conditional mu at some theta has the bits the fit's mu has at (a, theta).  The body is COPIED from k_detector_fit,
+// operation for operation, and not shared (as the ensemble's is: the existing kernels keep their code objects); arrays
+// of the free components are indexed i = j - 1.  What differs is what include/nusi.h's text says differs: the support
+// rule counts the held signal (a > 0 and s_c > 0), the start shares the counts among the live templates only, nothing
+// is FLAT or BOUNDARY, and component 0 sets no ZERO bit.  LDS: k_detector_fit<1 + NC>'s, a row of mu [C] and
+// theta_1 .. theta_K per spectrum of the block: fit_lds_max(NC + 1) doubles.
+// ---------------------------------------------------------------------------
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) void k_conditional_fit(const double* __restrict__ R, const double* __restrict__ S,
+                                                                const double* __restrict__ scale,
+                                                                const double* __restrict__ data,
+                                                                const double* __restrict__ bg, const double* __restrict__ T,
+                                                                const FitPrior pr, const double ku,
+                                                                double* __restrict__ theta, double* __restrict__ nll,
+                                                                double* __restrict__ mu, int* __restrict__ status, int M,
+                                                                int C, int lgC, int Q)
+{
+#pragma clang fp contract(off)
+    constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major), j, k = 1 .. K
+    __shared__ double smu[fit_lds_max(NC + 1)];
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, qb0 = (int)blockIdx.y * QB, q = qb0 + grp;
+    const int cc = c < C ? c : C - 1, RS = fit_row(C, NC + 1);
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)(q < Q ? q : Q - 1) * M;
+    const bool in = c < C;
+    double X0, X[NC];
+    {
+        double s0 = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
+        X0 = in ? s0 : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) X[i] = in ? T[(size_t)i * C + cc] : 0.0;
+    const double b = in ? bg[cc] : 0.0, d = in ? data[cc] : 0.0;
+    const double a = scale[q < Q ? q : Q - 1];   // (uniform over the group)
+    const double asig = a * X0;                  // the held term of den
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+
+    double S1[NC];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) S1[i] = X[i];
+    det_butterfly(S1, lgC, add);
+    bool live[NC];
+    bool sup = b > 0.0 || (a > 0.0 && X0 > 0.0);
+    int nl = 0;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        live[i] = S1[i] > 0.0;
+        sup = sup || (live[i] && X[i] > 0.0);
+        nl += live[i] ? 1 : 0;
+    }
+    const bool act = d > 0.0 && sup;
+    double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
+    det_butterfly(dsum, lgC, add);
+    det_butterfly(dmin, lgC, min);
+    const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+    double th[NC], the[NC], p[NC];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        const double x = D0 / ((double)nl * S1[i]);
+        th[i] = live[i] ? x : 0.0;
+        the[i] = th[i];
+        p[i] = 0.0;
+    }
+    double tt = 1.0;
+    int st = 0, steps = 0, halv = 0, trials = 0;
+    bool run = true, first = true, quad = false;
+    // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
+    while (__any(run)) {
+        double v[NS];
+        double den = asig;
+#pragma unroll
+        for (int i = 0; i < NC; ++i) den = den + the[i] * X[i];
+        den = den + b;
+        const double wq0 = d / den;
+        const double wq = act ? wq0 : 0.0;
+        const double r0 = wq / den;
+        const double r = act ? r0 : 0.0;
+        {
+            int i = NC;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                v[j] = X[j] * wq;
+                const double xr = X[j] * r;
+#pragma unroll
+                for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
+            }
+        }
+        det_butterfly(v, lgC, add);
+        const bool bad = any(act && !(den > 0.0));
+        if (run) {
+            double g[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j + 1] * (the[j] - pr.m[j + 1]);
+            bool ok, changed = true;
+            if (first) {
+                ok = !bad;
+                if (!ok) {
+                    run = false;
+                    st |= NUSI_FIT_NOT_CONVERGED;
+                }
+            } else {
+                double slope = 0.0;
+#pragma unroll
+                for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
+                ok = !bad && (quad || !(slope > 0.0));
+                if (!ok) {
+                    if (trials == NUSI_FIT_TRIALS_MAX) {
+                        run = false;
+                        st |= NUSI_FIT_NOT_CONVERGED;
+                    } else {
+                        ++trials;
+                        ++halv;
+                        tt = tt * 0.5;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
+                    }
+                } else {
+                    changed = false;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
+                    ++steps;
+                }
+            }
+            if (ok) {
+                bool fs[NC], conv = true;
+#pragma unroll
+                for (int j = 0; j < NC; ++j) {
+                    th[j] = the[j];
+                    fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
+                    const double sc = (S1[j] + v[j]) + pr.w[j + 1] * (th[j] + pr.m[j + 1]);
+                    const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                    if (fs[j] && !(ag <= ku * sc)) conv = false;
+                }
+                if (conv) {
+                    run = false;
+                } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
+                    run = false;
+                    st |= NUSI_FIT_NOT_CONVERGED;
+                } else {
+                    first = false;
+                    // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
+                    // a component at zero that the direction pushes below leaves fs and the solve is repeated
+                    bool sing = false;
+#pragma unroll 1
+                    for (int rep = 0; rep <= NC; ++rep) {
+                        double Lm[NC][NC], Dg[NC], y[NC];
+                        sing = false;
+                        int i0 = NC;
+                        double h[NC][NC];
+#pragma unroll
+                        for (int j = 0; j < NC; ++j)
+#pragma unroll
+                            for (int k = j; k < NC; ++k) {
+                                const double hv = v[i0++] + (j == k ? pr.w[j + 1] : 0.0);
+                                h[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
+                            }
+#pragma unroll
+                        for (int i = 0; i < NC; ++i) {
+                            double cw[NC];
+#pragma unroll
+                            for (int j = 0; j < i; ++j) {
+                                double x = h[i][j];
+#pragma unroll
+                                for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                cw[j] = x;
+                                Lm[i][j] = x / Dg[j];
+                            }
+                            double x = h[i][i];
+#pragma unroll
+                            for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                            if (!(x > 0.0)) sing = true;
+                            Dg[i] = x;
+                        }
+#pragma unroll
+                        for (int i = 0; i < NC; ++i) {
+                            double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                            for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                            y[i] = x;
+                        }
+#pragma unroll
+                        for (int i = NC - 1; i >= 0; --i) {
+                            double x = y[i] / Dg[i];
+#pragma unroll
+                            for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
+                            p[i] = x;
+                        }
+                        if (sing) break;
+                        bool rm = false;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j)
+                            if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
+                                fs[j] = false;
+                                rm = true;
+                            }
+                        if (!rm) break;
+                    }
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j)
+                        if (fs[j]) acc = acc + g[j] * p[j];
+                    if (sing || !(acc < 0.0)) {
+                        run = false;
+                        st |= NUSI_FIT_SINGULAR;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) p[j] = 0.0;
+                    } else {
+                        double ratio[NC];
+                        tt = 1.0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) {
+                            const double x = th[j] / -p[j];
+                            ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
+                            if (ratio[j] < tt) tt = ratio[j];
+                        }
+                        const bool clipped = tt < 1.0;
+                        quad = !clipped && -acc <= dq;
+                        trials = 0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) {
+                            const double x = th[j] + tt * p[j];
+                            the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    double m = asig;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) m = m + th[i] * X[i];
+    m = m + b;
+#pragma unroll
+    for (int i = 0; i < NC; ++i)
+        if (th[i] == 0.0) st |= NUSI_FIT_ZERO << (i + 1);
+    if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
+    st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+    if (in) {
+        smu[grp * RS + c] = m;
+        if (mu && q < Q) mu[((size_t)t * Q + q) * C + c] = m;
+    }
+    if (c == 0) {
+#pragma unroll
+        for (int i = 0; i < NC; ++i) smu[grp * RS + C + i] = th[i];
+        if (q < Q) {
+            theta[((size_t)t * Q + q) * (NC + 1)] = a;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) theta[((size_t)t * Q + q) * (NC + 1) + 1 + i] = th[i];
+            if (status) status[(size_t)t * Q + q] = st;
+        }
+    }
+    if (!nll) return;   // (uniform)
+    __syncthreads();
+    // (a block owns QB <= kEvThreads spectra)
+    if (tid < QB && qb0 + tid < Q) {
+        double sum = 0.0;
+        for (int k = 0; k < C; ++k) {
+            const double mk = smu[tid * RS + k], dk = data[k];
+            double term = mk;
+            if (dk != 0.0) {
+                const double pl = dk * nm::log_i(mk);
+                term = mk - pl;
+            }
+            sum = sum + term;
+        }
+#pragma unroll
+        for (int i = 0; i < NC; ++i)
+            if (pr.w[i + 1] > 0.0) {
+                const double dl = smu[tid * RS + C + i] - pr.m[i + 1];
+                const double pen = ((0.5 * pr.w[i + 1]) * dl) * dl;
+                sum = sum + pen;
+            }
+        nll[(size_t)t * Q + qb0 + tid] = sum;
+    }
+}
+
+hipError_t launch_conditional_fit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* scale,
+                                  const double* data, const double* bg, int C, int K, const double* T, const double* pm,
+                                  const double* pw, double* theta, double* nll, double* mu, int* status, hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0) return hipSuccess;
+    const DetGeom ge(C, 1, ntab, Q);
+    FitPrior pr;
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
+        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
+        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
+    }
+    const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;   // kappa(C, K) u: den is as long as the fit's (include/nusi.h)
+    const dim3 grid = ge.grid, block(kEvThreads);
+    const int M = g.T + 1;
+    switch (K) {
+    case 1: hipLaunchKernelGGL((k_conditional_fit<1>), grid, block, 0, s, R, S, scale, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
+    case 2: hipLaunchKernelGGL((k_conditional_fit<2>), grid, block, 0, s, R, S, scale, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
+    case 3: hipLaunchKernelGGL((k_conditional_fit<3>), grid, block, 0, s, R, S, scale, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_interval<NC>: profile-likelihood limits on the signal's scale (nusi_plan_response_limit), NC = 1 + K = 1 .. 4, on
+// k_detector_fit's block shape: lanes on (c, ONE spectrum), every sum over the bins a det_butterfly over the group's
+// lanes, everything after it uniform over the group and done redundantly on its lanes.  Three parts:
+//   the best fit   k_detector_fit<NC>'s iteration (NC = 1: k_detector_profile's, one chain a lane), COPIED operation for
+//                  operation as the ensemble copies them, so theta_hat, nll_hat and the word are those calls' bits;
+//   the search     per side asked for, Newton's iteration in a on lambda(a) = delta / 2 (include/nusi.h): each outer step
+//                  runs k_conditional_fit's iteration at the held a, started from the step before's theta (K = 0: one
+//                  evaluation), with ONE sum more in the round's butterfly, S2_0 = tree(s_c w_c), which is the
+//                  derivative g_0 = S1_0 - S2_0 by the envelope theorem; then lambda from ratios, one nm::log_i on the
+//                  bin's own lane, and its magnitude in one butterfly of two.  Groups of a wave need different numbers
+//                  of outer and inner steps: a stopped chain skips the logic, the wave leaves a loop when none of its
+//                  chains runs, every butterfly runs with full exec.  No LDS and no barrier in here;
+//   the records    lo, hi and the side words, then the best fit's statistic through LDS as k_detector_fit forms it (mu
+//                  and theta_1 .. theta_K per spectrum of the block, one barrier, the serial sum): fit_lds_max(NC) doubles.
+// Arrays of the K floated templates are indexed i = j - 1 and sized max(K, 1).
+// ---------------------------------------------------------------------------
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) void k_interval(const double* __restrict__ R, const double* __restrict__ S,
+                                                         const double* __restrict__ data, const double* __restrict__ bg,
+                                                         const double* __restrict__ T, const FitPrior pr, const double ku,
+                                                         const double klu, const double delta, const int which,
+                                                         double* __restrict__ lo, double* __restrict__ hi,
+                                                         double* __restrict__ theta_hat, double* __restrict__ nll_hat,
+                                                         int* __restrict__ status, int M, int C, int lgC, int Q)
+{
+#pragma clang fp contract(off)
+    constexpr int KT = NC - 1, KA = KT > 0 ? KT : 1;
+    __shared__ double smu[fit_lds_max(NC)];
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, qb0 = (int)blockIdx.y * QB, q = qb0 + grp;
+    const int cc = c < C ? c : C - 1, RS = fit_row(C, NC);
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)(q < Q ? q : Q - 1) * M;
+    const bool in = c < C;
+    double X[NC];
+    {
+        double s0 = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
+        X[0] = in ? s0 : 0.0;
+    }
+#pragma unroll
+    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
+    const double b = in ? bg[cc] : 0.0, d = in ? data[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+
+    // ---- the best fit ------------------------------------------------------------------------------------------------
+    double thh[NC], S1h[NC], muh;
+    int sth;
+    if constexpr (NC == 1) {
+        // --- k_detector_profile's iteration, copied (one chain) ---
+        auto max = [](double x, double y) { return y > x ? y : x; };
+        const double s = X[0];
+        double S1[1] = {s}, a[1];
+        const bool act = d > 0.0 && s > 0.0;
+        det_butterfly(S1, lgC, add);
+        bool run = S1[0] != 0.0 && (__ballot(act) & gmask) != 0;
+        int st = run ? 0 : NUSI_FIT_FLAT;
+        {
+            const double x0 = d / S1[0], x1 = b / s;
+            a[0] = act ? x0 - x1 : 0.0;
+        }
+        det_butterfly(a, lgC, max);
+        a[0] = (run && a[0] > 0.0) ? a[0] : 0.0;
+        // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
+        while (__any(run)) {
+            double v[2];
+            {
+                double den = a[0] * s;
+                den = den + b;
+                const double qq = s / den;
+                const double u = act ? qq : 0.0;
+                const double r = d * u;
+                v[0] = r;
+                v[1] = r * u;
+            }
+            det_butterfly(v, lgC, add);
+            {
+                const double S2 = v[0], S3 = v[1];
+                const double g = S1[0] - S2;
+                const double dn = S2 - S1[0];
+                const double an = a[0] + dn / S3;
+                if (run) {
+                    ++st;
+                    if (!(g < 0.0)) {
+                        run = false;
+                        if (a[0] == 0.0) st |= NUSI_FIT_BOUNDARY;
+                    } else if (!(an > a[0])) {
+                        run = false;
+                    } else {
+                        a[0] = an;
+                        if ((st & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        }
+                    }
+                }
+            }
+        }
+        double m = a[0] * s;
+        m = m + b;
+        if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st |= NUSI_FIT_INFINITE;
+        thh[0] = a[0];
+        S1h[0] = S1[0];
+        muh = m;
+        sth = st;
+    } else {
+        // --- k_detector_fit's iteration, copied ---
+        constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
+        double S1[NC];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) S1[j] = X[j];
+        det_butterfly(S1, lgC, add);
+        bool live[NC];
+        live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
+        bool sup = b > 0.0;
+        int nl = 0;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            if (j > 0) live[j] = S1[j] > 0.0;
+            sup = sup || (live[j] && X[j] > 0.0);
+            nl += live[j] ? 1 : 0;
+        }
+        const bool act = d > 0.0 && sup;
+        double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
+        det_butterfly(dsum, lgC, add);
+        det_butterfly(dmin, lgC, min);
+        const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+        double th[NC], the[NC], p[NC];
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            const double x = D0 / ((double)nl * S1[j]);
+            th[j] = live[j] ? x : 0.0;
+            the[j] = th[j];
+            p[j] = 0.0;
+        }
+        double tt = 1.0;
+        int st = 0, steps = 0, halv = 0, trials = 0;
+        bool run = true, first = true, quad = false;
+        // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
+        while (__any(run)) {
+            double v[NS];
+            double den = the[0] * X[0];
+#pragma unroll
+            for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
+            den = den + b;
+            const double wq0 = d / den;
+            const double wq = act ? wq0 : 0.0;
+            const double r0 = wq / den;
+            const double r = act ? r0 : 0.0;
+            {
+                int i = NC;
+#pragma unroll
+                for (int j = 0; j < NC; ++j) {
+                    v[j] = X[j] * wq;
+                    const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
+#pragma unroll
+                    for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
+                }
+            }
+            det_butterfly(v, lgC, add);
+            const bool bad = any(act && !(den > 0.0));
+            if (run) {
+                double g[NC];
+#pragma unroll
+                for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
+                bool ok, changed = true;
+                if (first) {
+                    ok = !bad;
+                    if (!ok) {
+                        run = false;
+                        st |= NUSI_FIT_NOT_CONVERGED;
+                    }
+                } else {
+                    double slope = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
+                    ok = !bad && (quad || !(slope > 0.0));
+                    if (!ok) {
+                        if (trials == NUSI_FIT_TRIALS_MAX) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        } else {
+                            ++trials;
+                            ++halv;
+                            tt = tt * 0.5;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
+                        }
+                    } else {
+                        changed = false;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
+                        ++steps;
+                    }
+                }
+                if (ok) {
+                    bool fs[NC], conv = true;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) {
+                        th[j] = the[j];
+                        fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
+                        const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
+                        const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                        if (fs[j] && !(ag <= ku * scale)) conv = false;
+                    }
+                    if (conv) {
+                        run = false;
+                    } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
+                        run = false;
+                        st |= NUSI_FIT_NOT_CONVERGED;
+                    } else {
+                        first = false;
+                        // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
+                        // a component at zero that the direction pushes below leaves fs and the solve is repeated
+                        bool sing = false;
+#pragma unroll 1
+                        for (int rep = 0; rep <= NC; ++rep) {
+                            double Lm[NC][NC], Dg[NC], y[NC];
+                            sing = false;
+                            int i0 = NC;
+                            double a[NC][NC];
+#pragma unroll
+                            for (int j = 0; j < NC; ++j)
+#pragma unroll
+                                for (int k = j; k < NC; ++k) {
+                                    const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
+                                    a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
+                                }
+#pragma unroll
+                            for (int i = 0; i < NC; ++i) {
+                                double cw[NC];
+#pragma unroll
+                                for (int j = 0; j < i; ++j) {
+                                    double x = a[i][j];
+#pragma unroll
+                                    for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                    cw[j] = x;
+                                    Lm[i][j] = x / Dg[j];
+                                }
+                                double x = a[i][i];
+#pragma unroll
+                                for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                                if (!(x > 0.0)) sing = true;
+                                Dg[i] = x;
+                            }
+#pragma unroll
+                            for (int i = 0; i < NC; ++i) {
+                                double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                                for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                                y[i] = x;
+                            }
+#pragma unroll
+                            for (int i = NC - 1; i >= 0; --i) {
+                                double x = y[i] / Dg[i];
+#pragma unroll
+                                for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
+                                p[i] = x;
+                            }
+                            if (sing) break;
+                            bool rm = false;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j)
+                                if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
+                                    fs[j] = false;
+                                    rm = true;
+                                }
+                            if (!rm) break;
+                        }
+                        double acc = 0.0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j)
+                            if (fs[j]) acc = acc + g[j] * p[j];
+                        if (sing || !(acc < 0.0)) {
+                            run = false;
+                            st |= NUSI_FIT_SINGULAR;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) p[j] = 0.0;
+                        } else {
+                            double ratio[NC];
+                            tt = 1.0;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) {
+                                const double x = th[j] / -p[j];
+                                ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
+                                if (ratio[j] < tt) tt = ratio[j];
+                            }
+                            const bool clipped = tt < 1.0;
+                            quad = !clipped && -acc <= dq;
+                            trials = 0;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) {
+                                const double x = th[j] + tt * p[j];
+                                the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        double m = th[0] * X[0];
+#pragma unroll
+        for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
+        m = m + b;
+        if (!live[0])
+            st |= NUSI_FIT_FLAT;
+        else if (th[0] == 0.0)
+            st |= NUSI_FIT_BOUNDARY;
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+            if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
+        if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
+        st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            thh[j] = th[j];
+            S1h[j] = S1[j];
+        }
+        muh = m;
+        sth = st;
+    }
+
+    // ---- the search --------------------------------------------------------------------------------------------------
+    // (uniform values the search holds for long, moved to vector registers: the scalar file is the tight one here)
+    double pm_[KA], pw_[KA], ku_ = ku, klu_ = klu, hd = 0.5 * delta;
+#pragma unroll
+    for (int i = 0; i < KA; ++i) {
+        pm_[i] = i < KT ? pr.m[(i + 1) < NC ? i + 1 : 0] : 0.0;
+        pw_[i] = i < KT ? pr.w[(i + 1) < NC ? i + 1 : 0] : 0.0;
+        asm volatile("" : "+v"(pm_[i]), "+v"(pw_[i]));
+    }
+    asm volatile("" : "+v"(ku_), "+v"(klu_), "+v"(hd));
+    const double S10 = S1h[0], ahat = thh[0];
+    // The chain's long-lived flags are bits of ONE vector register: held as bools they are lane masks, a pair of scalar
+    // registers each, and with the inner iteration's own the kernel ran out of scalar registers (73 spilled at NC = 4).
+    enum { kLact = 1, kSupt = 2, kZeroOk = 4, kRun = 8, kSeen = 16, kZeroDone = 32, kRan = 64, kIRun = 1, kFirst = 2, kWarm = 4, kQuad = 8 };
+    int cf = (in && d > 0.0 && muh > 0.0) ? kLact : 0;   // kSupt: a live template supports the bin
+    int nl = 0;
+#pragma unroll
+    for (int i = 0; i < KT; ++i) {
+        if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) cf |= kSupt;
+        nl += S1h[i + 1] > 0.0 ? 1 : 0;
+    }
+    if (!any(d > 0.0 && X[0] > 0.0 && !(b > 0.0) && !(cf & kSupt))) cf |= kZeroOk;
+    double step;
+    {
+        const double wq0 = d / muh;
+        const double wq = (cf & kLact) ? wq0 : 0.0;
+        const double r0 = wq / muh;
+        const double rq = (cf & kLact) ? r0 : 0.0;
+        double S3[1] = {(X[0] * rq) * X[0]};
+        det_butterfly(S3, lgC, add);
+        // the quadratic model's step rounded up to a power of two: 2^ceil(e / 2), delta / S3 = f 2^e, f in [1/2, 1)
+        const int e = __builtin_amdgcn_frexp_exp(delta / S3[0]);   // frexp's exponent (0 for inf), no stack slot
+        const double pw2 = ldexp(1.0, ((e + 1025) >> 1) - 512);
+        const double lin = hd / S10;
+        step = S3[0] > 0.0 ? pw2 : lin;
+    }
+    constexpr int NI = 1 + KT + KT * (KT + 1) / 2;   // an inner round's sums: S2_j, H_jk (1 <= j <= k), then S2_0
+#pragma unroll 1
+    for (int side = 1; side >= 0; --side) {   // 1: the upper side, 0: the lower
+        const bool upper = side == 1;
+        const bool asked = (which & (upper ? NUSI_LIMIT_UPPER : NUSI_LIMIT_LOWER)) != 0;
+        double a = 0.0, res = __builtin_nan("");
+        int word = 0, fl = 0;
+        if (asked) {
+            if (sth & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
+                word = NUSI_LIMIT_NO_FIT;
+            } else if (S10 == 0.0) {
+                res = upper ? __builtin_inf() : 0.0;
+                word = upper ? NUSI_LIMIT_UNBOUNDED : (NUSI_LIMIT_UNBOUNDED | NUSI_LIMIT_AT_ZERO);
+            } else if (upper) {
+                a = ahat + step;
+                fl = kRun | kRan;
+            } else if (ahat == 0.0) {
+                res = 0.0;
+                word = NUSI_LIMIT_AT_ZERO;
+            } else {
+                a = ahat - step;
+                if (!(a > 0.0)) a = 0.5 * ahat;
+                fl = kRun | kRan;
+            }
+        }
+        double th[KA], aprev = a;
+#pragma unroll
+        for (int i = 0; i < KA; ++i) th[i] = i < KT ? thh[(i + 1) < NC ? i + 1 : 0] : 0.0;
+        int steps = 0, inner = 0, flags = 0;
+        // (every round of the outer loop ends a chain or counts a step towards NUSI_LIMIT_ITER_MAX)
+        while (__any((fl & kRun) != 0)) {
+            // --- k_conditional_fit's iteration at a, from th (the header's start where an active den is not > 0 there) ---
+            const double asig = a * X[0];
+            const bool sup = b > 0.0 || (cf & kSupt) || (a > 0.0 && X[0] > 0.0);
+            const bool act = d > 0.0 && sup;
+            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};
+            det_butterfly(dsum, lgC, add);
+            det_butterfly(dmin, lgC, min);
+            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+            double the[KA], p[KA], S20 = 0.0;
+#pragma unroll
+            for (int i = 0; i < KA; ++i) {
+                the[i] = th[i];
+                p[i] = 0.0;
+            }
+            double tt = 1.0;
+            int ist = 0, isteps = 0, trials = 0;
+            int il = ((fl & kRun) ? kIRun : 0) | kFirst | kWarm;   // (the inner chain's flags, bits as well)
+            while (__any((il & kIRun) != 0)) {
+                double v[NI];
+                double den = asig;
+#pragma unroll
+                for (int i = 0; i < KT; ++i) den = den + the[i] * X[i + 1];
+                den = den + b;
+                const double wq0 = d / den;
+                const double wq = act ? wq0 : 0.0;
+                const double r0 = wq / den;
+                const double r = act ? r0 : 0.0;
+                {
+                    int i = KT;
+#pragma unroll
+                    for (int j = 0; j < KT; ++j) {
+                        v[j] = X[j + 1] * wq;
+                        const double xr = X[j + 1] * r;
+#pragma unroll
+                        for (int k = j; k < KT; ++k) v[i++] = xr * X[k + 1];
+                    }
+                    v[NI - 1] = X[0] * wq;
+                }
+                det_butterfly(v, lgC, add);
+                const bool bad = any(act && !(den > 0.0));
+                if (il & kIRun) {
+                    double g[KA];
+#pragma unroll
+                    for (int j = 0; j < KT; ++j) g[j] = (S1h[j + 1] - v[j]) + pw_[j] * (the[j] - pm_[j]);
+                    bool ok, changed = true;
+                    if (il & kFirst) {
+                        ok = !bad;
+                        if (!ok) {
+                            if (il & kWarm) {
+                                il &= ~kWarm;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) {
+                                    const double x = D0 / ((double)nl * S1h[j + 1]);
+                                    th[j] = S1h[j + 1] > 0.0 ? x : 0.0;
+                                    the[j] = th[j];
+                                }
+                            } else {
+                                il &= ~kIRun;
+                                ist |= NUSI_FIT_NOT_CONVERGED;
+                            }
+                        }
+                    } else {
+                        double slope = 0.0;
+#pragma unroll
+                        for (int j = 0; j < KT; ++j) slope = slope + p[j] * g[j];
+                        ok = !bad && ((il & kQuad) || !(slope > 0.0));
+                        if (!ok) {
+                            if (trials == NUSI_FIT_TRIALS_MAX) {
+                                il &= ~kIRun;
+                                ist |= NUSI_FIT_NOT_CONVERGED;
+                            } else {
+                                ++trials;
+                                tt = tt * 0.5;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) the[j] = th[j] + tt * p[j];
+                            }
+                        } else {
+                            changed = false;
+#pragma unroll
+                            for (int j = 0; j < KT; ++j) changed = changed || the[j] != th[j];
+                            ++isteps;
+                        }
+                    }
+                    if (ok) {
+                        bool fs[KA], conv = true;
+                        S20 = v[NI - 1];
+#pragma unroll
+                        for (int j = 0; j < KT; ++j) {
+                            th[j] = the[j];
+                            fs[j] = S1h[j + 1] > 0.0 && (th[j] > 0.0 || g[j] < 0.0);
+                            const double sc = (S1h[j + 1] + v[j]) + pw_[j] * (th[j] + pm_[j]);
+                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                            if (fs[j] && !(ag <= ku_ * sc)) conv = false;
+                        }
+                        if (conv) {
+                            il &= ~kIRun;
+                        } else if ((!(il & kFirst) && !changed) || isteps == NUSI_FIT_ITER_MAX) {
+                            il &= ~kIRun;
+                            ist |= NUSI_FIT_NOT_CONVERGED;
+                        } else {
+                            il &= ~kFirst;
+                            bool sing = false;
+#pragma unroll 1
+                            for (int rep = 0; rep <= KT; ++rep) {
+                                double Lm[KA][KA], Dg[KA], y[KA];
+                                sing = false;
+                                int i0 = KT;
+                                double hm[KA][KA];
+#pragma unroll
+                                for (int j = 0; j < KT; ++j)
+#pragma unroll
+                                    for (int k = j; k < KT; ++k) {
+                                        const double hv = v[i0++] + (j == k ? pw_[j] : 0.0);
+                                        hm[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
+                                    }
+#pragma unroll
+                                for (int i = 0; i < KT; ++i) {
+                                    double cw[KA];
+#pragma unroll
+                                    for (int j = 0; j < i; ++j) {
+                                        double x = hm[i][j];
+#pragma unroll
+                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                        cw[j] = x;
+                                        Lm[i][j] = x / Dg[j];
+                                    }
+                                    double x = hm[i][i];
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                                    if (!(x > 0.0)) sing = true;
+                                    Dg[i] = x;
+                                }
+#pragma unroll
+                                for (int i = 0; i < KT; ++i) {
+                                    double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                                    y[i] = x;
+                                }
+#pragma unroll
+                                for (int i = KT - 1; i >= 0; --i) {
+                                    double x = y[i] / Dg[i];
+#pragma unroll
+                                    for (int k = i + 1; k < KT; ++k) x = x - Lm[k][i] * p[k];
+                                    p[i] = x;
+                                }
+                                if (sing) break;
+                                bool rm = false;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j)
+                                    if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
+                                        fs[j] = false;
+                                        rm = true;
+                                    }
+                                if (!rm) break;
+                            }
+                            double acc = 0.0;
+#pragma unroll
+                            for (int j = 0; j < KT; ++j)
+                                if (fs[j]) acc = acc + g[j] * p[j];
+                            if (sing || !(acc < 0.0)) {
+                                il &= ~kIRun;
+                                ist |= NUSI_FIT_SINGULAR;
+                            } else {
+                                double ratio[KA];
+                                tt = 1.0;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) {
+                                    const double x = th[j] / -p[j];
+                                    ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
+                                    if (ratio[j] < tt) tt = ratio[j];
+                                }
+                                const bool clipped = tt < 1.0;
+                                il = (!clipped && -acc <= dq) ? (il | kQuad) : (il & ~kQuad);
+                                trials = 0;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) {
+                                    const double x = th[j] + tt * p[j];
+                                    the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            // --- lambda(a) - delta / 2 from ratios, its magnitude, and the step in a ---
+            double mu = asig;
+#pragma unroll
+            for (int i = 0; i < KT; ++i) mu = mu + th[i] * X[i + 1];
+            mu = mu + b;
+            double lv[2];
+            {
+                const double dmu = mu - muh;
+                const double ratio = mu / muh;
+                const double lr = ratio > 0.0 ? nm::log_i(ratio) : -__builtin_inf();
+                const double pl = d * lr;
+                const double admu = dmu < 0.0 ? -dmu : dmu, apl = pl < 0.0 ? -pl : pl;
+                const double tl = dmu - pl, ml = admu + apl;
+                lv[0] = (cf & kLact) ? tl : dmu;
+                lv[1] = (cf & kLact) ? ml : admu;
+            }
+            det_butterfly(lv, lgC, add);
+            if (fl & kRun) {
+                inner += isteps;
+                if (ist & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
+                    flags |= NUSI_LIMIT_NOT_CONVERGED;
+                    fl &= ~kRun;
+                } else {
+                    ++steps;
+                    double lam = lv[0], mg = lv[1];
+#pragma unroll
+                    for (int j = 0; j < KT; ++j)
+                        if (pw_[j] > 0.0) {
+                            const double dj = th[j] - thh[(j + 1) < NC ? j + 1 : 0];
+                            const double sj = (th[j] - pm_[j]) + (thh[(j + 1) < NC ? j + 1 : 0] - pm_[j]);
+                            const double pd = ((0.5 * pw_[j]) * dj) * sj;
+                            lam = lam + pd;
+                            mg = mg + (pd < 0.0 ? -pd : pd);
+                        }
+                    const double h = lam - hd;
+                    const double eps = klu_ * (mg + hd);
+                    const double g0 = S10 - S20;
+                    const double ah = h < 0.0 ? -h : h;
+                    if (!upper && a == 0.0) {   // the one look at zero: the limit is there, or the search goes back
+                        if (!(h > 0.0)) {
+                            flags |= NUSI_LIMIT_AT_ZERO;
+                            fl &= ~kRun;
+                        } else if (steps == NUSI_LIMIT_ITER_MAX) {
+                            flags |= NUSI_LIMIT_NOT_CONVERGED;
+                            fl &= ~kRun;
+                        } else {
+                            fl = (fl | kZeroDone) & ~kSeen;
+                            a = 0.5 * aprev;
+                        }
+                    } else if (ah <= eps || ((fl & kSeen) && !(h > 0.0))) {
+                        fl &= ~kRun;
+                    } else {
+                        fl = h > 0.0 ? (fl | kSeen) : (fl & ~kSeen);
+                        if (steps == NUSI_LIMIT_ITER_MAX || !(upper ? g0 > 0.0 : g0 < 0.0)) {
+                            flags |= NUSI_LIMIT_NOT_CONVERGED;
+                            fl &= ~kRun;
+                        } else {
+                            double an = a - h / g0;
+                            if (!upper && !(an > 0.0)) {
+                                fl &= ~kSeen;
+                                if ((cf & kZeroOk) && !(fl & kZeroDone)) {
+                                    aprev = a;
+                                    an = 0.0;
+                                } else {
+                                    an = 0.5 * a;
+                                }
+                            }
+                            if (!(an < __builtin_inf())) {
+                                flags |= NUSI_LIMIT_NOT_CONVERGED;
+                                fl &= ~kRun;
+                            } else if (an == a) {
+                                fl &= ~kRun;
+                            } else {
+                                a = an;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (fl & kRan) {
+            res = a;
+            word = steps | flags | ((inner < NUSI_LIMIT_INNER_MASK ? inner : NUSI_LIMIT_INNER_MASK) << NUSI_LIMIT_INNER_SHIFT);
+        }
+        if (c == 0 && q < Q) {
+            double* out = upper ? hi : lo;
+            if (out) out[(size_t)t * Q + q] = res;
+            if (status) status[((size_t)t * Q + q) * 3 + (upper ? 2 : 1)] = word;
+        }
+    }
+
+    // ---- the records of the best fit -------------------------------------------------------------------------------------
+    if (in) smu[grp * RS + c] = muh;
+    if (c == 0) {
+#pragma unroll
+        for (int j = 1; j < NC; ++j) smu[grp * RS + C + j - 1] = thh[j];
+        if (q < Q) {
+            if (theta_hat)
+#pragma unroll
+                for (int j = 0; j < NC; ++j) theta_hat[((size_t)t * Q + q) * NC + j] = thh[j];
+            if (status) status[((size_t)t * Q + q) * 3] = sth;
+        }
+    }
+    if (!nll_hat) return;   // (uniform)
+    __syncthreads();
+    // (a block owns QB <= kEvThreads spectra)
+    if (tid < QB && qb0 + tid < Q) {
+        double sum = 0.0;
+        for (int k = 0; k < C; ++k) {
+            const double mk = smu[tid * RS + k], dk = data[k];
+            double term = mk;
+            if (dk != 0.0) {
+                const double pl = dk * nm::log_i(mk);
+                term = mk - pl;
+            }
+            sum = sum + term;
+        }
+#pragma unroll
+        for (int j = 1; j < NC; ++j)
+            if (pr.w[j] > 0.0) {
+                const double dl = smu[tid * RS + C + j - 1] - pr.m[j];
+                const double pen = ((0.5 * pr.w[j]) * dl) * dl;
+                sum = sum + pen;
+            }
+        nll_hat[(size_t)t * Q + qb0 + tid] = sum;
+    }
+}
+
+hipError_t launch_detector_limit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                                 const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
+                                 double delta, int which, double* lo, double* hi, double* theta_hat, double* nll_hat,
+                                 int* status, hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0) return hipSuccess;
+    const DetGeom ge(C, 1, ntab, Q);
+    FitPrior pr;
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
+        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
+        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
+    }
+    const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;    // kappa(C, K) u (include/nusi.h)
+    const double klu = (double)(2 * (ge.lg + K) + 14) * 0x1p-53;   // kappa_lambda(C, K) u
+    const dim3 grid = ge.grid, block(kEvThreads);
+    const int M = g.T + 1;
+    switch (K) {
+    case 0: hipLaunchKernelGGL((k_interval<1>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, lo, hi, theta_hat, nll_hat, status, M, C, ge.lg, Q); break;
+    case 1: hipLaunchKernelGGL((k_interval<2>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, lo, hi, theta_hat, nll_hat, status, M, C, ge.lg, Q); break;
+    case 2: hipLaunchKernelGGL((k_interval<3>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, lo, hi, theta_hat, nll_hat, status, M, C, ge.lg, Q); break;
+    case 3: hipLaunchKernelGGL((k_interval<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, lo, hi, theta_hat, nll_hat, status, M, C, ge.lg, Q); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace nusi

@@ -176,6 +176,18 @@ hipError_t launch_detector_ensemble(const GridDev& g, const double* R, int ntab,
                                     int P, const double* bg, int C, int K, const double* T, const double* pm,
                                     const double* pw, int qslices, int pslices, void* scratch, int* oq, double* onll,
                                     double* otheta, int* ostatus, hipStream_t s);
+// k_conditional_fit<K>: the fit's iteration on the K templates alone with the signal's scale held at scale [Q] (device
+// memory, entries >= 0): theta [ntab][Q][1 + K] (theta_0 = the scale, copied), nll, mu, status as the fit's
+hipError_t launch_conditional_fit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* scale,
+                                  const double* data, const double* bg, int C, int K, const double* T, const double* pm,
+                                  const double* pw, double* theta, double* nll, double* mu, int* status, hipStream_t s);
+// k_interval<1 + K>: the best fit (the profile's at K = 0, the fit's else) and the roots of lambda(a) = delta / 2 on the
+// sides `which` asks for (include/nusi.h): lo, hi, nll_hat [ntab][Q], theta_hat [ntab][Q][1 + K], status [ntab][Q][3] in
+// device memory; any may be nullptr (a side asked for must not be: the caller checks)
+hipError_t launch_detector_limit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
+                                 const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
+                                 double delta, int which, double* lo, double* hi, double* theta_hat, double* nll_hat,
+                                 int* status, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

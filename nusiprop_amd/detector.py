@@ -27,6 +27,14 @@ same for nusi_plan_response_fit, the fit that floats K background templates with
 
     toys = detector.pseudo_data(mu[0, 0], 1000, np.random.default_rng(1))   # (P, C) Poisson counts
     q, nll, theta, st = plan.ensemble(R, spectra, toys)                  # ensemble_host on the CPU: (P, ntab) records
+
+``fit_fixed_host`` is nusi_plan_response_fit_fixed, the fit with the signal's scale held and only the templates
+floating (the background-only fit at scale 0), and ``limit_host`` nusi_plan_response_limit: the best fit and the
+scales at which q(a) = 2 (min_theta f(a, theta) - min f) = delta, by Newton's iteration in a with a conditional fit per
+step -- both the header's text operation for operation::
+
+    theta0, nll0, mu0, st0 = plan.fit_fixed(R, spectra, 0.0, data=counts)     # fit_fixed_host on the CPU
+    lo, hi, theta_hat, nll_hat, st = plan.limit(R, spectra, counts, delta=2.706, which="upper")   # limit_host
 """
 import numpy as np
 
@@ -42,6 +50,13 @@ FIT_TRIALS_MAX = 64
 FIT_SINGULAR = 0x1000
 FIT_ZERO = 0x10000
 FIT_TRIALS_SHIFT, FIT_TRIALS_MASK = 24, 0x7F
+# the limits on the signal's scale (nusi_plan_response_limit): the sides asked for, the outer cap, and a side's status word:
+# the outer steps in the low 8 bits (LIMIT_STEPS_MASK), the flags, the inner Newton steps (saturating) from LIMIT_INNER_SHIFT
+LIMIT_LOWER, LIMIT_UPPER = 1, 2
+LIMIT_ITER_MAX = 64
+LIMIT_STEPS_MASK = 0xFF
+LIMIT_AT_ZERO, LIMIT_UNBOUNDED, LIMIT_NO_FIT, LIMIT_NOT_CONVERGED = 0x100, 0x200, 0x400, 0x800
+LIMIT_INNER_SHIFT, LIMIT_INNER_MASK = 16, 0x7FFF
 
 
 def gamma(K):
@@ -422,6 +437,333 @@ def fit_host(R, S, data, templates, prior=None, background=None, log=np.log):
             dl = theta[..., j] - m[j]
             nll = nll + ((0.5 * w[j]) * dl) * dl
     return _squeeze(one_tab, one_q, theta, nll, mu, status)
+
+
+def _fit_fixed_one(a, s, X, B, d, m, w, ku, start=None):
+    """One conditional fit of nusi_plan_response_fit_fixed: the signal s (C,) held at the scale a, X (K, C) the
+    templates (K = 0: none, a single evaluation), B, d (C,), m, w (K,) the templates' priors, ku = kappa u.  _fit_one's
+    text on the components 1 .. K with the header's differences.  start: None = the header's start; a list = the
+    limit's warm start (nusi_plan_response_limit: the start of the header if an active den is not > 0 there).  Returns
+    (theta_1 .. theta_K as a list, status, S2_0 = tree(s_c w_c) of the last accepted evaluation)."""
+    n, C = X.shape
+    a = float(a)
+    S1 = [float(v) for v in tree(X)]
+    live = [S1[j] > 0.0 for j in range(n)]
+    sup = B > 0
+    if a > 0.0:
+        sup = sup | (s > 0)
+    for j in range(n):
+        if live[j]:
+            sup = sup | (X[j] > 0)
+    act = (d > 0) & sup
+    D0 = float(tree(np.where(act, d, 0.0)))
+    dmin = min(1.0, float(np.min(np.where(act, d, 1.0))))
+    nl = float(sum(live))
+    m = [float(v) for v in m]
+    w = [float(v) for v in w]
+    cold = [(D0 / (nl * S1[j]) if live[j] else 0.0) for j in range(n)]
+    th = list(cold) if start is None else [float(v) for v in start]
+    warm = start is not None
+    the = list(th)
+    XX = [(j, k) for j in range(n) for k in range(j, n)]
+    JJ, KK = np.array([j for j, _ in XX], dtype=int), np.array([k for _, k in XX], dtype=int)
+    held = a * s
+    S20 = 0.0
+    flags, steps, halv = 0, 0, 0
+    first, p, t, quad, trials = True, [0.0] * n, 1.0, False, 0
+    while True:
+        den = held
+        for j in range(n):
+            den = den + the[j] * X[j]
+        den = den + B
+        bad = bool(np.any(act & ~(den > 0)))
+        wq = np.where(act, d / den, 0.0)
+        r = np.where(act, wq / den, 0.0)
+        xr = X * r
+        sums = tree(np.concatenate([X * wq, xr[JJ] * X[KK], (s * wq)[None]]))
+        S2 = [float(v) for v in sums[:n]]
+        g = [(S1[j] - S2[j]) + w[j] * (the[j] - m[j]) for j in range(n)]
+        changed = True
+        if first:
+            if bad and warm:                        # (the limit's warm start does not hold here: the header's start)
+                warm = False
+                th = list(cold)
+                the = list(cold)
+                continue
+            if bad:
+                flags |= FIT_NOT_CONVERGED
+                break
+        else:
+            slope = 0.0
+            for j in range(n):
+                slope = slope + p[j] * g[j]
+            if bad or not (quad or not slope > 0.0):
+                if trials == FIT_TRIALS_MAX:
+                    flags |= FIT_NOT_CONVERGED
+                    break
+                trials += 1
+                halv += 1
+                t = t * 0.5
+                the = [th[j] + t * p[j] for j in range(n)]
+                continue
+            changed = any(the[j] != th[j] for j in range(n))
+            steps += 1
+        th = list(the)
+        S20 = float(sums[-1])
+        free = [live[j] and (th[j] > 0.0 or g[j] < 0.0) for j in range(n)]
+        if all(abs(g[j]) <= ku * ((S1[j] + S2[j]) + w[j] * (th[j] + m[j])) for j in range(n) if free[j]):
+            break
+        if (not first and not changed) or steps == FIT_ITER_MAX:
+            flags |= FIT_NOT_CONVERGED
+            break
+        first = False
+        A = [[0.0] * n for _ in range(n)]
+        for i, (j, k) in enumerate(XX):
+            A[k][j] = float(sums[n + i]) + (w[j] if j == k else 0.0)
+        fs = list(free)
+        while True:
+            p, sing = _fit_solve(A, g, fs, n)
+            if sing:
+                break
+            rm = [fs[j] and th[j] == 0.0 and p[j] < 0.0 for j in range(n)]
+            if not any(rm):
+                break
+            fs = [fs[j] and not rm[j] for j in range(n)]
+        acc = 0.0
+        if not sing:
+            for j in range(n):
+                if fs[j]:
+                    acc = acc + g[j] * p[j]
+        if sing or not acc < 0.0:
+            flags |= FIT_SINGULAR
+            break
+        ratio = [(th[j] / -p[j] if (fs[j] and p[j] < 0.0) else 1.0) for j in range(n)]
+        t = 1.0
+        for j in range(n):
+            if ratio[j] < t:
+                t = ratio[j]
+        clipped = t < 1.0
+        quad = (not clipped) and -acc <= 0.0625 * dmin
+        trials = 0
+        the = [(0.0 if (clipped and fs[j] and p[j] < 0.0 and ratio[j] == t) else th[j] + t * p[j]) for j in range(n)]
+    for j in range(n):
+        if th[j] == 0.0:
+            flags |= FIT_ZERO << (j + 1)
+    return th, steps | flags | (min(halv, FIT_TRIALS_MASK) << FIT_TRIALS_SHIFT), S20
+
+
+def fit_fixed_host(R, S, scale, data, templates, prior=None, background=None, log=np.log):
+    """The conditional fit: fit_host with the signal's scale HELD at ``scale`` and only the K templates floating, by
+    the iteration nusi_plan_response_fit_fixed defines (include/nusi.h), operation for operation: theta, mu and status
+    agree with the GPU bit for bit and nll to the last bits of the log.  At scale 0 it is the background-only fit.
+
+    R, S, data, templates, prior, background, log: as for fit_host.  scale: a number or (Q,), finite and >= 0.  Returns
+    (theta (ntab, Q, 1 + K) with theta[..., 0] = scale, nll (ntab, Q), mu (ntab, Q, C), status (ntab, Q) int32): the
+    word of fit_host without FIT_FLAT, FIT_BOUNDARY and FIT_ZERO << 0, which are never set; the axes events_host
+    squeezes are squeezed here."""
+    s, data, one_tab, one_q = _signal("fit_fixed_host", R, S, data)
+    ntab, Q, C = s.shape
+    T = _templates(templates, C)
+    K = T.shape[0]
+    m, w = _prior(K, prior)
+    sc = np.array(np.broadcast_to(np.asarray(scale, dtype=np.float64), (Q,)))
+    if not np.all(np.isfinite(sc)) or np.any(sc < 0):
+        raise ValueError("fit_fixed_host: a scale is negative or not finite")
+    B = np.zeros(C) if background is None else np.array(np.broadcast_to(np.asarray(background, dtype=np.float64), (C,)))
+    ku = fit_kappa(C, K) * 2.0 ** -53
+    theta = np.zeros((ntab, Q, 1 + K))
+    status = np.zeros((ntab, Q), dtype=np.int32)
+    mu = np.zeros((ntab, Q, C))
+    with np.errstate(all="ignore"):
+        for t in range(ntab):
+            for q in range(Q):
+                th, st, _ = _fit_fixed_one(sc[q], s[t, q], T, B, data, m[1:], w[1:], ku)
+                theta[t, q, 0], theta[t, q, 1:], status[t, q] = sc[q], th, st
+                den = sc[q] * s[t, q]
+                for j in range(K):
+                    den = den + th[j] * T[j]
+                mu[t, q] = den + B
+    status[np.any((data > 0) & (mu == 0), axis=-1)] |= FIT_INFINITE
+    nll = poisson_host(mu, data, log=log)
+    for j in range(1, 1 + K):                                  # the penalties, ascending j, each operation rounded
+        if w[j] > 0:
+            dl = theta[..., j] - m[j]
+            nll = nll + ((0.5 * w[j]) * dl) * dl
+    return _squeeze(one_tab, one_q, theta, nll, mu, status)
+
+
+def limit_kappa(C, K):
+    """kappa_lambda(C, K) = 2 (ceil(log2 C) + K) + 14: the outer stop of nusi_plan_response_limit, |lambda - delta / 2|
+    <= kappa_lambda u (magnitudes) (include/nusi.h; derived in DESIGN.md sec. 4, "The conditional fit and limits on the
+    signal scale")."""
+    return 2 * (_ceil_log2(C) + K) + 14
+
+
+K_limit = limit_kappa
+
+
+def _limit_lambda(a, th, mu, muh, thh, lact, d, m, w, log):
+    """(lambda, its magnitude) of nusi_plan_response_limit at the conditional optimum (a, th) with counts mu, against the
+    best fit (thh, muh): the statistic from ratios, bin by bin, tree(), then the penalties' differences ascending."""
+    C = len(d)
+    term, mag = np.zeros(C), np.zeros(C)
+    for c in range(C):
+        dmu = float(mu[c]) - float(muh[c])
+        if lact[c]:
+            ratio = float(mu[c]) / float(muh[c])
+            lr = float(log(ratio)) if ratio > 0.0 else -np.inf
+            pl = float(d[c]) * lr
+            term[c], mag[c] = dmu - pl, abs(dmu) + abs(pl)
+        else:
+            term[c], mag[c] = dmu, abs(dmu)
+    lam, mg = float(tree(term)), float(tree(mag))
+    for j in range(len(th)):
+        if w[j] > 0:
+            dj = th[j] - thh[j]
+            sj = (th[j] - m[j]) + (thh[j] - m[j])
+            pd = ((0.5 * w[j]) * dj) * sj
+            lam = lam + pd
+            mg = mg + abs(pd)
+    return lam, mg
+
+
+def _limit_side(upper, a, zero_ok, s, X, B, d, m, w, ku, klu, hd, S10, muh, thh, lact, log):
+    """One side's search of nusi_plan_response_limit from the start a: Newton's iteration in a on lambda(a) = delta / 2,
+    a conditional fit per step started from the one before.  zero_ok: the lower side may evaluate a = 0.  Returns (a,
+    the side's status word, the last h, eps, g0)."""
+    th = [float(v) for v in thh]
+    steps, inner, flags, seen, zero_done, aprev = 0, 0, 0, False, False, a
+    h = eps = g0 = float("nan")
+    while True:
+        th, ist, S20 = _fit_fixed_one(a, s, X, B, d, m, w, ku, start=th)
+        inner += ist & FIT_STEPS_MASK
+        if ist & (FIT_NOT_CONVERGED | FIT_SINGULAR):
+            flags |= LIMIT_NOT_CONVERGED
+            break
+        steps += 1
+        mu = a * s
+        for j in range(len(th)):
+            mu = mu + th[j] * X[j]
+        mu = mu + B
+        lam, mg = _limit_lambda(a, th, mu, muh, thh, lact, d, m, w, log)
+        h = lam - hd
+        eps = klu * (mg + hd)
+        g0 = S10 - S20
+        if not upper and a == 0.0:                  # the one look at zero: the limit is there, or the search goes back
+            if not h > 0.0:
+                flags |= LIMIT_AT_ZERO
+                break
+            if steps == LIMIT_ITER_MAX:
+                flags |= LIMIT_NOT_CONVERGED
+                break
+            zero_done, seen, a = True, False, 0.5 * aprev
+            continue
+        if abs(h) <= eps or (seen and not h > 0.0):
+            break
+        seen = h > 0.0
+        if steps == LIMIT_ITER_MAX:
+            flags |= LIMIT_NOT_CONVERGED
+            break
+        if not (g0 > 0.0 if upper else g0 < 0.0):
+            flags |= LIMIT_NOT_CONVERGED
+            break
+        an = a - h / g0
+        if not upper and not an > 0.0:
+            seen = False
+            if zero_ok and not zero_done:
+                aprev, an = a, 0.0
+            else:
+                an = 0.5 * a
+        if not an < np.inf:
+            flags |= LIMIT_NOT_CONVERGED
+            break
+        if an == a:
+            break
+        a = an
+    return a, steps | flags | (min(inner, LIMIT_INNER_MASK) << LIMIT_INNER_SHIFT), h, eps, g0
+
+
+def limit_host(R, S, data, delta, which="upper", templates=None, prior=None, background=None, log=np.log, details=None):
+    """Profile-likelihood limits on the signal's scale, by the search nusi_plan_response_limit defines (include/nusi.h),
+    operation for operation: for every table and spectrum the best fit (fit_host; profile_host without templates), and
+    the roots a_lo < theta_hat_0 < a_hi of lambda(a) = delta / 2, lambda(a) = min_theta f(a, theta) - min f -- so that
+    q(a) = 2 lambda(a) = delta: delta = 2.706 for a one-sided 95 % limit, 1 for a 68 % interval.
+
+    R, S, data, templates (None: K = 0), prior, background, log: as for fit_host.  delta: a finite number > 0.  which:
+    "upper", "lower" or "both" (LIMIT_UPPER, LIMIT_LOWER or their sum).  Returns (lo (ntab, Q), hi (ntab, Q), theta_hat
+    (ntab, Q, 1 + K), nll_hat (ntab, Q), status (ntab, Q, 3) int32): the best fit's word, then the lower and the upper
+    side's -- the outer steps in the low 8 bits, the LIMIT_* flags, the inner Newton steps of all the side's
+    conditional fits (saturating at LIMIT_INNER_MASK) from bit LIMIT_INNER_SHIFT.  A side not asked for is NaN with a word
+    of 0.  details: None, or a dict that receives 'h', 'eps' and 'g0' (ntab, Q, 2): each side's last lambda - delta / 2,
+    its stop's allowance and the derivative there (the tests' bounds), squeezed like the results.  The squeezed axes of events_host are squeezed."""
+    s, data, one_tab, one_q = _signal("limit_host", R, S, data)
+    ntab, Q, C = s.shape
+    wh = {"lower": LIMIT_LOWER, "upper": LIMIT_UPPER, "both": LIMIT_LOWER | LIMIT_UPPER}.get(which, which)
+    if wh not in (1, 2, 3):
+        raise ValueError("limit_host: which must be 'upper', 'lower' or 'both'")
+    delta = float(delta)
+    if not np.isfinite(delta) or not delta > 0:
+        raise ValueError("limit_host: delta must be finite and > 0")
+    K = 0 if templates is None else _templates(templates, C).shape[0]
+    T = np.zeros((0, C)) if K == 0 else _templates(templates, C)
+    m, w = _prior(K, prior)
+    B = np.zeros(C) if background is None else np.array(np.broadcast_to(np.asarray(background, dtype=np.float64), (C,)))
+    if K:
+        thh, nllh, muh, sth = fit_host(R, S, data, T, prior=prior, background=B, log=log)
+    else:
+        ah, nllh, muh, sth = profile_host(R, S, data, background=B, log=log)
+        thh = np.asarray(ah)[..., None]
+    thh, nllh = np.reshape(thh, (ntab, Q, 1 + K)), np.reshape(nllh, (ntab, Q))
+    muh, sth = np.reshape(muh, (ntab, Q, C)), np.reshape(sth, (ntab, Q))
+    ku, klu, hd = fit_kappa(C, K) * 2.0 ** -53, limit_kappa(C, K) * 2.0 ** -53, 0.5 * delta
+    lo, hi = np.full((ntab, Q), np.nan), np.full((ntab, Q), np.nan)
+    status = np.zeros((ntab, Q, 3), dtype=np.int32)
+    status[..., 0] = sth
+    det = {k: np.full((ntab, Q, 2), np.nan) for k in ("h", "eps", "g0")}
+    sup_t = np.zeros(C, dtype=bool)                 # a live template supports the bin (a template is never all zeros)
+    for j in range(K):
+        sup_t |= T[j] > 0
+    with np.errstate(all="ignore"):
+        for t in range(ntab):
+            for q in range(Q):
+                x0, ahat = s[t, q], float(thh[t, q, 0])
+                S10 = float(tree(x0))
+                if sth[t, q] & (FIT_NOT_CONVERGED | FIT_SINGULAR):
+                    if wh & LIMIT_LOWER:
+                        status[t, q, 1] = LIMIT_NO_FIT
+                    if wh & LIMIT_UPPER:
+                        status[t, q, 2] = LIMIT_NO_FIT
+                    continue
+                if S10 == 0.0:
+                    if wh & LIMIT_LOWER:
+                        lo[t, q], status[t, q, 1] = 0.0, LIMIT_UNBOUNDED | LIMIT_AT_ZERO
+                    if wh & LIMIT_UPPER:
+                        hi[t, q], status[t, q, 2] = np.inf, LIMIT_UNBOUNDED
+                    continue
+                mh = muh[t, q]
+                lact = (data > 0) & (mh > 0)
+                wq = np.where(lact, data / mh, 0.0)
+                rq = np.where(lact, wq / mh, 0.0)
+                S3 = float(tree((x0 * rq) * x0))
+                args = (x0, T, B, data, m[1:], w[1:], ku, klu, hd, S10, mh, thh[t, q, 1:], lact, log)
+                # the quadratic model's step, rounded up to a power of two: 2^ceil(e / 2) for delta / S3 = f 2^e, f in [1/2, 1)
+                step = float(np.ldexp(1.0, (int(np.frexp(delta / S3)[1]) + 1025) // 2 - 512)) if S3 > 0.0 else hd / S10
+                if wh & LIMIT_UPPER:
+                    hi[t, q], status[t, q, 2], det["h"][t, q, 1], det["eps"][t, q, 1], det["g0"][t, q, 1] = _limit_side(
+                        True, ahat + step, False, *args)
+                if wh & LIMIT_LOWER:
+                    if ahat == 0.0:
+                        lo[t, q], status[t, q, 1] = 0.0, LIMIT_AT_ZERO
+                    else:
+                        sigonly = bool(np.any((data > 0) & (x0 > 0) & ~(B > 0) & ~sup_t))
+                        a = ahat - step
+                        if not a > 0.0:
+                            a = 0.5 * ahat
+                        lo[t, q], status[t, q, 1], det["h"][t, q, 0], det["eps"][t, q, 0], det["g0"][t, q, 0] = _limit_side(
+                            False, a, not sigonly, *args)
+    if details is not None:
+        details.update({k: _squeeze(one_tab, one_q, v)[0] for k, v in det.items()})
+    return _squeeze(one_tab, one_q, lo, hi, thh, nllh, status)
 
 
 def argbest(nll, axis=-1):

@@ -388,6 +388,96 @@ class Plan:
         return self._minimise_device("fit", d_R_ptr, ntab, spectra, data, d_theta_ptr, d_nll_ptr, d_mu_ptr, d_status_ptr,
                                      stream_ptr)
 
+    def _held(self, who, scale, Q):
+        if scale is None:
+            raise ValueError("%s: the held scale is required (a number or (Q,))" % who)
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (Q,)))
+
+    def fit_fixed(self, R, spectra, scale, data):
+        """The conditional fit on the GPU: ``fit`` with the signal's scale HELD at ``scale`` (a number, or (Q,) one per
+        spectrum, >= 0) and only the templates' normalisations floating -- the background-only fit at scale 0, and
+        the inner minimum of the statistic q(a) = 2 (min_theta f(a, theta) - min f) at any a.  Returns (theta
+        (ntab, Q, 1 + K) with theta[..., 0] = scale, nll (ntab, Q), mu (ntab, Q, C), status (ntab, Q) int32) as ``fit``
+        does; the status word holds the steps, FIT_NOT_CONVERGED, FIT_SINGULAR, FIT_INFINITE, FIT_ZERO << j for a
+        template that ends at zero and the halvings -- never FIT_FLAT, FIT_BOUNDARY or FIT_ZERO << 0.  theta, mu and
+        status equal detector.fit_fixed_host bit for bit, and mu has the bits ``fit``'s mu has at the same theta."""
+        R, C = self._folded(R, "fit_fixed")
+        S, _ = self._spectra(spectra, None)
+        sc = self._held("fit_fixed", scale, len(S))
+        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
+        ntab, Q = R.shape[0], len(S)
+        theta, nll, mu = np.zeros((ntab, Q, 1 + self.templates())), np.zeros((ntab, Q)), np.zeros((ntab, Q, C))
+        status = np.zeros((ntab, Q), dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_fit_fixed_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, sc.ctypes.data_as(dp),
+            d.ctypes.data_as(dp) if d is not None else None, theta.ctypes.data_as(dp), nll.ctypes.data_as(dp),
+            mu.ctypes.data_as(dp), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return theta, nll, mu, status
+
+    def fit_fixed_device(self, d_R_ptr, ntab, spectra, scale, data, d_theta_ptr, d_nll_ptr=None, d_mu_ptr=None,
+                         d_status_ptr=None, stream_ptr=None):
+        """Asynchronous conditional fit on device-resident folded matrices: the pointers as for ``fit_device``; the
+        spectra, the held scales and the data are host data and are copied.  Returns Q."""
+        S, _ = self._spectra(spectra, None)
+        sc = self._held("fit_fixed_device", scale, len(S))
+        d = self._data(data)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_response_fit_fixed(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), sc.ctypes.data_as(dp),
+            d.ctypes.data_as(dp) if d is not None else None, vp(d_theta_ptr) if d_theta_ptr else None,
+            vp(d_nll_ptr) if d_nll_ptr else None, vp(d_mu_ptr) if d_mu_ptr else None,
+            vp(d_status_ptr) if d_status_ptr else None, vp(stream_ptr) if stream_ptr else None))
+        return len(S)
+
+    @staticmethod
+    def _which(which):
+        w = {"lower": _lib.LIMIT_LOWER, "upper": _lib.LIMIT_UPPER, "both": _lib.LIMIT_LOWER | _lib.LIMIT_UPPER}.get(which, which)
+        return int(w)
+
+    def limit(self, R, spectra, data, delta, which="upper"):
+        """Profile-likelihood limits on the signal's scale on the GPU: for every table and spectrum the best fit
+        (``fit``'s record; ``profile``'s on a plan without templates) and the roots a_lo < theta_hat_0 < a_hi of
+        q(a) = 2 (min_theta f(a, theta) - min f) = delta -- delta = 2.706 for a one-sided 95 % upper limit, 1 for a 68 %
+        interval -- found inside one kernel: the signal counts are computed once, and the search costs only its own
+        arithmetic.  which: "upper", "lower" or "both".  Returns (lo (ntab, Q), hi (ntab, Q), theta_hat (ntab, Q, 1 + K),
+        nll_hat (ntab, Q), status (ntab, Q, 3) int32): the best fit's word (bit for bit ``fit``'s or ``profile``'s, like
+        theta_hat and nll_hat), then the lower and the upper side's: the outer steps in the low 8 bits, _lib.LIMIT_AT_ZERO
+        (a_lo = 0: the statistic at zero is within delta), LIMIT_UNBOUNDED (no signal counts: a_hi = +inf),
+        LIMIT_NO_FIT (the best fit failed: NaN), LIMIT_NOT_CONVERGED, and the inner Newton steps from bit
+        LIMIT_INNER_SHIFT.  A side not asked for is NaN with a word of 0.  detector.limit_host is the same search in
+        numpy."""
+        R, C = self._folded(R, "limit")
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
+        ntab, Q = R.shape[0], len(S)
+        lo, hi = np.full((ntab, Q), np.nan), np.full((ntab, Q), np.nan)
+        theta, nll = np.zeros((ntab, Q, 1 + self.templates())), np.zeros((ntab, Q))
+        status = np.zeros((ntab, Q, 3), dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_limit_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp) if d is not None else None,
+            float(delta), self._which(which), lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), theta.ctypes.data_as(dp),
+            nll.ctypes.data_as(dp), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return lo, hi, theta, nll, status
+
+    def limit_device(self, d_R_ptr, ntab, spectra, data, delta, which, d_lo_ptr, d_hi_ptr, d_theta_hat_ptr=None,
+                     d_nll_hat_ptr=None, d_status_ptr=None, stream_ptr=None):
+        """Asynchronous limits on device-resident folded matrices: d_R [ntab][M][C], d_lo, d_hi and d_nll_hat [ntab][Q],
+        d_theta_hat [ntab][Q][1 + K] (doubles) and d_status [ntab][Q][3] (ints) are raw pointers; any may be 0 / None
+        but the result of a side asked for; the spectra and data are host data and are copied.  Returns Q."""
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_response_limit(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None,
+            float(delta), self._which(which), vp(d_lo_ptr) if d_lo_ptr else None, vp(d_hi_ptr) if d_hi_ptr else None,
+            vp(d_theta_hat_ptr) if d_theta_hat_ptr else None, vp(d_nll_hat_ptr) if d_nll_hat_ptr else None,
+            vp(d_status_ptr) if d_status_ptr else None, vp(stream_ptr) if stream_ptr else None))
+        return len(S)
+
     def _datasets(self, datasets):
         d = np.ascontiguousarray(datasets, dtype=np.float64)
         if d.ndim == 1:
