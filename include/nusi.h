@@ -525,6 +525,64 @@ int nusi_plan_response_ensemble(nusi_plan *plan, const double *d_R /* [ntab][M][
                                 void *stream);
 int nusi_plan_response_ensemble_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q,
                                      const double *data, int P, int *q, double *nll, double *theta, int *status);
+/* nusi_plan_response_ensemble_limit (k_toys_limit, k_toys_band): the limits of nusi_plan_response_limit for P data sets
+ * data[p][C] -- an ensemble of pseudo-experiments -- in ONE call, and of each (table, spectrum) the order statistics of
+ * its P limits: the median expected limit and its bands, when the toys are background-only.  The front half
+ * s[t][q][c] = sum_n R[t][n][c] S[q][n] does not depend on the data: it is computed once and the P searches run on it.
+ * K = nusi_plan_templates(plan) = 0 .. 3.
+ *
+ * The record of (p, t, q) is exactly what nusi_plan_response_limit gives for table t and spectrum q against data[p]
+ * with the same delta and `which`: lo, hi and the two side words (that call's status[t][q][1] and [2]).  The same
+ * operations in the same order, the device log included: that call's bits.  It depends on no other table, spectrum or
+ * data set of the call.
+ *
+ * The band.  Per side asked for and per (t, q): the order statistics of the P limits under the key
+ *     (isnan(x), x)   ascending, x compared as a number:
+ * band[t][q][k] is the value v that has at most rank[k] entries before it under the key and more than rank[k] entries
+ * before or equal to it -- entry rank[k] of the sorted limits.  NaN (NUSI_LIMIT_NO_FIT) sorts after everything, +inf
+ * (NUSI_LIMIT_UNBOUNDED) included.  A side's limits are never -0.0, so equal keys are equal bits and the result does
+ * not depend on how the selection is arranged.  A NUSI_LIMIT_NOT_CONVERGED record enters with its last a, as a number;
+ * the tally says how many there are.  rank [NR] are host ints, 0 <= rank[k] < P, duplicates allowed, NR = 0 ..
+ * NUSI_BAND_RANKS_MAX; P = 1 .. NUSI_BAND_DATASETS_MAX.
+ *
+ * The tally.  tally[t][q][side][4] (ints; side 0 = lower, 1 = upper) counts the toys whose side word carries
+ * NUSI_LIMIT_AT_ZERO, _UNBOUNDED, _NO_FIT and _NOT_CONVERGED, in that order.
+ *
+ * Outputs, all DEVICE pointers: d_band_lo, d_band_hi [ntab][Q][NR] (doubles), d_tally [ntab][Q][2][4] (ints), and the
+ * raw records d_lo_all, d_hi_all [ntab][Q][P] (doubles) and d_words_all [ntab][Q][P][2] (ints; [..][0] the lower side's
+ * word, [1] the upper's), the toy index fastest: the layout the selection reads.  Any may be NULL, except that NR > 0
+ * needs the band of every side asked for.  A side not asked for: NaN bands and raw limits where a pointer is given, a
+ * tally of 0 and raw words of 0.  The best fits are not returned per toy: nusi_plan_response_ensemble has them.
+ *
+ * Scratch and the grid.  Where a side's raw array is not given and NR > 0, its P limits per spectrum live in scratch
+ * owned by the plan, at most NUSI_OPT_ENSEMBLE_LIMIT_MB (below).  The work is cut into units of one table and one
+ * block of QB = 256 >> ceil(log2 C) spectra; a unit takes QB P 8 bytes of scratch per side kept there, and the call runs
+ * in chunks of as many units as fit, each chunk a launch of k_toys_limit and one of k_toys_band on the call's stream.  A
+ * budget below one unit is refused.  Whatever the budget, and also with the raw arrays given, a chunk holds at most
+ * 2^22 spectra, so that no launch exceeds the grid a device accepts.  Inside a chunk the data sets are split into p-slices (the grid's z): automatic --
+ * as many as fill the card, of at least 16 data sets each --, or NUSI_OPT_ENSEMBLE_PSLICES > 0: min(that, P); a
+ * p-slice repeats the front half, writes its own section of [P] and adds its tallies (integer adds commute).
+ * NUSI_OPT_ENSEMBLE_QSLICES does not apply.  Every budget and every slicing give the same bits.
+ *
+ * S [Q][M], data [P][C] and rank are host arrays and are copied.  Asynchronous and ordered with the plan's other
+ * detector calls like nusi_plan_response_fit.  NUSI_ESTATE without a detector; NUSI_EPARAM for a NULL d_R, S or data,
+ * a NULL rank with NR > 0, P, NR or a rank out of range, ntab < 1, Q outside 1 .. 2^19, a delta that is not finite or
+ * not > 0, `which` outside 1 .. 3, a negative or non-finite entry of S or data, NR > 0 without the band of a side asked
+ * for, NR = 0 with no tally and no raw output (nothing to do), or a budget too small for one unit; a refused call
+ * changes nothing.  _host: R and the outputs in host memory, synchronous. */
+#define NUSI_BAND_RANKS_MAX 16
+#define NUSI_BAND_DATASETS_MAX 4096
+int nusi_plan_response_ensemble_limit(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab,
+                                      const double *S /* [Q][M] */, int Q, const double *data /* [P][C] */, int P,
+                                      double delta, int which, const int *rank /* [NR] */, int NR,
+                                      double *d_band_lo /* [ntab][Q][NR] */, double *d_band_hi /* [ntab][Q][NR] */,
+                                      int *d_tally /* [ntab][Q][2][4] or NULL */, double *d_lo_all /* [ntab][Q][P] or NULL */,
+                                      double *d_hi_all /* [ntab][Q][P] or NULL */,
+                                      int *d_words_all /* [ntab][Q][P][2] or NULL */, void *stream);
+int nusi_plan_response_ensemble_limit_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q,
+                                           const double *data, int P, double delta, int which, const int *rank, int NR,
+                                           double *band_lo, double *band_hi, int *tally, double *lo_all, double *hi_all,
+                                           int *words_all);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);
@@ -672,6 +730,21 @@ int nusi_plan_set_cascade(nusi_plan *plan, int kind);
  *                          bits. */
 #define NUSI_OPT_ENSEMBLE_QSLICES 13
 #define NUSI_OPT_ENSEMBLE_PSLICES 14
+/*   NUSI_OPT_ENSEMBLE_LIMIT_MB  the scratch of nusi_plan_response_ensemble_limit
+ *                          (a spectrum's P limits per side whose raw array
+ *                          the caller does not give): at most this many MiB,
+ *                          the call runs in chunks of (table, spectrum block)
+ *                          units that fit; 0 = 256.  A budget below one unit
+ *                          (QB P 8 bytes per such side) makes the call fail
+ *                          with NUSI_EPARAM.  Any value gives the same bits.
+ *   NUSI_OPT_ENSEMBLE_LIMIT_BYTES  the same budget in bytes, up to 2^30 (> 0:
+ *                          it holds instead of NUSI_OPT_ENSEMBLE_LIMIT_MB):
+ *                          for calls whose units are far smaller than a MiB
+ *                          (a unit at C = 64 and P = 16 is 512 bytes a side),
+ *                          where a budget in MiB cannot bound the scratch any
+ *                          closer than to the whole call. */
+#define NUSI_OPT_ENSEMBLE_LIMIT_MB 15
+#define NUSI_OPT_ENSEMBLE_LIMIT_BYTES 16
 int nusi_plan_set_option(nusi_plan *plan, int option, int value);
 /* per-point NUSI_WARN_* bits of the last call */
 int nusi_plan_warnings(nusi_plan *plan, int *out, int n);

@@ -80,6 +80,7 @@ EXPORTS = [
     "nusi_plan_response_fit_fixed", "nusi_plan_response_fit_fixed_host",
     "nusi_plan_response_limit", "nusi_plan_response_limit_host",
     "nusi_plan_response_ensemble", "nusi_plan_response_ensemble_host",
+    "nusi_plan_response_ensemble_limit", "nusi_plan_response_ensemble_limit_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -92,6 +93,10 @@ OPT_GA_BATCH, OPT_GA_PRE_MB, OPT_GA_PRE_KB = 9, 10, 11
 OPT_RESPONSE_FIFO_KB = 12
 OPT_ENSEMBLE_QSLICES, OPT_ENSEMBLE_PSLICES = 13, 14    # Plan.ensemble's grid (tables, q-slices, p-slices); 0 = automatic
 ENSEMBLE_DATASETS_MAX = 65536
+# Plan.ensemble_limit: its scratch budget in MiB (0 = 256) or, where > 0, in bytes; the most ranks of a band and data sets
+OPT_ENSEMBLE_LIMIT_MB, OPT_ENSEMBLE_LIMIT_BYTES = 15, 16
+BAND_RANKS_MAX = 16
+BAND_DATASETS_MAX = 4096
 
 _lib = None
 
@@ -171,6 +176,8 @@ def load():
         "nusi_plan_response_limit_host": (i, [vp, dp, i, dp, i, dp, d, i, dp, dp, dp, dp, ip]),
         "nusi_plan_response_ensemble": (i, [vp, vp, i, dp, i, dp, i, vp, vp, vp, vp, vp]),
         "nusi_plan_response_ensemble_host": (i, [vp, dp, i, dp, i, dp, i, ip, dp, dp, ip]),
+        "nusi_plan_response_ensemble_limit": (i, [vp, vp, i, dp, i, dp, i, d, i, ip, i, vp, vp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_ensemble_limit_host": (i, [vp, dp, i, dp, i, dp, i, d, i, ip, i, dp, dp, ip, dp, dp, ip]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

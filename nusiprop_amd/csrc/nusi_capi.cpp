@@ -472,6 +472,11 @@ struct nusi_plan {
     int ens_pslices = 0;
     void* d_ens = nullptr;          // the ensemble's q-slice records [qslices][P][ntab] (at most kEnsScratchBytes when
     size_t ens_bytes = 0;           // the slices are automatic)
+    int toys_mb = 0, toys_b = 0;   // NUSI_OPT_ENSEMBLE_LIMIT_MB, _BYTES: the ensemble limit's scratch budget (0 = kToysScratchBytes)
+    double* d_toys = nullptr;       // a chunk's limits per side kept here [units QB][P] (grown on demand)
+    size_t toys_bytes = 0;
+    int* d_rank = nullptr;          // the band's ranks [NUSI_BAND_RANKS_MAX], staged from h_rank
+    int h_rank[NUSI_BAND_RANKS_MAX] = {};
     std::vector<double> h_evt;
     hipEvent_t ev_det = nullptr;    // end of the latest fold / events call (set_detector and the next events wait for it)
     bool det_ran = false;
@@ -937,6 +942,8 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->d_tpl);
     hipFree(pl->d_evt);
     hipFree(pl->d_ens);
+    hipFree(pl->d_toys);
+    hipFree(pl->d_rank);
     nusi::alpha_tiles_destroy(&pl->atiles);
     hipFree(pl->mc.buf);
     hipFree(pl->mc.eu);
@@ -2186,6 +2193,126 @@ int nusi_plan_response_limit_host(nusi_plan* pl, const double* R, int ntab, cons
                        });
 }
 
+// The limits of an ensemble and their bands (nusi_detector.hip k_toys_limit / k_toys_band).  A unit is one table and one
+// block of QB spectra; a side asked for whose raw array the caller does not give keeps its limits in the plan's scratch,
+// QB P doubles per unit, and the call runs in chunks of the units that fit the budget: per chunk one launch of each
+// kernel, on the call's stream.  The p-slices of a chunk: NUSI_OPT_ENSEMBLE_PSLICES, or automatic by the ensemble's own
+// rule (kEnsBlocksPerCU blocks per compute unit wanted, slices of at least kEnsSliceDatasets).
+constexpr size_t kToysScratchBytes = kEnsScratchBytes;
+constexpr int kToysChunkSpectra = 1 << 22;   // a chunk holds at most so many spectra (units QB): k_toys_limit's grid of units and
+                                             // k_toys_band's of spectra, 256 threads a block, stay below 2^32 threads a launch
+struct ToysPlan {
+    int QB, units, upc, nscr;   // spectra per unit, units of the call, units per chunk, sides kept in scratch
+    bool lo_scr, hi_scr;
+};
+static int toys_check(const nusi_plan* pl, const double* data, int P, double delta, int which, const int* rank, int NR,
+                      const void* band_lo, const void* band_hi, const void* tally, const void* lo_all, const void* hi_all,
+                      const void* words_all)
+{
+    if (int r = detector_plan(pl, "response ensemble_limit")) return r;
+    if (!data) return fail(NUSI_EPARAM, "response ensemble_limit: data must not be NULL");
+    if (P < 1 || P > NUSI_BAND_DATASETS_MAX) return fail(NUSI_EPARAM, "response ensemble_limit: P outside 1 .. NUSI_BAND_DATASETS_MAX");
+    if (NR < 0 || NR > NUSI_BAND_RANKS_MAX) return fail(NUSI_EPARAM, "response ensemble_limit: NR outside 0 .. NUSI_BAND_RANKS_MAX");
+    if (NR > 0 && !rank) return fail(NUSI_EPARAM, "response ensemble_limit: rank must not be NULL with NR > 0");
+    for (int k = 0; k < NR; ++k)
+        if (rank[k] < 0 || rank[k] >= P) return fail(NUSI_EPARAM, "response ensemble_limit: a rank outside 0 .. P - 1");
+    if (!std::isfinite(delta) || !(delta > 0.0)) return fail(NUSI_EPARAM, "response ensemble_limit: delta must be finite and > 0");
+    if (which < 1 || which > 3) return fail(NUSI_EPARAM, "response ensemble_limit: which outside NUSI_LIMIT_LOWER | NUSI_LIMIT_UPPER");
+    if (NR > 0 && (((which & NUSI_LIMIT_LOWER) && !band_lo) || ((which & NUSI_LIMIT_UPPER) && !band_hi)))
+        return fail(NUSI_EPARAM, "response ensemble_limit: the band of a side asked for is NULL");
+    if (NR == 0 && !tally && !lo_all && !hi_all && !words_all)
+        return fail(NUSI_EPARAM, "response ensemble_limit: NR = 0 and no tally or raw output: nothing to do");
+    return NUSI_OK;
+}
+static int toys_plan(const nusi_plan* pl, int ntab, int Q, int P, int which, int NR, const void* lo_all, const void* hi_all,
+                     ToysPlan& tp)
+{
+    tp.QB = nusi::toys_limit_block(pl->det_C);
+    const long long nqb = (Q + tp.QB - 1) / tp.QB, units = (long long)ntab * nqb;
+    if (units > (long long)INT_MAX / tp.QB) return fail(NUSI_EPARAM, "response ensemble_limit: too many spectra (ntab Q >= 2^31)");
+    tp.units = (int)units;
+    tp.lo_scr = NR > 0 && (which & NUSI_LIMIT_LOWER) && !lo_all;
+    tp.hi_scr = NR > 0 && (which & NUSI_LIMIT_UPPER) && !hi_all;
+    tp.nscr = (tp.lo_scr ? 1 : 0) + (tp.hi_scr ? 1 : 0);
+    tp.upc = std::min(tp.units, std::max(kToysChunkSpectra / tp.QB, 1));   // (also with the raw arrays given)
+    if (tp.nscr) {
+        const size_t budget = pl->toys_b > 0 ? (size_t)pl->toys_b : pl->toys_mb > 0 ? (size_t)pl->toys_mb << 20 : kToysScratchBytes;
+        const size_t per = (size_t)tp.QB * P * sizeof(double) * tp.nscr;
+        if (budget < per)
+            return fail(NUSI_EPARAM, "response ensemble_limit: NUSI_OPT_ENSEMBLE_LIMIT_MB / _BYTES is below one unit's scratch (QB P 8 bytes per side)");
+        tp.upc = (int)std::min<size_t>(budget / per, (size_t)tp.upc);
+    }
+    return NUSI_OK;
+}
+
+int nusi_plan_response_ensemble_limit(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data,
+                                      int P, double delta, int which, const int* rank, int NR, double* d_band_lo,
+                                      double* d_band_hi, int* d_tally, double* d_lo_all, double* d_hi_all, int* d_words_all,
+                                      void* stream)
+{
+    if (int r = detector_plan(pl, "response ensemble_limit")) return r;
+    if (!d_R || !S || ntab < 1 || Q < 1 || Q > (1 << 19))   // (events_check's, before Q enters toys_plan)
+        return fail(NUSI_EPARAM, "response ensemble_limit: R and S must not be NULL, need ntab >= 1 and 1 <= Q <= 2^19");
+    if (int r = toys_check(pl, data, P, delta, which, rank, NR, d_band_lo, d_band_hi, d_tally, d_lo_all, d_hi_all, d_words_all)) return r;
+    ToysPlan tp;
+    if (int r = toys_plan(pl, ntab, Q, P, which, NR, d_lo_all, d_hi_all, tp)) return r;
+    EventsArgs a;
+    if (int r = events_begin(pl, "response ensemble_limit", d_R, ntab, S, Q, nullptr, data, P, stream, a)) return r;
+    // (every earlier detector call has finished: events_stage -- the scratch and the ranks are free)
+    const size_t rows = (size_t)tp.upc * tp.QB, need = rows * P * sizeof(double) * tp.nscr;
+    if (pl->toys_bytes < need) {
+        hipFree(pl->d_toys);
+        pl->d_toys = nullptr;
+        pl->toys_bytes = 0;
+        HIPCHECK(hipMalloc(&pl->d_toys, need));
+        pl->toys_bytes = need;
+    }
+    if (NR > 0) {
+        if (!pl->d_rank) HIPCHECK(hipMalloc(&pl->d_rank, sizeof(pl->h_rank)));
+        memcpy(pl->h_rank, rank, sizeof(int) * NR);
+        HIPCHECK(hipMemcpyAsync(pl->d_rank, pl->h_rank, sizeof(int) * NR, hipMemcpyHostToDevice, a.s));
+    }
+    const size_t nn = (size_t)ntab * Q;
+    if (d_tally) HIPCHECK(hipMemsetAsync(d_tally, 0, sizeof(int) * nn * 8, a.s));
+    double* lo = tp.lo_scr ? pl->d_toys : d_lo_all;
+    double* hi = tp.hi_scr ? pl->d_toys + (tp.lo_scr ? rows * P : 0) : d_hi_all;
+    int ncu = 0;
+    HIPCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device));
+    const long long want = (long long)kEnsBlocksPerCU * (ncu > 0 ? ncu : 1);
+    for (int u0 = 0; u0 < tp.units; u0 += tp.upc) {
+        const int nu = std::min(tp.upc, tp.units - u0);
+        const int ps = pl->ens_pslices > 0 ? std::min(pl->ens_pslices, P)
+                                           : (int)std::min<long long>(std::max(P / kEnsSliceDatasets, 1), (want + nu - 1) / nu);
+        HIPCHECK(nusi::launch_toys_limit(pl->gd, d_R, a.S, Q, a.data, P, a.bg, pl->det_C, pl->fit_K, pl->d_tpl, pl->fit_m,
+                                         pl->fit_w, delta, which, u0, nu, ps, lo, tp.lo_scr, hi, tp.hi_scr, d_words_all, d_tally,
+                                         a.s));
+        if (NR > 0)
+            HIPCHECK(nusi::launch_toys_band(pl->det_C, Q, P, u0, nu, lo, tp.lo_scr, hi, tp.hi_scr, d_band_lo, d_band_hi,
+                                            pl->d_rank, NR, a.s));
+    }
+    return detector_mark(pl, a.s);
+}
+
+int nusi_plan_response_ensemble_limit_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
+                                           int P, double delta, int which, const int* rank, int NR, double* band_lo,
+                                           double* band_hi, int* tally, double* lo_all, double* hi_all, int* words_all)
+{
+    if (int r = toys_check(pl, data, P, delta, which, rank, NR, band_lo, band_hi, tally, lo_all, hi_all, words_all)) return r;
+    if (!R || !S || ntab < 1 || Q < 1 || Q > (1 << 19))
+        return fail(NUSI_EPARAM, "response ensemble_limit: R and S must not be NULL, need ntab >= 1 and 1 <= Q <= 2^19");
+    ToysPlan tp;   // (the budget's refusal too, before the device buffers)
+    if (int r = toys_plan(pl, ntab, Q, P, which, NR, lo_all, hi_all, tp)) return r;
+    const size_t nn = (size_t)ntab * Q;
+    return events_host(pl, R, ntab,
+                       {{band_lo, nn * NR, sizeof(double)}, {band_hi, nn * NR, sizeof(double)}, {tally, nn * 8, sizeof(int)},
+                        {lo_all, nn * P, sizeof(double)}, {hi_all, nn * P, sizeof(double)}, {words_all, nn * P * 2, sizeof(int)}},
+                       "response ensemble_limit", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_ensemble_limit(pl, dI, ntab, S, Q, data, P, delta, which, rank, NR,
+                                                                    (double*)d[0], (double*)d[1], (int*)d[2], (double*)d[3],
+                                                                    (double*)d[4], (int*)d[5], nullptr);
+                       });
+}
+
 int nusi_plan_profile_begin(nusi_plan* pl, int max_calls)
 {
     HIPCHECK(hipSetDevice(pl->device));
@@ -2289,6 +2416,14 @@ int nusi_plan_set_option(nusi_plan* pl, int option, int value)
     case NUSI_OPT_ENSEMBLE_PSLICES:
         if (value < 0 || value > 65535) return fail(NUSI_EPARAM, "NUSI_OPT_ENSEMBLE_PSLICES outside [0, 65535]");
         pl->ens_pslices = value;
+        return NUSI_OK;
+    case NUSI_OPT_ENSEMBLE_LIMIT_MB:
+        if (value < 0 || value > (1 << 20)) return fail(NUSI_EPARAM, "NUSI_OPT_ENSEMBLE_LIMIT_MB outside [0, 2^20]");
+        pl->toys_mb = value;
+        return NUSI_OK;
+    case NUSI_OPT_ENSEMBLE_LIMIT_BYTES:
+        if (value < 0 || value > (1 << 30)) return fail(NUSI_EPARAM, "NUSI_OPT_ENSEMBLE_LIMIT_BYTES outside [0, 2^30]");
+        pl->toys_b = value;
         return NUSI_OK;
     case NUSI_OPT_REFERENCE_ORDER:
         if (value < 0 || value > 1) return fail(NUSI_EPARAM, "NUSI_OPT_REFERENCE_ORDER outside [0, 1]");

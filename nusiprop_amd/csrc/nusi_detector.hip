@@ -12,6 +12,12 @@
 //   k_ensemble_profile, k_ensemble_fit<NC>, k_ensemble_best
 //                         those two iterations for P data sets on one front half, and per (data set, table) the best
 //                         spectrum's record only (nusi_plan_response_ensemble)
+//   k_conditional_fit<K>, k_interval<NC>
+//                         the fit with the signal's scale held, and the limits on that scale (nusi_plan_response_fit_fixed,
+//                         nusi_plan_response_limit)
+//   k_toys_limit<NC>, k_toys_band
+//                         those limits for P data sets on one front half, and per (table, spectrum) the order statistics
+//                         of the P limits (nusi_plan_response_ensemble_limit)
 #include <hip/hip_runtime.h>
 
 #include "nusi_internal.hpp"
@@ -2414,6 +2420,796 @@ hipError_t launch_detector_limit(const GridDev& g, const double* R, int ntab, co
     case 3: hipLaunchKernelGGL((k_interval<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, lo, hi, theta_hat, nll_hat, status, M, C, ge.lg, Q); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_toys_limit<NC>: the limits of P data sets on one front half (nusi_plan_response_ensemble_limit), NC = 1 + K =
+// 1 .. 4, on k_interval<NC>'s block shape.  (The names of the two kernels of this call hold neither "k_ensemble" nor
+// "k_interval": the resource tests of those kernels count theirs by substring.)  A block takes one unit u = u0 +
+// blockIdx.x of the call's chunk -- table t = u / nqb, spectrum block u % nqb -- and the data sets of its p-slice
+// (blockIdx.z, ens_share).  Before the loop: the front half, the templates, the background and S1 = tree(X), none of
+// which reads the data.  Per data set: k_interval's best fit and search, COPIED operation for operation (the rule of
+// the ensemble kernels), so the record of (p, t, q) has nusi_plan_response_limit's bits; every per-toy value is set
+// anew at the top of the loop.  No LDS: the best fit's statistic is not formed.
+// A side's limit goes to row[P] + p, row = the spectrum's place in the chunk's scratch ((u - u0) QB + grp; compact) or
+// t Q + q in the caller's [ntab][Q][P]; its word to words[t][q][p][side]; a flag among NUSI_LIMIT_AT_ZERO .. _NOT_CONVERGED
+// adds one to tally[t][q][side][flag] (integer atomics: the order is free; the caller zeroes the tally).
+// ---------------------------------------------------------------------------
+struct ToysOut {
+    double *lo, *hi;   // a side's values, or nullptr
+    int lo_compact, hi_compact;
+    int* words;        // [ntab][Q][P][2] or nullptr
+    int* tally;        // [ntab][Q][2][4] or nullptr
+};
+
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) void k_toys_limit(const double* __restrict__ R, const double* __restrict__ S,
+                                                           const double* __restrict__ data, const double* __restrict__ bg,
+                                                           const double* __restrict__ T, const FitPrior pr, const double ku,
+                                                           const double klu, const double delta, const int which,
+                                                           const ToysOut o, int u0, int nqb, int M, int C, int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    constexpr int KT = NC - 1, KA = KT > 0 ? KT : 1;
+    const int tid = (int)threadIdx.x, u = u0 + (int)blockIdx.x, t = u / nqb;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, qb0 = (u - t * nqb) * QB, q = qb0 + grp;
+    const int cc = c < C ? c : C - 1;
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)(q < Q ? q : Q - 1) * M;
+    const bool in = c < C;
+    int p0, p1;
+    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
+    double X[NC];
+    {
+        double s0 = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
+        X[0] = in ? s0 : 0.0;
+    }
+#pragma unroll
+    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
+    const double b = in ? bg[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+    double S1h[NC];   // tree(X_j): the data do not enter
+#pragma unroll
+    for (int j = 0; j < NC; ++j) S1h[j] = X[j];
+    det_butterfly(S1h, lgC, add);
+    const size_t rq = (size_t)t * Q + q;                      // the spectrum's row of the call's arrays
+    const size_t rc = (size_t)(u - u0) * QB + grp;            // ... and of the chunk's scratch
+    const size_t rlo = (o.lo_compact ? rc : rq) * P, rhi = (o.hi_compact ? rc : rq) * P;
+
+#pragma unroll 1
+    for (int p = p0; p < p1; ++p) {
+        const double d = in ? data[(size_t)p * C + cc] : 0.0;
+
+        // ---- the best fit --------------------------------------------------------------------------------------------
+        double thh[NC], muh;
+        int sth;
+        if constexpr (NC == 1) {
+            // --- k_detector_profile's iteration, copied (one chain) ---
+            auto max = [](double x, double y) { return y > x ? y : x; };
+            const double s = X[0];
+            double S1[1] = {S1h[0]}, a[1];
+            const bool act = d > 0.0 && s > 0.0;
+            bool run = S1[0] != 0.0 && (__ballot(act) & gmask) != 0;
+            int st = run ? 0 : NUSI_FIT_FLAT;
+            {
+                const double x0 = d / S1[0], x1 = b / s;
+                a[0] = act ? x0 - x1 : 0.0;
+            }
+            det_butterfly(a, lgC, max);
+            a[0] = (run && a[0] > 0.0) ? a[0] : 0.0;
+            // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
+            while (__any(run)) {
+                double v[2];
+                {
+                    double den = a[0] * s;
+                    den = den + b;
+                    const double qq = s / den;
+                    const double uu = act ? qq : 0.0;
+                    const double r = d * uu;
+                    v[0] = r;
+                    v[1] = r * uu;
+                }
+                det_butterfly(v, lgC, add);
+                {
+                    const double S2 = v[0], S3 = v[1];
+                    const double g = S1[0] - S2;
+                    const double dn = S2 - S1[0];
+                    const double an = a[0] + dn / S3;
+                    if (run) {
+                        ++st;
+                        if (!(g < 0.0)) {
+                            run = false;
+                            if (a[0] == 0.0) st |= NUSI_FIT_BOUNDARY;
+                        } else if (!(an > a[0])) {
+                            run = false;
+                        } else {
+                            a[0] = an;
+                            if ((st & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
+                                run = false;
+                                st |= NUSI_FIT_NOT_CONVERGED;
+                            }
+                        }
+                    }
+                }
+            }
+            double m = a[0] * s;
+            m = m + b;
+            if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st |= NUSI_FIT_INFINITE;
+            thh[0] = a[0];
+            muh = m;
+            sth = st;
+        } else {
+            // --- k_detector_fit's iteration, copied ---
+            constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
+            double S1[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) S1[j] = S1h[j];
+            bool live[NC];
+            live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
+            bool sup = b > 0.0;
+            int nl = 0;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                if (j > 0) live[j] = S1[j] > 0.0;
+                sup = sup || (live[j] && X[j] > 0.0);
+                nl += live[j] ? 1 : 0;
+            }
+            const bool act = d > 0.0 && sup;
+            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
+            det_butterfly(dsum, lgC, add);
+            det_butterfly(dmin, lgC, min);
+            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+            double th[NC], the[NC], pp[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const double x = D0 / ((double)nl * S1[j]);
+                th[j] = live[j] ? x : 0.0;
+                the[j] = th[j];
+                pp[j] = 0.0;
+            }
+            double tt = 1.0;
+            int st = 0, steps = 0, halv = 0, trials = 0;
+            bool run = true, first = true, quad = false;
+            // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
+            while (__any(run)) {
+                double v[NS];
+                double den = the[0] * X[0];
+#pragma unroll
+                for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
+                den = den + b;
+                const double wq0 = d / den;
+                const double wq = act ? wq0 : 0.0;
+                const double r0 = wq / den;
+                const double r = act ? r0 : 0.0;
+                {
+                    int i = NC;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) {
+                        v[j] = X[j] * wq;
+                        const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
+#pragma unroll
+                        for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
+                    }
+                }
+                det_butterfly(v, lgC, add);
+                const bool bad = any(act && !(den > 0.0));
+                if (run) {
+                    double g[NC];
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
+                    bool ok, changed = true;
+                    if (first) {
+                        ok = !bad;
+                        if (!ok) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        }
+                    } else {
+                        double slope = 0.0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) slope = slope + pp[j] * g[j];
+                        ok = !bad && (quad || !(slope > 0.0));
+                        if (!ok) {
+                            if (trials == NUSI_FIT_TRIALS_MAX) {
+                                run = false;
+                                st |= NUSI_FIT_NOT_CONVERGED;
+                            } else {
+                                ++trials;
+                                ++halv;
+                                tt = tt * 0.5;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * pp[j];
+                            }
+                        } else {
+                            changed = false;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
+                            ++steps;
+                        }
+                    }
+                    if (ok) {
+                        bool fs[NC], conv = true;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) {
+                            th[j] = the[j];
+                            fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
+                            const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
+                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                            if (fs[j] && !(ag <= ku * scale)) conv = false;
+                        }
+                        if (conv) {
+                            run = false;
+                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        } else {
+                            first = false;
+                            // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
+                            // a component at zero that the direction pushes below leaves fs and the solve is repeated
+                            bool sing = false;
+#pragma unroll 1
+                            for (int rep = 0; rep <= NC; ++rep) {
+                                double Lm[NC][NC], Dg[NC], y[NC];
+                                sing = false;
+                                int i0 = NC;
+                                double a[NC][NC];
+#pragma unroll
+                                for (int j = 0; j < NC; ++j)
+#pragma unroll
+                                    for (int k = j; k < NC; ++k) {
+                                        const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
+                                        a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
+                                    }
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) {
+                                    double cw[NC];
+#pragma unroll
+                                    for (int j = 0; j < i; ++j) {
+                                        double x = a[i][j];
+#pragma unroll
+                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                        cw[j] = x;
+                                        Lm[i][j] = x / Dg[j];
+                                    }
+                                    double x = a[i][i];
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                                    if (!(x > 0.0)) sing = true;
+                                    Dg[i] = x;
+                                }
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) {
+                                    double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                                    y[i] = x;
+                                }
+#pragma unroll
+                                for (int i = NC - 1; i >= 0; --i) {
+                                    double x = y[i] / Dg[i];
+#pragma unroll
+                                    for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * pp[k];
+                                    pp[i] = x;
+                                }
+                                if (sing) break;
+                                bool rm = false;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j)
+                                    if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
+                                        fs[j] = false;
+                                        rm = true;
+                                    }
+                                if (!rm) break;
+                            }
+                            double acc = 0.0;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j)
+                                if (fs[j]) acc = acc + g[j] * pp[j];
+                            if (sing || !(acc < 0.0)) {
+                                run = false;
+                                st |= NUSI_FIT_SINGULAR;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) pp[j] = 0.0;
+                            } else {
+                                double ratio[NC];
+                                tt = 1.0;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) {
+                                    const double x = th[j] / -pp[j];
+                                    ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
+                                    if (ratio[j] < tt) tt = ratio[j];
+                                }
+                                const bool clipped = tt < 1.0;
+                                quad = !clipped && -acc <= dq;
+                                trials = 0;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) {
+                                    const double x = th[j] + tt * pp[j];
+                                    the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            double m = th[0] * X[0];
+#pragma unroll
+            for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
+            m = m + b;
+            if (!live[0])
+                st |= NUSI_FIT_FLAT;
+            else if (th[0] == 0.0)
+                st |= NUSI_FIT_BOUNDARY;
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+                if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
+            if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
+            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) thh[j] = th[j];
+            muh = m;
+            sth = st;
+        }
+
+        // ---- the search ----------------------------------------------------------------------------------------------
+        // (uniform values the search holds for long, moved to vector registers: the scalar file is the tight one here)
+        double pm_[KA], pw_[KA], ku_ = ku, klu_ = klu, hd = 0.5 * delta;
+#pragma unroll
+        for (int i = 0; i < KA; ++i) {
+            pm_[i] = i < KT ? pr.m[(i + 1) < NC ? i + 1 : 0] : 0.0;
+            pw_[i] = i < KT ? pr.w[(i + 1) < NC ? i + 1 : 0] : 0.0;
+            asm volatile("" : "+v"(pm_[i]), "+v"(pw_[i]));
+        }
+        asm volatile("" : "+v"(ku_), "+v"(klu_), "+v"(hd));
+        const double S10 = S1h[0], ahat = thh[0];
+        // (the chain's long-lived flags are bits of one vector register, as in k_interval)
+        enum { kLact = 1, kSupt = 2, kZeroOk = 4, kRun = 8, kSeen = 16, kZeroDone = 32, kRan = 64, kIRun = 1, kFirst = 2, kWarm = 4, kQuad = 8 };
+        int cf = (in && d > 0.0 && muh > 0.0) ? kLact : 0;   // kSupt: a live template supports the bin
+        int nl = 0;
+#pragma unroll
+        for (int i = 0; i < KT; ++i) {
+            if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) cf |= kSupt;
+            nl += S1h[i + 1] > 0.0 ? 1 : 0;
+        }
+        if (!any(d > 0.0 && X[0] > 0.0 && !(b > 0.0) && !(cf & kSupt))) cf |= kZeroOk;
+        double step;
+        {
+            const double wq0 = d / muh;
+            const double wq = (cf & kLact) ? wq0 : 0.0;
+            const double r0 = wq / muh;
+            const double rqq = (cf & kLact) ? r0 : 0.0;
+            double S3[1] = {(X[0] * rqq) * X[0]};
+            det_butterfly(S3, lgC, add);
+            // the quadratic model's step rounded up to a power of two: 2^ceil(e / 2), delta / S3 = f 2^e, f in [1/2, 1)
+            const int e = __builtin_amdgcn_frexp_exp(delta / S3[0]);   // frexp's exponent (0 for inf), no stack slot
+            const double pw2 = ldexp(1.0, ((e + 1025) >> 1) - 512);
+            const double lin = hd / S10;
+            step = S3[0] > 0.0 ? pw2 : lin;
+        }
+        constexpr int NI = 1 + KT + KT * (KT + 1) / 2;   // an inner round's sums: S2_j, H_jk (1 <= j <= k), then S2_0
+#pragma unroll 1
+        for (int side = 1; side >= 0; --side) {   // 1: the upper side, 0: the lower
+            const bool upper = side == 1;
+            const bool asked = (which & (upper ? NUSI_LIMIT_UPPER : NUSI_LIMIT_LOWER)) != 0;
+            double a = 0.0, res = __builtin_nan("");
+            int word = 0, fl = 0;
+            if (asked) {
+                if (sth & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
+                    word = NUSI_LIMIT_NO_FIT;
+                } else if (S10 == 0.0) {
+                    res = upper ? __builtin_inf() : 0.0;
+                    word = upper ? NUSI_LIMIT_UNBOUNDED : (NUSI_LIMIT_UNBOUNDED | NUSI_LIMIT_AT_ZERO);
+                } else if (upper) {
+                    a = ahat + step;
+                    fl = kRun | kRan;
+                } else if (ahat == 0.0) {
+                    res = 0.0;
+                    word = NUSI_LIMIT_AT_ZERO;
+                } else {
+                    a = ahat - step;
+                    if (!(a > 0.0)) a = 0.5 * ahat;
+                    fl = kRun | kRan;
+                }
+            }
+            double th[KA], aprev = a;
+#pragma unroll
+            for (int i = 0; i < KA; ++i) th[i] = i < KT ? thh[(i + 1) < NC ? i + 1 : 0] : 0.0;
+            int steps = 0, inner = 0, flags = 0;
+            // (every round of the outer loop ends a chain or counts a step towards NUSI_LIMIT_ITER_MAX)
+            while (__any((fl & kRun) != 0)) {
+                // --- k_conditional_fit's iteration at a, from th (the header's start where an active den is not > 0 there) ---
+                const double asig = a * X[0];
+                const bool sup = b > 0.0 || (cf & kSupt) || (a > 0.0 && X[0] > 0.0);
+                const bool act = d > 0.0 && sup;
+                double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};
+                det_butterfly(dsum, lgC, add);
+                det_butterfly(dmin, lgC, min);
+                const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+                double the[KA], pp[KA], S20 = 0.0;
+#pragma unroll
+                for (int i = 0; i < KA; ++i) {
+                    the[i] = th[i];
+                    pp[i] = 0.0;
+                }
+                double tt = 1.0;
+                int ist = 0, isteps = 0, trials = 0;
+                int il = ((fl & kRun) ? kIRun : 0) | kFirst | kWarm;   // (the inner chain's flags, bits as well)
+                while (__any((il & kIRun) != 0)) {
+                    double v[NI];
+                    double den = asig;
+#pragma unroll
+                    for (int i = 0; i < KT; ++i) den = den + the[i] * X[i + 1];
+                    den = den + b;
+                    const double wq0 = d / den;
+                    const double wq = act ? wq0 : 0.0;
+                    const double r0 = wq / den;
+                    const double r = act ? r0 : 0.0;
+                    {
+                        int i = KT;
+#pragma unroll
+                        for (int j = 0; j < KT; ++j) {
+                            v[j] = X[j + 1] * wq;
+                            const double xr = X[j + 1] * r;
+#pragma unroll
+                            for (int k = j; k < KT; ++k) v[i++] = xr * X[k + 1];
+                        }
+                        v[NI - 1] = X[0] * wq;
+                    }
+                    det_butterfly(v, lgC, add);
+                    const bool bad = any(act && !(den > 0.0));
+                    if (il & kIRun) {
+                        double g[KA];
+#pragma unroll
+                        for (int j = 0; j < KT; ++j) g[j] = (S1h[j + 1] - v[j]) + pw_[j] * (the[j] - pm_[j]);
+                        bool ok, changed = true;
+                        if (il & kFirst) {
+                            ok = !bad;
+                            if (!ok) {
+                                if (il & kWarm) {
+                                    il &= ~kWarm;
+#pragma unroll
+                                    for (int j = 0; j < KT; ++j) {
+                                        const double x = D0 / ((double)nl * S1h[j + 1]);
+                                        th[j] = S1h[j + 1] > 0.0 ? x : 0.0;
+                                        the[j] = th[j];
+                                    }
+                                } else {
+                                    il &= ~kIRun;
+                                    ist |= NUSI_FIT_NOT_CONVERGED;
+                                }
+                            }
+                        } else {
+                            double slope = 0.0;
+#pragma unroll
+                            for (int j = 0; j < KT; ++j) slope = slope + pp[j] * g[j];
+                            ok = !bad && ((il & kQuad) || !(slope > 0.0));
+                            if (!ok) {
+                                if (trials == NUSI_FIT_TRIALS_MAX) {
+                                    il &= ~kIRun;
+                                    ist |= NUSI_FIT_NOT_CONVERGED;
+                                } else {
+                                    ++trials;
+                                    tt = tt * 0.5;
+#pragma unroll
+                                    for (int j = 0; j < KT; ++j) the[j] = th[j] + tt * pp[j];
+                                }
+                            } else {
+                                changed = false;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) changed = changed || the[j] != th[j];
+                                ++isteps;
+                            }
+                        }
+                        if (ok) {
+                            bool fs[KA], conv = true;
+                            S20 = v[NI - 1];
+#pragma unroll
+                            for (int j = 0; j < KT; ++j) {
+                                th[j] = the[j];
+                                fs[j] = S1h[j + 1] > 0.0 && (th[j] > 0.0 || g[j] < 0.0);
+                                const double sc = (S1h[j + 1] + v[j]) + pw_[j] * (th[j] + pm_[j]);
+                                const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                                if (fs[j] && !(ag <= ku_ * sc)) conv = false;
+                            }
+                            if (conv) {
+                                il &= ~kIRun;
+                            } else if ((!(il & kFirst) && !changed) || isteps == NUSI_FIT_ITER_MAX) {
+                                il &= ~kIRun;
+                                ist |= NUSI_FIT_NOT_CONVERGED;
+                            } else {
+                                il &= ~kFirst;
+                                bool sing = false;
+#pragma unroll 1
+                                for (int rep = 0; rep <= KT; ++rep) {
+                                    double Lm[KA][KA], Dg[KA], y[KA];
+                                    sing = false;
+                                    int i0 = KT;
+                                    double hm[KA][KA];
+#pragma unroll
+                                    for (int j = 0; j < KT; ++j)
+#pragma unroll
+                                        for (int k = j; k < KT; ++k) {
+                                            const double hv = v[i0++] + (j == k ? pw_[j] : 0.0);
+                                            hm[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
+                                        }
+#pragma unroll
+                                    for (int i = 0; i < KT; ++i) {
+                                        double cw[KA];
+#pragma unroll
+                                        for (int j = 0; j < i; ++j) {
+                                            double x = hm[i][j];
+#pragma unroll
+                                            for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                            cw[j] = x;
+                                            Lm[i][j] = x / Dg[j];
+                                        }
+                                        double x = hm[i][i];
+#pragma unroll
+                                        for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                                        if (!(x > 0.0)) sing = true;
+                                        Dg[i] = x;
+                                    }
+#pragma unroll
+                                    for (int i = 0; i < KT; ++i) {
+                                        double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                                        for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                                        y[i] = x;
+                                    }
+#pragma unroll
+                                    for (int i = KT - 1; i >= 0; --i) {
+                                        double x = y[i] / Dg[i];
+#pragma unroll
+                                        for (int k = i + 1; k < KT; ++k) x = x - Lm[k][i] * pp[k];
+                                        pp[i] = x;
+                                    }
+                                    if (sing) break;
+                                    bool rm = false;
+#pragma unroll
+                                    for (int j = 0; j < KT; ++j)
+                                        if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
+                                            fs[j] = false;
+                                            rm = true;
+                                        }
+                                    if (!rm) break;
+                                }
+                                double acc = 0.0;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j)
+                                    if (fs[j]) acc = acc + g[j] * pp[j];
+                                if (sing || !(acc < 0.0)) {
+                                    il &= ~kIRun;
+                                    ist |= NUSI_FIT_SINGULAR;
+                                } else {
+                                    double ratio[KA];
+                                    tt = 1.0;
+#pragma unroll
+                                    for (int j = 0; j < KT; ++j) {
+                                        const double x = th[j] / -pp[j];
+                                        ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
+                                        if (ratio[j] < tt) tt = ratio[j];
+                                    }
+                                    const bool clipped = tt < 1.0;
+                                    il = (!clipped && -acc <= dq) ? (il | kQuad) : (il & ~kQuad);
+                                    trials = 0;
+#pragma unroll
+                                    for (int j = 0; j < KT; ++j) {
+                                        const double x = th[j] + tt * pp[j];
+                                        the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+                // --- lambda(a) - delta / 2 from ratios, its magnitude, and the step in a ---
+                double mu = asig;
+#pragma unroll
+                for (int i = 0; i < KT; ++i) mu = mu + th[i] * X[i + 1];
+                mu = mu + b;
+                double lv[2];
+                {
+                    const double dmu = mu - muh;
+                    const double ratio = mu / muh;
+                    const double lr = ratio > 0.0 ? nm::log_i(ratio) : -__builtin_inf();
+                    const double pl = d * lr;
+                    const double admu = dmu < 0.0 ? -dmu : dmu, apl = pl < 0.0 ? -pl : pl;
+                    const double tl = dmu - pl, ml = admu + apl;
+                    lv[0] = (cf & kLact) ? tl : dmu;
+                    lv[1] = (cf & kLact) ? ml : admu;
+                }
+                det_butterfly(lv, lgC, add);
+                if (fl & kRun) {
+                    inner += isteps;
+                    if (ist & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
+                        flags |= NUSI_LIMIT_NOT_CONVERGED;
+                        fl &= ~kRun;
+                    } else {
+                        ++steps;
+                        double lam = lv[0], mg = lv[1];
+#pragma unroll
+                        for (int j = 0; j < KT; ++j)
+                            if (pw_[j] > 0.0) {
+                                const double dj = th[j] - thh[(j + 1) < NC ? j + 1 : 0];
+                                const double sj = (th[j] - pm_[j]) + (thh[(j + 1) < NC ? j + 1 : 0] - pm_[j]);
+                                const double pd = ((0.5 * pw_[j]) * dj) * sj;
+                                lam = lam + pd;
+                                mg = mg + (pd < 0.0 ? -pd : pd);
+                            }
+                        const double h = lam - hd;
+                        const double eps = klu_ * (mg + hd);
+                        const double g0 = S10 - S20;
+                        const double ah = h < 0.0 ? -h : h;
+                        if (!upper && a == 0.0) {   // the one look at zero: the limit is there, or the search goes back
+                            if (!(h > 0.0)) {
+                                flags |= NUSI_LIMIT_AT_ZERO;
+                                fl &= ~kRun;
+                            } else if (steps == NUSI_LIMIT_ITER_MAX) {
+                                flags |= NUSI_LIMIT_NOT_CONVERGED;
+                                fl &= ~kRun;
+                            } else {
+                                fl = (fl | kZeroDone) & ~kSeen;
+                                a = 0.5 * aprev;
+                            }
+                        } else if (ah <= eps || ((fl & kSeen) && !(h > 0.0))) {
+                            fl &= ~kRun;
+                        } else {
+                            fl = h > 0.0 ? (fl | kSeen) : (fl & ~kSeen);
+                            if (steps == NUSI_LIMIT_ITER_MAX || !(upper ? g0 > 0.0 : g0 < 0.0)) {
+                                flags |= NUSI_LIMIT_NOT_CONVERGED;
+                                fl &= ~kRun;
+                            } else {
+                                double an = a - h / g0;
+                                if (!upper && !(an > 0.0)) {
+                                    fl &= ~kSeen;
+                                    if ((cf & kZeroOk) && !(fl & kZeroDone)) {
+                                        aprev = a;
+                                        an = 0.0;
+                                    } else {
+                                        an = 0.5 * a;
+                                    }
+                                }
+                                if (!(an < __builtin_inf())) {
+                                    flags |= NUSI_LIMIT_NOT_CONVERGED;
+                                    fl &= ~kRun;
+                                } else if (an == a) {
+                                    fl &= ~kRun;
+                                } else {
+                                    a = an;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            if (fl & kRan) {
+                res = a;
+                word = steps | flags | ((inner < NUSI_LIMIT_INNER_MASK ? inner : NUSI_LIMIT_INNER_MASK) << NUSI_LIMIT_INNER_SHIFT);
+            }
+            if (c == 0 && q < Q) {
+                double* out = upper ? o.hi : o.lo;
+                if (out) out[(upper ? rhi : rlo) + p] = res;
+                if (o.words) o.words[(rq * P + p) * 2 + side] = word;
+                if (o.tally) {
+                    int* ty = o.tally + (rq * 2 + side) * 4;
+                    if (word & NUSI_LIMIT_AT_ZERO) atomicAdd(ty + 0, 1);
+                    if (word & NUSI_LIMIT_UNBOUNDED) atomicAdd(ty + 1, 1);
+                    if (word & NUSI_LIMIT_NO_FIT) atomicAdd(ty + 2, 1);
+                    if (word & NUSI_LIMIT_NOT_CONVERGED) atomicAdd(ty + 3, 1);
+                }
+            }
+        }
+    }
+}
+
+int toys_limit_block(int C) { return kEvThreads >> ceil_log2(C); }
+
+hipError_t launch_toys_limit(const GridDev& g, const double* R, const double* S, int Q, const double* data, int P,
+                             const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
+                             double delta, int which, int u0, int nu, int pslices, double* lo, bool lo_compact, double* hi,
+                             bool hi_compact, int* words, int* tally, hipStream_t s)
+{
+    if (nu <= 0 || Q <= 0 || P <= 0) return hipSuccess;
+    const int lg = ceil_log2(C), QB = kEvThreads >> lg, nqb = (Q + QB - 1) / QB;
+    FitPrior pr;
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
+        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
+        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
+    }
+    const double ku = (double)(2 * (lg + K) + 18) * 0x1p-53;    // kappa(C, K) u (include/nusi.h)
+    const double klu = (double)(2 * (lg + K) + 14) * 0x1p-53;   // kappa_lambda(C, K) u
+    const ToysOut o{lo, hi, lo_compact ? 1 : 0, hi_compact ? 1 : 0, words, tally};
+    const dim3 grid((unsigned)nu, 1, (unsigned)pslices), block(kEvThreads);
+    const int M = g.T + 1;
+    switch (K) {
+    case 0: hipLaunchKernelGGL((k_toys_limit<1>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, o, u0, nqb, M, C, lg, Q, P); break;
+    case 1: hipLaunchKernelGGL((k_toys_limit<2>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, o, u0, nqb, M, C, lg, Q, P); break;
+    case 2: hipLaunchKernelGGL((k_toys_limit<3>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, o, u0, nqb, M, C, lg, Q, P); break;
+    case 3: hipLaunchKernelGGL((k_toys_limit<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, klu, delta, which, o, u0, nqb, M, C, lg, Q, P); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_toys_band: the order statistics of a spectrum's P limits (the band of nusi_plan_response_ensemble_limit).  A block
+// takes one spectrum of the chunk (blockIdx.x: unit u0 + x / QBe, the unit's spectrum x % QBe, QBe = min(QB, Q) -- a
+// call of fewer spectra than a block launches no blocks for the rest; past Q: nothing) and one side (blockIdx.y).  A limit is a non-negative double, +inf or NaN, never -0.0, so its bit pattern with NaN mapped to
+// all ones is a monotone 64-bit key under (isnan(x), x): the keys are sorted in LDS by a bitonic network over
+// npad = 2^ceil(log2 P) slots (the padding: all ones, behind every rank < P) and band[t][q][k] is the key at rank[k],
+// all ones read back as NaN; rank [NR] is device memory.  Equal keys are equal bits, so the result does not depend on
+// the network.
+// A side with src == nullptr (not asked for) writes NaN.
+// ---------------------------------------------------------------------------
+constexpr int kBandThreads = 256;
+
+__global__ __launch_bounds__(kBandThreads) void k_toys_band(const double* __restrict__ lo, int lo_compact,
+                                                            const double* __restrict__ hi, int hi_compact,
+                                                            double* __restrict__ band_lo, double* __restrict__ band_hi,
+                                                            const int* __restrict__ rank, int NR, int u0, int nqb, int QB,
+                                                            int QBe, int Q, int P, int npad)
+{
+    extern __shared__ unsigned long long skey[];   // [npad]
+    const int tid = (int)threadIdx.x, nth = (int)blockDim.x;
+    const int x = (int)blockIdx.x, du = x / QBe, g = x - du * QBe, u = u0 + du, t = u / nqb, q = (u - t * nqb) * QB + g;
+    const bool upper = blockIdx.y == 1;
+    double* __restrict__ band = upper ? band_hi : band_lo;
+    if (q >= Q || !band) return;   // (uniform over the block)
+    const double* __restrict__ src = upper ? hi : lo;
+    const size_t rq = (size_t)t * Q + q;
+    if (!src) {
+        for (int k = tid; k < NR; k += nth) band[rq * NR + k] = __builtin_nan("");
+        return;
+    }
+    src += ((upper ? hi_compact : lo_compact) ? (size_t)du * QB + g : rq) * P;
+    for (int i = tid; i < npad; i += nth) {
+        unsigned long long key = ~0ull;
+        if (i < P) {
+            const double v = src[i];
+            key = v != v ? ~0ull : (unsigned long long)__double_as_longlong(v);
+        }
+        skey[i] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= npad; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < (npad >> 1); i += nth) {
+                const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1)), bb = a | j;   // the pair (a, a + j) of this stage
+                const unsigned long long ka = skey[a], kb = skey[bb];
+                const bool up = (a & k) == 0;
+                if ((ka > kb) == up) {
+                    skey[a] = kb;
+                    skey[bb] = ka;
+                }
+            }
+            __syncthreads();
+        }
+    for (int k = tid; k < NR; k += nth) {
+        const unsigned long long key = skey[rank[k]];
+        band[rq * NR + k] = key == ~0ull ? __builtin_nan("") : __longlong_as_double((long long)key);
+    }
+}
+
+hipError_t launch_toys_band(int C, int Q, int P, int u0, int nu, const double* lo, bool lo_compact, const double* hi,
+                            bool hi_compact, double* band_lo, double* band_hi, const int* rank, int NR, hipStream_t s)
+{
+    if (nu <= 0 || NR <= 0 || NR > NUSI_BAND_RANKS_MAX || (!band_lo && !band_hi)) return hipSuccess;
+    const int lg = ceil_log2(C), QB = kEvThreads >> lg, nqb = (Q + QB - 1) / QB;
+    int npad = 1;
+    while (npad < P) npad <<= 1;
+    int nth = npad >> 1;
+    nth = nth < 64 ? 64 : (nth > kBandThreads ? kBandThreads : nth);
+    const int QBe = QB < Q ? QB : Q;
+    const dim3 grid((unsigned)((long long)nu * QBe), 2), block((unsigned)nth);
+    hipLaunchKernelGGL(k_toys_band, grid, block, sizeof(unsigned long long) * (size_t)npad, s, lo, lo_compact ? 1 : 0, hi,
+                       hi_compact ? 1 : 0, band_lo, band_hi, rank, NR, u0, nqb, QB, QBe, Q, P, npad);
     return hipGetLastError();
 }
 

@@ -188,6 +188,20 @@ hipError_t launch_detector_limit(const GridDev& g, const double* R, int ntab, co
                                  const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
                                  double delta, int which, double* lo, double* hi, double* theta_hat, double* nll_hat,
                                  int* status, hipStream_t s);
+// k_toys_limit<1 + K> and k_toys_band (nusi_plan_response_ensemble_limit).  The work of a call is cut into units: unit u
+// is table u / nqb and spectrum block u % nqb, nqb = ceil(Q / QB), QB = toys_limit_block(C) spectra.  launch_toys_limit
+// runs units u0 .. u0 + nu - 1 against the P data sets data [P][C] (device memory) in `pslices` slices: a side's limits
+// go to lo / hi (nullptr: not kept) -- compact: the chunk's scratch [nu QB][P], else the call's [ntab][Q][P] --, the
+// side words to words [ntab][Q][P][2] and the counted flags are ADDED to tally [ntab][Q][2][4] (either may be nullptr).
+// launch_toys_band selects the NR ranks rank [NR] (device memory, 0 <= r < P) of those units' limits into band_lo,
+// band_hi [ntab][Q][NR] (nullptr: skipped; a side without values, lo / hi == nullptr: NaN).
+int toys_limit_block(int C);
+hipError_t launch_toys_limit(const GridDev& g, const double* R, const double* S, int Q, const double* data, int P,
+                             const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
+                             double delta, int which, int u0, int nu, int pslices, double* lo, bool lo_compact, double* hi,
+                             bool hi_compact, int* words, int* tally, hipStream_t s);
+hipError_t launch_toys_band(int C, int Q, int P, int u0, int nu, const double* lo, bool lo_compact, const double* hi,
+                            bool hi_compact, double* band_lo, double* band_hi, const int* rank, int NR, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

@@ -822,6 +822,84 @@ def ensemble_host(R, S, datasets, templates=None, prior=None, background=None, l
     return q, nll, theta, status
 
 
+def order_stat(x, ranks, axis=-1):
+    """The band's rule of nusi_plan_response_ensemble_limit (include/nusi.h): along ``axis`` the order statistics of x at
+    ``ranks`` (ints, 0 <= r < n, duplicates allowed) under the key (isnan(x), x), ascending -- a NaN sorts after
+    everything, +inf included.  The result has the ranks on a new LAST axis in place of ``axis``: shape
+    x.shape-without-axis + (len(ranks),).  Entry r is the value with at most r entries before it and more than r before
+    or equal to it, so the result does not depend on the order of the input or on how the selection is arranged."""
+    x = np.asarray(x, dtype=np.float64)
+    r = np.asarray(ranks, dtype=np.int64).reshape(-1)
+    if x.ndim == 0 or x.shape[axis] == 0:
+        raise ValueError("order_stat: nothing to select from along axis %d of shape %s" % (axis, x.shape))
+    n = x.shape[axis]
+    if np.any(r < 0) or np.any(r >= n):
+        raise ValueError("order_stat: a rank outside 0 .. %d" % (n - 1))
+    return np.sort(np.moveaxis(x, axis, -1), axis=-1)[..., r]      # (numpy sorts NaN to the end, behind +inf)
+
+
+def band_ranks(P, probs=(0.025, 0.16, 0.5, 0.84, 0.975)):
+    """The ranks of the quantiles ``probs`` among P toys by the inverted empirical CDF: r = min(P - 1, max(0,
+    ceil(f P) - 1)) -- the smallest order statistic with at least a fraction f of the toys at or below it.  The default:
+    the median expected limit with its 68 % and 95 % bands.  Returns an int32 array."""
+    P = int(P)
+    if P < 1:
+        raise ValueError("band_ranks: P must be >= 1")
+    f = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if np.any(~(f >= 0)) or np.any(f > 1):
+        raise ValueError("band_ranks: a probability outside [0, 1]")
+    return np.minimum(P - 1, np.maximum(0, np.ceil(f * P).astype(np.int64) - 1)).astype(np.int32)
+
+
+def limit_tally(words):
+    """tally[..., side, 4] of nusi_plan_response_ensemble_limit from the side words (..., P, 2): per side the toys whose
+    word carries LIMIT_AT_ZERO, LIMIT_UNBOUNDED, LIMIT_NO_FIT and LIMIT_NOT_CONVERGED, in that order (int32)."""
+    w = np.asarray(words)
+    flags = np.array([LIMIT_AT_ZERO, LIMIT_UNBOUNDED, LIMIT_NO_FIT, LIMIT_NOT_CONVERGED])
+    return ((w[..., None] & flags) != 0).sum(axis=-3).astype(np.int32)
+
+
+def ensemble_limit_host(R, S, datasets, delta, which="upper", ranks=None, templates=None, prior=None, background=None,
+                        log=np.log, raw=False):
+    """nusi_plan_response_ensemble_limit on the CPU: a loop of limit_host over the data sets, then order_stat over the
+    toys and the tally of the side words.
+
+    R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  datasets: (C,) or (P, C), entries finite and >= 0.  delta, which,
+    templates, prior, background, log: as for limit_host.  ranks: ints in 0 .. P - 1 (None: band_ranks(P)).  Returns
+    (band_lo (ntab, Q, NR), band_hi (ntab, Q, NR), tally (ntab, Q, 2, 4) int32) and, with raw, also (lo_all (ntab, Q, P),
+    hi_all (ntab, Q, P), words_all (ntab, Q, P, 2) int32); a side not asked for has NaN bands, a tally of 0 and words of
+    0.  No axis is squeezed."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    data = np.asarray(datasets, dtype=np.float64)
+    if R.ndim == 2:
+        R = R[None]
+    if S.ndim == 1:
+        S = S[None]
+    if data.ndim == 1:
+        data = data[None]
+    if R.ndim != 3 or S.ndim != 2 or R.shape[1] != S.shape[1]:
+        raise ValueError("ensemble_limit_host: R (.., M, C) and S (.., M) do not match: %s, %s" % (R.shape, S.shape))
+    ntab, C, Q = R.shape[0], R.shape[2], S.shape[0]
+    if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] != C:
+        raise ValueError("ensemble_limit_host: datasets must have shape (P, %d), P >= 1, got %s" % (C, data.shape))
+    if not np.all(np.isfinite(data)) or np.any(data < 0):
+        raise ValueError("ensemble_limit_host: a datum is negative or not finite")
+    P = data.shape[0]
+    r = band_ranks(P) if ranks is None else np.asarray(ranks, dtype=np.int64).reshape(-1)
+    if np.any(r < 0) or np.any(r >= P):
+        raise ValueError("ensemble_limit_host: a rank outside 0 .. %d" % (P - 1))
+    lo_all, hi_all = np.full((ntab, Q, P), np.nan), np.full((ntab, Q, P), np.nan)
+    words = np.zeros((ntab, Q, P, 2), dtype=np.int32)
+    for p in range(P):
+        lo, hi, _, _, st = limit_host(R, S, data[p], delta, which=which, templates=templates, prior=prior,
+                                      background=background, log=log)
+        lo_all[..., p], hi_all[..., p] = np.reshape(lo, (ntab, Q)), np.reshape(hi, (ntab, Q))
+        words[..., p, :] = np.reshape(st, (ntab, Q, 3))[..., 1:]
+    out = (order_stat(lo_all, r), order_stat(hi_all, r), limit_tally(words))
+    return out + (lo_all, hi_all, words) if raw else out
+
+
 def pseudo_data(mu, P, rng):
     """P Poisson pseudo-experiments around the expected counts mu (C,): counts (P, C) as float64, drawn from ``rng``, a
     numpy.random.Generator (the device generates no random numbers: toys are host data)."""

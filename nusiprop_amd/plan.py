@@ -524,6 +524,64 @@ class Plan:
             vp(stream_ptr) if stream_ptr else None))
         return len(S), (d.shape[0] if d is not None else 0)
 
+    def _ranks(self, ranks, P):
+        from . import detector
+        r = detector.band_ranks(P) if ranks is None else np.asarray(ranks, dtype=np.int64).reshape(-1)
+        return np.ascontiguousarray(r, dtype=np.int32)
+
+    def ensemble_limit(self, R, spectra, datasets, delta, which="upper", ranks=None, raw=False):
+        """The limits of ``limit`` for P data sets -- datasets (P, C), an ensemble of pseudo-experiments -- in one call on
+        the GPU, and per table and spectrum the order statistics of its P limits: with background-only toys the median
+        expected limit and its bands.  The signal counts of (t, q) are computed once and the P searches run on them; the
+        record of (p, t, q) is what ``limit`` gives against datasets[p], bit for bit.  ranks: ints in 0 .. P - 1, at most
+        _lib.BAND_RANKS_MAX of them (None: detector.band_ranks(P), the 2.5, 16, 50, 84 and 97.5 % points); the band is
+        detector.order_stat of the P limits -- a NaN (no fit) sorts after +inf (no signal).  Returns (band_lo (ntab, Q,
+        NR), band_hi (ntab, Q, NR), tally (ntab, Q, 2, 4) int32): per side (0 lower, 1 upper) the toys flagged
+        _lib.LIMIT_AT_ZERO, LIMIT_UNBOUNDED, LIMIT_NO_FIT and LIMIT_NOT_CONVERGED; with raw also (lo_all (ntab, Q, P),
+        hi_all (ntab, Q, P), words_all (ntab, Q, P, 2) int32), every toy's limits and side words.  A side not asked for
+        has NaN bands, a tally of 0 and words of 0.  detector.ensemble_limit_host is the same in numpy."""
+        R, C = self._folded(R, "ensemble_limit")
+        S, _ = self._spectra(spectra, None)
+        d = self._datasets(datasets)
+        ntab, Q, P = R.shape[0], len(S), d.shape[0]
+        r = self._ranks(ranks, P)
+        NR = len(r)
+        band_lo, band_hi = np.full((ntab, Q, NR), np.nan), np.full((ntab, Q, NR), np.nan)
+        tally = np.zeros((ntab, Q, 2, 4), dtype=np.int32)
+        lo_all = hi_all = words = None
+        if raw:
+            lo_all, hi_all = np.full((ntab, Q, P), np.nan), np.full((ntab, Q, P), np.nan)
+            words = np.zeros((ntab, Q, P, 2), dtype=np.int32)
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        _lib.check(_lib.load().nusi_plan_response_ensemble_limit_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp), P, float(delta),
+            self._which(which), r.ctypes.data_as(ip), NR, band_lo.ctypes.data_as(dp), band_hi.ctypes.data_as(dp),
+            tally.ctypes.data_as(ip), lo_all.ctypes.data_as(dp) if raw else None, hi_all.ctypes.data_as(dp) if raw else None,
+            words.ctypes.data_as(ip) if raw else None))
+        return (band_lo, band_hi, tally) + ((lo_all, hi_all, words) if raw else ())
+
+    def ensemble_limit_device(self, d_R_ptr, ntab, spectra, datasets, delta, which, ranks, d_band_lo_ptr, d_band_hi_ptr,
+                              d_tally_ptr=None, d_lo_all_ptr=None, d_hi_all_ptr=None, d_words_all_ptr=None, stream_ptr=None):
+        """Asynchronous ensemble_limit on device-resident folded matrices: d_R [ntab][M][C], d_band_lo and d_band_hi
+        [ntab][Q][NR], d_lo_all and d_hi_all [ntab][Q][P] (doubles), d_tally [ntab][Q][2][4] and d_words_all
+        [ntab][Q][P][2] (ints) are raw pointers; any may be 0 / None, but with ranks the band of a side asked for is
+        needed.  ranks: ints (None: detector.band_ranks(P); an empty list: no band).  The spectra, the data sets and
+        the ranks are host data and are copied.  Returns (Q, P, NR)."""
+        S, _ = self._spectra(spectra, None)
+        d = self._datasets(datasets) if datasets is not None else None
+        P = d.shape[0] if d is not None else 0
+        r = self._ranks(ranks, max(P, 1))
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_response_ensemble_limit(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp) if d is not None else None, P,
+            float(delta), self._which(which), r.ctypes.data_as(ip) if len(r) else None, len(r),
+            vp(d_band_lo_ptr) if d_band_lo_ptr else None, vp(d_band_hi_ptr) if d_band_hi_ptr else None,
+            vp(d_tally_ptr) if d_tally_ptr else None, vp(d_lo_all_ptr) if d_lo_all_ptr else None,
+            vp(d_hi_all_ptr) if d_hi_all_ptr else None, vp(d_words_all_ptr) if d_words_all_ptr else None,
+            vp(stream_ptr) if stream_ptr else None))
+        return len(S), P, len(r)
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since
@@ -542,7 +600,9 @@ class Plan:
         budget in MiB, 0 = 512; OPT_GA_PRE_KB: the same in KiB), OPT_RESPONSE_FIFO_KB (the response's impulse
         cascade: its step-pass FIFO budget in KiB, 0 = 1 GiB; the tables run in chunks that fit), OPT_ENSEMBLE_QSLICES
         and OPT_ENSEMBLE_PSLICES (``ensemble``'s grid is (tables, q-slices, p-slices): 0 = automatic, n >= 1 = exactly
-        min(n, what there is to split); any value gives the same bits); include/nusi.h."""
+        min(n, what there is to split); any value gives the same bits), OPT_ENSEMBLE_LIMIT_MB (``ensemble_limit``'s
+        scratch budget in MiB, 0 = 256; the call runs in chunks that fit; OPT_ENSEMBLE_LIMIT_BYTES: the same in bytes);
+        include/nusi.h."""
         _lib.check(_lib.load().nusi_plan_set_option(self._h, int(option), int(value)))
 
     def profile_begin(self, max_calls):
