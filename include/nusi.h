@@ -583,6 +583,113 @@ int nusi_plan_response_ensemble_limit_host(nusi_plan *plan, const double *R, int
                                            const double *data, int P, double delta, int which, const int *rank, int NR,
                                            double *band_lo, double *band_hi, int *tally, double *lo_all, double *hi_all,
                                            int *words_all);
+/* Drawing counts (k_poisson_draw; nusi_draw.hpp, detector.draw_host): Poisson pseudo-experiments from a counter-based
+ * generator on the device, every operation defined, so that a host form with the same exp and log gives the same bits.
+ *
+ * Random bits.  Philox4x32-10 with the multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57 and the key increments 0x9E3779B9,
+ * 0xBB67AE85: ten rounds of
+ *     c <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),   then k0 += 0x9E3779B9, k1 += 0xBB67AE85
+ * (hi, lo: the words of the 64-bit product).  The key (k0, k1) is the call's 64-bit seed, low word first; the counter is
+ * (block, p 64 + c, row, stream): p the toy, c the bin, row and stream the caller's, block = 0, 1, .. the 128-bit blocks
+ * one draw consumes.  A draw's identity is global: no result depends on a chunk, a slice or the launch.  A block x gives
+ * two uniforms in [0, 1):  U0 = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53,  U1 the same from x2 and x3.
+ *
+ * Poisson(mu), the count k a double; every operation rounded on its own (no fma), exp and log the library's (nm::exp_i,
+ * nm::log_i; the oracle's ora_exp, ora_log).
+ *   mu == 0: 0, no bits are drawn.  mu negative, NaN or infinite: NaN (the calls refuse such a mu where it is an input).
+ *   0 < mu < 10, inversion on U0 of block 0:
+ *     p = exp(-mu); F = p; k = 0;
+ *     while (!(u < F)) { k += 1; p = (p mu) / k; Fn = F + p; if ((Fn == F && k > mu) || k == 255) break; F = Fn; }
+ *   mu >= 10, Hoermann's PTRS (numpy's constants): slam = sqrt(mu), loglam = log(mu), b = 0.931 + 2.53 slam,
+ *     a = -0.059 + 0.02483 b, invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2).  Round r = 0, 1, ..
+ *     uses block r: U = U0 - 0.5, V = U1, us = 0.5 - |U|; us == 0 rejects (k stays);
+ *     k = floor(((((2 a) / us + b) U) + mu) + 0.43);  accept if us >= 0.07 && V <= vr;  reject if k < 0 || (us < 0.013
+ *     && V > us);  else accept if
+ *         (log(V) + log(invalpha)) - log(a / (us us) + b)  <=  (-mu + k loglam) - loggam(k + 1),    log(0) = -inf.
+ *     After 64 rejected rounds the draw is max(k, 0) of the last round that formed a k (0 if none did).
+ *   loggam(x) is numpy's random_loggam: 0 at x == 1 and x == 2; n = x < 7 ? (int)(7 - x) : 0, x0 = x + n,
+ *     x2 = (1 / x0) (1 / x0); gl0 = a9, then for k = 8 .. 0: gl0 = gl0 x2 + a_k (two roundings), a_k = 8.333333333333333e-02,
+ *     -2.777777777777778e-03, 7.936507936507937e-04, -5.952380952380952e-04, 8.417508417508418e-04, -1.917526917526918e-03,
+ *     6.410256410256410e-03, -2.955065359477124e-02, 1.796443723688307e-01, -1.39243221690590e+00;
+ *     gl = ((gl0 / x0 + 0.5 * 1.8378770664093453) + (x0 - 0.5) log(x0)) - x0;  then n times: x0 -= 1, gl -= log(x0).
+ *
+ * nusi_plan_draw_counts: d_out[row][p][c] = the draw of mu[row][c] with the identity (seed, stream, row, p, c), for
+ * p < P: rows P C doubles in device memory.  mu [rows][C] is a host array and is copied (entries finite and >= 0).  The
+ * plan's detector is not needed: C = 1 .. NUSI_DETECTOR_BINS_MAX is an argument.  Asynchronous on `stream` (NULL: the
+ * plan's); the plan keeps mu's copy until the next draw, which waits for this one.  NUSI_EPARAM for a NULL mu or d_out,
+ * rows < 1, C out of range, P outside 1 .. NUSI_DRAW_DATASETS_MAX (the counter holds p 64 + c), rows P C above
+ * NUSI_DRAW_COUNTS_MAX = (2^31 - 1) 256 (one launch of 256 counts a block), or a negative or non-finite mu; a refused
+ * call changes nothing.  _host: the output in host memory, synchronous. */
+#define NUSI_DRAW_DATASETS_MAX 67108864
+#define NUSI_DRAW_COUNTS_MAX 549755813632
+int nusi_plan_draw_counts(nusi_plan *plan, const double *mu /* [rows][C] */, int rows, int C, int P,
+                          unsigned long long seed, unsigned stream_id, double *d_out /* [rows][P][C] */, void *stream);
+int nusi_plan_draw_counts_host(nusi_plan *plan, const double *mu, int rows, int C, int P, unsigned long long seed,
+                               unsigned stream_id, double *out);
+/* nusi_plan_response_inject (k_inject, k_toys_band): the distribution of the statistic q(a) at a hypothesis, on toys drawn
+ * from that hypothesis's own expectation -- critical values, toy-calibrated p-values, the coverage of a delta, discovery
+ * power under an injected signal.  The toys exist only in registers: each is drawn where it is fitted.  The front half
+ * s[t][q][c] = sum_n R[t][n][c] S[q][n] is computed once.  K = nusi_plan_templates(plan) = 0 .. 3.  For every table t,
+ * spectrum q and toy p < P <= NUSI_BAND_DATASETS_MAX:
+ *
+ *   1. The datum of bin c is the draw ("Drawing counts", above) of
+ *          mu_inj[c] = a_inj[q] s[t][q][c] (+ theta_inj[j] T_j[c], j ascending) + B[c]
+ *      (nusi_plan_response_fit_fixed's order for mu) with the identity (seed, stream = t, row = q, p, c): the value
+ *      nusi_plan_draw_counts gives at [q][p][c] for the rows mu_inj[t][.] and stream_id = t.  a_inj [Q] and theta_inj [K]
+ *      are host arrays, finite and >= 0; a NULL theta_inj stands for the templates' prior means (0 without a prior).
+ *   2. The best fit: nusi_plan_response_fit's record against that datum (nusi_plan_response_profile's at K = 0): its bits
+ *      for theta_hat and its status word.
+ *   3. The conditional fit with the signal held at a_test[q] (a NULL a_test: a_inj): nusi_plan_response_fit_fixed's, from
+ *      that call's cold start, so its bits and its word.  It runs whatever the best fit did.  K = 0: the single
+ *      evaluation mu = a_test s + B, word 0.
+ *   4. lambda as nusi_plan_response_limit forms it at (a_test, theta) against the best fit -- per bin the ratio's term,
+ *      the tree over the bins, then the penalties' differences ascending --, and
+ *          stat = lambda > 0 ? 2 lambda : +0.0.
+ *      mode NUSI_INJECT_TWO_SIDED: that; NUSI_INJECT_UPPER: stat = +0.0 where theta_hat_0 > a_test (the one-sided
+ *      convention of an upper limit); NUSI_INJECT_DISCOVERY: stat = +0.0 where theta_hat_0 < a_test.  A best fit that is
+ *      NUSI_FIT_NOT_CONVERGED or _SINGULAR: theta_hat_0 and stat are NaN; a conditional fit so flagged: stat is NaN.
+ *      There is no other special case: a spectrum of zeros gets what these rules give.
+ *   5. Per (t, q), on the device: d_band_theta and d_band_stat [ntab][Q][NR], the order statistics of the P values of
+ *      theta_hat_0 and of stat at rank [NR] under the key (isnan(x), x) (nusi_plan_response_ensemble_limit's band; both
+ *      series are non-negative doubles or NaN, never -0.0).  d_tally [ntab][Q][4] (ints) counts the toys whose best fit
+ *      failed (NOT_CONVERGED or SINGULAR); whose conditional fit failed and whose best fit did not, so that the toys with
+ *      a statistic are P - tally[0] - tally[1]; whose best fit has theta_hat_0 = 0 (NUSI_FIT_BOUNDARY or _FLAT); and whose
+ *      best fit is NUSI_FIT_INFINITE.  d_exceed [ntab][Q] (ints) counts the toys with stat >= q_obs[t][q]; it comes with
+ *      the host array q_obs [ntab][Q] and only with it; a NaN on either side never counts.  The toy p-value is
+ *      exceed / (P - tally[0] - tally[1]).
+ *   6. The raw records, the toy index fastest: d_theta_all, d_stat_all [ntab][Q][P] (doubles), d_words_all [ntab][Q][P][2]
+ *      (ints; [0] the best fit's word, [1] the conditional fit's) and d_data_all [ntab][Q][P][C], the drawn counts.
+ *
+ * Every output is a DEVICE pointer and may be NULL; NR > 0 needs one band at least, and a band not given is not formed.
+ * Scratch and the grid are nusi_plan_response_ensemble_limit's: units of one table and QB spectra, a series whose band
+ * is asked for and whose raw array is not given kept in the plan's scratch (QB P 8 bytes a unit and series), chunks under
+ * NUSI_OPT_ENSEMBLE_LIMIT_MB / _BYTES of at most 2^22 spectra, p-slices on the grid's z (NUSI_OPT_ENSEMBLE_PSLICES, or
+ * automatic), the tally and exceed zeroed on the stream and added to with integer atomics.  A draw's identity is global,
+ * so every budget and every slicing give the same bits.
+ *
+ * S, a_inj, theta_inj, a_test, rank and q_obs are host arrays and are copied.  Asynchronous and ordered with the plan's
+ * other detector calls like nusi_plan_response_fit.  NUSI_ESTATE without a detector; NUSI_EPARAM for a NULL d_R, S or
+ * a_inj, ntab < 1, Q outside 1 .. 2^19, P, NR or a rank out of range, a NULL rank with NR > 0, a mode outside 0 .. 2, NR >
+ * 0 without a band, q_obs without d_exceed or the reverse, NR = 0 with no tally, exceed or raw output (nothing to do), a
+ * negative or non-finite entry of S, a_inj, theta_inj or a_test, or a budget too small for one unit; a refused call
+ * changes nothing.  _host: R and the outputs in host memory, synchronous. */
+#define NUSI_INJECT_TWO_SIDED 0
+#define NUSI_INJECT_UPPER 1
+#define NUSI_INJECT_DISCOVERY 2
+int nusi_plan_response_inject(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab, const double *S /* [Q][M] */,
+                              int Q, const double *a_inj /* [Q] */, const double *theta_inj /* [K] or NULL */,
+                              const double *a_test /* [Q] or NULL */, int P, unsigned long long seed, int mode,
+                              const int *rank /* [NR] */, int NR, const double *q_obs /* [ntab][Q] or NULL */,
+                              double *d_band_theta /* [ntab][Q][NR] */, double *d_band_stat /* [ntab][Q][NR] */,
+                              int *d_tally /* [ntab][Q][4] */, int *d_exceed /* [ntab][Q] */,
+                              double *d_theta_all /* [ntab][Q][P] */, double *d_stat_all /* [ntab][Q][P] */,
+                              int *d_words_all /* [ntab][Q][P][2] */, double *d_data_all /* [ntab][Q][P][C] */,
+                              void *stream);
+int nusi_plan_response_inject_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *a_inj,
+                                   const double *theta_inj, const double *a_test, int P, unsigned long long seed, int mode,
+                                   const int *rank, int NR, const double *q_obs, double *band_theta, double *band_stat,
+                                   int *tally, int *exceed, double *theta_all, double *stat_all, int *words_all,
+                                   double *data_all);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);

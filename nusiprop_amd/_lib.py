@@ -81,6 +81,8 @@ EXPORTS = [
     "nusi_plan_response_limit", "nusi_plan_response_limit_host",
     "nusi_plan_response_ensemble", "nusi_plan_response_ensemble_host",
     "nusi_plan_response_ensemble_limit", "nusi_plan_response_ensemble_limit_host",
+    "nusi_plan_draw_counts", "nusi_plan_draw_counts_host",
+    "nusi_plan_response_inject", "nusi_plan_response_inject_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -97,6 +99,9 @@ ENSEMBLE_DATASETS_MAX = 65536
 OPT_ENSEMBLE_LIMIT_MB, OPT_ENSEMBLE_LIMIT_BYTES = 15, 16
 BAND_RANKS_MAX = 16
 BAND_DATASETS_MAX = 4096
+INJECT_TWO_SIDED, INJECT_UPPER, INJECT_DISCOVERY = 0, 1, 2     # Plan.inject's mode (include/nusi.h NUSI_INJECT_*)
+DRAW_DATASETS_MAX = 1 << 26     # Plan.draw: the toys per bin (the generator's counter holds p * 64 + c)
+DRAW_COUNTS_MAX = ((1 << 31) - 1) * 256     # ... and the counts of a call, rows * P * C (one launch, 256 counts a block)
 
 _lib = None
 
@@ -178,6 +183,12 @@ def load():
         "nusi_plan_response_ensemble_host": (i, [vp, dp, i, dp, i, dp, i, ip, dp, dp, ip]),
         "nusi_plan_response_ensemble_limit": (i, [vp, vp, i, dp, i, dp, i, d, i, ip, i, vp, vp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_ensemble_limit_host": (i, [vp, dp, i, dp, i, dp, i, d, i, ip, i, dp, dp, ip, dp, dp, ip]),
+        "nusi_plan_draw_counts": (i, [vp, dp, i, i, i, ctypes.c_ulonglong, ctypes.c_uint, vp, vp]),
+        "nusi_plan_draw_counts_host": (i, [vp, dp, i, i, i, ctypes.c_ulonglong, ctypes.c_uint, dp]),
+        "nusi_plan_response_inject": (i, [vp, vp, i, dp, i, dp, dp, dp, i, ctypes.c_ulonglong, i, ip, i, dp,
+                                          vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_inject_host": (i, [vp, dp, i, dp, i, dp, dp, dp, i, ctypes.c_ulonglong, i, ip, i, dp,
+                                               dp, dp, ip, ip, dp, dp, ip, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -478,6 +478,11 @@ struct nusi_plan {
     int* d_rank = nullptr;          // the band's ranks [NUSI_BAND_RANKS_MAX], staged from h_rank
     int h_rank[NUSI_BAND_RANKS_MAX] = {};
     std::vector<double> h_evt;
+    double* d_draw = nullptr;       // nusi_plan_draw_counts: the expectations mu [rows][C], staged from h_draw
+    size_t draw_doubles = 0;
+    std::vector<double> h_draw;
+    hipEvent_t ev_draw = nullptr;   // end of the latest draw (the next one reuses d_draw / h_draw)
+    bool draw_ran = false;
     hipEvent_t ev_det = nullptr;    // end of the latest fold / events call (set_detector and the next events wait for it)
     bool det_ran = false;
     std::vector<int> slot_of;       // table slot of each point of the last call
@@ -944,6 +949,8 @@ void nusi_plan_destroy(nusi_plan* pl)
     hipFree(pl->d_ens);
     hipFree(pl->d_toys);
     hipFree(pl->d_rank);
+    if (pl->ev_draw) hipEventDestroy(pl->ev_draw);
+    hipFree(pl->d_draw);
     nusi::alpha_tiles_destroy(&pl->atiles);
     hipFree(pl->mc.buf);
     hipFree(pl->mc.eu);
@@ -1865,13 +1872,29 @@ static int events_check(const nusi_plan* pl, const char* what, const double* d_R
             if (!(data[c] >= 0.0) || !std::isfinite(data[c])) return fail(NUSI_EPARAM, std::string(what) + ": a datum is negative or not finite");
     return NUSI_OK;
 }
-static int events_stage(nusi_plan* pl, const double* S, int Q, const double* scale, const double* data, int P, hipStream_t s)
+// d_evt's layout, written down here and nowhere else: S [Q][M], scale [Q], data [P][C], then a call's further host
+// vectors, extra [nextra] (the calibration call's a_test and q_obs); offsets in doubles
+struct EvtLayout {
+    size_t scale, data, extra, total;
+};
+static EvtLayout evt_layout(const nusi_plan* pl, int Q, int P, size_t nextra)
+{
+    EvtLayout l;
+    l.scale = (size_t)Q * ((size_t)pl->grid.T + 1);
+    l.data = l.scale + (size_t)Q;
+    l.extra = l.data + (size_t)P * pl->det_C;
+    l.total = l.extra + nextra;
+    return l;
+}
+static int events_stage(nusi_plan* pl, const double* S, int Q, const double* scale, const double* data, int P, hipStream_t s,
+                        const double* extra = nullptr, size_t nextra = 0)
 {
     const size_t M = (size_t)pl->grid.T + 1;
     const int C = pl->det_C;
     if (pl->det_ran) HIPCHECK(hipEventSynchronize(pl->ev_det));   // d_evt / h_evt are reused (every earlier detector
                                                                   // call has finished: detector_chain)
-    const size_t need = (size_t)Q * M + (size_t)Q + (size_t)P * C;
+    const EvtLayout l = evt_layout(pl, Q, P, nextra);
+    const size_t need = l.total;
     if (pl->evt_doubles < need) {
         hipFree(pl->d_evt);
         pl->d_evt = nullptr;
@@ -1881,8 +1904,9 @@ static int events_stage(nusi_plan* pl, const double* S, int Q, const double* sca
     }
     pl->h_evt.assign(S, S + (size_t)Q * M);
     pl->h_evt.resize(need, 0.0);
-    if (scale) memcpy(pl->h_evt.data() + (size_t)Q * M, scale, sizeof(double) * Q);
-    if (data) memcpy(pl->h_evt.data() + (size_t)Q * M + Q, data, sizeof(double) * P * C);
+    if (scale) memcpy(pl->h_evt.data() + l.scale, scale, sizeof(double) * Q);
+    if (data) memcpy(pl->h_evt.data() + l.data, data, sizeof(double) * P * C);
+    if (extra) memcpy(pl->h_evt.data() + l.extra, extra, sizeof(double) * nextra);
     HIPCHECK(hipMemcpyAsync(pl->d_evt, pl->h_evt.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
     return NUSI_OK;
 }
@@ -1900,10 +1924,10 @@ static int events_begin(nusi_plan* pl, const char* what, const double* d_R, int 
     HIPCHECK(hipSetDevice(pl->device));
     a.s = stream ? (hipStream_t)stream : pl->stream;
     if (int r = events_stage(pl, S, Q, scale, data, P, a.s)) return r;
-    const double* d_sc = pl->d_evt + (size_t)Q * ((size_t)pl->grid.T + 1);
+    const EvtLayout l = evt_layout(pl, Q, P, 0);
     a.S = pl->d_evt;
-    a.scale = scale ? d_sc : nullptr;
-    a.data = d_sc + Q;
+    a.scale = scale ? pl->d_evt + l.scale : nullptr;
+    a.data = pl->d_evt + l.data;
     a.bg = detector_bg(pl);
     return NUSI_OK;
 }
@@ -2310,6 +2334,204 @@ int nusi_plan_response_ensemble_limit_host(nusi_plan* pl, const double* R, int n
                            return nusi_plan_response_ensemble_limit(pl, dI, ntab, S, Q, data, P, delta, which, rank, NR,
                                                                     (double*)d[0], (double*)d[1], (int*)d[2], (double*)d[3],
                                                                     (double*)d[4], (int*)d[5], nullptr);
+                       });
+}
+
+// nusi_plan_draw_counts: the checks, then mu staged into the plan's d_draw on s (the earlier draw has finished with it)
+static int draw_check(const nusi_plan* pl, const double* mu, int rows, int C, int P, const void* out)
+{
+    if (!pl) return no_plan();
+    if (!mu || !out) return fail(NUSI_EPARAM, "draw counts: mu and the output must not be NULL");
+    if (rows < 1 || C < 1 || C > NUSI_DETECTOR_BINS_MAX || P < 1 || P > NUSI_DRAW_DATASETS_MAX)
+        return fail(NUSI_EPARAM, "draw counts: need rows >= 1, 1 <= C <= NUSI_DETECTOR_BINS_MAX and 1 <= P <= NUSI_DRAW_DATASETS_MAX");
+    if ((unsigned long long)rows * P * C > (unsigned long long)NUSI_DRAW_COUNTS_MAX)
+        return fail(NUSI_EPARAM, "draw counts: rows P C above NUSI_DRAW_COUNTS_MAX");
+    for (size_t e = 0; e < (size_t)rows * C; ++e)
+        if (!(mu[e] >= 0.0) || !std::isfinite(mu[e])) return fail(NUSI_EPARAM, "draw counts: an expectation is negative or not finite");
+    return NUSI_OK;
+}
+
+int nusi_plan_draw_counts(nusi_plan* pl, const double* mu, int rows, int C, int P, unsigned long long seed, unsigned stream_id,
+                          double* d_out, void* stream)
+{
+    if (int r = draw_check(pl, mu, rows, C, P, d_out)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (pl->draw_ran) HIPCHECK(hipEventSynchronize(pl->ev_draw));
+    const size_t need = (size_t)rows * C;
+    if (pl->draw_doubles < need) {
+        hipFree(pl->d_draw);
+        pl->d_draw = nullptr;
+        pl->draw_doubles = 0;
+        HIPCHECK(hipMalloc(&pl->d_draw, sizeof(double) * need));
+        pl->draw_doubles = need;
+    }
+    pl->h_draw.assign(mu, mu + need);
+    HIPCHECK(hipMemcpyAsync(pl->d_draw, pl->h_draw.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
+    HIPCHECK(nusi::launch_poisson_draw(pl->d_draw, rows, C, P, seed, stream_id, d_out, s));
+    if (!pl->ev_draw) HIPCHECK(hipEventCreateWithFlags(&pl->ev_draw, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(pl->ev_draw, s));
+    pl->draw_ran = true;
+    return NUSI_OK;
+}
+
+int nusi_plan_draw_counts_host(nusi_plan* pl, const double* mu, int rows, int C, int P, unsigned long long seed,
+                               unsigned stream_id, double* out)
+{
+    if (int r = draw_check(pl, mu, rows, C, P, out)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    const size_t n = (size_t)rows * P * C;
+    double* dO = nullptr;
+    if (hipMalloc(&dO, sizeof(double) * n) != hipSuccess) return fail(NUSI_EHIP, "draw counts: no device memory");
+    int r = nusi_plan_draw_counts(pl, mu, rows, C, P, seed, stream_id, dO, nullptr);
+    if (!r && hipStreamSynchronize(pl->stream) != hipSuccess) r = fail(NUSI_EHIP, "draw counts: the stream failed");
+    if (!r && hipMemcpy(out, dO, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess)
+        r = fail(NUSI_EHIP, "draw counts: copy to the host failed");
+    hipFree(dO);
+    return r;
+}
+
+// The calibration call (nusi_detector.hip k_inject, then k_toys_band): the ensemble limit's units, chunks, scratch budget
+// and p-slices; the toys are drawn in the kernel.  The host vectors ride in d_evt behind the spectra (evt_layout): a_inj
+// in the scales' place, then a_test [Q] and q_obs [ntab][Q] (with exceed) as the extra vectors.
+struct InjectPlan {
+    int QB, units, upc, nscr;
+    bool th_scr, st_scr;
+};
+static int inject_check(const nusi_plan* pl, const void* R, int ntab, const double* S, int Q, const double* a_inj,
+                        const double* theta_inj, const double* a_test, int P, int mode, const int* rank, int NR,
+                        const double* q_obs, const void* band_theta, const void* band_stat, const void* tally,
+                        const void* exceed, const void* theta_all, const void* stat_all, const void* words_all,
+                        const void* data_all)
+{
+    const std::string w = "response inject: ";
+    if (int r = detector_plan(pl, "response inject")) return r;
+    if (!R || !S || !a_inj) return fail(NUSI_EPARAM, w + "R, S and a_inj must not be NULL");
+    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, w + "need ntab >= 1 and 1 <= Q <= 2^19");
+    if (P < 1 || P > NUSI_BAND_DATASETS_MAX) return fail(NUSI_EPARAM, w + "P outside 1 .. NUSI_BAND_DATASETS_MAX");
+    if (NR < 0 || NR > NUSI_BAND_RANKS_MAX) return fail(NUSI_EPARAM, w + "NR outside 0 .. NUSI_BAND_RANKS_MAX");
+    if (NR > 0 && !rank) return fail(NUSI_EPARAM, w + "rank must not be NULL with NR > 0");
+    for (int k = 0; k < NR; ++k)
+        if (rank[k] < 0 || rank[k] >= P) return fail(NUSI_EPARAM, w + "a rank outside 0 .. P - 1");
+    if (mode < NUSI_INJECT_TWO_SIDED || mode > NUSI_INJECT_DISCOVERY) return fail(NUSI_EPARAM, w + "mode outside 0 .. 2");
+    if (NR > 0 && !band_theta && !band_stat) return fail(NUSI_EPARAM, w + "NR > 0 needs a band");
+    if ((q_obs != nullptr) != (exceed != nullptr)) return fail(NUSI_EPARAM, w + "q_obs and exceed come together");
+    if (NR == 0 && !tally && !exceed && !theta_all && !stat_all && !words_all && !data_all)
+        return fail(NUSI_EPARAM, w + "NR = 0 and no tally, exceed or raw output: nothing to do");
+    for (int q = 0; q < Q; ++q) {
+        if (!(a_inj[q] >= 0.0) || !std::isfinite(a_inj[q])) return fail(NUSI_EPARAM, w + "an a_inj is negative or not finite");
+        if (a_test && (!(a_test[q] >= 0.0) || !std::isfinite(a_test[q]))) return fail(NUSI_EPARAM, w + "an a_test is negative or not finite");
+    }
+    if (theta_inj)
+        for (int j = 0; j < pl->fit_K; ++j)
+            if (!(theta_inj[j] >= 0.0) || !std::isfinite(theta_inj[j])) return fail(NUSI_EPARAM, w + "a theta_inj is negative or not finite");
+    return NUSI_OK;
+}
+static int inject_plan(const nusi_plan* pl, int ntab, int Q, int P, int NR, const void* band_theta, const void* band_stat,
+                       const void* theta_all, const void* stat_all, InjectPlan& ip)
+{
+    ip.QB = nusi::toys_limit_block(pl->det_C);
+    const long long nqb = (Q + ip.QB - 1) / ip.QB, units = (long long)ntab * nqb;
+    if (units > (long long)INT_MAX / ip.QB) return fail(NUSI_EPARAM, "response inject: too many spectra (ntab Q >= 2^31)");
+    ip.units = (int)units;
+    ip.th_scr = NR > 0 && band_theta && !theta_all;
+    ip.st_scr = NR > 0 && band_stat && !stat_all;
+    ip.nscr = (ip.th_scr ? 1 : 0) + (ip.st_scr ? 1 : 0);
+    ip.upc = std::min(ip.units, std::max(kToysChunkSpectra / ip.QB, 1));   // (also with the raw arrays given)
+    if (ip.nscr) {
+        const size_t budget = pl->toys_b > 0 ? (size_t)pl->toys_b : pl->toys_mb > 0 ? (size_t)pl->toys_mb << 20 : kToysScratchBytes;
+        const size_t per = (size_t)ip.QB * P * sizeof(double) * ip.nscr;
+        if (budget < per)
+            return fail(NUSI_EPARAM, "response inject: NUSI_OPT_ENSEMBLE_LIMIT_MB / _BYTES is below one unit's scratch (QB P 8 bytes per series)");
+        ip.upc = (int)std::min<size_t>(budget / per, (size_t)ip.upc);
+    }
+    return NUSI_OK;
+}
+
+int nusi_plan_response_inject(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* a_inj,
+                              const double* theta_inj, const double* a_test, int P, unsigned long long seed, int mode,
+                              const int* rank, int NR, const double* q_obs, double* d_band_theta, double* d_band_stat,
+                              int* d_tally, int* d_exceed, double* d_theta_all, double* d_stat_all, int* d_words_all,
+                              double* d_data_all, void* stream)
+{
+    if (int r = inject_check(pl, d_R, ntab, S, Q, a_inj, theta_inj, a_test, P, mode, rank, NR, q_obs, d_band_theta, d_band_stat,
+                             d_tally, d_exceed, d_theta_all, d_stat_all, d_words_all, d_data_all))
+        return r;
+    InjectPlan ip;
+    if (int r = inject_plan(pl, ntab, Q, P, NR, d_band_theta, d_band_stat, d_theta_all, d_stat_all, ip)) return r;
+    const size_t nn = (size_t)ntab * Q;
+    // a_test [Q] and q_obs [ntab][Q] travel behind the spectra and a_inj as events_stage's extra vectors (evt_layout)
+    std::vector<double> extra((size_t)Q + (q_obs ? nn : 0));
+    memcpy(extra.data(), a_test ? a_test : a_inj, sizeof(double) * Q);
+    if (q_obs) memcpy(extra.data() + Q, q_obs, sizeof(double) * nn);
+    if (int r = events_check(pl, "response inject", d_R, ntab, S, Q, a_inj, nullptr, 0)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    const int C = pl->det_C;
+    if (int r = events_stage(pl, S, Q, a_inj, nullptr, 0, s, extra.data(), extra.size())) return r;
+    const EvtLayout l = evt_layout(pl, Q, 0, extra.size());
+    const double* dS = pl->d_evt;
+    const double* d_ainj = pl->d_evt + l.scale;
+    const double* d_atest = pl->d_evt + l.extra;
+    const double* d_qobs = q_obs ? d_atest + Q : nullptr;
+    // (every earlier detector call has finished: events_stage -- the scratch and the ranks are free)
+    const size_t rows = (size_t)ip.upc * ip.QB, need = rows * P * sizeof(double) * ip.nscr;
+    if (pl->toys_bytes < need) {
+        hipFree(pl->d_toys);
+        pl->d_toys = nullptr;
+        pl->toys_bytes = 0;
+        HIPCHECK(hipMalloc(&pl->d_toys, need));
+        pl->toys_bytes = need;
+    }
+    if (NR > 0) {
+        if (!pl->d_rank) HIPCHECK(hipMalloc(&pl->d_rank, sizeof(pl->h_rank)));
+        memcpy(pl->h_rank, rank, sizeof(int) * NR);
+        HIPCHECK(hipMemcpyAsync(pl->d_rank, pl->h_rank, sizeof(int) * NR, hipMemcpyHostToDevice, s));
+    }
+    if (d_tally) HIPCHECK(hipMemsetAsync(d_tally, 0, sizeof(int) * nn * 4, s));
+    if (d_exceed) HIPCHECK(hipMemsetAsync(d_exceed, 0, sizeof(int) * nn, s));
+    // a series is kept where its band or its raw array is asked for
+    double* th = ip.th_scr ? pl->d_toys : d_theta_all;
+    double* st = ip.st_scr ? pl->d_toys + (ip.th_scr ? rows * P : 0) : d_stat_all;
+    double th_inj[NUSI_FIT_TEMPLATES_MAX] = {};
+    for (int j = 0; j < pl->fit_K; ++j) th_inj[j] = theta_inj ? theta_inj[j] : pl->fit_m[j];
+    int ncu = 0;
+    HIPCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device));
+    const long long want = (long long)kEnsBlocksPerCU * (ncu > 0 ? ncu : 1);
+    for (int u0 = 0; u0 < ip.units; u0 += ip.upc) {
+        const int nu = std::min(ip.upc, ip.units - u0);
+        const int ps = pl->ens_pslices > 0 ? std::min(pl->ens_pslices, P)
+                                           : (int)std::min<long long>(std::max(P / kEnsSliceDatasets, 1), (want + nu - 1) / nu);
+        HIPCHECK(nusi::launch_inject(pl->gd, d_R, dS, Q, d_ainj, d_atest, th_inj, d_qobs, P, seed, mode, detector_bg(pl), C,
+                                     pl->fit_K, pl->d_tpl, pl->fit_m, pl->fit_w, u0, nu, ps, th, ip.th_scr, st, ip.st_scr,
+                                     d_words_all, d_tally, d_exceed, d_data_all, s));
+        if (NR > 0)
+            HIPCHECK(nusi::launch_toys_band(C, Q, P, u0, nu, d_band_theta ? th : nullptr, ip.th_scr, d_band_stat ? st : nullptr,
+                                            ip.st_scr, d_band_theta, d_band_stat, pl->d_rank, NR, s));
+    }
+    return detector_mark(pl, s);
+}
+
+int nusi_plan_response_inject_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* a_inj,
+                                   const double* theta_inj, const double* a_test, int P, unsigned long long seed, int mode,
+                                   const int* rank, int NR, const double* q_obs, double* band_theta, double* band_stat,
+                                   int* tally, int* exceed, double* theta_all, double* stat_all, int* words_all,
+                                   double* data_all)
+{
+    if (int r = inject_check(pl, R, ntab, S, Q, a_inj, theta_inj, a_test, P, mode, rank, NR, q_obs, band_theta, band_stat, tally,
+                             exceed, theta_all, stat_all, words_all, data_all))
+        return r;
+    InjectPlan ip;   // (the budget's refusal too, before the device buffers)
+    if (int r = inject_plan(pl, ntab, Q, P, NR, band_theta, band_stat, theta_all, stat_all, ip)) return r;
+    const size_t nn = (size_t)ntab * Q;
+    return events_host(pl, R, ntab,
+                       {{band_theta, nn * NR, sizeof(double)}, {band_stat, nn * NR, sizeof(double)}, {tally, nn * 4, sizeof(int)},
+                        {exceed, nn, sizeof(int)}, {theta_all, nn * P, sizeof(double)}, {stat_all, nn * P, sizeof(double)},
+                        {words_all, nn * P * 2, sizeof(int)}, {data_all, nn * P * pl->det_C, sizeof(double)}},
+                       "response inject", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_inject(pl, dI, ntab, S, Q, a_inj, theta_inj, a_test, P, seed, mode, rank, NR,
+                                                            q_obs, (double*)d[0], (double*)d[1], (int*)d[2], (int*)d[3],
+                                                            (double*)d[4], (double*)d[5], (int*)d[6], (double*)d[7], nullptr);
                        });
 }
 

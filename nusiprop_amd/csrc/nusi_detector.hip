@@ -18,10 +18,16 @@
 //   k_toys_limit<NC>, k_toys_band
 //                         those limits for P data sets on one front half, and per (table, spectrum) the order statistics
 //                         of the P limits (nusi_plan_response_ensemble_limit)
+//   k_poisson_draw        Poisson counts around expectations mu [rows][C], P per bin, from the counter-based generator
+//                         of nusi_draw.hpp (nusi_plan_draw_counts)
+//   k_inject<NC>          per (table, spectrum) P toys drawn from the injected expectation where they are fitted: the
+//                         best fit, one conditional fit and the statistic per toy; k_toys_band then selects the order
+//                         statistics of theta_hat_0 and of the statistic (nusi_plan_response_inject)
 #include <hip/hip_runtime.h>
 
 #include "nusi_internal.hpp"
 #include "nusi_libm.hpp"
+#include "nusi_draw.hpp"
 
 namespace nusi {
 
@@ -3210,6 +3216,667 @@ hipError_t launch_toys_band(int C, int Q, int P, int u0, int nu, const double* l
     const dim3 grid((unsigned)((long long)nu * QBe), 2), block((unsigned)nth);
     hipLaunchKernelGGL(k_toys_band, grid, block, sizeof(unsigned long long) * (size_t)npad, s, lo, lo_compact ? 1 : 0, hi,
                        hi_compact ? 1 : 0, band_lo, band_hi, rank, NR, u0, nqb, QB, QBe, Q, P, npad);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_poisson_draw: out[row][p][c] = draw::poisson(mu[row][c]) under the identity (seed, stream, row, p, c)
+// (nusi_plan_draw_counts): one lane per count, no lane reads another's.  n = rows P C <= NUSI_DRAW_COUNTS_MAX =
+// (2^31 - 1) 256: the grid of one launch.
+// ---------------------------------------------------------------------------
+constexpr int kDrawThreads = 256;
+
+__global__ __launch_bounds__(kDrawThreads) void k_poisson_draw(const double* __restrict__ mu, double* __restrict__ out, int C,
+                                                               int P, unsigned long long n, unsigned long long seed,
+                                                               unsigned stream)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * kDrawThreads + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long rp = i / (unsigned)C;
+    const unsigned c = (unsigned)(i - rp * (unsigned)C), row = (unsigned)(rp / (unsigned)P), p = (unsigned)(rp - (unsigned long long)row * (unsigned)P);
+    out[i] = draw::poisson(mu[(size_t)row * C + c], draw::ident(seed, stream, row, p, c));
+}
+
+hipError_t launch_poisson_draw(const double* mu, int rows, int C, int P, unsigned long long seed, unsigned stream, double* out,
+                               hipStream_t s)
+{
+    if (rows <= 0 || C <= 0 || P <= 0) return hipSuccess;
+    const unsigned long long n = (unsigned long long)rows * P * C, nb = (n + kDrawThreads - 1) / kDrawThreads;
+    if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_poisson_draw, dim3((unsigned)nb), dim3(kDrawThreads), 0, s, mu, out, C, P, n, seed, stream);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_inject<NC>: the calibration call (nusi_plan_response_inject), NC = 1 + K = 1 .. 4, on k_toys_limit<NC>'s block
+// shape, units and p-slices.  Per (t, q) and toy p the datum of lane c is DRAWN where it is fitted: draw::poisson of
+// mu_inj[c] = a_inj[q] s_c + sum_j theta_inj[j] T_jc + B_c (the conditional fit's order for mu) under the identity
+// (seed, stream = t, row = q, p, c), which is global -- no chunk, slice or launch shape enters.  Then, against that
+// datum: the best fit (k_detector_profile's / k_detector_fit's iteration, COPIED operation for operation as in
+// k_toys_limit), ONE conditional fit at a_test[q] from the header's cold start (k_conditional_fit's iteration and word,
+// copied; K = 0: a single evaluation, word 0), lambda as k_interval forms it, and the statistic under `mode`.  No LDS.
+// theta_hat_0 goes to row[P] + p of o.theta and the statistic to o.stat (row: the spectrum's place in the chunk's
+// scratch, compact, or t Q + q in the caller's [ntab][Q][P]) -- k_toys_band then selects from them, theta_hat_0 on its
+// lo side and the statistic on hi --, the two words to words[t][q][p][2], the counts to tally[t][q][4] and exceed[t][q]
+// (integer atomics; the caller zeroes both), the drawn counts to data[t][q][p][C].
+// ---------------------------------------------------------------------------
+struct InjectOut {
+    double *theta, *stat;   // theta_hat_0 and the statistic per toy, or nullptr
+    int theta_compact, stat_compact;
+    int* words;             // [ntab][Q][P][2] or nullptr
+    int* tally;             // [ntab][Q][4] or nullptr
+    int* exceed;            // [ntab][Q] or nullptr (with qobs)
+    double* data;           // [ntab][Q][P][C] or nullptr
+};
+struct InjectIn {
+    const double *a_inj, *a_test, *qobs;   // [Q], [Q], [ntab][Q] (qobs: nullptr without exceed)
+    double th_inj[NUSI_FIT_TEMPLATES_MAX + 1];   // [0] unused
+    unsigned long long seed;
+    int mode;
+};
+
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict__ R, const double* __restrict__ S,
+                                                       const double* __restrict__ bg, const double* __restrict__ T,
+                                                       const FitPrior pr, const double ku, const InjectIn ii, const InjectOut o,
+                                                       int u0, int nqb, int M, int C, int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    constexpr int KT = NC - 1, KA = KT > 0 ? KT : 1;
+    const int tid = (int)threadIdx.x, u = u0 + (int)blockIdx.x, t = u / nqb;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, qb0 = (u - t * nqb) * QB, q = qb0 + grp;
+    const int cc = c < C ? c : C - 1, qc = q < Q ? q : Q - 1;
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)qc * M;
+    const bool in = c < C;
+    int p0, p1;
+    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
+    double X[NC];
+    {
+        double s0 = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
+        X[0] = in ? s0 : 0.0;
+    }
+#pragma unroll
+    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
+    const double b = in ? bg[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+    double S1h[NC];   // tree(X_j): the data do not enter
+#pragma unroll
+    for (int j = 0; j < NC; ++j) S1h[j] = X[j];
+    det_butterfly(S1h, lgC, add);
+    const size_t rq = (size_t)t * Q + qc;                     // the spectrum's row of the call's arrays
+    const size_t rc = (size_t)(u - u0) * QB + grp;            // ... and of the chunk's scratch
+    const size_t rth = (o.theta_compact ? rc : rq) * P, rst = (o.stat_compact ? rc : rq) * P;
+    const double atest = ii.a_test[qc];
+    const double qobs = ii.qobs ? ii.qobs[rq] : __builtin_nan("");
+    // the expectation the toys are drawn from (padding lanes: 0, which draws nothing)
+    double mu_inj = ii.a_inj[qc] * X[0];
+#pragma unroll
+    for (int j = 1; j < NC; ++j) mu_inj = mu_inj + ii.th_inj[j] * X[j];
+    mu_inj = mu_inj + b;
+    const double asig = atest * X[0];   // the held term of the conditional fit's den
+    bool supt = false;                  // a live template supports the bin
+    int nlt = 0;                        // the live templates
+#pragma unroll
+    for (int i = 0; i < KT; ++i) {
+        if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) supt = true;
+        nlt += S1h[i + 1] > 0.0 ? 1 : 0;
+    }
+
+#pragma unroll 1
+    for (int p = p0; p < p1; ++p) {
+        // (the expectation through an opaque copy: the sampler's set-up is formed per toy and not held across the fits)
+        double mup = mu_inj;
+        asm volatile("" : "+v"(mup));
+        const double d = in ? draw::poisson(mup, draw::ident(ii.seed, (unsigned)t, (unsigned)qc, (unsigned)p, (unsigned)c)) : 0.0;
+        if (o.data && in && q < Q) o.data[(rq * P + p) * C + c] = d;
+
+        // ---- the best fit --------------------------------------------------------------------------------------------
+        double thh[NC], muh;
+        int sth;
+        if constexpr (NC == 1) {
+            // --- k_detector_profile's iteration, copied (one chain) ---
+            auto max = [](double x, double y) { return y > x ? y : x; };
+            const double s = X[0];
+            double S1[1] = {S1h[0]}, a[1];
+            const bool act = d > 0.0 && s > 0.0;
+            bool run = S1[0] != 0.0 && (__ballot(act) & gmask) != 0;
+            int st = run ? 0 : NUSI_FIT_FLAT;
+            {
+                const double x0 = d / S1[0], x1 = b / s;
+                a[0] = act ? x0 - x1 : 0.0;
+            }
+            det_butterfly(a, lgC, max);
+            a[0] = (run && a[0] > 0.0) ? a[0] : 0.0;
+            // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
+            while (__any(run)) {
+                double v[2];
+                {
+                    double den = a[0] * s;
+                    den = den + b;
+                    const double qq = s / den;
+                    const double uu = act ? qq : 0.0;
+                    const double r = d * uu;
+                    v[0] = r;
+                    v[1] = r * uu;
+                }
+                det_butterfly(v, lgC, add);
+                {
+                    const double S2 = v[0], S3 = v[1];
+                    const double g = S1[0] - S2;
+                    const double dn = S2 - S1[0];
+                    const double an = a[0] + dn / S3;
+                    if (run) {
+                        ++st;
+                        if (!(g < 0.0)) {
+                            run = false;
+                            if (a[0] == 0.0) st |= NUSI_FIT_BOUNDARY;
+                        } else if (!(an > a[0])) {
+                            run = false;
+                        } else {
+                            a[0] = an;
+                            if ((st & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
+                                run = false;
+                                st |= NUSI_FIT_NOT_CONVERGED;
+                            }
+                        }
+                    }
+                }
+            }
+            double m = a[0] * s;
+            m = m + b;
+            if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st |= NUSI_FIT_INFINITE;
+            thh[0] = a[0];
+            muh = m;
+            sth = st;
+        } else {
+            // --- k_detector_fit's iteration, copied ---
+            constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
+            double S1[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) S1[j] = S1h[j];
+            bool live[NC];
+            live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
+            bool sup = b > 0.0;
+            int nl = 0;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                if (j > 0) live[j] = S1[j] > 0.0;
+                sup = sup || (live[j] && X[j] > 0.0);
+                nl += live[j] ? 1 : 0;
+            }
+            const bool act = d > 0.0 && sup;
+            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
+            det_butterfly(dsum, lgC, add);
+            det_butterfly(dmin, lgC, min);
+            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+            double th[NC], the[NC], pp[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const double x = D0 / ((double)nl * S1[j]);
+                th[j] = live[j] ? x : 0.0;
+                the[j] = th[j];
+                pp[j] = 0.0;
+            }
+            double tt = 1.0;
+            int st = 0, steps = 0, halv = 0, trials = 0;
+            bool run = true, first = true, quad = false;
+            // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
+            while (__any(run)) {
+                double v[NS];
+                double den = the[0] * X[0];
+#pragma unroll
+                for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
+                den = den + b;
+                const double wq0 = d / den;
+                const double wq = act ? wq0 : 0.0;
+                const double r0 = wq / den;
+                const double r = act ? r0 : 0.0;
+                {
+                    int i = NC;
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) {
+                        v[j] = X[j] * wq;
+                        const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
+#pragma unroll
+                        for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
+                    }
+                }
+                det_butterfly(v, lgC, add);
+                const bool bad = any(act && !(den > 0.0));
+                if (run) {
+                    double g[NC];
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
+                    bool ok, changed = true;
+                    if (first) {
+                        ok = !bad;
+                        if (!ok) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        }
+                    } else {
+                        double slope = 0.0;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) slope = slope + pp[j] * g[j];
+                        ok = !bad && (quad || !(slope > 0.0));
+                        if (!ok) {
+                            if (trials == NUSI_FIT_TRIALS_MAX) {
+                                run = false;
+                                st |= NUSI_FIT_NOT_CONVERGED;
+                            } else {
+                                ++trials;
+                                ++halv;
+                                tt = tt * 0.5;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * pp[j];
+                            }
+                        } else {
+                            changed = false;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
+                            ++steps;
+                        }
+                    }
+                    if (ok) {
+                        bool fs[NC], conv = true;
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) {
+                            th[j] = the[j];
+                            fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
+                            const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
+                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                            if (fs[j] && !(ag <= ku * scale)) conv = false;
+                        }
+                        if (conv) {
+                            run = false;
+                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
+                            run = false;
+                            st |= NUSI_FIT_NOT_CONVERGED;
+                        } else {
+                            first = false;
+                            // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
+                            // a component at zero that the direction pushes below leaves fs and the solve is repeated
+                            bool sing = false;
+#pragma unroll 1
+                            for (int rep = 0; rep <= NC; ++rep) {
+                                double Lm[NC][NC], Dg[NC], y[NC];
+                                sing = false;
+                                int i0 = NC;
+                                double a[NC][NC];
+#pragma unroll
+                                for (int j = 0; j < NC; ++j)
+#pragma unroll
+                                    for (int k = j; k < NC; ++k) {
+                                        const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
+                                        a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
+                                    }
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) {
+                                    double cw[NC];
+#pragma unroll
+                                    for (int j = 0; j < i; ++j) {
+                                        double x = a[i][j];
+#pragma unroll
+                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                        cw[j] = x;
+                                        Lm[i][j] = x / Dg[j];
+                                    }
+                                    double x = a[i][i];
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                                    if (!(x > 0.0)) sing = true;
+                                    Dg[i] = x;
+                                }
+#pragma unroll
+                                for (int i = 0; i < NC; ++i) {
+                                    double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                                    y[i] = x;
+                                }
+#pragma unroll
+                                for (int i = NC - 1; i >= 0; --i) {
+                                    double x = y[i] / Dg[i];
+#pragma unroll
+                                    for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * pp[k];
+                                    pp[i] = x;
+                                }
+                                if (sing) break;
+                                bool rm = false;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j)
+                                    if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
+                                        fs[j] = false;
+                                        rm = true;
+                                    }
+                                if (!rm) break;
+                            }
+                            double acc = 0.0;
+#pragma unroll
+                            for (int j = 0; j < NC; ++j)
+                                if (fs[j]) acc = acc + g[j] * pp[j];
+                            if (sing || !(acc < 0.0)) {
+                                run = false;
+                                st |= NUSI_FIT_SINGULAR;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) pp[j] = 0.0;
+                            } else {
+                                double ratio[NC];
+                                tt = 1.0;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) {
+                                    const double x = th[j] / -pp[j];
+                                    ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
+                                    if (ratio[j] < tt) tt = ratio[j];
+                                }
+                                const bool clipped = tt < 1.0;
+                                quad = !clipped && -acc <= dq;
+                                trials = 0;
+#pragma unroll
+                                for (int j = 0; j < NC; ++j) {
+                                    const double x = th[j] + tt * pp[j];
+                                    the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            double m = th[0] * X[0];
+#pragma unroll
+            for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
+            m = m + b;
+            if (!live[0])
+                st |= NUSI_FIT_FLAT;
+            else if (th[0] == 0.0)
+                st |= NUSI_FIT_BOUNDARY;
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+                if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
+            if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
+            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) thh[j] = th[j];
+            muh = m;
+            sth = st;
+        }
+
+        // ---- the conditional fit at a_test, from the header's cold start ------------------------------------------------
+        double th[KA];
+        int stc = 0;
+        if constexpr (KT > 0) {
+            // --- k_conditional_fit's iteration, copied (the free components indexed i = j - 1) ---
+            constexpr int NS = KT + KT * (KT + 1) / 2;
+            const bool sup = b > 0.0 || (atest > 0.0 && X[0] > 0.0) || supt;
+            const bool act = d > 0.0 && sup;
+            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};
+            det_butterfly(dsum, lgC, add);
+            det_butterfly(dmin, lgC, min);
+            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
+            double the[KT], pp[KT];
+#pragma unroll
+            for (int i = 0; i < KT; ++i) {
+                const double x = D0 / ((double)nlt * S1h[i + 1]);
+                th[i] = S1h[i + 1] > 0.0 ? x : 0.0;
+                the[i] = th[i];
+                pp[i] = 0.0;
+            }
+            double tt = 1.0;
+            int steps = 0, halv = 0, trials = 0;
+            bool run = true, first = true, quad = false;
+            while (__any(run)) {
+                double v[NS];
+                double den = asig;
+#pragma unroll
+                for (int i = 0; i < KT; ++i) den = den + the[i] * X[i + 1];
+                den = den + b;
+                const double wq0 = d / den;
+                const double wq = act ? wq0 : 0.0;
+                const double r0 = wq / den;
+                const double r = act ? r0 : 0.0;
+                {
+                    int i = KT;
+#pragma unroll
+                    for (int j = 0; j < KT; ++j) {
+                        v[j] = X[j + 1] * wq;
+                        const double xr = X[j + 1] * r;
+#pragma unroll
+                        for (int k = j; k < KT; ++k) v[i++] = xr * X[k + 1];
+                    }
+                }
+                det_butterfly(v, lgC, add);
+                const bool bad = any(act && !(den > 0.0));
+                if (run) {
+                    double g[KT];
+#pragma unroll
+                    for (int j = 0; j < KT; ++j) g[j] = (S1h[j + 1] - v[j]) + pr.w[j + 1] * (the[j] - pr.m[j + 1]);
+                    bool ok, changed = true;
+                    if (first) {
+                        ok = !bad;
+                        if (!ok) {
+                            run = false;
+                            stc |= NUSI_FIT_NOT_CONVERGED;
+                        }
+                    } else {
+                        double slope = 0.0;
+#pragma unroll
+                        for (int j = 0; j < KT; ++j) slope = slope + pp[j] * g[j];
+                        ok = !bad && (quad || !(slope > 0.0));
+                        if (!ok) {
+                            if (trials == NUSI_FIT_TRIALS_MAX) {
+                                run = false;
+                                stc |= NUSI_FIT_NOT_CONVERGED;
+                            } else {
+                                ++trials;
+                                ++halv;
+                                tt = tt * 0.5;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) the[j] = th[j] + tt * pp[j];
+                            }
+                        } else {
+                            changed = false;
+#pragma unroll
+                            for (int j = 0; j < KT; ++j) changed = changed || the[j] != th[j];
+                            ++steps;
+                        }
+                    }
+                    if (ok) {
+                        bool fs[KT], conv = true;
+#pragma unroll
+                        for (int j = 0; j < KT; ++j) {
+                            th[j] = the[j];
+                            fs[j] = S1h[j + 1] > 0.0 && (th[j] > 0.0 || g[j] < 0.0);
+                            const double sc = (S1h[j + 1] + v[j]) + pr.w[j + 1] * (th[j] + pr.m[j + 1]);
+                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
+                            if (fs[j] && !(ag <= ku * sc)) conv = false;
+                        }
+                        if (conv) {
+                            run = false;
+                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
+                            run = false;
+                            stc |= NUSI_FIT_NOT_CONVERGED;
+                        } else {
+                            first = false;
+                            bool sing = false;
+#pragma unroll 1
+                            for (int rep = 0; rep <= KT; ++rep) {
+                                double Lm[KT][KT], Dg[KT], y[KT];
+                                sing = false;
+                                int i0 = KT;
+                                double hm[KT][KT];
+#pragma unroll
+                                for (int j = 0; j < KT; ++j)
+#pragma unroll
+                                    for (int k = j; k < KT; ++k) {
+                                        const double hv = v[i0++] + (j == k ? pr.w[j + 1] : 0.0);
+                                        hm[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
+                                    }
+#pragma unroll
+                                for (int i = 0; i < KT; ++i) {
+                                    double cw[KT];
+#pragma unroll
+                                    for (int j = 0; j < i; ++j) {
+                                        double x = hm[i][j];
+#pragma unroll
+                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
+                                        cw[j] = x;
+                                        Lm[i][j] = x / Dg[j];
+                                    }
+                                    double x = hm[i][i];
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
+                                    if (!(x > 0.0)) sing = true;
+                                    Dg[i] = x;
+                                }
+#pragma unroll
+                                for (int i = 0; i < KT; ++i) {
+                                    double x = fs[i] ? -g[i] : 0.0;
+#pragma unroll
+                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
+                                    y[i] = x;
+                                }
+#pragma unroll
+                                for (int i = KT - 1; i >= 0; --i) {
+                                    double x = y[i] / Dg[i];
+#pragma unroll
+                                    for (int k = i + 1; k < KT; ++k) x = x - Lm[k][i] * pp[k];
+                                    pp[i] = x;
+                                }
+                                if (sing) break;
+                                bool rm = false;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j)
+                                    if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
+                                        fs[j] = false;
+                                        rm = true;
+                                    }
+                                if (!rm) break;
+                            }
+                            double acc = 0.0;
+#pragma unroll
+                            for (int j = 0; j < KT; ++j)
+                                if (fs[j]) acc = acc + g[j] * pp[j];
+                            if (sing || !(acc < 0.0)) {
+                                run = false;
+                                stc |= NUSI_FIT_SINGULAR;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) pp[j] = 0.0;
+                            } else {
+                                double ratio[KT];
+                                tt = 1.0;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) {
+                                    const double x = th[j] / -pp[j];
+                                    ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
+                                    if (ratio[j] < tt) tt = ratio[j];
+                                }
+                                const bool clipped = tt < 1.0;
+                                quad = !clipped && -acc <= dq;
+                                trials = 0;
+#pragma unroll
+                                for (int j = 0; j < KT; ++j) {
+                                    const double x = th[j] + tt * pp[j];
+                                    the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            stc |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+        } else {
+            th[0] = 0.0;
+        }
+        double mu = asig;
+#pragma unroll
+        for (int i = 0; i < KT; ++i) mu = mu + th[i] * X[i + 1];
+        mu = mu + b;
+        if constexpr (KT > 0) {
+#pragma unroll
+            for (int i = 0; i < KT; ++i)
+                if (th[i] == 0.0) stc |= NUSI_FIT_ZERO << (i + 1);
+            if (any(in && d > 0.0 && mu == 0.0)) stc |= NUSI_FIT_INFINITE;
+        }
+
+        // ---- lambda from ratios against the best fit's counts (k_interval's), and the statistic -----------------------
+        double lv[1];
+        {
+            const bool lact = in && d > 0.0 && muh > 0.0;
+            const double dmu = mu - muh;
+            const double ratio = mu / muh;
+            const double lr = ratio > 0.0 ? nm::log_i(ratio) : -__builtin_inf();
+            const double pl = d * lr;
+            const double tl = dmu - pl;
+            lv[0] = lact ? tl : dmu;
+        }
+        det_butterfly(lv, lgC, add);
+        double lam = lv[0];
+#pragma unroll
+        for (int j = 0; j < KT; ++j)
+            if (pr.w[j + 1] > 0.0) {
+                const double dj = th[j] - thh[(j + 1) < NC ? j + 1 : 0];
+                const double sj = (th[j] - pr.m[j + 1]) + (thh[(j + 1) < NC ? j + 1 : 0] - pr.m[j + 1]);
+                const double pd = ((0.5 * pr.w[j + 1]) * dj) * sj;
+                lam = lam + pd;
+            }
+        double stat = lam > 0.0 ? 2.0 * lam : 0.0, th0 = thh[0];
+        if ((ii.mode == 1 && th0 > atest) || (ii.mode == 2 && th0 < atest)) stat = 0.0;
+        const bool nofit = (sth & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) != 0;
+        const bool nocond = (stc & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) != 0;
+        if (nofit) th0 = __builtin_nan("");
+        if (nofit || nocond) stat = __builtin_nan("");
+        if (c == 0 && q < Q) {
+            if (o.theta) o.theta[rth + p] = th0;
+            if (o.stat) o.stat[rst + p] = stat;
+            if (o.words) {
+                o.words[(rq * P + p) * 2] = sth;
+                o.words[(rq * P + p) * 2 + 1] = stc;
+            }
+            if (o.tally) {
+                int* ty = o.tally + rq * 4;
+                if (nofit) atomicAdd(ty + 0, 1);
+                if (nocond && !nofit) atomicAdd(ty + 1, 1);
+                if (sth & (NUSI_FIT_BOUNDARY | NUSI_FIT_FLAT)) atomicAdd(ty + 2, 1);
+                if (sth & NUSI_FIT_INFINITE) atomicAdd(ty + 3, 1);
+            }
+            if (o.exceed && stat >= qobs) atomicAdd(o.exceed + rq, 1);
+        }
+    }
+}
+
+hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int Q, const double* a_inj, const double* a_test,
+                         const double* th_inj, const double* qobs, int P, unsigned long long seed, int mode, const double* bg,
+                         int C, int K, const double* T, const double* pm, const double* pw, int u0, int nu, int pslices,
+                         double* theta, bool theta_compact, double* stat, bool stat_compact, int* words, int* tally, int* exceed,
+                         double* data, hipStream_t s)
+{
+    if (nu <= 0 || Q <= 0 || P <= 0) return hipSuccess;
+    const int lg = ceil_log2(C), QB = kEvThreads >> lg, nqb = (Q + QB - 1) / QB;
+    FitPrior pr;
+    InjectIn ii{a_inj, a_test, qobs, {}, seed, mode};
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
+        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
+        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
+        ii.th_inj[j] = (j >= 1 && j <= K) ? th_inj[j - 1] : 0.0;
+    }
+    const double ku = (double)(2 * (lg + K) + 18) * 0x1p-53;    // kappa(C, K) u (include/nusi.h)
+    const InjectOut o{theta, stat, theta_compact ? 1 : 0, stat_compact ? 1 : 0, words, tally, exceed, data};
+    const dim3 grid((unsigned)nu, 1, (unsigned)pslices), block(kEvThreads);
+    const int M = g.T + 1;
+    switch (K) {
+    case 0: hipLaunchKernelGGL((k_inject<1>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nqb, M, C, lg, Q, P); break;
+    case 1: hipLaunchKernelGGL((k_inject<2>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nqb, M, C, lg, Q, P); break;
+    case 2: hipLaunchKernelGGL((k_inject<3>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nqb, M, C, lg, Q, P); break;
+    case 3: hipLaunchKernelGGL((k_inject<4>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nqb, M, C, lg, Q, P); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

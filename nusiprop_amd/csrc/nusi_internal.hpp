@@ -202,6 +202,22 @@ hipError_t launch_toys_limit(const GridDev& g, const double* R, const double* S,
                              bool hi_compact, int* words, int* tally, hipStream_t s);
 hipError_t launch_toys_band(int C, int Q, int P, int u0, int nu, const double* lo, bool lo_compact, const double* hi,
                             bool hi_compact, double* band_lo, double* band_hi, const int* rank, int NR, hipStream_t s);
+// k_poisson_draw: out[row][p][c] = a Poisson count around mu[row][c] under the identity (seed, stream, row, p, c) of
+// include/nusi.h ("Drawing counts"); mu [rows][C] and out [rows][P][C] in device memory, rows P C <= NUSI_DRAW_COUNTS_MAX
+hipError_t launch_poisson_draw(const double* mu, int rows, int C, int P, unsigned long long seed, unsigned stream, double* out,
+                               hipStream_t s);
+// k_inject<1 + K>: the calibration call (include/nusi.h nusi_plan_response_inject) on launch_toys_limit's units u0 ..
+// u0 + nu - 1 and p-slices: per (t, q, p) a toy drawn from a_inj[q] s + sum_j th_inj[j] T_j + bg under (seed, stream = t,
+// row = q, p, c), its best fit, the conditional fit at a_test[q] and the statistic under `mode`.  a_inj, a_test [Q] and
+// qobs [ntab][Q] (or nullptr) in device memory, th_inj [K] on the host.  theta_hat_0 and the statistic per toy go to
+// theta / stat (nullptr: not kept; compact: the chunk's scratch [nu QB][P], else the call's [ntab][Q][P]) -- the layout
+// launch_toys_band selects from --, the words to words [ntab][Q][P][2], the drawn counts to data [ntab][Q][P][C], and the
+// counts are ADDED to tally [ntab][Q][4] and exceed [ntab][Q] (any may be nullptr).
+hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int Q, const double* a_inj, const double* a_test,
+                         const double* th_inj, const double* qobs, int P, unsigned long long seed, int mode, const double* bg,
+                         int C, int K, const double* T, const double* pm, const double* pw, int u0, int nu, int pslices,
+                         double* theta, bool theta_compact, double* stat, bool stat_compact, int* words, int* tally, int* exceed,
+                         double* data, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

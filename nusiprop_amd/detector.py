@@ -35,6 +35,14 @@ step -- both the header's text operation for operation::
 
     theta0, nll0, mu0, st0 = plan.fit_fixed(R, spectra, 0.0, data=counts)     # fit_fixed_host on the CPU
     lo, hi, theta_hat, nll_hat, st = plan.limit(R, spectra, counts, delta=2.706, which="upper")   # limit_host
+
+``draw_host`` is nusi_plan_draw_counts, the counter-based generator of Poisson counts (``philox4x32``, ``uniforms``,
+``loggam`` are its parts), every integer the GPU's with the same exp and log, and ``inject_host`` nusi_plan_response_inject:
+per table and spectrum the statistic q(a_test) on toys drawn from a_inj s + sum_j theta_inj_j T_j + B, a loop of the forms
+above over draw_host's toys::
+
+    toys = plan.draw(mu0[0, 0], 1000, seed=7)                                 # draw_host on the CPU
+    band_theta, band_q, tally, exceed = plan.inject(R, spectra, hi[0], 1000, seed=7, mode="upper", q_obs=2.706)   # inject_host
 """
 import numpy as np
 
@@ -909,6 +917,270 @@ def pseudo_data(mu, P, rng):
     if int(P) < 1:
         raise ValueError("pseudo_data: P must be >= 1")
     return np.ascontiguousarray(rng.poisson(mu, size=(int(P), mu.shape[0])), dtype=np.float64)
+
+
+# --- the generator of nusi_plan_draw_counts (include/nusi.h "Drawing counts"), operation for operation ---
+PHILOX_M0, PHILOX_M1, PHILOX_W0, PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+DRAW_INVERSION_MAX, DRAW_PTRS_ROUNDS = 255, 64
+DRAW_DATASETS_MAX = 1 << 26    # NUSI_DRAW_DATASETS_MAX
+_LOGGAM_A = (8.333333333333333e-02, -2.777777777777778e-03, 7.936507936507937e-04, -5.952380952380952e-04,
+             8.417508417508418e-04, -1.917526917526918e-03, 6.410256410256410e-03, -2.955065359477124e-02,
+             1.796443723688307e-01, -1.39243221690590e+00)
+_M32 = 0xFFFFFFFF
+
+
+def _philox(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on Python ints: the four output words."""
+    for _ in range(10):
+        p0, p1 = PHILOX_M0 * c0, PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + PHILOX_W0) & _M32, (k1 + PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10: counter (..., 4) and key (..., 2), 32-bit words (broadcast against each other), to the block
+    (..., 4) as uint32.  Ten rounds of c <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), the key
+    bumped by (0x9E3779B9, 0xBB67AE85) after each."""
+    c = np.asarray(counter, dtype=np.uint64)
+    k = np.asarray(key, dtype=np.uint64)
+    if c.shape[-1:] != (4,) or k.shape[-1:] != (2,) or np.any(c > _M32) or np.any(k > _M32):
+        raise ValueError("philox4x32: counter (..., 4) and key (..., 2) of 32-bit words")
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape) for i in range(2))
+    m32 = np.uint64(_M32)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(PHILOX_M0) * c0, np.uint64(PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(PHILOX_W0)) & m32, (k1 + np.uint64(PHILOX_W1)) & m32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def uniforms(block):
+    """The two uniforms in [0, 1) of Philox blocks (..., 4): U0 = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 and U1 the same
+    from x2, x3 -- 53 bits each, exact.  Returns (..., 2) float64."""
+    x = np.asarray(block, dtype=np.uint64)
+    if x.shape[-1:] != (4,) or np.any(x > _M32):
+        raise ValueError("uniforms: blocks (..., 4) of 32-bit words")
+    hi, lo = x[..., 0::2] >> np.uint64(5), x[..., 1::2] >> np.uint64(6)
+    return ((hi << np.uint64(26)) + lo).astype(np.float64) * 2.0 ** -53
+
+
+def _uniform2(seed, stream, row, p, c, block):
+    x = _philox(block, p * 64 + c, row, stream, seed & _M32, (seed >> 32) & _M32)
+    return (((x[0] >> 5) << 26) + (x[1] >> 6)) * 2.0 ** -53, (((x[2] >> 5) << 26) + (x[3] >> 6)) * 2.0 ** -53
+
+
+def loggam(x, log=np.log):
+    """numpy's random_loggam as include/nusi.h writes it out: log Gamma(x) for a float x > 0 by a shift up to x0 >= 7,
+    ten terms of Stirling's series in 1 / x0^2 (Horner), + 0.5 log 2 pi + (x0 - 0.5) log x0 - x0, and the shift undone
+    by subtracting logs; exactly 0 at 1 and 2.  log: a scalar function of a float."""
+    x = float(x)
+    if x == 1.0 or x == 2.0:
+        return 0.0
+    n = int(7.0 - x) if x < 7.0 else 0
+    x0 = x + float(n)
+    ix = 1.0 / x0
+    x2 = ix * ix
+    gl0 = _LOGGAM_A[9]
+    for k in range(8, -1, -1):
+        gl0 = gl0 * x2
+        gl0 = gl0 + _LOGGAM_A[k]
+    gl = gl0 / x0
+    gl = gl + 0.5 * 1.8378770664093453
+    gl = gl + (x0 - 0.5) * float(log(x0))
+    gl = gl - x0
+    for _ in range(n):
+        x0 = x0 - 1.0
+        gl = gl - float(log(x0))
+    return gl
+
+
+def _draw_one(mu, seed, stream, row, p, c, exp, log, rounds=None):
+    """One Poisson(mu) count of the identity (seed, stream, row, p, c), as a float.  rounds: None, or a list that
+    receives the number of blocks the draw consumed."""
+    used = 0
+    try:
+        if mu == 0.0:
+            return 0.0
+        if not mu > 0.0 or mu == np.inf:
+            return float("nan")
+        if mu < 10.0:
+            u, _ = _uniform2(seed, stream, row, p, c, 0)
+            used = 1
+            pk = float(exp(-mu))
+            F, k = pk, 0.0
+            while not u < F:
+                k = k + 1.0
+                pk = (pk * mu) / k
+                Fn = F + pk
+                if (Fn == F and k > mu) or k == float(DRAW_INVERSION_MAX):
+                    break
+                F = Fn
+            return k
+        slam, loglam = float(np.sqrt(mu)), float(log(mu))
+        b = 0.931 + 2.53 * slam
+        a = -0.059 + 0.02483 * b
+        invalpha = 1.1239 + 1.1328 / (b - 3.4)
+        vr = 0.9277 - 3.6224 / (b - 2.0)
+        lia = float(log(invalpha))
+        k = 0.0
+        for r in range(DRAW_PTRS_ROUNDS):
+            u0, V = _uniform2(seed, stream, row, p, c, r)
+            used = r + 1
+            U = u0 - 0.5
+            us = 0.5 - abs(U)
+            if us == 0.0:
+                continue
+            x = (2.0 * a) / us
+            x = x + b
+            x = x * U
+            x = x + mu
+            x = x + 0.43
+            k = float(np.floor(x))
+            if us >= 0.07 and V <= vr:
+                return k
+            if k < 0.0 or (us < 0.013 and V > us):
+                continue
+            lhs = (float(log(V)) if V > 0.0 else -np.inf) + lia
+            y = a / (us * us)
+            y = y + b
+            lhs = lhs - float(log(y))
+            rhs = -mu + k * loglam
+            rhs = rhs - loggam(k + 1.0, log)
+            if lhs <= rhs:
+                return k
+        return k if k > 0.0 else 0.0
+    finally:
+        if rounds is not None:
+            rounds.append(used)
+
+
+def draw_host(mu, P, seed, stream=0, exp=np.exp, log=np.log, rounds=None):
+    """nusi_plan_draw_counts on the CPU: P Poisson counts around every expectation of mu (rows, C) or (C,), by the
+    generator include/nusi.h defines, operation for operation -- inversion below mu = 10, Hoermann's PTRS from there, the
+    bits from Philox4x32-10 under the key ``seed`` (64 bits) and the counter (block, p 64 + c, row, stream).  Returns
+    float64 counts (rows, P, C), or (P, C) for a vector; entry [row, p, c] depends on (seed, stream, row, p, c) and
+    mu[row, c] alone.  exp, log: scalar functions of a float (the oracle's ora_exp, ora_log give Plan.draw's integers).
+    rounds: None, or a list that receives the blocks each draw consumed, in the output's order."""
+    m = np.asarray(mu, dtype=np.float64)
+    one = m.ndim == 1
+    if one:
+        m = m[None]
+    if m.ndim != 2 or m.shape[0] < 1 or not 1 <= m.shape[1] <= BINS_MAX:
+        raise ValueError("draw_host: mu must have shape (C,) or (rows, C), 1 <= C <= %d, got %s" % (BINS_MAX, m.shape))
+    if not np.all(np.isfinite(m)) or np.any(m < 0):
+        raise ValueError("draw_host: an expectation is negative or not finite")
+    P, seed, stream = int(P), int(seed), int(stream)
+    if not 1 <= P <= DRAW_DATASETS_MAX:
+        raise ValueError("draw_host: P must be 1 .. %d" % DRAW_DATASETS_MAX)
+    if not 0 <= seed < 2 ** 64 or not 0 <= stream < 2 ** 32:
+        raise ValueError("draw_host: seed must fit 64 bits and stream 32, unsigned")
+    rows, C = m.shape
+    out = np.zeros((rows, P, C))
+    with np.errstate(all="ignore"):
+        for row in range(rows):
+            for p in range(P):
+                for c in range(C):
+                    out[row, p, c] = _draw_one(float(m[row, c]), seed, stream, row, p, c, exp, log, rounds)
+    return out[0] if one else out
+
+
+INJECT_TWO_SIDED, INJECT_UPPER, INJECT_DISCOVERY = 0, 1, 2     # NUSI_INJECT_*
+
+
+def inject_tally(words):
+    """tally[..., 4] of nusi_plan_response_inject from the words (..., P, 2): the toys whose best fit failed
+    (FIT_NOT_CONVERGED | FIT_SINGULAR in word 0), whose conditional fit failed (word 1) and whose best fit did not, whose
+    best fit ends at theta_hat_0 = 0 (FIT_BOUNDARY | FIT_FLAT) and whose best fit is FIT_INFINITE (int32)."""
+    w = np.asarray(words)
+    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
+    nofit, nocond = (w[..., 0] & fail) != 0, (w[..., 1] & fail) != 0
+    cols = [nofit, nocond & ~nofit, (w[..., 0] & (FIT_BOUNDARY | FIT_FLAT)) != 0, (w[..., 0] & FIT_INFINITE) != 0]
+    return np.stack([c.sum(axis=-1) for c in cols], axis=-1).astype(np.int32)
+
+
+def inject_host(R, S, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sided", ranks=None, q_obs=None,
+                templates=None, prior=None, background=None, exp=np.exp, log=np.log, raw=False):
+    """nusi_plan_response_inject on the CPU: per table t the toys draw_host(mu_inj[t], P, seed, stream=t) around
+    mu_inj[t, q] = a_inj[q] s + sum_j theta_inj[j] T_j + B, and per toy a loop of the existing host forms: the best fit
+    (fit_host; profile_host without templates), the conditional fit at a_test[q] (fit_fixed_host; without templates the
+    single evaluation events_host, word 0), lambda by limit_host's rule and stat = 2 lambda where lambda > 0, else +0.0;
+    then order_stat over the toys.
+
+    R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  a_inj, a_test (None: a_inj): a number or (Q,), finite and >= 0.
+    theta_inj: (K,), None = the prior means.  mode: "two-sided", "upper" (stat = +0.0 where theta_hat_0 > a_test),
+    "discovery" (where theta_hat_0 < a_test) or INJECT_*.  ranks: None = band_ranks(P).  q_obs: None, a number or
+    (ntab, Q).  templates, prior, background, log: as for fit_host; exp: as for draw_host.  Returns (band_theta (ntab, Q,
+    NR), band_stat (ntab, Q, NR), tally (ntab, Q, 4) int32 -- inject_tally), with q_obs also exceed (ntab, Q) int32, the
+    toys with stat >= q_obs, and with raw also (theta_all (ntab, Q, P), stat_all (ntab, Q, P), words_all (ntab, Q, P, 2)
+    int32, data_all (ntab, Q, P, C)).  A failed best fit: theta_hat_0 and stat are NaN; a failed conditional fit: stat is
+    NaN.  No axis is squeezed."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    if R.ndim == 2:
+        R = R[None]
+    if S.ndim == 1:
+        S = S[None]
+    if R.ndim != 3 or S.ndim != 2 or R.shape[1] != S.shape[1]:
+        raise ValueError("inject_host: R (.., M, C) and S (.., M) do not match: %s, %s" % (R.shape, S.shape))
+    ntab, C, Q, P = R.shape[0], R.shape[2], S.shape[0], int(P)
+    if not 1 <= P:
+        raise ValueError("inject_host: P must be >= 1")
+    md = {"two-sided": INJECT_TWO_SIDED, "upper": INJECT_UPPER, "discovery": INJECT_DISCOVERY}.get(mode, mode)
+    if md not in (0, 1, 2):
+        raise ValueError("inject_host: mode must be 'two-sided', 'upper' or 'discovery'")
+    K = 0 if templates is None else _templates(templates, C).shape[0]
+    T = np.zeros((0, C)) if K == 0 else _templates(templates, C)
+    m, w = _prior(K, prior)
+    B = np.zeros(C) if background is None else np.array(np.broadcast_to(np.asarray(background, dtype=np.float64), (C,)))
+    ai = np.array(np.broadcast_to(np.asarray(a_inj, dtype=np.float64), (Q,)))
+    at = ai if a_test is None else np.array(np.broadcast_to(np.asarray(a_test, dtype=np.float64), (Q,)))
+    ti = m[1:].copy() if theta_inj is None else np.array(np.broadcast_to(np.asarray(theta_inj, dtype=np.float64), (K,)))
+    for v in (ai, at, ti):
+        if not np.all(np.isfinite(v)) or np.any(v < 0):
+            raise ValueError("inject_host: a_inj, a_test and theta_inj must be finite and >= 0")
+    r = band_ranks(P) if ranks is None else np.asarray(ranks, dtype=np.int64).reshape(-1)
+    if np.any(r < 0) or np.any(r >= P):
+        raise ValueError("inject_host: a rank outside 0 .. %d" % (P - 1))
+    s = np.reshape(events_host(R, S), (ntab, Q, C))
+    th_all, st_all = np.full((ntab, Q, P), np.nan), np.full((ntab, Q, P), np.nan)
+    words, data_all = np.zeros((ntab, Q, P, 2), dtype=np.int32), np.zeros((ntab, Q, P, C))
+    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
+    with np.errstate(all="ignore"):
+        for t in range(ntab):
+            mu_inj = ai[:, None] * s[t]
+            for j in range(K):
+                mu_inj = mu_inj + ti[j] * T[j][None, :]
+            mu_inj = mu_inj + B[None, :]
+            data_all[t] = draw_host(mu_inj, P, seed, stream=t, exp=exp, log=log)
+            for q in range(Q):
+                for p in range(P):
+                    d = data_all[t, q, p]
+                    if K:
+                        thh, _, muh, sth = fit_host(R[t], S[q], d, T, prior=prior, background=B, log=log)
+                        thc, _, muc, stc = fit_fixed_host(R[t], S[q], at[q], d, T, prior=prior, background=B, log=log)
+                    else:
+                        ah, _, muh, sth = profile_host(R[t], S[q], d, background=B, log=log)
+                        thh, thc, stc = np.array([float(ah)]), np.array([at[q]]), 0
+                        muc = events_host(R[t], S[q], scale=at[q], background=B)
+                    lam, _ = _limit_lambda(at[q], thc[1:], muc, muh, thh[1:], (d > 0) & (muh > 0), d, m[1:], w[1:], log)
+                    stat, th0 = (2.0 * lam if lam > 0.0 else 0.0), float(thh[0])
+                    if (md == INJECT_UPPER and th0 > at[q]) or (md == INJECT_DISCOVERY and th0 < at[q]):
+                        stat = 0.0
+                    if int(sth) & fail:
+                        th0 = stat = np.nan
+                    if int(stc) & fail:
+                        stat = np.nan
+                    th_all[t, q, p], st_all[t, q, p], words[t, q, p] = th0, stat, (int(sth), int(stc))
+    out = (order_stat(th_all, r), order_stat(st_all, r), inject_tally(words))
+    if q_obs is not None:
+        qo = np.broadcast_to(np.asarray(q_obs, dtype=np.float64), (ntab, Q))
+        with np.errstate(invalid="ignore"):
+            out = out + ((st_all >= qo[..., None]).sum(axis=-1).astype(np.int32),)
+    return out + ((th_all, st_all, words, data_all) if raw else ())
 
 
 def matrix(lo, hi, aeff, migration=None, exposure=1.0):

@@ -494,8 +494,8 @@ class Plan:
         (``profile`` on a plan without templates, K = 0: theta is ahat), bit for bit; the best is the minimum under the
         key (isnan(nll), nll, q) -- detector.argbest: a NaN loses to everything, ties go to the lowest q.  Returns
         (q (P, ntab) int32, nll (P, ntab), theta (P, ntab, 1 + K), status (P, ntab) int32), the same as
-        detector.ensemble_host up to the last bits of nll's log.  The device draws no random numbers: the toys are host
-        data (detector.pseudo_data)."""
+        detector.ensemble_host up to the last bits of nll's log.  This call draws no random numbers: the toys are host
+        data (detector.pseudo_data, or ``draw``)."""
         R, C = self._folded(R, "ensemble")
         S, _ = self._spectra(spectra, None)
         d = self._datasets(datasets)
@@ -581,6 +581,124 @@ class Plan:
             vp(d_hi_all_ptr) if d_hi_all_ptr else None, vp(d_words_all_ptr) if d_words_all_ptr else None,
             vp(stream_ptr) if stream_ptr else None))
         return len(S), P, len(r)
+
+    # --- the generator (include/nusi.h "Drawing counts") ---
+    @staticmethod
+    def _expectations(mu):
+        m = np.ascontiguousarray(mu, dtype=np.float64)
+        one = m.ndim == 1
+        if one:
+            m = m[None]
+        if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+            raise ValueError("draw: mu must have shape (C,) or (rows, C), got %s" % (np.shape(mu),))
+        return m, one
+
+    def draw(self, mu, P, seed, stream=0):
+        """P Poisson pseudo-experiments around the expected counts mu (rows, C) or (C,), drawn on the GPU by the
+        counter-based generator include/nusi.h defines: counts (rows, P, C), or (P, C) for a vector, as float64.  The
+        count of (row, p, c) depends on (seed, stream, row, p, c) alone -- seed a 64-bit, stream a 32-bit unsigned
+        int -- and is detector.draw_host's, every integer.  No detector is needed; C <= 64, mu finite and >= 0."""
+        m, one = self._expectations(mu)
+        out = np.zeros((m.shape[0], int(P), m.shape[1]))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_draw_counts_host(self._h, m.ctypes.data_as(dp), m.shape[0], m.shape[1], int(P),
+                                                          int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 32 - 1),
+                                                          out.ctypes.data_as(dp)))
+        return out[0] if one else out
+
+    def draw_device(self, mu, P, seed, d_out_ptr, stream=0, stream_ptr=None):
+        """Asynchronous ``draw`` into device memory: d_out [rows][P][C] doubles (a raw pointer); mu is host data and is
+        copied.  Returns (rows, C)."""
+        m, _ = self._expectations(mu)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_draw_counts(self._h, m.ctypes.data_as(dp), m.shape[0], m.shape[1], int(P),
+                                                     int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 32 - 1),
+                                                     vp(d_out_ptr) if d_out_ptr else None,
+                                                     vp(stream_ptr) if stream_ptr else None))
+        return m.shape
+
+    # --- the calibration call (include/nusi.h nusi_plan_response_inject) ---
+    @staticmethod
+    def _mode(mode):
+        return int({"two-sided": _lib.INJECT_TWO_SIDED, "upper": _lib.INJECT_UPPER,
+                    "discovery": _lib.INJECT_DISCOVERY}.get(mode, mode))
+
+    def _inject_args(self, spectra, a_inj, theta_inj, a_test, ranks, P, q_obs, ntab):
+        S, _ = self._spectra(spectra, None)
+        Q = len(S)
+        ai = self._held("inject", a_inj, Q)
+        at = None if a_test is None else self._held("inject", a_test, Q)
+        ti = None
+        if theta_inj is not None:
+            ti = np.ascontiguousarray(np.broadcast_to(np.asarray(theta_inj, dtype=np.float64), (self.templates(),)))
+        qo = None
+        if q_obs is not None:
+            qo = np.ascontiguousarray(np.broadcast_to(np.asarray(q_obs, dtype=np.float64), (ntab, Q)))
+        return S, ai, ti, at, self._ranks(ranks, max(int(P), 1)), qo
+
+    def inject(self, R, spectra, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sided", ranks=None, q_obs=None,
+               raw=False):
+        """The distribution of the statistic q(a_test) on toys drawn from a hypothesis's own expectation, in one call on
+        the GPU.  For every table t, spectrum q and toy p < P the counts are drawn on the device from
+        a_inj[q] s + sum_j theta_inj[j] T_j + B -- ``draw`` of that expectation with stream = t at [q, p] --, fitted
+        (``fit``'s record; ``profile``'s without templates), fitted again with the signal held at a_test[q] (None: a_inj;
+        ``fit_fixed``'s record from its cold start) and stat = max(2 lambda, 0) is formed as ``limit`` forms lambda.  mode:
+        "two-sided", "upper" (stat = 0 where theta_hat_0 > a_test) or "discovery" (stat = 0 where theta_hat_0 < a_test).
+        a_inj, a_test: a number or (Q,); theta_inj: (K,), None = the templates' prior means; ranks: None =
+        detector.band_ranks(P); q_obs: None, a number or (ntab, Q).  Returns (band_theta (ntab, Q, NR), band_stat (ntab,
+        Q, NR), tally (ntab, Q, 4) int32) -- the order statistics of theta_hat_0 and of stat over the toys, NaN (a failed
+        fit) last, and the toys whose best fit failed, whose conditional fit alone failed, with theta_hat_0 = 0 and with an
+        infinite best fit --, with q_obs also exceed (ntab, Q) int32, the toys with stat >= q_obs (the p-value:
+        exceed / (P - tally[..., 0] - tally[..., 1])), and with raw also (theta_all (ntab, Q, P), stat_all (ntab, Q, P),
+        words_all (ntab, Q, P, 2) int32, data_all (ntab, Q, P, C)).  detector.inject_host is the same in numpy."""
+        R, C = self._folded(R, "inject")
+        ntab, P = R.shape[0], int(P)
+        S, ai, ti, at, r, qo = self._inject_args(spectra, a_inj, theta_inj, a_test, ranks, P, q_obs, ntab)
+        Q, NR = len(S), len(r)
+        band_th, band_st = np.full((ntab, Q, NR), np.nan), np.full((ntab, Q, NR), np.nan)
+        tally = np.zeros((ntab, Q, 4), dtype=np.int32)
+        exceed = np.zeros((ntab, Q), dtype=np.int32) if qo is not None else None
+        th_all = st_all = words = data = None
+        if raw:
+            th_all, st_all = np.full((ntab, Q, max(P, 0)), np.nan), np.full((ntab, Q, max(P, 0)), np.nan)
+            words, data = np.zeros((ntab, Q, max(P, 0), 2), dtype=np.int32), np.zeros((ntab, Q, max(P, 0), C))
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+
+        def ptr(x, t):
+            return x.ctypes.data_as(t) if x is not None else None
+        _lib.check(_lib.load().nusi_plan_response_inject_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, ai.ctypes.data_as(dp), ptr(ti, dp), ptr(at, dp), P,
+            int(seed) & (2 ** 64 - 1), self._mode(mode), ptr(r, ip) if NR else None, NR, ptr(qo, dp),
+            ptr(band_th, dp) if NR else None, ptr(band_st, dp) if NR else None, tally.ctypes.data_as(ip), ptr(exceed, ip),
+            ptr(th_all, dp), ptr(st_all, dp), ptr(words, ip), ptr(data, dp)))
+        out = (band_th, band_st, tally) + ((exceed,) if qo is not None else ())
+        return out + ((th_all, st_all, words, data) if raw else ())
+
+    def inject_device(self, d_R_ptr, ntab, spectra, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sided",
+                      ranks=None, q_obs=None, d_band_theta_ptr=None, d_band_stat_ptr=None, d_tally_ptr=None,
+                      d_exceed_ptr=None, d_theta_all_ptr=None, d_stat_all_ptr=None, d_words_all_ptr=None,
+                      d_data_all_ptr=None, stream_ptr=None):
+        """Asynchronous ``inject`` on device-resident folded matrices d_R [ntab][M][C]: the outputs are raw pointers
+        (d_band_theta, d_band_stat [ntab][Q][NR], d_theta_all, d_stat_all [ntab][Q][P] and d_data_all [ntab][Q][P][C]
+        doubles; d_tally [ntab][Q][4], d_exceed [ntab][Q] and d_words_all [ntab][Q][P][2] ints), any may be 0 / None; with
+        ranks one band is needed, and d_exceed comes with q_obs.  ranks: ints (None: detector.band_ranks(P); an empty
+        list: no band).  The other arguments are host data and are copied.  Returns (Q, NR)."""
+        S, ai, ti, at, r, qo = self._inject_args(spectra, a_inj, theta_inj, a_test, ranks, P, q_obs, int(ntab))
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        vp = ctypes.c_void_p
+
+        def ptr(x, t):
+            return x.ctypes.data_as(t) if x is not None else None
+
+        def dev(x):
+            return vp(x) if x else None
+        _lib.check(_lib.load().nusi_plan_response_inject(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), ai.ctypes.data_as(dp), ptr(ti, dp), ptr(at, dp),
+            int(P), int(seed) & (2 ** 64 - 1), self._mode(mode), ptr(r, ip) if len(r) else None, len(r), ptr(qo, dp),
+            dev(d_band_theta_ptr), dev(d_band_stat_ptr), dev(d_tally_ptr), dev(d_exceed_ptr), dev(d_theta_all_ptr),
+            dev(d_stat_all_ptr), dev(d_words_all_ptr), dev(d_data_all_ptr), dev(stream_ptr)))
+        return len(S), len(r)
 
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
