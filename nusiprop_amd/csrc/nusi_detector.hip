@@ -23,6 +23,19 @@
 //   k_inject<NC>          per (table, spectrum) P toys drawn from the injected expectation where they are fitted: the
 //                         best fit, one conditional fit and the statistic per toy; k_toys_band then selects the order
 //                         statistics of theta_hat_0 and of the statistic (nusi_plan_response_inject)
+//
+// The iterations several of these kernels run exist once, as text the kernels #include inside their bodies (not as
+// __device__ helpers, which moved the kernels' registers: DESIGN.md sec. 4, "The shared iterations"):
+//   nusi_fit_newton.inc          k_detector_fit's iteration: k_detector_fit, k_ensemble_fit, and for NC > 1 the best fit
+//                                of k_interval, k_toys_limit, k_inject
+//   nusi_profile_chain4.inc      k_detector_profile's, four chains a lane: k_detector_profile, k_ensemble_profile
+//   nusi_profile_chain1.inc      k_detector_profile's, one chain a lane: the best fit at NC = 1 of k_interval,
+//                                k_toys_limit, k_inject
+//   nusi_conditional_newton.inc  k_conditional_fit's rounds: k_conditional_fit, k_inject
+//   nusi_search_setup.inc, nusi_search_side.inc
+//                                the search for a limit: k_interval, k_toys_limit
+//   nusi_ldlt_solve.inc          the Newton direction, inside the fit's, the conditional fit's and the search's text
+//   nusi_fit_statistic.inc       the statistic's serial sum from LDS: k_detector_fit, k_conditional_fit, k_interval
 #include <hip/hip_runtime.h>
 
 #include "nusi_internal.hpp"
@@ -359,46 +372,7 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_profile(const double* _
         const double x0 = d / S1[j], x1 = b / s[j];
         a[j] = act[j] ? x0 - x1 : 0.0;
     }
-    det_butterfly(a, lgC, max);
-#pragma unroll
-    for (int j = 0; j < kEvQ; ++j) a[j] = (run[j] && a[j] > 0.0) ? a[j] : 0.0;
-    // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
-    while (__any(run[0] || run[1] || run[2] || run[3])) {
-        double v[2 * kEvQ];
-#pragma unroll
-        for (int j = 0; j < kEvQ; ++j) {
-            double den = a[j] * s[j];
-            den = den + b;
-            const double q = s[j] / den;
-            const double u = act[j] ? q : 0.0;
-            const double r = d * u;
-            v[j] = r;
-            v[kEvQ + j] = r * u;
-        }
-        det_butterfly(v, lgC, add);
-#pragma unroll
-        for (int j = 0; j < kEvQ; ++j) {
-            const double S2 = v[j], S3 = v[kEvQ + j];
-            const double g = S1[j] - S2;
-            const double dn = S2 - S1[j];
-            const double an = a[j] + dn / S3;
-            if (run[j]) {
-                ++st[j];
-                if (!(g < 0.0)) {
-                    run[j] = false;
-                    if (a[j] == 0.0) st[j] |= NUSI_FIT_BOUNDARY;
-                } else if (!(an > a[j])) {
-                    run[j] = false;
-                } else {
-                    a[j] = an;
-                    if ((st[j] & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
-                        run[j] = false;
-                        st[j] |= NUSI_FIT_NOT_CONVERGED;
-                    }
-                }
-            }
-        }
-    }
+#include "nusi_profile_chain4.inc"
 #pragma unroll
     for (int j = 0; j < kEvQ; ++j) {
         const int q = q0 + j;
@@ -459,6 +433,21 @@ constexpr int fit_lds_max(int NC)
 struct FitPrior {
     double m[NUSI_FIT_TEMPLATES_MAX + 1], w[NUSI_FIT_TEMPLATES_MAX + 1];
 };
+// a call's priors (pm, pw: K entries) as the kernels take them: template j's in slot j, zeros in the signal's slot and
+// behind slot K
+static FitPrior fit_prior(int K, const double* pm, const double* pw)
+{
+    FitPrior pr;
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
+        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
+        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
+    }
+    return pr;
+}
+// the stop rules' kappa(C, K) u and kappa_lambda(C, K) u of include/nusi.h, lg = ceil_log2(C) (the conditional fit's
+// den is as long as the fit's: the same kappa)
+static double fit_ku(int lg, int K) { return (double)(2 * (lg + K) + 18) * 0x1p-53; }
+static double fit_klu(int lg, int K) { return (double)(2 * (lg + K) + 14) * 0x1p-53; }
 
 template <int NC>
 __global__ __launch_bounds__(kEvThreads) void k_detector_fit(const double* __restrict__ R, const double* __restrict__ S,
@@ -498,207 +487,7 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_fit(const double* __res
 #pragma unroll
     for (int j = 0; j < NC; ++j) S1[j] = X[j];
     det_butterfly(S1, lgC, add);
-    bool live[NC];
-    live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
-    bool sup = b > 0.0;
-    int nl = 0;
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        if (j > 0) live[j] = S1[j] > 0.0;
-        sup = sup || (live[j] && X[j] > 0.0);
-        nl += live[j] ? 1 : 0;
-    }
-    const bool act = d > 0.0 && sup;
-    double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
-    det_butterfly(dsum, lgC, add);
-    det_butterfly(dmin, lgC, min);
-    const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-    double th[NC], the[NC], p[NC];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const double x = D0 / ((double)nl * S1[j]);
-        th[j] = live[j] ? x : 0.0;
-        the[j] = th[j];
-        p[j] = 0.0;
-    }
-    double tt = 1.0;
-    int st = 0, steps = 0, halv = 0, trials = 0;
-    bool run = true, first = true, quad = false;
-    // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
-    while (__any(run)) {
-        double v[NS];
-        double den = the[0] * X[0];
-#pragma unroll
-        for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
-        den = den + b;
-        const double wq0 = d / den;
-        const double wq = act ? wq0 : 0.0;
-        const double r0 = wq / den;
-        const double r = act ? r0 : 0.0;
-        {
-            int i = NC;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                v[j] = X[j] * wq;
-                const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
-#pragma unroll
-                for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
-            }
-        }
-        det_butterfly(v, lgC, add);
-        const bool bad = any(act && !(den > 0.0));
-        if (run) {
-            double g[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
-            bool ok, changed = true;
-            if (first) {
-                ok = !bad;
-                if (!ok) {
-                    run = false;
-                    st |= NUSI_FIT_NOT_CONVERGED;
-                }
-            } else {
-                double slope = 0.0;
-#pragma unroll
-                for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
-                ok = !bad && (quad || !(slope > 0.0));
-                if (!ok) {
-                    if (trials == NUSI_FIT_TRIALS_MAX) {
-                        run = false;
-                        st |= NUSI_FIT_NOT_CONVERGED;
-                    } else {
-                        ++trials;
-                        ++halv;
-                        tt = tt * 0.5;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
-                    }
-                } else {
-                    changed = false;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
-                    ++steps;
-                }
-            }
-            if (ok) {
-                bool fs[NC], conv = true;
-#pragma unroll
-                for (int j = 0; j < NC; ++j) {
-                    th[j] = the[j];
-                    fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
-                    const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
-                    const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                    if (fs[j] && !(ag <= ku * scale)) conv = false;
-                }
-                if (conv) {
-                    run = false;
-                } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
-                    run = false;
-                    st |= NUSI_FIT_NOT_CONVERGED;
-                } else {
-                    first = false;
-                    // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
-                    // a component at zero that the direction pushes below leaves fs and the solve is repeated
-                    bool sing = false;
-#pragma unroll 1
-                    for (int rep = 0; rep <= NC; ++rep) {
-                        double Lm[NC][NC], Dg[NC], y[NC];
-                        sing = false;
-                        int i0 = NC;
-                        double a[NC][NC];
-#pragma unroll
-                        for (int j = 0; j < NC; ++j)
-#pragma unroll
-                            for (int k = j; k < NC; ++k) {
-                                const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
-                                a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
-                            }
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) {
-                            double cw[NC];
-#pragma unroll
-                            for (int j = 0; j < i; ++j) {
-                                double x = a[i][j];
-#pragma unroll
-                                for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                cw[j] = x;
-                                Lm[i][j] = x / Dg[j];
-                            }
-                            double x = a[i][i];
-#pragma unroll
-                            for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                            if (!(x > 0.0)) sing = true;
-                            Dg[i] = x;
-                        }
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) {
-                            double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                            for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                            y[i] = x;
-                        }
-#pragma unroll
-                        for (int i = NC - 1; i >= 0; --i) {
-                            double x = y[i] / Dg[i];
-#pragma unroll
-                            for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
-                            p[i] = x;
-                        }
-                        if (sing) break;
-                        bool rm = false;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j)
-                            if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
-                                fs[j] = false;
-                                rm = true;
-                            }
-                        if (!rm) break;
-                    }
-                    double acc = 0.0;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j)
-                        if (fs[j]) acc = acc + g[j] * p[j];
-                    if (sing || !(acc < 0.0)) {
-                        run = false;
-                        st |= NUSI_FIT_SINGULAR;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) p[j] = 0.0;
-                    } else {
-                        double ratio[NC];
-                        tt = 1.0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) {
-                            const double x = th[j] / -p[j];
-                            ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
-                            if (ratio[j] < tt) tt = ratio[j];
-                        }
-                        const bool clipped = tt < 1.0;
-                        quad = !clipped && -acc <= dq;
-                        trials = 0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) {
-                            const double x = th[j] + tt * p[j];
-                            the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    double m = th[0] * X[0];
-#pragma unroll
-    for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
-    m = m + b;
-    if (!live[0])
-        st |= NUSI_FIT_FLAT;
-    else if (th[0] == 0.0)
-        st |= NUSI_FIT_BOUNDARY;
-#pragma unroll
-    for (int j = 0; j < NC; ++j)
-        if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
-    if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
-    st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#include "nusi_fit_newton.inc"
     if (in) {
         smu[grp * RS + c] = m;
         if (mu && q < Q) mu[((size_t)t * Q + q) * C + c] = m;
@@ -716,23 +505,8 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_fit(const double* __res
     __syncthreads();
     // (a block owns QB <= kEvThreads spectra)
     if (tid < QB && qb0 + tid < Q) {
-        double sum = 0.0;
-        for (int k = 0; k < C; ++k) {
-            const double mk = smu[tid * RS + k], dk = data[k];
-            double term = mk;
-            if (dk != 0.0) {
-                const double pl = dk * nm::log_i(mk);
-                term = mk - pl;
-            }
-            sum = sum + term;
-        }
-#pragma unroll
-        for (int j = 1; j < NC; ++j)
-            if (pr.w[j] > 0.0) {
-                const double dl = smu[tid * RS + C + j - 1] - pr.m[j];
-                const double pen = ((0.5 * pr.w[j]) * dl) * dl;
-                sum = sum + pen;
-            }
+        constexpr int NP = NC;
+#include "nusi_fit_statistic.inc"
         nll[(size_t)t * Q + qb0 + tid] = sum;
     }
 }
@@ -743,12 +517,8 @@ hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, cons
 {
     if (ntab <= 0 || Q <= 0) return hipSuccess;
     const DetGeom ge(C, 1, ntab, Q);
-    FitPrior pr;
-    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
-        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
-        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
-    }
-    const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;   // kappa(C, K) u (include/nusi.h)
+    const FitPrior pr = fit_prior(K, pm, pw);
+    const double ku = fit_ku(ge.lg, K);
     const dim3 grid = ge.grid, block(kEvThreads);
     const int M = g.T + 1;
     switch (K) {
@@ -764,10 +534,10 @@ hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, cons
 // The ensemble kernels (nusi_plan_response_ensemble): P data sets data[p][C] against every table and spectrum, and of
 // each (p, t) only the BEST spectrum's record (q, nll, theta, status) under the key include/nusi.h defines,
 // (isnan(nll), nll, q) compared lexicographically.  k_ensemble_profile runs k_detector_profile's iteration (no
-// templates, theta = ahat), k_ensemble_fit<NC> k_detector_fit<NC>'s, on those kernels' block shapes; their bodies are
-// COPIED here, operation for operation, and not shared: moving the existing kernels' bodies into helpers moved their
-// code objects and their timing, and they keep theirs.  det_front, det_poisson and det_butterfly are
-// the existing helpers, called as they are.
+// templates, theta = ahat), k_ensemble_fit<NC> k_detector_fit<NC>'s, on those kernels' block shapes: the iterations are
+// those kernels' own text, shared by #include (nusi_profile_chain4.inc, nusi_fit_newton.inc) and not by a helper, which
+// moved the existing kernels' code objects and their timing.  det_front, det_poisson and
+// det_butterfly are the existing helpers, called as they are.
 //
 // Grid (tables, q-slices, p-slices).  A block walks the spectrum blocks qb of its q-slice and, per spectrum block, the
 // data sets of its p-slice: the front half s = sum_n R S, the sums S1 and the templates' liveness do not depend on the
@@ -913,7 +683,6 @@ __global__ __launch_bounds__(kEvThreads) void k_ensemble_profile(const double* _
         for (int p = p0; p < p1; ++p, ++it) {
             const double* __restrict__ dat = data + (size_t)p * C;
             const double d = in ? dat[cc] : 0.0;
-            // --- k_detector_profile's iteration, copied ---
             double a[kEvQ];
             bool act[kEvQ], run[kEvQ];
             int st[kEvQ];
@@ -925,46 +694,7 @@ __global__ __launch_bounds__(kEvThreads) void k_ensemble_profile(const double* _
                 const double x0 = d / S1[j], x1 = b / s[j];
                 a[j] = act[j] ? x0 - x1 : 0.0;
             }
-            det_butterfly(a, lgC, max);
-#pragma unroll
-            for (int j = 0; j < kEvQ; ++j) a[j] = (run[j] && a[j] > 0.0) ? a[j] : 0.0;
-            // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
-            while (__any(run[0] || run[1] || run[2] || run[3])) {
-                double v[2 * kEvQ];
-#pragma unroll
-                for (int j = 0; j < kEvQ; ++j) {
-                    double den = a[j] * s[j];
-                    den = den + b;
-                    const double q = s[j] / den;
-                    const double u = act[j] ? q : 0.0;
-                    const double r = d * u;
-                    v[j] = r;
-                    v[kEvQ + j] = r * u;
-                }
-                det_butterfly(v, lgC, add);
-#pragma unroll
-                for (int j = 0; j < kEvQ; ++j) {
-                    const double S2 = v[j], S3 = v[kEvQ + j];
-                    const double g = S1[j] - S2;
-                    const double dn = S2 - S1[j];
-                    const double an = a[j] + dn / S3;
-                    if (run[j]) {
-                        ++st[j];
-                        if (!(g < 0.0)) {
-                            run[j] = false;
-                            if (a[j] == 0.0) st[j] |= NUSI_FIT_BOUNDARY;
-                        } else if (!(an > a[j])) {
-                            run[j] = false;
-                        } else {
-                            a[j] = an;
-                            if ((st[j] & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
-                                run[j] = false;
-                                st[j] |= NUSI_FIT_NOT_CONVERGED;
-                            }
-                        }
-                    }
-                }
-            }
+#include "nusi_profile_chain4.inc"
             const int buf = it & 1;
             double* rows = srow + buf * kRows;
 #pragma unroll
@@ -1062,206 +792,7 @@ __global__ __launch_bounds__(kEvThreads) __attribute__((amdgpu_waves_per_eu(NC =
         for (int pi = p0; pi < p1; ++pi, ++it) {
             const double* __restrict__ dat = data + (size_t)pi * C;
             const double d = in ? dat[cc] : 0.0;
-            // --- k_detector_fit's iteration, copied ---
-            bool live[NC];
-            live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
-            bool sup = b > 0.0;
-            int nl = 0;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                if (j > 0) live[j] = S1[j] > 0.0;
-                sup = sup || (live[j] && X[j] > 0.0);
-                nl += live[j] ? 1 : 0;
-            }
-            const bool act = d > 0.0 && sup;
-            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
-            det_butterfly(dsum, lgC, add);
-            det_butterfly(dmin, lgC, min);
-            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-            double th[NC], the[NC], p[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                const double x = D0 / ((double)nl * S1[j]);
-                th[j] = live[j] ? x : 0.0;
-                the[j] = th[j];
-                p[j] = 0.0;
-            }
-            double tt = 1.0;
-            int st = 0, steps = 0, halv = 0, trials = 0;
-            bool run = true, first = true, quad = false;
-            // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
-            while (__any(run)) {
-                double v[NS];
-                double den = the[0] * X[0];
-#pragma unroll
-                for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
-                den = den + b;
-                const double wq0 = d / den;
-                const double wq = act ? wq0 : 0.0;
-                const double r0 = wq / den;
-                const double r = act ? r0 : 0.0;
-                {
-                    int i = NC;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) {
-                        v[j] = X[j] * wq;
-                        const double xr = X[j] * r;
-#pragma unroll
-                        for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
-                    }
-                }
-                det_butterfly(v, lgC, add);
-                const bool bad = any(act && !(den > 0.0));
-                if (run) {
-                    double g[NC];
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
-                    bool ok, changed = true;
-                    if (first) {
-                        ok = !bad;
-                        if (!ok) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        }
-                    } else {
-                        double slope = 0.0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
-                        ok = !bad && (quad || !(slope > 0.0));
-                        if (!ok) {
-                            if (trials == NUSI_FIT_TRIALS_MAX) {
-                                run = false;
-                                st |= NUSI_FIT_NOT_CONVERGED;
-                            } else {
-                                ++trials;
-                                ++halv;
-                                tt = tt * 0.5;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
-                            }
-                        } else {
-                            changed = false;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
-                            ++steps;
-                        }
-                    }
-                    if (ok) {
-                        bool fs[NC], conv = true;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) {
-                            th[j] = the[j];
-                            fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
-                            const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
-                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                            if (fs[j] && !(ag <= ku * scale)) conv = false;
-                        }
-                        if (conv) {
-                            run = false;
-                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        } else {
-                            first = false;
-                            bool sing = false;
-#pragma unroll 1
-                            for (int rep = 0; rep <= NC; ++rep) {
-                                double Lm[NC][NC], Dg[NC], y[NC];
-                                sing = false;
-                                int i0 = NC;
-                                double a[NC][NC];
-#pragma unroll
-                                for (int j = 0; j < NC; ++j)
-#pragma unroll
-                                    for (int k = j; k < NC; ++k) {
-                                        const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
-                                        a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
-                                    }
-#pragma unroll
-                                for (int i = 0; i < NC; ++i) {
-                                    double cw[NC];
-#pragma unroll
-                                    for (int j = 0; j < i; ++j) {
-                                        double x = a[i][j];
-#pragma unroll
-                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                        cw[j] = x;
-                                        Lm[i][j] = x / Dg[j];
-                                    }
-                                    double x = a[i][i];
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                                    if (!(x > 0.0)) sing = true;
-                                    Dg[i] = x;
-                                }
-#pragma unroll
-                                for (int i = 0; i < NC; ++i) {
-                                    double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                                    y[i] = x;
-                                }
-#pragma unroll
-                                for (int i = NC - 1; i >= 0; --i) {
-                                    double x = y[i] / Dg[i];
-#pragma unroll
-                                    for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
-                                    p[i] = x;
-                                }
-                                if (sing) break;
-                                bool rm = false;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j)
-                                    if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
-                                        fs[j] = false;
-                                        rm = true;
-                                    }
-                                if (!rm) break;
-                            }
-                            double acc = 0.0;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j)
-                                if (fs[j]) acc = acc + g[j] * p[j];
-                            if (sing || !(acc < 0.0)) {
-                                run = false;
-                                st |= NUSI_FIT_SINGULAR;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) p[j] = 0.0;
-                            } else {
-                                double ratio[NC];
-                                tt = 1.0;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) {
-                                    const double x = th[j] / -p[j];
-                                    ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
-                                    if (ratio[j] < tt) tt = ratio[j];
-                                }
-                                const bool clipped = tt < 1.0;
-                                quad = !clipped && -acc <= dq;
-                                trials = 0;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) {
-                                    const double x = th[j] + tt * p[j];
-                                    the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            double m = th[0] * X[0];
-#pragma unroll
-            for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
-            m = m + b;
-            if (!live[0])
-                st |= NUSI_FIT_FLAT;
-            else if (th[0] == 0.0)
-                st |= NUSI_FIT_BOUNDARY;
-#pragma unroll
-            for (int j = 0; j < NC; ++j)
-                if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
-            if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
-            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#include "nusi_fit_newton.inc"
             const int buf = it & 1;
             double* rows = srow + buf * kRows;
             double term = m;   // the statistic's term of (spectrum, c), on the bin's own lane
@@ -1362,12 +893,8 @@ hipError_t launch_detector_ensemble(const GridDev& g, const double* R, int ntab,
     if (K == 0) {
         hipLaunchKernelGGL(k_ensemble_profile, grid, block, 0, s, R, S, data, bg, rec, M, C, ge.lg, Q, P);
     } else {
-        FitPrior pr;
-        for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
-            pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
-            pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
-        }
-        const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;   // kappa(C, K) u (include/nusi.h)
+        const FitPrior pr = fit_prior(K, pm, pw);
+        const double ku = fit_ku(ge.lg, K);
         switch (K) {
         case 1: hipLaunchKernelGGL((k_ensemble_fit<2>), grid, block, 0, s, R, S, data, bg, T, pr, ku, rec, M, C, ge.lg, Q, P); break;
         case 2: hipLaunchKernelGGL((k_ensemble_fit<3>), grid, block, 0, s, R, S, data, bg, T, pr, ku, rec, M, C, ge.lg, Q, P); break;
@@ -1389,9 +916,10 @@ hipError_t launch_detector_ensemble(const GridDev& g, const double* R, int ntab,
 // components 1 .. K alone, on that kernel's block shape -- lanes on (c, ONE spectrum), a round's NC + NC (NC + 1) / 2
 // sums in one det_butterfly, the logic after it redundant on a group's lanes, full exec in every butterfly -- with the
 // signal's term a s_c held in den: den_c = a s_c, + theta_j T_jc (j ascending), + B_c, the fit's order, so the
-// conditional mu at some theta has the bits the fit's mu has at (a, theta).  The body is COPIED from k_detector_fit,
-// operation for operation, and not shared (as the ensemble's is: the existing kernels keep their code objects); arrays
-// of the free components are indexed i = j - 1.  What differs is what include/nusi.h's text says differs: the support
+// conditional mu at some theta has the bits the fit's mu has at (a, theta).  The rounds are a text of their own,
+// nusi_conditional_newton.inc (shared with k_inject), operation for operation nusi_fit_newton.inc's on the free
+// components, and the Newton direction inside both is one text, nusi_ldlt_solve.inc; arrays of the free components
+// are indexed i = j - 1.  What differs is what include/nusi.h's text says differs: the support
 // rule counts the held signal (a > 0 and s_c > 0), the start shares the counts among the live templates only, nothing
 // is FLAT or BOUNDARY, and component 0 sets no ZERO bit.  LDS: k_detector_fit<1 + NC>'s, a row of mu [C] and
 // theta_1 .. theta_K per spectrum of the block: fit_lds_max(NC + 1) doubles.
@@ -1451,179 +979,26 @@ __global__ __launch_bounds__(kEvThreads) void k_conditional_fit(const double* __
     det_butterfly(dsum, lgC, add);
     det_butterfly(dmin, lgC, min);
     const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-    double th[NC], the[NC], p[NC];
+    double th[NC], the[NC], pp[NC];
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
         const double x = D0 / ((double)nl * S1[i]);
         th[i] = live[i] ? x : 0.0;
         the[i] = th[i];
-        p[i] = 0.0;
+        pp[i] = 0.0;
     }
     double tt = 1.0;
     int st = 0, steps = 0, halv = 0, trials = 0;
     bool run = true, first = true, quad = false;
-    // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
-    while (__any(run)) {
-        double v[NS];
-        double den = asig;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) den = den + the[i] * X[i];
-        den = den + b;
-        const double wq0 = d / den;
-        const double wq = act ? wq0 : 0.0;
-        const double r0 = wq / den;
-        const double r = act ? r0 : 0.0;
-        {
-            int i = NC;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                v[j] = X[j] * wq;
-                const double xr = X[j] * r;
-#pragma unroll
-                for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
-            }
-        }
-        det_butterfly(v, lgC, add);
-        const bool bad = any(act && !(den > 0.0));
-        if (run) {
-            double g[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j + 1] * (the[j] - pr.m[j + 1]);
-            bool ok, changed = true;
-            if (first) {
-                ok = !bad;
-                if (!ok) {
-                    run = false;
-                    st |= NUSI_FIT_NOT_CONVERGED;
-                }
-            } else {
-                double slope = 0.0;
-#pragma unroll
-                for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
-                ok = !bad && (quad || !(slope > 0.0));
-                if (!ok) {
-                    if (trials == NUSI_FIT_TRIALS_MAX) {
-                        run = false;
-                        st |= NUSI_FIT_NOT_CONVERGED;
-                    } else {
-                        ++trials;
-                        ++halv;
-                        tt = tt * 0.5;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
-                    }
-                } else {
-                    changed = false;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
-                    ++steps;
-                }
-            }
-            if (ok) {
-                bool fs[NC], conv = true;
-#pragma unroll
-                for (int j = 0; j < NC; ++j) {
-                    th[j] = the[j];
-                    fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
-                    const double sc = (S1[j] + v[j]) + pr.w[j + 1] * (th[j] + pr.m[j + 1]);
-                    const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                    if (fs[j] && !(ag <= ku * sc)) conv = false;
-                }
-                if (conv) {
-                    run = false;
-                } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
-                    run = false;
-                    st |= NUSI_FIT_NOT_CONVERGED;
-                } else {
-                    first = false;
-                    // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
-                    // a component at zero that the direction pushes below leaves fs and the solve is repeated
-                    bool sing = false;
-#pragma unroll 1
-                    for (int rep = 0; rep <= NC; ++rep) {
-                        double Lm[NC][NC], Dg[NC], y[NC];
-                        sing = false;
-                        int i0 = NC;
-                        double h[NC][NC];
-#pragma unroll
-                        for (int j = 0; j < NC; ++j)
-#pragma unroll
-                            for (int k = j; k < NC; ++k) {
-                                const double hv = v[i0++] + (j == k ? pr.w[j + 1] : 0.0);
-                                h[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
-                            }
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) {
-                            double cw[NC];
-#pragma unroll
-                            for (int j = 0; j < i; ++j) {
-                                double x = h[i][j];
-#pragma unroll
-                                for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                cw[j] = x;
-                                Lm[i][j] = x / Dg[j];
-                            }
-                            double x = h[i][i];
-#pragma unroll
-                            for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                            if (!(x > 0.0)) sing = true;
-                            Dg[i] = x;
-                        }
-#pragma unroll
-                        for (int i = 0; i < NC; ++i) {
-                            double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                            for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                            y[i] = x;
-                        }
-#pragma unroll
-                        for (int i = NC - 1; i >= 0; --i) {
-                            double x = y[i] / Dg[i];
-#pragma unroll
-                            for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
-                            p[i] = x;
-                        }
-                        if (sing) break;
-                        bool rm = false;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j)
-                            if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
-                                fs[j] = false;
-                                rm = true;
-                            }
-                        if (!rm) break;
-                    }
-                    double acc = 0.0;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j)
-                        if (fs[j]) acc = acc + g[j] * p[j];
-                    if (sing || !(acc < 0.0)) {
-                        run = false;
-                        st |= NUSI_FIT_SINGULAR;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) p[j] = 0.0;
-                    } else {
-                        double ratio[NC];
-                        tt = 1.0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) {
-                            const double x = th[j] / -p[j];
-                            ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
-                            if (ratio[j] < tt) tt = ratio[j];
-                        }
-                        const bool clipped = tt < 1.0;
-                        quad = !clipped && -acc <= dq;
-                        trials = 0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) {
-                            const double x = th[j] + tt * p[j];
-                            the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                        }
-                    }
-                }
-            }
-        }
-    }
+#define CF_N NC
+#define CF_X(i) X[i]
+#define CF_S1(i) S1[i]
+#define CF_LIVE(i) live[i]
+#include "nusi_conditional_newton.inc"
+#undef CF_N
+#undef CF_X
+#undef CF_S1
+#undef CF_LIVE
     double m = asig;
 #pragma unroll
     for (int i = 0; i < NC; ++i) m = m + th[i] * X[i];
@@ -1651,23 +1026,8 @@ __global__ __launch_bounds__(kEvThreads) void k_conditional_fit(const double* __
     __syncthreads();
     // (a block owns QB <= kEvThreads spectra)
     if (tid < QB && qb0 + tid < Q) {
-        double sum = 0.0;
-        for (int k = 0; k < C; ++k) {
-            const double mk = smu[tid * RS + k], dk = data[k];
-            double term = mk;
-            if (dk != 0.0) {
-                const double pl = dk * nm::log_i(mk);
-                term = mk - pl;
-            }
-            sum = sum + term;
-        }
-#pragma unroll
-        for (int i = 0; i < NC; ++i)
-            if (pr.w[i + 1] > 0.0) {
-                const double dl = smu[tid * RS + C + i] - pr.m[i + 1];
-                const double pen = ((0.5 * pr.w[i + 1]) * dl) * dl;
-                sum = sum + pen;
-            }
+        constexpr int NP = NC + 1;   // (NC counts the templates alone here)
+#include "nusi_fit_statistic.inc"
         nll[(size_t)t * Q + qb0 + tid] = sum;
     }
 }
@@ -1678,12 +1038,8 @@ hipError_t launch_conditional_fit(const GridDev& g, const double* R, int ntab, c
 {
     if (ntab <= 0 || Q <= 0) return hipSuccess;
     const DetGeom ge(C, 1, ntab, Q);
-    FitPrior pr;
-    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
-        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
-        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
-    }
-    const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;   // kappa(C, K) u: den is as long as the fit's (include/nusi.h)
+    const FitPrior pr = fit_prior(K, pm, pw);
+    const double ku = fit_ku(ge.lg, K);
     const dim3 grid = ge.grid, block(kEvThreads);
     const int M = g.T + 1;
     switch (K) {
@@ -1699,17 +1055,20 @@ hipError_t launch_conditional_fit(const GridDev& g, const double* R, int ntab, c
 // k_interval<NC>: profile-likelihood limits on the signal's scale (nusi_plan_response_limit), NC = 1 + K = 1 .. 4, on
 // k_detector_fit's block shape: lanes on (c, ONE spectrum), every sum over the bins a det_butterfly over the group's
 // lanes, everything after it uniform over the group and done redundantly on its lanes.  Three parts:
-//   the best fit   k_detector_fit<NC>'s iteration (NC = 1: k_detector_profile's, one chain a lane), COPIED operation for
-//                  operation as the ensemble copies them, so theta_hat, nll_hat and the word are those calls' bits;
+//   the best fit   k_detector_fit<NC>'s iteration (NC = 1: k_detector_profile's, one chain a lane): those kernels' text,
+//                  by #include (nusi_fit_newton.inc, nusi_profile_chain1.inc), so theta_hat, nll_hat and the word are
+//                  those calls' bits;
 //   the search     per side asked for, Newton's iteration in a on lambda(a) = delta / 2 (include/nusi.h): each outer step
 //                  runs k_conditional_fit's iteration at the held a, started from the step before's theta (K = 0: one
 //                  evaluation), with ONE sum more in the round's butterfly, S2_0 = tree(s_c w_c), which is the
 //                  derivative g_0 = S1_0 - S2_0 by the envelope theorem; then lambda from ratios, one nm::log_i on the
 //                  bin's own lane, and its magnitude in one butterfly of two.  Groups of a wave need different numbers
 //                  of outer and inner steps: a stopped chain skips the logic, the wave leaves a loop when none of its
-//                  chains runs, every butterfly runs with full exec.  No LDS and no barrier in here;
+//                  chains runs, every butterfly runs with full exec.  No LDS and no barrier in here.  The text is
+//                  nusi_search_setup.inc and, per side, nusi_search_side.inc, which k_toys_limit includes as well;
 //   the records    lo, hi and the side words, then the best fit's statistic through LDS as k_detector_fit forms it (mu
-//                  and theta_1 .. theta_K per spectrum of the block, one barrier, the serial sum): fit_lds_max(NC) doubles.
+//                  and theta_1 .. theta_K per spectrum of the block, one barrier, the serial sum of
+//                  nusi_fit_statistic.inc): fit_lds_max(NC) doubles.
 // Arrays of the K floated templates are indexed i = j - 1 and sized max(K, 1).
 // ---------------------------------------------------------------------------
 template <int NC>
@@ -1750,270 +1109,20 @@ __global__ __launch_bounds__(kEvThreads) void k_interval(const double* __restric
     double thh[NC], S1h[NC], muh;
     int sth;
     if constexpr (NC == 1) {
-        // --- k_detector_profile's iteration, copied (one chain) ---
-        auto max = [](double x, double y) { return y > x ? y : x; };
-        const double s = X[0];
-        double S1[1] = {s}, a[1];
-        const bool act = d > 0.0 && s > 0.0;
+        double S1[1] = {X[0]};
         det_butterfly(S1, lgC, add);
-        bool run = S1[0] != 0.0 && (__ballot(act) & gmask) != 0;
-        int st = run ? 0 : NUSI_FIT_FLAT;
-        {
-            const double x0 = d / S1[0], x1 = b / s;
-            a[0] = act ? x0 - x1 : 0.0;
-        }
-        det_butterfly(a, lgC, max);
-        a[0] = (run && a[0] > 0.0) ? a[0] : 0.0;
-        // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
-        while (__any(run)) {
-            double v[2];
-            {
-                double den = a[0] * s;
-                den = den + b;
-                const double qq = s / den;
-                const double u = act ? qq : 0.0;
-                const double r = d * u;
-                v[0] = r;
-                v[1] = r * u;
-            }
-            det_butterfly(v, lgC, add);
-            {
-                const double S2 = v[0], S3 = v[1];
-                const double g = S1[0] - S2;
-                const double dn = S2 - S1[0];
-                const double an = a[0] + dn / S3;
-                if (run) {
-                    ++st;
-                    if (!(g < 0.0)) {
-                        run = false;
-                        if (a[0] == 0.0) st |= NUSI_FIT_BOUNDARY;
-                    } else if (!(an > a[0])) {
-                        run = false;
-                    } else {
-                        a[0] = an;
-                        if ((st & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        }
-                    }
-                }
-            }
-        }
-        double m = a[0] * s;
-        m = m + b;
-        if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st |= NUSI_FIT_INFINITE;
+#include "nusi_profile_chain1.inc"
         thh[0] = a[0];
         S1h[0] = S1[0];
         muh = m;
         sth = st;
     } else {
-        // --- k_detector_fit's iteration, copied ---
         constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
         double S1[NC];
 #pragma unroll
         for (int j = 0; j < NC; ++j) S1[j] = X[j];
         det_butterfly(S1, lgC, add);
-        bool live[NC];
-        live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
-        bool sup = b > 0.0;
-        int nl = 0;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            if (j > 0) live[j] = S1[j] > 0.0;
-            sup = sup || (live[j] && X[j] > 0.0);
-            nl += live[j] ? 1 : 0;
-        }
-        const bool act = d > 0.0 && sup;
-        double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
-        det_butterfly(dsum, lgC, add);
-        det_butterfly(dmin, lgC, min);
-        const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-        double th[NC], the[NC], p[NC];
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const double x = D0 / ((double)nl * S1[j]);
-            th[j] = live[j] ? x : 0.0;
-            the[j] = th[j];
-            p[j] = 0.0;
-        }
-        double tt = 1.0;
-        int st = 0, steps = 0, halv = 0, trials = 0;
-        bool run = true, first = true, quad = false;
-        // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
-        while (__any(run)) {
-            double v[NS];
-            double den = the[0] * X[0];
-#pragma unroll
-            for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
-            den = den + b;
-            const double wq0 = d / den;
-            const double wq = act ? wq0 : 0.0;
-            const double r0 = wq / den;
-            const double r = act ? r0 : 0.0;
-            {
-                int i = NC;
-#pragma unroll
-                for (int j = 0; j < NC; ++j) {
-                    v[j] = X[j] * wq;
-                    const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
-#pragma unroll
-                    for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
-                }
-            }
-            det_butterfly(v, lgC, add);
-            const bool bad = any(act && !(den > 0.0));
-            if (run) {
-                double g[NC];
-#pragma unroll
-                for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
-                bool ok, changed = true;
-                if (first) {
-                    ok = !bad;
-                    if (!ok) {
-                        run = false;
-                        st |= NUSI_FIT_NOT_CONVERGED;
-                    }
-                } else {
-                    double slope = 0.0;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) slope = slope + p[j] * g[j];
-                    ok = !bad && (quad || !(slope > 0.0));
-                    if (!ok) {
-                        if (trials == NUSI_FIT_TRIALS_MAX) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        } else {
-                            ++trials;
-                            ++halv;
-                            tt = tt * 0.5;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * p[j];
-                        }
-                    } else {
-                        changed = false;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
-                        ++steps;
-                    }
-                }
-                if (ok) {
-                    bool fs[NC], conv = true;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) {
-                        th[j] = the[j];
-                        fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
-                        const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
-                        const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                        if (fs[j] && !(ag <= ku * scale)) conv = false;
-                    }
-                    if (conv) {
-                        run = false;
-                    } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
-                        run = false;
-                        st |= NUSI_FIT_NOT_CONVERGED;
-                    } else {
-                        first = false;
-                        // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
-                        // a component at zero that the direction pushes below leaves fs and the solve is repeated
-                        bool sing = false;
-#pragma unroll 1
-                        for (int rep = 0; rep <= NC; ++rep) {
-                            double Lm[NC][NC], Dg[NC], y[NC];
-                            sing = false;
-                            int i0 = NC;
-                            double a[NC][NC];
-#pragma unroll
-                            for (int j = 0; j < NC; ++j)
-#pragma unroll
-                                for (int k = j; k < NC; ++k) {
-                                    const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
-                                    a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
-                                }
-#pragma unroll
-                            for (int i = 0; i < NC; ++i) {
-                                double cw[NC];
-#pragma unroll
-                                for (int j = 0; j < i; ++j) {
-                                    double x = a[i][j];
-#pragma unroll
-                                    for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                    cw[j] = x;
-                                    Lm[i][j] = x / Dg[j];
-                                }
-                                double x = a[i][i];
-#pragma unroll
-                                for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                                if (!(x > 0.0)) sing = true;
-                                Dg[i] = x;
-                            }
-#pragma unroll
-                            for (int i = 0; i < NC; ++i) {
-                                double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                                for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                                y[i] = x;
-                            }
-#pragma unroll
-                            for (int i = NC - 1; i >= 0; --i) {
-                                double x = y[i] / Dg[i];
-#pragma unroll
-                                for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * p[k];
-                                p[i] = x;
-                            }
-                            if (sing) break;
-                            bool rm = false;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j)
-                                if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
-                                    fs[j] = false;
-                                    rm = true;
-                                }
-                            if (!rm) break;
-                        }
-                        double acc = 0.0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j)
-                            if (fs[j]) acc = acc + g[j] * p[j];
-                        if (sing || !(acc < 0.0)) {
-                            run = false;
-                            st |= NUSI_FIT_SINGULAR;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j) p[j] = 0.0;
-                        } else {
-                            double ratio[NC];
-                            tt = 1.0;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j) {
-                                const double x = th[j] / -p[j];
-                                ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
-                                if (ratio[j] < tt) tt = ratio[j];
-                            }
-                            const bool clipped = tt < 1.0;
-                            quad = !clipped && -acc <= dq;
-                            trials = 0;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j) {
-                                const double x = th[j] + tt * p[j];
-                                the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        double m = th[0] * X[0];
-#pragma unroll
-        for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
-        m = m + b;
-        if (!live[0])
-            st |= NUSI_FIT_FLAT;
-        else if (th[0] == 0.0)
-            st |= NUSI_FIT_BOUNDARY;
-#pragma unroll
-        for (int j = 0; j < NC; ++j)
-            if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
-        if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
-        st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#include "nusi_fit_newton.inc"
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
             thh[j] = th[j];
@@ -2024,341 +1133,10 @@ __global__ __launch_bounds__(kEvThreads) void k_interval(const double* __restric
     }
 
     // ---- the search --------------------------------------------------------------------------------------------------
-    // (uniform values the search holds for long, moved to vector registers: the scalar file is the tight one here)
-    double pm_[KA], pw_[KA], ku_ = ku, klu_ = klu, hd = 0.5 * delta;
-#pragma unroll
-    for (int i = 0; i < KA; ++i) {
-        pm_[i] = i < KT ? pr.m[(i + 1) < NC ? i + 1 : 0] : 0.0;
-        pw_[i] = i < KT ? pr.w[(i + 1) < NC ? i + 1 : 0] : 0.0;
-        asm volatile("" : "+v"(pm_[i]), "+v"(pw_[i]));
-    }
-    asm volatile("" : "+v"(ku_), "+v"(klu_), "+v"(hd));
-    const double S10 = S1h[0], ahat = thh[0];
-    // The chain's long-lived flags are bits of ONE vector register: held as bools they are lane masks, a pair of scalar
-    // registers each, and with the inner iteration's own the kernel ran out of scalar registers (73 spilled at NC = 4).
-    enum { kLact = 1, kSupt = 2, kZeroOk = 4, kRun = 8, kSeen = 16, kZeroDone = 32, kRan = 64, kIRun = 1, kFirst = 2, kWarm = 4, kQuad = 8 };
-    int cf = (in && d > 0.0 && muh > 0.0) ? kLact : 0;   // kSupt: a live template supports the bin
-    int nl = 0;
-#pragma unroll
-    for (int i = 0; i < KT; ++i) {
-        if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) cf |= kSupt;
-        nl += S1h[i + 1] > 0.0 ? 1 : 0;
-    }
-    if (!any(d > 0.0 && X[0] > 0.0 && !(b > 0.0) && !(cf & kSupt))) cf |= kZeroOk;
-    double step;
-    {
-        const double wq0 = d / muh;
-        const double wq = (cf & kLact) ? wq0 : 0.0;
-        const double r0 = wq / muh;
-        const double rq = (cf & kLact) ? r0 : 0.0;
-        double S3[1] = {(X[0] * rq) * X[0]};
-        det_butterfly(S3, lgC, add);
-        // the quadratic model's step rounded up to a power of two: 2^ceil(e / 2), delta / S3 = f 2^e, f in [1/2, 1)
-        const int e = __builtin_amdgcn_frexp_exp(delta / S3[0]);   // frexp's exponent (0 for inf), no stack slot
-        const double pw2 = ldexp(1.0, ((e + 1025) >> 1) - 512);
-        const double lin = hd / S10;
-        step = S3[0] > 0.0 ? pw2 : lin;
-    }
-    constexpr int NI = 1 + KT + KT * (KT + 1) / 2;   // an inner round's sums: S2_j, H_jk (1 <= j <= k), then S2_0
+#include "nusi_search_setup.inc"
 #pragma unroll 1
     for (int side = 1; side >= 0; --side) {   // 1: the upper side, 0: the lower
-        const bool upper = side == 1;
-        const bool asked = (which & (upper ? NUSI_LIMIT_UPPER : NUSI_LIMIT_LOWER)) != 0;
-        double a = 0.0, res = __builtin_nan("");
-        int word = 0, fl = 0;
-        if (asked) {
-            if (sth & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
-                word = NUSI_LIMIT_NO_FIT;
-            } else if (S10 == 0.0) {
-                res = upper ? __builtin_inf() : 0.0;
-                word = upper ? NUSI_LIMIT_UNBOUNDED : (NUSI_LIMIT_UNBOUNDED | NUSI_LIMIT_AT_ZERO);
-            } else if (upper) {
-                a = ahat + step;
-                fl = kRun | kRan;
-            } else if (ahat == 0.0) {
-                res = 0.0;
-                word = NUSI_LIMIT_AT_ZERO;
-            } else {
-                a = ahat - step;
-                if (!(a > 0.0)) a = 0.5 * ahat;
-                fl = kRun | kRan;
-            }
-        }
-        double th[KA], aprev = a;
-#pragma unroll
-        for (int i = 0; i < KA; ++i) th[i] = i < KT ? thh[(i + 1) < NC ? i + 1 : 0] : 0.0;
-        int steps = 0, inner = 0, flags = 0;
-        // (every round of the outer loop ends a chain or counts a step towards NUSI_LIMIT_ITER_MAX)
-        while (__any((fl & kRun) != 0)) {
-            // --- k_conditional_fit's iteration at a, from th (the header's start where an active den is not > 0 there) ---
-            const double asig = a * X[0];
-            const bool sup = b > 0.0 || (cf & kSupt) || (a > 0.0 && X[0] > 0.0);
-            const bool act = d > 0.0 && sup;
-            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};
-            det_butterfly(dsum, lgC, add);
-            det_butterfly(dmin, lgC, min);
-            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-            double the[KA], p[KA], S20 = 0.0;
-#pragma unroll
-            for (int i = 0; i < KA; ++i) {
-                the[i] = th[i];
-                p[i] = 0.0;
-            }
-            double tt = 1.0;
-            int ist = 0, isteps = 0, trials = 0;
-            int il = ((fl & kRun) ? kIRun : 0) | kFirst | kWarm;   // (the inner chain's flags, bits as well)
-            while (__any((il & kIRun) != 0)) {
-                double v[NI];
-                double den = asig;
-#pragma unroll
-                for (int i = 0; i < KT; ++i) den = den + the[i] * X[i + 1];
-                den = den + b;
-                const double wq0 = d / den;
-                const double wq = act ? wq0 : 0.0;
-                const double r0 = wq / den;
-                const double r = act ? r0 : 0.0;
-                {
-                    int i = KT;
-#pragma unroll
-                    for (int j = 0; j < KT; ++j) {
-                        v[j] = X[j + 1] * wq;
-                        const double xr = X[j + 1] * r;
-#pragma unroll
-                        for (int k = j; k < KT; ++k) v[i++] = xr * X[k + 1];
-                    }
-                    v[NI - 1] = X[0] * wq;
-                }
-                det_butterfly(v, lgC, add);
-                const bool bad = any(act && !(den > 0.0));
-                if (il & kIRun) {
-                    double g[KA];
-#pragma unroll
-                    for (int j = 0; j < KT; ++j) g[j] = (S1h[j + 1] - v[j]) + pw_[j] * (the[j] - pm_[j]);
-                    bool ok, changed = true;
-                    if (il & kFirst) {
-                        ok = !bad;
-                        if (!ok) {
-                            if (il & kWarm) {
-                                il &= ~kWarm;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) {
-                                    const double x = D0 / ((double)nl * S1h[j + 1]);
-                                    th[j] = S1h[j + 1] > 0.0 ? x : 0.0;
-                                    the[j] = th[j];
-                                }
-                            } else {
-                                il &= ~kIRun;
-                                ist |= NUSI_FIT_NOT_CONVERGED;
-                            }
-                        }
-                    } else {
-                        double slope = 0.0;
-#pragma unroll
-                        for (int j = 0; j < KT; ++j) slope = slope + p[j] * g[j];
-                        ok = !bad && ((il & kQuad) || !(slope > 0.0));
-                        if (!ok) {
-                            if (trials == NUSI_FIT_TRIALS_MAX) {
-                                il &= ~kIRun;
-                                ist |= NUSI_FIT_NOT_CONVERGED;
-                            } else {
-                                ++trials;
-                                tt = tt * 0.5;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) the[j] = th[j] + tt * p[j];
-                            }
-                        } else {
-                            changed = false;
-#pragma unroll
-                            for (int j = 0; j < KT; ++j) changed = changed || the[j] != th[j];
-                            ++isteps;
-                        }
-                    }
-                    if (ok) {
-                        bool fs[KA], conv = true;
-                        S20 = v[NI - 1];
-#pragma unroll
-                        for (int j = 0; j < KT; ++j) {
-                            th[j] = the[j];
-                            fs[j] = S1h[j + 1] > 0.0 && (th[j] > 0.0 || g[j] < 0.0);
-                            const double sc = (S1h[j + 1] + v[j]) + pw_[j] * (th[j] + pm_[j]);
-                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                            if (fs[j] && !(ag <= ku_ * sc)) conv = false;
-                        }
-                        if (conv) {
-                            il &= ~kIRun;
-                        } else if ((!(il & kFirst) && !changed) || isteps == NUSI_FIT_ITER_MAX) {
-                            il &= ~kIRun;
-                            ist |= NUSI_FIT_NOT_CONVERGED;
-                        } else {
-                            il &= ~kFirst;
-                            bool sing = false;
-#pragma unroll 1
-                            for (int rep = 0; rep <= KT; ++rep) {
-                                double Lm[KA][KA], Dg[KA], y[KA];
-                                sing = false;
-                                int i0 = KT;
-                                double hm[KA][KA];
-#pragma unroll
-                                for (int j = 0; j < KT; ++j)
-#pragma unroll
-                                    for (int k = j; k < KT; ++k) {
-                                        const double hv = v[i0++] + (j == k ? pw_[j] : 0.0);
-                                        hm[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
-                                    }
-#pragma unroll
-                                for (int i = 0; i < KT; ++i) {
-                                    double cw[KA];
-#pragma unroll
-                                    for (int j = 0; j < i; ++j) {
-                                        double x = hm[i][j];
-#pragma unroll
-                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                        cw[j] = x;
-                                        Lm[i][j] = x / Dg[j];
-                                    }
-                                    double x = hm[i][i];
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                                    if (!(x > 0.0)) sing = true;
-                                    Dg[i] = x;
-                                }
-#pragma unroll
-                                for (int i = 0; i < KT; ++i) {
-                                    double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                                    y[i] = x;
-                                }
-#pragma unroll
-                                for (int i = KT - 1; i >= 0; --i) {
-                                    double x = y[i] / Dg[i];
-#pragma unroll
-                                    for (int k = i + 1; k < KT; ++k) x = x - Lm[k][i] * p[k];
-                                    p[i] = x;
-                                }
-                                if (sing) break;
-                                bool rm = false;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j)
-                                    if (fs[j] && th[j] == 0.0 && p[j] < 0.0) {
-                                        fs[j] = false;
-                                        rm = true;
-                                    }
-                                if (!rm) break;
-                            }
-                            double acc = 0.0;
-#pragma unroll
-                            for (int j = 0; j < KT; ++j)
-                                if (fs[j]) acc = acc + g[j] * p[j];
-                            if (sing || !(acc < 0.0)) {
-                                il &= ~kIRun;
-                                ist |= NUSI_FIT_SINGULAR;
-                            } else {
-                                double ratio[KA];
-                                tt = 1.0;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) {
-                                    const double x = th[j] / -p[j];
-                                    ratio[j] = (fs[j] && p[j] < 0.0) ? x : 1.0;
-                                    if (ratio[j] < tt) tt = ratio[j];
-                                }
-                                const bool clipped = tt < 1.0;
-                                il = (!clipped && -acc <= dq) ? (il | kQuad) : (il & ~kQuad);
-                                trials = 0;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) {
-                                    const double x = th[j] + tt * p[j];
-                                    the[j] = (clipped && fs[j] && p[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            // --- lambda(a) - delta / 2 from ratios, its magnitude, and the step in a ---
-            double mu = asig;
-#pragma unroll
-            for (int i = 0; i < KT; ++i) mu = mu + th[i] * X[i + 1];
-            mu = mu + b;
-            double lv[2];
-            {
-                const double dmu = mu - muh;
-                const double ratio = mu / muh;
-                const double lr = ratio > 0.0 ? nm::log_i(ratio) : -__builtin_inf();
-                const double pl = d * lr;
-                const double admu = dmu < 0.0 ? -dmu : dmu, apl = pl < 0.0 ? -pl : pl;
-                const double tl = dmu - pl, ml = admu + apl;
-                lv[0] = (cf & kLact) ? tl : dmu;
-                lv[1] = (cf & kLact) ? ml : admu;
-            }
-            det_butterfly(lv, lgC, add);
-            if (fl & kRun) {
-                inner += isteps;
-                if (ist & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
-                    flags |= NUSI_LIMIT_NOT_CONVERGED;
-                    fl &= ~kRun;
-                } else {
-                    ++steps;
-                    double lam = lv[0], mg = lv[1];
-#pragma unroll
-                    for (int j = 0; j < KT; ++j)
-                        if (pw_[j] > 0.0) {
-                            const double dj = th[j] - thh[(j + 1) < NC ? j + 1 : 0];
-                            const double sj = (th[j] - pm_[j]) + (thh[(j + 1) < NC ? j + 1 : 0] - pm_[j]);
-                            const double pd = ((0.5 * pw_[j]) * dj) * sj;
-                            lam = lam + pd;
-                            mg = mg + (pd < 0.0 ? -pd : pd);
-                        }
-                    const double h = lam - hd;
-                    const double eps = klu_ * (mg + hd);
-                    const double g0 = S10 - S20;
-                    const double ah = h < 0.0 ? -h : h;
-                    if (!upper && a == 0.0) {   // the one look at zero: the limit is there, or the search goes back
-                        if (!(h > 0.0)) {
-                            flags |= NUSI_LIMIT_AT_ZERO;
-                            fl &= ~kRun;
-                        } else if (steps == NUSI_LIMIT_ITER_MAX) {
-                            flags |= NUSI_LIMIT_NOT_CONVERGED;
-                            fl &= ~kRun;
-                        } else {
-                            fl = (fl | kZeroDone) & ~kSeen;
-                            a = 0.5 * aprev;
-                        }
-                    } else if (ah <= eps || ((fl & kSeen) && !(h > 0.0))) {
-                        fl &= ~kRun;
-                    } else {
-                        fl = h > 0.0 ? (fl | kSeen) : (fl & ~kSeen);
-                        if (steps == NUSI_LIMIT_ITER_MAX || !(upper ? g0 > 0.0 : g0 < 0.0)) {
-                            flags |= NUSI_LIMIT_NOT_CONVERGED;
-                            fl &= ~kRun;
-                        } else {
-                            double an = a - h / g0;
-                            if (!upper && !(an > 0.0)) {
-                                fl &= ~kSeen;
-                                if ((cf & kZeroOk) && !(fl & kZeroDone)) {
-                                    aprev = a;
-                                    an = 0.0;
-                                } else {
-                                    an = 0.5 * a;
-                                }
-                            }
-                            if (!(an < __builtin_inf())) {
-                                flags |= NUSI_LIMIT_NOT_CONVERGED;
-                                fl &= ~kRun;
-                            } else if (an == a) {
-                                fl &= ~kRun;
-                            } else {
-                                a = an;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        if (fl & kRan) {
-            res = a;
-            word = steps | flags | ((inner < NUSI_LIMIT_INNER_MASK ? inner : NUSI_LIMIT_INNER_MASK) << NUSI_LIMIT_INNER_SHIFT);
-        }
+#include "nusi_search_side.inc"
         if (c == 0 && q < Q) {
             double* out = upper ? hi : lo;
             if (out) out[(size_t)t * Q + q] = res;
@@ -2382,23 +1160,8 @@ __global__ __launch_bounds__(kEvThreads) void k_interval(const double* __restric
     __syncthreads();
     // (a block owns QB <= kEvThreads spectra)
     if (tid < QB && qb0 + tid < Q) {
-        double sum = 0.0;
-        for (int k = 0; k < C; ++k) {
-            const double mk = smu[tid * RS + k], dk = data[k];
-            double term = mk;
-            if (dk != 0.0) {
-                const double pl = dk * nm::log_i(mk);
-                term = mk - pl;
-            }
-            sum = sum + term;
-        }
-#pragma unroll
-        for (int j = 1; j < NC; ++j)
-            if (pr.w[j] > 0.0) {
-                const double dl = smu[tid * RS + C + j - 1] - pr.m[j];
-                const double pen = ((0.5 * pr.w[j]) * dl) * dl;
-                sum = sum + pen;
-            }
+        constexpr int NP = NC;
+#include "nusi_fit_statistic.inc"
         nll_hat[(size_t)t * Q + qb0 + tid] = sum;
     }
 }
@@ -2410,13 +1173,9 @@ hipError_t launch_detector_limit(const GridDev& g, const double* R, int ntab, co
 {
     if (ntab <= 0 || Q <= 0) return hipSuccess;
     const DetGeom ge(C, 1, ntab, Q);
-    FitPrior pr;
-    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
-        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
-        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
-    }
-    const double ku = (double)(2 * (ge.lg + K) + 18) * 0x1p-53;    // kappa(C, K) u (include/nusi.h)
-    const double klu = (double)(2 * (ge.lg + K) + 14) * 0x1p-53;   // kappa_lambda(C, K) u
+    const FitPrior pr = fit_prior(K, pm, pw);
+    const double ku = fit_ku(ge.lg, K);
+    const double klu = fit_klu(ge.lg, K);
     const dim3 grid = ge.grid, block(kEvThreads);
     const int M = g.T + 1;
     switch (K) {
@@ -2435,8 +1194,8 @@ hipError_t launch_detector_limit(const GridDev& g, const double* R, int ntab, co
 // "k_interval": the resource tests of those kernels count theirs by substring.)  A block takes one unit u = u0 +
 // blockIdx.x of the call's chunk -- table t = u / nqb, spectrum block u % nqb -- and the data sets of its p-slice
 // (blockIdx.z, ens_share).  Before the loop: the front half, the templates, the background and S1 = tree(X), none of
-// which reads the data.  Per data set: k_interval's best fit and search, COPIED operation for operation (the rule of
-// the ensemble kernels), so the record of (p, t, q) has nusi_plan_response_limit's bits; every per-toy value is set
+// which reads the data.  Per data set: k_interval's best fit and search, the same text by #include (as in the
+// ensemble kernels), so the record of (p, t, q) has nusi_plan_response_limit's bits; every per-toy value is set
 // anew at the top of the loop.  No LDS: the best fit's statistic is not formed.
 // A side's limit goes to row[P] + p, row = the spectrum's place in the chunk's scratch ((u - u0) QB + grp; compact) or
 // t Q + q in the caller's [ntab][Q][P]; its word to words[t][q][p][side]; a flag among NUSI_LIMIT_AT_ZERO .. _NOT_CONVERGED
@@ -2497,267 +1256,17 @@ __global__ __launch_bounds__(kEvThreads) void k_toys_limit(const double* __restr
         double thh[NC], muh;
         int sth;
         if constexpr (NC == 1) {
-            // --- k_detector_profile's iteration, copied (one chain) ---
-            auto max = [](double x, double y) { return y > x ? y : x; };
-            const double s = X[0];
-            double S1[1] = {S1h[0]}, a[1];
-            const bool act = d > 0.0 && s > 0.0;
-            bool run = S1[0] != 0.0 && (__ballot(act) & gmask) != 0;
-            int st = run ? 0 : NUSI_FIT_FLAT;
-            {
-                const double x0 = d / S1[0], x1 = b / s;
-                a[0] = act ? x0 - x1 : 0.0;
-            }
-            det_butterfly(a, lgC, max);
-            a[0] = (run && a[0] > 0.0) ? a[0] : 0.0;
-            // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
-            while (__any(run)) {
-                double v[2];
-                {
-                    double den = a[0] * s;
-                    den = den + b;
-                    const double qq = s / den;
-                    const double uu = act ? qq : 0.0;
-                    const double r = d * uu;
-                    v[0] = r;
-                    v[1] = r * uu;
-                }
-                det_butterfly(v, lgC, add);
-                {
-                    const double S2 = v[0], S3 = v[1];
-                    const double g = S1[0] - S2;
-                    const double dn = S2 - S1[0];
-                    const double an = a[0] + dn / S3;
-                    if (run) {
-                        ++st;
-                        if (!(g < 0.0)) {
-                            run = false;
-                            if (a[0] == 0.0) st |= NUSI_FIT_BOUNDARY;
-                        } else if (!(an > a[0])) {
-                            run = false;
-                        } else {
-                            a[0] = an;
-                            if ((st & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
-                                run = false;
-                                st |= NUSI_FIT_NOT_CONVERGED;
-                            }
-                        }
-                    }
-                }
-            }
-            double m = a[0] * s;
-            m = m + b;
-            if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st |= NUSI_FIT_INFINITE;
+            double S1[1] = {S1h[0]};
+#include "nusi_profile_chain1.inc"
             thh[0] = a[0];
             muh = m;
             sth = st;
         } else {
-            // --- k_detector_fit's iteration, copied ---
             constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
             double S1[NC];
 #pragma unroll
             for (int j = 0; j < NC; ++j) S1[j] = S1h[j];
-            bool live[NC];
-            live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
-            bool sup = b > 0.0;
-            int nl = 0;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                if (j > 0) live[j] = S1[j] > 0.0;
-                sup = sup || (live[j] && X[j] > 0.0);
-                nl += live[j] ? 1 : 0;
-            }
-            const bool act = d > 0.0 && sup;
-            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
-            det_butterfly(dsum, lgC, add);
-            det_butterfly(dmin, lgC, min);
-            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-            double th[NC], the[NC], pp[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                const double x = D0 / ((double)nl * S1[j]);
-                th[j] = live[j] ? x : 0.0;
-                the[j] = th[j];
-                pp[j] = 0.0;
-            }
-            double tt = 1.0;
-            int st = 0, steps = 0, halv = 0, trials = 0;
-            bool run = true, first = true, quad = false;
-            // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
-            while (__any(run)) {
-                double v[NS];
-                double den = the[0] * X[0];
-#pragma unroll
-                for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
-                den = den + b;
-                const double wq0 = d / den;
-                const double wq = act ? wq0 : 0.0;
-                const double r0 = wq / den;
-                const double r = act ? r0 : 0.0;
-                {
-                    int i = NC;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) {
-                        v[j] = X[j] * wq;
-                        const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
-#pragma unroll
-                        for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
-                    }
-                }
-                det_butterfly(v, lgC, add);
-                const bool bad = any(act && !(den > 0.0));
-                if (run) {
-                    double g[NC];
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
-                    bool ok, changed = true;
-                    if (first) {
-                        ok = !bad;
-                        if (!ok) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        }
-                    } else {
-                        double slope = 0.0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) slope = slope + pp[j] * g[j];
-                        ok = !bad && (quad || !(slope > 0.0));
-                        if (!ok) {
-                            if (trials == NUSI_FIT_TRIALS_MAX) {
-                                run = false;
-                                st |= NUSI_FIT_NOT_CONVERGED;
-                            } else {
-                                ++trials;
-                                ++halv;
-                                tt = tt * 0.5;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * pp[j];
-                            }
-                        } else {
-                            changed = false;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
-                            ++steps;
-                        }
-                    }
-                    if (ok) {
-                        bool fs[NC], conv = true;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) {
-                            th[j] = the[j];
-                            fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
-                            const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
-                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                            if (fs[j] && !(ag <= ku * scale)) conv = false;
-                        }
-                        if (conv) {
-                            run = false;
-                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        } else {
-                            first = false;
-                            // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
-                            // a component at zero that the direction pushes below leaves fs and the solve is repeated
-                            bool sing = false;
-#pragma unroll 1
-                            for (int rep = 0; rep <= NC; ++rep) {
-                                double Lm[NC][NC], Dg[NC], y[NC];
-                                sing = false;
-                                int i0 = NC;
-                                double a[NC][NC];
-#pragma unroll
-                                for (int j = 0; j < NC; ++j)
-#pragma unroll
-                                    for (int k = j; k < NC; ++k) {
-                                        const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
-                                        a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
-                                    }
-#pragma unroll
-                                for (int i = 0; i < NC; ++i) {
-                                    double cw[NC];
-#pragma unroll
-                                    for (int j = 0; j < i; ++j) {
-                                        double x = a[i][j];
-#pragma unroll
-                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                        cw[j] = x;
-                                        Lm[i][j] = x / Dg[j];
-                                    }
-                                    double x = a[i][i];
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                                    if (!(x > 0.0)) sing = true;
-                                    Dg[i] = x;
-                                }
-#pragma unroll
-                                for (int i = 0; i < NC; ++i) {
-                                    double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                                    y[i] = x;
-                                }
-#pragma unroll
-                                for (int i = NC - 1; i >= 0; --i) {
-                                    double x = y[i] / Dg[i];
-#pragma unroll
-                                    for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * pp[k];
-                                    pp[i] = x;
-                                }
-                                if (sing) break;
-                                bool rm = false;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j)
-                                    if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
-                                        fs[j] = false;
-                                        rm = true;
-                                    }
-                                if (!rm) break;
-                            }
-                            double acc = 0.0;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j)
-                                if (fs[j]) acc = acc + g[j] * pp[j];
-                            if (sing || !(acc < 0.0)) {
-                                run = false;
-                                st |= NUSI_FIT_SINGULAR;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) pp[j] = 0.0;
-                            } else {
-                                double ratio[NC];
-                                tt = 1.0;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) {
-                                    const double x = th[j] / -pp[j];
-                                    ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
-                                    if (ratio[j] < tt) tt = ratio[j];
-                                }
-                                const bool clipped = tt < 1.0;
-                                quad = !clipped && -acc <= dq;
-                                trials = 0;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) {
-                                    const double x = th[j] + tt * pp[j];
-                                    the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            double m = th[0] * X[0];
-#pragma unroll
-            for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
-            m = m + b;
-            if (!live[0])
-                st |= NUSI_FIT_FLAT;
-            else if (th[0] == 0.0)
-                st |= NUSI_FIT_BOUNDARY;
-#pragma unroll
-            for (int j = 0; j < NC; ++j)
-                if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
-            if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
-            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#include "nusi_fit_newton.inc"
 #pragma unroll
             for (int j = 0; j < NC; ++j) thh[j] = th[j];
             muh = m;
@@ -2765,340 +1274,10 @@ __global__ __launch_bounds__(kEvThreads) void k_toys_limit(const double* __restr
         }
 
         // ---- the search ----------------------------------------------------------------------------------------------
-        // (uniform values the search holds for long, moved to vector registers: the scalar file is the tight one here)
-        double pm_[KA], pw_[KA], ku_ = ku, klu_ = klu, hd = 0.5 * delta;
-#pragma unroll
-        for (int i = 0; i < KA; ++i) {
-            pm_[i] = i < KT ? pr.m[(i + 1) < NC ? i + 1 : 0] : 0.0;
-            pw_[i] = i < KT ? pr.w[(i + 1) < NC ? i + 1 : 0] : 0.0;
-            asm volatile("" : "+v"(pm_[i]), "+v"(pw_[i]));
-        }
-        asm volatile("" : "+v"(ku_), "+v"(klu_), "+v"(hd));
-        const double S10 = S1h[0], ahat = thh[0];
-        // (the chain's long-lived flags are bits of one vector register, as in k_interval)
-        enum { kLact = 1, kSupt = 2, kZeroOk = 4, kRun = 8, kSeen = 16, kZeroDone = 32, kRan = 64, kIRun = 1, kFirst = 2, kWarm = 4, kQuad = 8 };
-        int cf = (in && d > 0.0 && muh > 0.0) ? kLact : 0;   // kSupt: a live template supports the bin
-        int nl = 0;
-#pragma unroll
-        for (int i = 0; i < KT; ++i) {
-            if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) cf |= kSupt;
-            nl += S1h[i + 1] > 0.0 ? 1 : 0;
-        }
-        if (!any(d > 0.0 && X[0] > 0.0 && !(b > 0.0) && !(cf & kSupt))) cf |= kZeroOk;
-        double step;
-        {
-            const double wq0 = d / muh;
-            const double wq = (cf & kLact) ? wq0 : 0.0;
-            const double r0 = wq / muh;
-            const double rqq = (cf & kLact) ? r0 : 0.0;
-            double S3[1] = {(X[0] * rqq) * X[0]};
-            det_butterfly(S3, lgC, add);
-            // the quadratic model's step rounded up to a power of two: 2^ceil(e / 2), delta / S3 = f 2^e, f in [1/2, 1)
-            const int e = __builtin_amdgcn_frexp_exp(delta / S3[0]);   // frexp's exponent (0 for inf), no stack slot
-            const double pw2 = ldexp(1.0, ((e + 1025) >> 1) - 512);
-            const double lin = hd / S10;
-            step = S3[0] > 0.0 ? pw2 : lin;
-        }
-        constexpr int NI = 1 + KT + KT * (KT + 1) / 2;   // an inner round's sums: S2_j, H_jk (1 <= j <= k), then S2_0
+#include "nusi_search_setup.inc"
 #pragma unroll 1
         for (int side = 1; side >= 0; --side) {   // 1: the upper side, 0: the lower
-            const bool upper = side == 1;
-            const bool asked = (which & (upper ? NUSI_LIMIT_UPPER : NUSI_LIMIT_LOWER)) != 0;
-            double a = 0.0, res = __builtin_nan("");
-            int word = 0, fl = 0;
-            if (asked) {
-                if (sth & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
-                    word = NUSI_LIMIT_NO_FIT;
-                } else if (S10 == 0.0) {
-                    res = upper ? __builtin_inf() : 0.0;
-                    word = upper ? NUSI_LIMIT_UNBOUNDED : (NUSI_LIMIT_UNBOUNDED | NUSI_LIMIT_AT_ZERO);
-                } else if (upper) {
-                    a = ahat + step;
-                    fl = kRun | kRan;
-                } else if (ahat == 0.0) {
-                    res = 0.0;
-                    word = NUSI_LIMIT_AT_ZERO;
-                } else {
-                    a = ahat - step;
-                    if (!(a > 0.0)) a = 0.5 * ahat;
-                    fl = kRun | kRan;
-                }
-            }
-            double th[KA], aprev = a;
-#pragma unroll
-            for (int i = 0; i < KA; ++i) th[i] = i < KT ? thh[(i + 1) < NC ? i + 1 : 0] : 0.0;
-            int steps = 0, inner = 0, flags = 0;
-            // (every round of the outer loop ends a chain or counts a step towards NUSI_LIMIT_ITER_MAX)
-            while (__any((fl & kRun) != 0)) {
-                // --- k_conditional_fit's iteration at a, from th (the header's start where an active den is not > 0 there) ---
-                const double asig = a * X[0];
-                const bool sup = b > 0.0 || (cf & kSupt) || (a > 0.0 && X[0] > 0.0);
-                const bool act = d > 0.0 && sup;
-                double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};
-                det_butterfly(dsum, lgC, add);
-                det_butterfly(dmin, lgC, min);
-                const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-                double the[KA], pp[KA], S20 = 0.0;
-#pragma unroll
-                for (int i = 0; i < KA; ++i) {
-                    the[i] = th[i];
-                    pp[i] = 0.0;
-                }
-                double tt = 1.0;
-                int ist = 0, isteps = 0, trials = 0;
-                int il = ((fl & kRun) ? kIRun : 0) | kFirst | kWarm;   // (the inner chain's flags, bits as well)
-                while (__any((il & kIRun) != 0)) {
-                    double v[NI];
-                    double den = asig;
-#pragma unroll
-                    for (int i = 0; i < KT; ++i) den = den + the[i] * X[i + 1];
-                    den = den + b;
-                    const double wq0 = d / den;
-                    const double wq = act ? wq0 : 0.0;
-                    const double r0 = wq / den;
-                    const double r = act ? r0 : 0.0;
-                    {
-                        int i = KT;
-#pragma unroll
-                        for (int j = 0; j < KT; ++j) {
-                            v[j] = X[j + 1] * wq;
-                            const double xr = X[j + 1] * r;
-#pragma unroll
-                            for (int k = j; k < KT; ++k) v[i++] = xr * X[k + 1];
-                        }
-                        v[NI - 1] = X[0] * wq;
-                    }
-                    det_butterfly(v, lgC, add);
-                    const bool bad = any(act && !(den > 0.0));
-                    if (il & kIRun) {
-                        double g[KA];
-#pragma unroll
-                        for (int j = 0; j < KT; ++j) g[j] = (S1h[j + 1] - v[j]) + pw_[j] * (the[j] - pm_[j]);
-                        bool ok, changed = true;
-                        if (il & kFirst) {
-                            ok = !bad;
-                            if (!ok) {
-                                if (il & kWarm) {
-                                    il &= ~kWarm;
-#pragma unroll
-                                    for (int j = 0; j < KT; ++j) {
-                                        const double x = D0 / ((double)nl * S1h[j + 1]);
-                                        th[j] = S1h[j + 1] > 0.0 ? x : 0.0;
-                                        the[j] = th[j];
-                                    }
-                                } else {
-                                    il &= ~kIRun;
-                                    ist |= NUSI_FIT_NOT_CONVERGED;
-                                }
-                            }
-                        } else {
-                            double slope = 0.0;
-#pragma unroll
-                            for (int j = 0; j < KT; ++j) slope = slope + pp[j] * g[j];
-                            ok = !bad && ((il & kQuad) || !(slope > 0.0));
-                            if (!ok) {
-                                if (trials == NUSI_FIT_TRIALS_MAX) {
-                                    il &= ~kIRun;
-                                    ist |= NUSI_FIT_NOT_CONVERGED;
-                                } else {
-                                    ++trials;
-                                    tt = tt * 0.5;
-#pragma unroll
-                                    for (int j = 0; j < KT; ++j) the[j] = th[j] + tt * pp[j];
-                                }
-                            } else {
-                                changed = false;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) changed = changed || the[j] != th[j];
-                                ++isteps;
-                            }
-                        }
-                        if (ok) {
-                            bool fs[KA], conv = true;
-                            S20 = v[NI - 1];
-#pragma unroll
-                            for (int j = 0; j < KT; ++j) {
-                                th[j] = the[j];
-                                fs[j] = S1h[j + 1] > 0.0 && (th[j] > 0.0 || g[j] < 0.0);
-                                const double sc = (S1h[j + 1] + v[j]) + pw_[j] * (th[j] + pm_[j]);
-                                const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                                if (fs[j] && !(ag <= ku_ * sc)) conv = false;
-                            }
-                            if (conv) {
-                                il &= ~kIRun;
-                            } else if ((!(il & kFirst) && !changed) || isteps == NUSI_FIT_ITER_MAX) {
-                                il &= ~kIRun;
-                                ist |= NUSI_FIT_NOT_CONVERGED;
-                            } else {
-                                il &= ~kFirst;
-                                bool sing = false;
-#pragma unroll 1
-                                for (int rep = 0; rep <= KT; ++rep) {
-                                    double Lm[KA][KA], Dg[KA], y[KA];
-                                    sing = false;
-                                    int i0 = KT;
-                                    double hm[KA][KA];
-#pragma unroll
-                                    for (int j = 0; j < KT; ++j)
-#pragma unroll
-                                        for (int k = j; k < KT; ++k) {
-                                            const double hv = v[i0++] + (j == k ? pw_[j] : 0.0);
-                                            hm[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
-                                        }
-#pragma unroll
-                                    for (int i = 0; i < KT; ++i) {
-                                        double cw[KA];
-#pragma unroll
-                                        for (int j = 0; j < i; ++j) {
-                                            double x = hm[i][j];
-#pragma unroll
-                                            for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                            cw[j] = x;
-                                            Lm[i][j] = x / Dg[j];
-                                        }
-                                        double x = hm[i][i];
-#pragma unroll
-                                        for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                                        if (!(x > 0.0)) sing = true;
-                                        Dg[i] = x;
-                                    }
-#pragma unroll
-                                    for (int i = 0; i < KT; ++i) {
-                                        double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                                        for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                                        y[i] = x;
-                                    }
-#pragma unroll
-                                    for (int i = KT - 1; i >= 0; --i) {
-                                        double x = y[i] / Dg[i];
-#pragma unroll
-                                        for (int k = i + 1; k < KT; ++k) x = x - Lm[k][i] * pp[k];
-                                        pp[i] = x;
-                                    }
-                                    if (sing) break;
-                                    bool rm = false;
-#pragma unroll
-                                    for (int j = 0; j < KT; ++j)
-                                        if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
-                                            fs[j] = false;
-                                            rm = true;
-                                        }
-                                    if (!rm) break;
-                                }
-                                double acc = 0.0;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j)
-                                    if (fs[j]) acc = acc + g[j] * pp[j];
-                                if (sing || !(acc < 0.0)) {
-                                    il &= ~kIRun;
-                                    ist |= NUSI_FIT_SINGULAR;
-                                } else {
-                                    double ratio[KA];
-                                    tt = 1.0;
-#pragma unroll
-                                    for (int j = 0; j < KT; ++j) {
-                                        const double x = th[j] / -pp[j];
-                                        ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
-                                        if (ratio[j] < tt) tt = ratio[j];
-                                    }
-                                    const bool clipped = tt < 1.0;
-                                    il = (!clipped && -acc <= dq) ? (il | kQuad) : (il & ~kQuad);
-                                    trials = 0;
-#pragma unroll
-                                    for (int j = 0; j < KT; ++j) {
-                                        const double x = th[j] + tt * pp[j];
-                                        the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-                // --- lambda(a) - delta / 2 from ratios, its magnitude, and the step in a ---
-                double mu = asig;
-#pragma unroll
-                for (int i = 0; i < KT; ++i) mu = mu + th[i] * X[i + 1];
-                mu = mu + b;
-                double lv[2];
-                {
-                    const double dmu = mu - muh;
-                    const double ratio = mu / muh;
-                    const double lr = ratio > 0.0 ? nm::log_i(ratio) : -__builtin_inf();
-                    const double pl = d * lr;
-                    const double admu = dmu < 0.0 ? -dmu : dmu, apl = pl < 0.0 ? -pl : pl;
-                    const double tl = dmu - pl, ml = admu + apl;
-                    lv[0] = (cf & kLact) ? tl : dmu;
-                    lv[1] = (cf & kLact) ? ml : admu;
-                }
-                det_butterfly(lv, lgC, add);
-                if (fl & kRun) {
-                    inner += isteps;
-                    if (ist & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) {
-                        flags |= NUSI_LIMIT_NOT_CONVERGED;
-                        fl &= ~kRun;
-                    } else {
-                        ++steps;
-                        double lam = lv[0], mg = lv[1];
-#pragma unroll
-                        for (int j = 0; j < KT; ++j)
-                            if (pw_[j] > 0.0) {
-                                const double dj = th[j] - thh[(j + 1) < NC ? j + 1 : 0];
-                                const double sj = (th[j] - pm_[j]) + (thh[(j + 1) < NC ? j + 1 : 0] - pm_[j]);
-                                const double pd = ((0.5 * pw_[j]) * dj) * sj;
-                                lam = lam + pd;
-                                mg = mg + (pd < 0.0 ? -pd : pd);
-                            }
-                        const double h = lam - hd;
-                        const double eps = klu_ * (mg + hd);
-                        const double g0 = S10 - S20;
-                        const double ah = h < 0.0 ? -h : h;
-                        if (!upper && a == 0.0) {   // the one look at zero: the limit is there, or the search goes back
-                            if (!(h > 0.0)) {
-                                flags |= NUSI_LIMIT_AT_ZERO;
-                                fl &= ~kRun;
-                            } else if (steps == NUSI_LIMIT_ITER_MAX) {
-                                flags |= NUSI_LIMIT_NOT_CONVERGED;
-                                fl &= ~kRun;
-                            } else {
-                                fl = (fl | kZeroDone) & ~kSeen;
-                                a = 0.5 * aprev;
-                            }
-                        } else if (ah <= eps || ((fl & kSeen) && !(h > 0.0))) {
-                            fl &= ~kRun;
-                        } else {
-                            fl = h > 0.0 ? (fl | kSeen) : (fl & ~kSeen);
-                            if (steps == NUSI_LIMIT_ITER_MAX || !(upper ? g0 > 0.0 : g0 < 0.0)) {
-                                flags |= NUSI_LIMIT_NOT_CONVERGED;
-                                fl &= ~kRun;
-                            } else {
-                                double an = a - h / g0;
-                                if (!upper && !(an > 0.0)) {
-                                    fl &= ~kSeen;
-                                    if ((cf & kZeroOk) && !(fl & kZeroDone)) {
-                                        aprev = a;
-                                        an = 0.0;
-                                    } else {
-                                        an = 0.5 * a;
-                                    }
-                                }
-                                if (!(an < __builtin_inf())) {
-                                    flags |= NUSI_LIMIT_NOT_CONVERGED;
-                                    fl &= ~kRun;
-                                } else if (an == a) {
-                                    fl &= ~kRun;
-                                } else {
-                                    a = an;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            if (fl & kRan) {
-                res = a;
-                word = steps | flags | ((inner < NUSI_LIMIT_INNER_MASK ? inner : NUSI_LIMIT_INNER_MASK) << NUSI_LIMIT_INNER_SHIFT);
-            }
+#include "nusi_search_side.inc"
             if (c == 0 && q < Q) {
                 double* out = upper ? o.hi : o.lo;
                 if (out) out[(upper ? rhi : rlo) + p] = res;
@@ -3124,13 +1303,9 @@ hipError_t launch_toys_limit(const GridDev& g, const double* R, const double* S,
 {
     if (nu <= 0 || Q <= 0 || P <= 0) return hipSuccess;
     const int lg = ceil_log2(C), QB = kEvThreads >> lg, nqb = (Q + QB - 1) / QB;
-    FitPrior pr;
-    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
-        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
-        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
-    }
-    const double ku = (double)(2 * (lg + K) + 18) * 0x1p-53;    // kappa(C, K) u (include/nusi.h)
-    const double klu = (double)(2 * (lg + K) + 14) * 0x1p-53;   // kappa_lambda(C, K) u
+    const FitPrior pr = fit_prior(K, pm, pw);
+    const double ku = fit_ku(lg, K);
+    const double klu = fit_klu(lg, K);
     const ToysOut o{lo, hi, lo_compact ? 1 : 0, hi_compact ? 1 : 0, words, tally};
     const dim3 grid((unsigned)nu, 1, (unsigned)pslices), block(kEvThreads);
     const int M = g.T + 1;
@@ -3252,9 +1427,9 @@ hipError_t launch_poisson_draw(const double* mu, int rows, int C, int P, unsigne
 // shape, units and p-slices.  Per (t, q) and toy p the datum of lane c is DRAWN where it is fitted: draw::poisson of
 // mu_inj[c] = a_inj[q] s_c + sum_j theta_inj[j] T_jc + B_c (the conditional fit's order for mu) under the identity
 // (seed, stream = t, row = q, p, c), which is global -- no chunk, slice or launch shape enters.  Then, against that
-// datum: the best fit (k_detector_profile's / k_detector_fit's iteration, COPIED operation for operation as in
-// k_toys_limit), ONE conditional fit at a_test[q] from the header's cold start (k_conditional_fit's iteration and word,
-// copied; K = 0: a single evaluation, word 0), lambda as k_interval forms it, and the statistic under `mode`.  No LDS.
+// datum: the best fit (k_detector_profile's / k_detector_fit's iteration, the same text by #include as in
+// k_toys_limit), ONE conditional fit at a_test[q] from the header's cold start (k_conditional_fit's rounds,
+// nusi_conditional_newton.inc, and its word; K = 0: a single evaluation, word 0), lambda as k_interval forms it, and the statistic under `mode`.  No LDS.
 // theta_hat_0 goes to row[P] + p of o.theta and the statistic to o.stat (row: the spectrum's place in the chunk's
 // scratch, compact, or t Q + q in the caller's [ntab][Q][P]) -- k_toys_band then selects from them, theta_hat_0 on its
 // lo side and the statistic on hi --, the two words to words[t][q][p][2], the counts to tally[t][q][4] and exceed[t][q]
@@ -3341,267 +1516,17 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
         double thh[NC], muh;
         int sth;
         if constexpr (NC == 1) {
-            // --- k_detector_profile's iteration, copied (one chain) ---
-            auto max = [](double x, double y) { return y > x ? y : x; };
-            const double s = X[0];
-            double S1[1] = {S1h[0]}, a[1];
-            const bool act = d > 0.0 && s > 0.0;
-            bool run = S1[0] != 0.0 && (__ballot(act) & gmask) != 0;
-            int st = run ? 0 : NUSI_FIT_FLAT;
-            {
-                const double x0 = d / S1[0], x1 = b / s;
-                a[0] = act ? x0 - x1 : 0.0;
-            }
-            det_butterfly(a, lgC, max);
-            a[0] = (run && a[0] > 0.0) ? a[0] : 0.0;
-            // (every running chain counts its steps and stops at NUSI_FIT_ITER_MAX: the loop is bounded)
-            while (__any(run)) {
-                double v[2];
-                {
-                    double den = a[0] * s;
-                    den = den + b;
-                    const double qq = s / den;
-                    const double uu = act ? qq : 0.0;
-                    const double r = d * uu;
-                    v[0] = r;
-                    v[1] = r * uu;
-                }
-                det_butterfly(v, lgC, add);
-                {
-                    const double S2 = v[0], S3 = v[1];
-                    const double g = S1[0] - S2;
-                    const double dn = S2 - S1[0];
-                    const double an = a[0] + dn / S3;
-                    if (run) {
-                        ++st;
-                        if (!(g < 0.0)) {
-                            run = false;
-                            if (a[0] == 0.0) st |= NUSI_FIT_BOUNDARY;
-                        } else if (!(an > a[0])) {
-                            run = false;
-                        } else {
-                            a[0] = an;
-                            if ((st & NUSI_FIT_STEPS_MASK) == NUSI_FIT_ITER_MAX) {
-                                run = false;
-                                st |= NUSI_FIT_NOT_CONVERGED;
-                            }
-                        }
-                    }
-                }
-            }
-            double m = a[0] * s;
-            m = m + b;
-            if ((__ballot(in && d > 0.0 && m == 0.0) & gmask) != 0) st |= NUSI_FIT_INFINITE;
+            double S1[1] = {S1h[0]};
+#include "nusi_profile_chain1.inc"
             thh[0] = a[0];
             muh = m;
             sth = st;
         } else {
-            // --- k_detector_fit's iteration, copied ---
             constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
             double S1[NC];
 #pragma unroll
             for (int j = 0; j < NC; ++j) S1[j] = S1h[j];
-            bool live[NC];
-            live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
-            bool sup = b > 0.0;
-            int nl = 0;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                if (j > 0) live[j] = S1[j] > 0.0;
-                sup = sup || (live[j] && X[j] > 0.0);
-                nl += live[j] ? 1 : 0;
-            }
-            const bool act = d > 0.0 && sup;
-            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};   // (1.0: dmin = min(1, the smallest active datum))
-            det_butterfly(dsum, lgC, add);
-            det_butterfly(dmin, lgC, min);
-            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-            double th[NC], the[NC], pp[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                const double x = D0 / ((double)nl * S1[j]);
-                th[j] = live[j] ? x : 0.0;
-                the[j] = th[j];
-                pp[j] = 0.0;
-            }
-            double tt = 1.0;
-            int st = 0, steps = 0, halv = 0, trials = 0;
-            bool run = true, first = true, quad = false;
-            // (every round ends a chain, counts a step towards NUSI_FIT_ITER_MAX or a trial towards NUSI_FIT_TRIALS_MAX)
-            while (__any(run)) {
-                double v[NS];
-                double den = the[0] * X[0];
-#pragma unroll
-                for (int j = 1; j < NC; ++j) den = den + the[j] * X[j];
-                den = den + b;
-                const double wq0 = d / den;
-                const double wq = act ? wq0 : 0.0;
-                const double r0 = wq / den;
-                const double r = act ? r0 : 0.0;
-                {
-                    int i = NC;
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) {
-                        v[j] = X[j] * wq;
-                        const double xr = X[j] * r;   // (not (X_j X_k) r: ten loop-invariant products would stay in registers)
-#pragma unroll
-                        for (int k = j; k < NC; ++k) v[i++] = xr * X[k];
-                    }
-                }
-                det_butterfly(v, lgC, add);
-                const bool bad = any(act && !(den > 0.0));
-                if (run) {
-                    double g[NC];
-#pragma unroll
-                    for (int j = 0; j < NC; ++j) g[j] = (S1[j] - v[j]) + pr.w[j] * (the[j] - pr.m[j]);
-                    bool ok, changed = true;
-                    if (first) {
-                        ok = !bad;
-                        if (!ok) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        }
-                    } else {
-                        double slope = 0.0;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) slope = slope + pp[j] * g[j];
-                        ok = !bad && (quad || !(slope > 0.0));
-                        if (!ok) {
-                            if (trials == NUSI_FIT_TRIALS_MAX) {
-                                run = false;
-                                st |= NUSI_FIT_NOT_CONVERGED;
-                            } else {
-                                ++trials;
-                                ++halv;
-                                tt = tt * 0.5;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) the[j] = th[j] + tt * pp[j];
-                            }
-                        } else {
-                            changed = false;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j) changed = changed || the[j] != th[j];
-                            ++steps;
-                        }
-                    }
-                    if (ok) {
-                        bool fs[NC], conv = true;
-#pragma unroll
-                        for (int j = 0; j < NC; ++j) {
-                            th[j] = the[j];
-                            fs[j] = live[j] && (th[j] > 0.0 || g[j] < 0.0);
-                            const double scale = (S1[j] + v[j]) + pr.w[j] * (th[j] + pr.m[j]);
-                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                            if (fs[j] && !(ag <= ku * scale)) conv = false;
-                        }
-                        if (conv) {
-                            run = false;
-                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
-                            run = false;
-                            st |= NUSI_FIT_NOT_CONVERGED;
-                        } else {
-                            first = false;
-                            // p = -H^-1 g on fs by L D L^T in ascending order (the other components: an identity row, p = 0);
-                            // a component at zero that the direction pushes below leaves fs and the solve is repeated
-                            bool sing = false;
-#pragma unroll 1
-                            for (int rep = 0; rep <= NC; ++rep) {
-                                double Lm[NC][NC], Dg[NC], y[NC];
-                                sing = false;
-                                int i0 = NC;
-                                double a[NC][NC];
-#pragma unroll
-                                for (int j = 0; j < NC; ++j)
-#pragma unroll
-                                    for (int k = j; k < NC; ++k) {
-                                        const double h = v[i0++] + (j == k ? pr.w[j] : 0.0);
-                                        a[k][j] = (fs[j] && fs[k]) ? h : (j == k ? 1.0 : 0.0);
-                                    }
-#pragma unroll
-                                for (int i = 0; i < NC; ++i) {
-                                    double cw[NC];
-#pragma unroll
-                                    for (int j = 0; j < i; ++j) {
-                                        double x = a[i][j];
-#pragma unroll
-                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                        cw[j] = x;
-                                        Lm[i][j] = x / Dg[j];
-                                    }
-                                    double x = a[i][i];
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                                    if (!(x > 0.0)) sing = true;
-                                    Dg[i] = x;
-                                }
-#pragma unroll
-                                for (int i = 0; i < NC; ++i) {
-                                    double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                                    y[i] = x;
-                                }
-#pragma unroll
-                                for (int i = NC - 1; i >= 0; --i) {
-                                    double x = y[i] / Dg[i];
-#pragma unroll
-                                    for (int k = i + 1; k < NC; ++k) x = x - Lm[k][i] * pp[k];
-                                    pp[i] = x;
-                                }
-                                if (sing) break;
-                                bool rm = false;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j)
-                                    if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
-                                        fs[j] = false;
-                                        rm = true;
-                                    }
-                                if (!rm) break;
-                            }
-                            double acc = 0.0;
-#pragma unroll
-                            for (int j = 0; j < NC; ++j)
-                                if (fs[j]) acc = acc + g[j] * pp[j];
-                            if (sing || !(acc < 0.0)) {
-                                run = false;
-                                st |= NUSI_FIT_SINGULAR;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) pp[j] = 0.0;
-                            } else {
-                                double ratio[NC];
-                                tt = 1.0;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) {
-                                    const double x = th[j] / -pp[j];
-                                    ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
-                                    if (ratio[j] < tt) tt = ratio[j];
-                                }
-                                const bool clipped = tt < 1.0;
-                                quad = !clipped && -acc <= dq;
-                                trials = 0;
-#pragma unroll
-                                for (int j = 0; j < NC; ++j) {
-                                    const double x = th[j] + tt * pp[j];
-                                    the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            double m = th[0] * X[0];
-#pragma unroll
-            for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
-            m = m + b;
-            if (!live[0])
-                st |= NUSI_FIT_FLAT;
-            else if (th[0] == 0.0)
-                st |= NUSI_FIT_BOUNDARY;
-#pragma unroll
-            for (int j = 0; j < NC; ++j)
-                if (th[j] == 0.0) st |= NUSI_FIT_ZERO << j;
-            if (any(in && d > 0.0 && m == 0.0)) st |= NUSI_FIT_INFINITE;
-            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#include "nusi_fit_newton.inc"
 #pragma unroll
             for (int j = 0; j < NC; ++j) thh[j] = th[j];
             muh = m;
@@ -3610,9 +1535,8 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
 
         // ---- the conditional fit at a_test, from the header's cold start ------------------------------------------------
         double th[KA];
-        int stc = 0;
+        int st = 0;   // (the conditional fit's word; sth: the best fit's)
         if constexpr (KT > 0) {
-            // --- k_conditional_fit's iteration, copied (the free components indexed i = j - 1) ---
             constexpr int NS = KT + KT * (KT + 1) / 2;
             const bool sup = b > 0.0 || (atest > 0.0 && X[0] > 0.0) || supt;
             const bool act = d > 0.0 && sup;
@@ -3631,166 +1555,16 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
             double tt = 1.0;
             int steps = 0, halv = 0, trials = 0;
             bool run = true, first = true, quad = false;
-            while (__any(run)) {
-                double v[NS];
-                double den = asig;
-#pragma unroll
-                for (int i = 0; i < KT; ++i) den = den + the[i] * X[i + 1];
-                den = den + b;
-                const double wq0 = d / den;
-                const double wq = act ? wq0 : 0.0;
-                const double r0 = wq / den;
-                const double r = act ? r0 : 0.0;
-                {
-                    int i = KT;
-#pragma unroll
-                    for (int j = 0; j < KT; ++j) {
-                        v[j] = X[j + 1] * wq;
-                        const double xr = X[j + 1] * r;
-#pragma unroll
-                        for (int k = j; k < KT; ++k) v[i++] = xr * X[k + 1];
-                    }
-                }
-                det_butterfly(v, lgC, add);
-                const bool bad = any(act && !(den > 0.0));
-                if (run) {
-                    double g[KT];
-#pragma unroll
-                    for (int j = 0; j < KT; ++j) g[j] = (S1h[j + 1] - v[j]) + pr.w[j + 1] * (the[j] - pr.m[j + 1]);
-                    bool ok, changed = true;
-                    if (first) {
-                        ok = !bad;
-                        if (!ok) {
-                            run = false;
-                            stc |= NUSI_FIT_NOT_CONVERGED;
-                        }
-                    } else {
-                        double slope = 0.0;
-#pragma unroll
-                        for (int j = 0; j < KT; ++j) slope = slope + pp[j] * g[j];
-                        ok = !bad && (quad || !(slope > 0.0));
-                        if (!ok) {
-                            if (trials == NUSI_FIT_TRIALS_MAX) {
-                                run = false;
-                                stc |= NUSI_FIT_NOT_CONVERGED;
-                            } else {
-                                ++trials;
-                                ++halv;
-                                tt = tt * 0.5;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) the[j] = th[j] + tt * pp[j];
-                            }
-                        } else {
-                            changed = false;
-#pragma unroll
-                            for (int j = 0; j < KT; ++j) changed = changed || the[j] != th[j];
-                            ++steps;
-                        }
-                    }
-                    if (ok) {
-                        bool fs[KT], conv = true;
-#pragma unroll
-                        for (int j = 0; j < KT; ++j) {
-                            th[j] = the[j];
-                            fs[j] = S1h[j + 1] > 0.0 && (th[j] > 0.0 || g[j] < 0.0);
-                            const double sc = (S1h[j + 1] + v[j]) + pr.w[j + 1] * (th[j] + pr.m[j + 1]);
-                            const double ag = g[j] < 0.0 ? -g[j] : g[j];
-                            if (fs[j] && !(ag <= ku * sc)) conv = false;
-                        }
-                        if (conv) {
-                            run = false;
-                        } else if ((!first && !changed) || steps == NUSI_FIT_ITER_MAX) {
-                            run = false;
-                            stc |= NUSI_FIT_NOT_CONVERGED;
-                        } else {
-                            first = false;
-                            bool sing = false;
-#pragma unroll 1
-                            for (int rep = 0; rep <= KT; ++rep) {
-                                double Lm[KT][KT], Dg[KT], y[KT];
-                                sing = false;
-                                int i0 = KT;
-                                double hm[KT][KT];
-#pragma unroll
-                                for (int j = 0; j < KT; ++j)
-#pragma unroll
-                                    for (int k = j; k < KT; ++k) {
-                                        const double hv = v[i0++] + (j == k ? pr.w[j + 1] : 0.0);
-                                        hm[k][j] = (fs[j] && fs[k]) ? hv : (j == k ? 1.0 : 0.0);
-                                    }
-#pragma unroll
-                                for (int i = 0; i < KT; ++i) {
-                                    double cw[KT];
-#pragma unroll
-                                    for (int j = 0; j < i; ++j) {
-                                        double x = hm[i][j];
-#pragma unroll
-                                        for (int k = 0; k < j; ++k) x = x - cw[k] * Lm[j][k];
-                                        cw[j] = x;
-                                        Lm[i][j] = x / Dg[j];
-                                    }
-                                    double x = hm[i][i];
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - cw[k] * Lm[i][k];
-                                    if (!(x > 0.0)) sing = true;
-                                    Dg[i] = x;
-                                }
-#pragma unroll
-                                for (int i = 0; i < KT; ++i) {
-                                    double x = fs[i] ? -g[i] : 0.0;
-#pragma unroll
-                                    for (int k = 0; k < i; ++k) x = x - Lm[i][k] * y[k];
-                                    y[i] = x;
-                                }
-#pragma unroll
-                                for (int i = KT - 1; i >= 0; --i) {
-                                    double x = y[i] / Dg[i];
-#pragma unroll
-                                    for (int k = i + 1; k < KT; ++k) x = x - Lm[k][i] * pp[k];
-                                    pp[i] = x;
-                                }
-                                if (sing) break;
-                                bool rm = false;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j)
-                                    if (fs[j] && th[j] == 0.0 && pp[j] < 0.0) {
-                                        fs[j] = false;
-                                        rm = true;
-                                    }
-                                if (!rm) break;
-                            }
-                            double acc = 0.0;
-#pragma unroll
-                            for (int j = 0; j < KT; ++j)
-                                if (fs[j]) acc = acc + g[j] * pp[j];
-                            if (sing || !(acc < 0.0)) {
-                                run = false;
-                                stc |= NUSI_FIT_SINGULAR;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) pp[j] = 0.0;
-                            } else {
-                                double ratio[KT];
-                                tt = 1.0;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) {
-                                    const double x = th[j] / -pp[j];
-                                    ratio[j] = (fs[j] && pp[j] < 0.0) ? x : 1.0;
-                                    if (ratio[j] < tt) tt = ratio[j];
-                                }
-                                const bool clipped = tt < 1.0;
-                                quad = !clipped && -acc <= dq;
-                                trials = 0;
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) {
-                                    const double x = th[j] + tt * pp[j];
-                                    the[j] = (clipped && fs[j] && pp[j] < 0.0 && ratio[j] == tt) ? 0.0 : x;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            stc |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
+#define CF_N KT
+#define CF_X(i) X[(i) + 1]
+#define CF_S1(i) S1h[(i) + 1]
+#define CF_LIVE(i) (S1h[(i) + 1] > 0.0)
+#include "nusi_conditional_newton.inc"
+#undef CF_N
+#undef CF_X
+#undef CF_S1
+#undef CF_LIVE
+            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
         } else {
             th[0] = 0.0;
         }
@@ -3801,8 +1575,8 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
         if constexpr (KT > 0) {
 #pragma unroll
             for (int i = 0; i < KT; ++i)
-                if (th[i] == 0.0) stc |= NUSI_FIT_ZERO << (i + 1);
-            if (any(in && d > 0.0 && mu == 0.0)) stc |= NUSI_FIT_INFINITE;
+                if (th[i] == 0.0) st |= NUSI_FIT_ZERO << (i + 1);
+            if (any(in && d > 0.0 && mu == 0.0)) st |= NUSI_FIT_INFINITE;
         }
 
         // ---- lambda from ratios against the best fit's counts (k_interval's), and the statistic -----------------------
@@ -3829,7 +1603,7 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
         double stat = lam > 0.0 ? 2.0 * lam : 0.0, th0 = thh[0];
         if ((ii.mode == 1 && th0 > atest) || (ii.mode == 2 && th0 < atest)) stat = 0.0;
         const bool nofit = (sth & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) != 0;
-        const bool nocond = (stc & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) != 0;
+        const bool nocond = (st & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) != 0;
         if (nofit) th0 = __builtin_nan("");
         if (nofit || nocond) stat = __builtin_nan("");
         if (c == 0 && q < Q) {
@@ -3837,7 +1611,7 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
             if (o.stat) o.stat[rst + p] = stat;
             if (o.words) {
                 o.words[(rq * P + p) * 2] = sth;
-                o.words[(rq * P + p) * 2 + 1] = stc;
+                o.words[(rq * P + p) * 2 + 1] = st;
             }
             if (o.tally) {
                 int* ty = o.tally + rq * 4;
@@ -3859,14 +1633,10 @@ hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int
 {
     if (nu <= 0 || Q <= 0 || P <= 0) return hipSuccess;
     const int lg = ceil_log2(C), QB = kEvThreads >> lg, nqb = (Q + QB - 1) / QB;
-    FitPrior pr;
+    const FitPrior pr = fit_prior(K, pm, pw);
     InjectIn ii{a_inj, a_test, qobs, {}, seed, mode};
-    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) {
-        pr.m[j] = (j >= 1 && j <= K) ? pm[j - 1] : 0.0;
-        pr.w[j] = (j >= 1 && j <= K) ? pw[j - 1] : 0.0;
-        ii.th_inj[j] = (j >= 1 && j <= K) ? th_inj[j - 1] : 0.0;
-    }
-    const double ku = (double)(2 * (lg + K) + 18) * 0x1p-53;    // kappa(C, K) u (include/nusi.h)
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) ii.th_inj[j] = (j >= 1 && j <= K) ? th_inj[j - 1] : 0.0;
+    const double ku = fit_ku(lg, K);
     const InjectOut o{theta, stat, theta_compact ? 1 : 0, stat_compact ? 1 : 0, words, tally, exceed, data};
     const dim3 grid((unsigned)nu, 1, (unsigned)pslices), block(kEvThreads);
     const int M = g.T + 1;
