@@ -1102,6 +1102,31 @@ def inject_tally(words):
     return np.stack([c.sum(axis=-1) for c in cols], axis=-1).astype(np.int32)
 
 
+def _inject_one(Rt, Sq, at, d, T, prior, B, m, w, md, log):
+    """One data set d (C,) through steps 2 - 4 of nusi_plan_response_inject at the test scale ``at``: the best fit
+    (fit_host; profile_host without templates), the conditional fit (fit_fixed_host; without templates the single
+    evaluation events_host, word 0), lambda by limit_host's rule and the statistic under the mode ``md``.  Returns
+    (theta_hat_0, stat, the best fit's word, the conditional fit's, theta_hat (1 + K,), the conditional fit's theta
+    (1 + K,), its mu (C,) and lambda's magnitude); a failed best fit: theta_hat_0 and stat are NaN; a failed conditional fit: stat is NaN."""
+    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
+    if len(T):
+        thh, _, muh, sth = fit_host(Rt, Sq, d, T, prior=prior, background=B, log=log)
+        thc, _, muc, stc = fit_fixed_host(Rt, Sq, at, d, T, prior=prior, background=B, log=log)
+    else:
+        ah, _, muh, sth = profile_host(Rt, Sq, d, background=B, log=log)
+        thh, thc, stc = np.array([float(ah)]), np.array([at]), 0
+        muc = events_host(Rt, Sq, scale=at, background=B)
+    lam, mg = _limit_lambda(at, thc[1:], muc, muh, thh[1:], (d > 0) & (muh > 0), d, m[1:], w[1:], log)
+    stat, th0 = (2.0 * lam if lam > 0.0 else 0.0), float(thh[0])
+    if (md == INJECT_UPPER and th0 > at) or (md == INJECT_DISCOVERY and th0 < at):
+        stat = 0.0
+    if int(sth) & fail:
+        th0 = stat = np.nan
+    if int(stc) & fail:
+        stat = np.nan
+    return th0, stat, int(sth), int(stc), thh, thc, muc, mg
+
+
 def inject_host(R, S, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sided", ranks=None, q_obs=None,
                 templates=None, prior=None, background=None, exp=np.exp, log=np.log, raw=False):
     """nusi_plan_response_inject on the CPU: per table t the toys draw_host(mu_inj[t], P, seed, stream=t) around
@@ -1148,7 +1173,6 @@ def inject_host(R, S, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sid
     s = np.reshape(events_host(R, S), (ntab, Q, C))
     th_all, st_all = np.full((ntab, Q, P), np.nan), np.full((ntab, Q, P), np.nan)
     words, data_all = np.zeros((ntab, Q, P, 2), dtype=np.int32), np.zeros((ntab, Q, P, C))
-    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
     with np.errstate(all="ignore"):
         for t in range(ntab):
             mu_inj = ai[:, None] * s[t]
@@ -1158,28 +1182,136 @@ def inject_host(R, S, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sid
             data_all[t] = draw_host(mu_inj, P, seed, stream=t, exp=exp, log=log)
             for q in range(Q):
                 for p in range(P):
-                    d = data_all[t, q, p]
-                    if K:
-                        thh, _, muh, sth = fit_host(R[t], S[q], d, T, prior=prior, background=B, log=log)
-                        thc, _, muc, stc = fit_fixed_host(R[t], S[q], at[q], d, T, prior=prior, background=B, log=log)
-                    else:
-                        ah, _, muh, sth = profile_host(R[t], S[q], d, background=B, log=log)
-                        thh, thc, stc = np.array([float(ah)]), np.array([at[q]]), 0
-                        muc = events_host(R[t], S[q], scale=at[q], background=B)
-                    lam, _ = _limit_lambda(at[q], thc[1:], muc, muh, thh[1:], (d > 0) & (muh > 0), d, m[1:], w[1:], log)
-                    stat, th0 = (2.0 * lam if lam > 0.0 else 0.0), float(thh[0])
-                    if (md == INJECT_UPPER and th0 > at[q]) or (md == INJECT_DISCOVERY and th0 < at[q]):
-                        stat = 0.0
-                    if int(sth) & fail:
-                        th0 = stat = np.nan
-                    if int(stc) & fail:
-                        stat = np.nan
-                    th_all[t, q, p], st_all[t, q, p], words[t, q, p] = th0, stat, (int(sth), int(stc))
+                    th0, stat, sth, stc = _inject_one(R[t], S[q], at[q], data_all[t, q, p], T, prior, B, m, w, md, log)[:4]
+                    th_all[t, q, p], st_all[t, q, p], words[t, q, p] = th0, stat, (sth, stc)
     out = (order_stat(th_all, r), order_stat(st_all, r), inject_tally(words))
     if q_obs is not None:
         qo = np.broadcast_to(np.asarray(q_obs, dtype=np.float64), (ntab, Q))
         with np.errstate(invalid="ignore"):
             out = out + ((st_all >= qo[..., None]).sum(axis=-1).astype(np.int32),)
+    return out + ((th_all, st_all, words, data_all) if raw else ())
+
+
+BELT_GRID_MAX = 64                                             # the most grid points of belt_host; its status bits:
+BELT_NO_GRID, BELT_NO_FIT, BELT_BAD_POINT, BELT_EMPTY, BELT_LO_EDGE, BELT_HI_EDGE, BELT_GAPS = 1, 2, 4, 8, 16, 32, 64
+
+
+def belt_accept(exceed, tally, a, alpha, valid, P, flags=0):
+    """The acceptance and interval rule of belt_host on arrays.  exceed (..., G) and tally
+    (..., G, 4): the counts of P toys a point; a (..., G): the test scales; valid (..., G) bool (or None: all): the
+    points whose observed fits held -- the others have no toys; flags (...): the observed side's bits (BELT_NO_GRID,
+    BELT_NO_FIT, BELT_BAD_POINT of a failed conditional fit), OR-ed into the word.  nv = P - tally[..., 0] -
+    tally[..., 1]; a point is accepted iff it is valid, nv > 0 and float(exceed) > alpha * float(nv), one multiplication
+    and one comparison.  Returns (lo (...), hi (...), idx (..., 2) int32, status (...) int32): the first and the last
+    accepted grid point and the scales there -- NaN and -1 without one, BELT_EMPTY --, BELT_BAD_POINT where a point has
+    nv = 0, BELT_LO_EDGE where idx[0] = 0, BELT_HI_EDGE where idx[1] = G - 1 and BELT_GAPS where a point between the two
+    is not accepted.  Nothing is interpolated."""
+    ex = np.asarray(exceed)
+    ty = np.asarray(tally)
+    a = np.asarray(a, dtype=np.float64)
+    G = ex.shape[-1]
+    if ty.shape != ex.shape + (4,) or a.shape != ex.shape:
+        raise ValueError("belt_accept: exceed (..., G), tally (..., G, 4) and a (..., G) do not match")
+    ok = np.ones(ex.shape, dtype=bool) if valid is None else np.broadcast_to(np.asarray(valid, dtype=bool), ex.shape)
+    nv = int(P) - ty[..., 0].astype(np.int64) - ty[..., 1].astype(np.int64)
+    acc = ok & (nv > 0) & (ex.astype(np.float64) > np.float64(alpha) * nv.astype(np.float64))
+    nacc = acc.sum(axis=-1)
+    first = np.where(nacc > 0, np.argmax(acc, axis=-1), -1)
+    last = np.where(nacc > 0, G - 1 - np.argmax(acc[..., ::-1], axis=-1), -1)
+    st = np.array(np.broadcast_to(np.asarray(flags, dtype=np.int32), nacc.shape))
+    st[np.any(nv <= 0, axis=-1)] |= BELT_BAD_POINT
+    st[nacc == 0] |= BELT_EMPTY
+    st[first == 0] |= BELT_LO_EDGE
+    st[last == G - 1] |= BELT_HI_EDGE
+    st[(nacc > 0) & (nacc != last - first + 1)] |= BELT_GAPS
+    lo = np.where(nacc > 0, np.take_along_axis(a, np.maximum(first, 0)[..., None], axis=-1)[..., 0], np.nan)
+    hi = np.where(nacc > 0, np.take_along_axis(a, np.maximum(last, 0)[..., None], axis=-1)[..., 0], np.nan)
+    return lo, hi, np.stack([first, last], axis=-1).astype(np.int32), st.astype(np.int32)
+
+
+def belt_host(R, S, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, templates=None, prior=None, background=None,
+              exp=np.exp, log=np.log, raw=False):
+    """The toy-calibrated confidence interval of the signal's scale -- the Feldman-Cousins interval by the profile
+    construction -- on a grid of test scales, as a loop of the existing host forms (numpy only; there is no device call
+    yet: DESIGN.md sec. 4, "The calibrated interval: the host form").  Per table t, spectrum q and grid point g the test
+    scale is a = frac[g] * ref[t, q]; the data get inject_host's loop body at a (fit_host / profile_host,
+    fit_fixed_host, _limit_lambda), which gives the observed records and q_obs; the toys are draw_host of the conditional
+    fit's own mu with stream = t at row q G + g, and each gets the same loop body at a.
+
+    R: (M, C) or (ntab, M, C).  S: (M,) or (Q, M).  data: (C,).  frac: (G,), finite, >= 0, strictly ascending.  ref: None
+    (1), a number or (ntab, Q); NaN, infinite or negative: BELT_NO_GRID.  mode: "two-sided", "upper" or INJECT_*.  alpha in
+    (0, 1).  templates, prior, background, log: as for fit_host; exp: as for draw_host.  Returns (lo (ntab, Q), hi (ntab,
+    Q), idx (ntab, Q, 2) int32, status (ntab, Q) int32, exceed (ntab, Q, G) int32, tally (ntab, Q, G, 4) int32, q_obs
+    (ntab, Q, G), theta_obs (ntab, Q, 1 + G, 1 + K), words_obs (ntab, Q, 1 + G) int32) and with raw also (theta_all
+    (ntab, Q, G, P), stat_all (ntab, Q, G, P), words_all (ntab, Q, G, P, 2) int32, data_all (ntab, Q, G, P, C)).  A point
+    without toys (no grid value, a failed observed fit) has q_obs NaN, counts of 0 and raw outputs of NaN / 0.  No axis
+    is squeezed."""
+    R = np.asarray(R, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    if R.ndim == 2:
+        R = R[None]
+    if S.ndim == 1:
+        S = S[None]
+    if R.ndim != 3 or S.ndim != 2 or R.shape[1] != S.shape[1]:
+        raise ValueError("belt_host: R (.., M, C) and S (.., M) do not match: %s, %s" % (R.shape, S.shape))
+    ntab, C, Q, P = R.shape[0], R.shape[2], S.shape[0], int(P)
+    if not 1 <= P:
+        raise ValueError("belt_host: P must be >= 1")
+    md = {"two-sided": INJECT_TWO_SIDED, "upper": INJECT_UPPER}.get(mode, mode)
+    if md not in (INJECT_TWO_SIDED, INJECT_UPPER):
+        raise ValueError("belt_host: mode must be 'two-sided' or 'upper'")
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("belt_host: alpha must lie in (0, 1)")
+    fr = np.asarray(frac, dtype=np.float64).reshape(-1)
+    G = len(fr)
+    if not 1 <= G <= BELT_GRID_MAX or not np.all(np.isfinite(fr)) or np.any(fr < 0) or np.any(np.diff(fr) <= 0):
+        raise ValueError("belt_host: frac must hold 1 .. %d finite values >= 0, strictly ascending" % BELT_GRID_MAX)
+    d = np.asarray(data, dtype=np.float64).reshape(-1)
+    if d.shape != (C,) or not np.all(np.isfinite(d)) or np.any(d < 0):
+        raise ValueError("belt_host: data must be (C,), finite and >= 0")
+    K = 0 if templates is None else _templates(templates, C).shape[0]
+    T = np.zeros((0, C)) if K == 0 else _templates(templates, C)
+    m, w = _prior(K, prior)
+    B = np.zeros(C) if background is None else np.array(np.broadcast_to(np.asarray(background, dtype=np.float64), (C,)))
+    rf = np.array(np.broadcast_to(np.asarray(1.0 if ref is None else ref, dtype=np.float64), (ntab, Q)))
+    with np.errstate(invalid="ignore"):
+        a = fr[None, None, :] * rf[:, :, None]
+        agood = (rf >= 0)[:, :, None] & (a < np.inf)               # (a ref of -1 at frac = 0 gives -0.0: the ref decides)
+    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
+    q_obs = np.full((ntab, Q, G), np.nan)
+    theta_obs, words_obs = np.full((ntab, Q, 1 + G, 1 + K), np.nan), np.zeros((ntab, Q, 1 + G), dtype=np.int32)
+    th_all, st_all = np.full((ntab, Q, G, P), np.nan), np.full((ntab, Q, G, P), np.nan)
+    words, data_all = np.zeros((ntab, Q, G, P, 2), dtype=np.int32), np.zeros((ntab, Q, G, P, C))
+    valid = np.zeros((ntab, Q, G), dtype=bool)
+    flags = np.zeros((ntab, Q), dtype=np.int32)
+    with np.errstate(all="ignore"):
+        for t in range(ntab):
+            mu_inj = np.zeros((Q, G, C))
+            for q in range(Q):
+                for g in range(G):
+                    at = float(a[t, q, g]) if agood[t, q, g] else 0.0
+                    _, stat, sth, stc, thh, thc, muc, _ = _inject_one(R[t], S[q], at, d, T, prior, B, m, w, md, log)
+                    theta_obs[t, q, 0], words_obs[t, q, 0] = thh, sth
+                    if sth & fail:
+                        flags[t, q] |= BELT_NO_FIT
+                    if not agood[t, q, g]:
+                        flags[t, q] |= BELT_NO_GRID
+                        continue
+                    theta_obs[t, q, 1 + g], words_obs[t, q, 1 + g] = thc, stc
+                    if not sth & fail and stc & fail:
+                        flags[t, q] |= BELT_BAD_POINT
+                    if not (sth | stc) & fail:
+                        valid[t, q, g], q_obs[t, q, g], mu_inj[q, g] = True, stat, muc
+            toys = np.reshape(draw_host(mu_inj.reshape(Q * G, C), P, seed, stream=t, exp=exp, log=log), (Q, G, P, C))
+            for q, g in zip(*np.nonzero(valid[t])):
+                data_all[t, q, g] = toys[q, g]
+                for p in range(P):
+                    th0, stat, sth, stc = _inject_one(R[t], S[q], float(a[t, q, g]), toys[q, g, p], T, prior, B, m, w, md, log)[:4]
+                    th_all[t, q, g, p], st_all[t, q, g, p], words[t, q, g, p] = th0, stat, (sth, stc)
+    tally = np.where(valid[..., None], inject_tally(words), 0).astype(np.int32)
+    with np.errstate(invalid="ignore"):
+        exceed = (st_all >= q_obs[..., None]).sum(axis=-1).astype(np.int32)
+    out = belt_accept(exceed, tally, a, alpha, valid, P, flags) + (exceed, tally, q_obs, theta_obs, words_obs)
     return out + ((th_all, st_all, words, data_all) if raw else ())
 
 
