@@ -690,6 +690,84 @@ int nusi_plan_response_inject_host(nusi_plan *plan, const double *R, int ntab, c
                                    const int *rank, int NR, const double *q_obs, double *band_theta, double *band_stat,
                                    int *tally, int *exceed, double *theta_all, double *stat_all, int *words_all,
                                    double *data_all);
+/* nusi_plan_response_belt (k_belt, k_belt_accept): the toy-calibrated confidence interval of the signal's scale -- the
+ * Feldman-Cousins interval by the profile construction -- on a grid of test scales, in one call.  What
+ * nusi_plan_response_inject samples, this call inverts: per table t and spectrum q the set of grid points whose toy
+ * p-value of the data exceeds alpha.  detector.belt_host / detector.belt_accept (numpy) are the same rules, and the call
+ * reproduces them: the toys, theta_hat, the words' flags, the counts and the interval to the bit, q_obs and stat as
+ * nusi_plan_response_inject reproduces inject_host's.  K = nusi_plan_templates(plan) = 0 .. 3.
+ *
+ *   The grid.  a[t][q][g] = frac[g] ref[t][q], one multiplication; frac [G] finite, >= 0 and strictly ascending, G = 1 ..
+ *     NUSI_BELT_GRID_MAX; ref [ntab][Q], NULL = 1.  A ref that is NaN, infinite or negative -- what
+ *     nusi_plan_response_limit returns for a failed or unbounded record -- or a product that is infinite gives
+ *     NUSI_BELT_NO_GRID and is not refused: agood = ref >= 0 && a < inf, and the fits of such a point run at 0.
+ *   The observed side.  d_theta_obs [ntab][Q][1 + G][1 + K] and d_words_obs [ntab][Q][1 + G]: [0] is
+ *     nusi_plan_response_fit's record against data [C] (nusi_plan_response_profile's at K = 0), theta_hat and its word;
+ *     NOT_CONVERGED or SINGULAR there gives NUSI_BELT_NO_FIT and no valid point.  [1 + g] is
+ *     nusi_plan_response_fit_fixed's record at a from that call's cold start (K = 0: the single evaluation, word 0), theta
+ *     with [0] = a; a point that is not agood has NaN and word 0 there.  A conditional fit so flagged after a good best
+ *     fit gives NUSI_BELT_BAD_POINT.  d_q_obs [ntab][Q][G]: steps 2 - 4 of nusi_plan_response_inject applied to the data
+ *     at a -- lambda by the ratio form, q_obs = lambda > 0 ? 2 lambda : +0.0, and +0.0 under NUSI_INJECT_UPPER where
+ *     theta_hat_0 > a --, so a toy equal to the data in every bin has stat == q_obs to the bit.  A point is VALID iff it
+ *     is agood and neither observed word is flagged; an invalid point has q_obs = NaN, no toys, counts of 0 and raw
+ *     outputs of NaN (doubles) and 0 (ints and the counts of data_all).
+ *   The toys.  Toy p < P of a valid point is the draw ("Drawing counts") of the observed conditional fit's own mu,
+ *         mu_inj[c] = a s[t][q][c] (+ theta_j T_j[c], j ascending) + B[c],
+ *     with the identity (seed, stream = t, row = q G + g, p, c), and gets steps 2 - 4 of nusi_plan_response_inject at
+ *     a_test = a under `mode` (NUSI_INJECT_TWO_SIDED or NUSI_INJECT_UPPER).  d_theta_all, d_stat_all [ntab][Q][G][P],
+ *     d_words_all [..][P][2] and d_data_all [..][P][C] are that call's raw records with g in front of p; d_tally
+ *     [ntab][Q][G][4] and d_exceed [ntab][Q][G] its counts, exceed against q_obs[t][q][g] (a NaN on either side never
+ *     counts), zeroed on the stream and added to with integer atomics.
+ *   Acceptance.  nv = P - tally[0] - tally[1]; a point is accepted iff it is valid, nv > 0 and (double)exceed > alpha
+ *     (double)nv -- one multiplication, one strict comparison; alpha in (0, 1).  d_idx [ntab][Q][2]: the first and the
+ *     last accepted g; d_lo, d_hi [ntab][Q]: a there; none accepted: -1 and NaN.  d_status [ntab][Q]: NUSI_BELT_NO_GRID,
+ *     _NO_FIT, _BAD_POINT (above, or a point with nv <= 0), _EMPTY (no point accepted), _LO_EDGE (idx[0] = 0), _HI_EDGE
+ *     (idx[1] = G - 1), _GAPS (a point between the two is not accepted).  Nothing is interpolated.
+ *
+ * Every output is a DEVICE pointer and may be NULL, but not all of them.  The grid is nusi_plan_response_inject's with
+ * the records in the spectra's place: units of one table and QB rows of its Q G, p-slices on the grid's z
+ * (NUSI_OPT_ENSEMBLE_PSLICES, or automatic); every p-slice recomputes a record's observed side and slice 0 stores it.
+ * Where the interval is asked for (d_lo, d_hi, d_idx or d_status), exceed, tally and words_obs are needed: one the caller
+ * does not give lives in the plan's scratch, 4 G, 16 G and 4 (1 + G) bytes a (t, q) pair, and the call runs in chunks of
+ * whole pairs under NUSI_OPT_ENSEMBLE_LIMIT_MB / _BYTES, of at most 2^22 records.  A draw's identity is global, so every
+ * budget and every slicing give the same bits.
+ *
+ * nusi_belt_shape: the call's size limits as a pure function -- no plan, no device; the call itself applies it with the
+ * detector's C.  NUSI_OK and *units (if not NULL) = ntab ceil(Q G / QB), the units of the whole call, or NUSI_EPARAM for
+ * C outside 1 .. NUSI_DETECTOR_BINS_MAX, ntab < 1, Q outside 1 .. 2^19, G outside 1 .. NUSI_BELT_GRID_MAX, P outside 1 ..
+ * NUSI_DRAW_DATASETS_MAX (no series is kept, so the band's 4096 does not bind; element counts are size_t) or ntab Q G >=
+ * 2^31 (a record's row in an int).
+ *
+ * S, data, frac and ref are host arrays and are copied (they ride behind the spectra in the plan's staging block).
+ * Asynchronous and ordered with the plan's other detector calls like nusi_plan_response_fit.  NUSI_ESTATE without a
+ * detector; NUSI_EPARAM for nusi_belt_shape's limits, a NULL d_R, S, data or frac, a frac that is not finite, negative or
+ * not strictly ascending, a mode other than the two, an alpha outside (0, 1), a negative or non-finite entry of S or
+ * data, every output NULL (nothing to do), or a budget below one pair's scratch; a refused call changes nothing and does
+ * no device work.  _host: R and the outputs in host memory, synchronous. */
+#define NUSI_BELT_GRID_MAX 64
+#define NUSI_BELT_NO_GRID 1
+#define NUSI_BELT_NO_FIT 2
+#define NUSI_BELT_BAD_POINT 4
+#define NUSI_BELT_EMPTY 8
+#define NUSI_BELT_LO_EDGE 16
+#define NUSI_BELT_HI_EDGE 32
+#define NUSI_BELT_GAPS 64
+int nusi_belt_shape(int C, int ntab, int Q, int G, int P, long long *units);
+int nusi_plan_response_belt(nusi_plan *plan, const double *d_R /* [ntab][M][C] */, int ntab, const double *S /* [Q][M] */,
+                            int Q, const double *data /* [C] */, const double *frac /* [G] */, int G,
+                            const double *ref /* NULL = 1, else [ntab][Q] */, int P, unsigned long long seed, int mode,
+                            double alpha, double *d_lo /* [ntab][Q] */, double *d_hi /* [ntab][Q] */,
+                            int *d_idx /* [ntab][Q][2] */, int *d_status /* [ntab][Q] */, int *d_exceed /* [ntab][Q][G] */,
+                            int *d_tally /* [ntab][Q][G][4] */, double *d_q_obs /* [ntab][Q][G] */,
+                            double *d_theta_obs /* [ntab][Q][1 + G][1 + K] */, int *d_words_obs /* [ntab][Q][1 + G] */,
+                            double *d_theta_all /* [ntab][Q][G][P] */, double *d_stat_all /* [ntab][Q][G][P] */,
+                            int *d_words_all /* [ntab][Q][G][P][2] */, double *d_data_all /* [ntab][Q][G][P][C] */,
+                            void *stream);
+int nusi_plan_response_belt_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
+                                 const double *frac, int G, const double *ref, int P, unsigned long long seed, int mode,
+                                 double alpha, double *lo, double *hi, int *idx, int *status, int *exceed, int *tally,
+                                 double *q_obs, double *theta_obs, int *words_obs, double *theta_all, double *stat_all,
+                                 int *words_all, double *data_all);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);

@@ -83,6 +83,7 @@ EXPORTS = [
     "nusi_plan_response_ensemble_limit", "nusi_plan_response_ensemble_limit_host",
     "nusi_plan_draw_counts", "nusi_plan_draw_counts_host",
     "nusi_plan_response_inject", "nusi_plan_response_inject_host",
+    "nusi_belt_shape", "nusi_plan_response_belt", "nusi_plan_response_belt_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -100,6 +101,9 @@ OPT_ENSEMBLE_LIMIT_MB, OPT_ENSEMBLE_LIMIT_BYTES = 15, 16
 BAND_RANKS_MAX = 16
 BAND_DATASETS_MAX = 4096
 INJECT_TWO_SIDED, INJECT_UPPER, INJECT_DISCOVERY = 0, 1, 2     # Plan.inject's mode (include/nusi.h NUSI_INJECT_*)
+# Plan.belt: the most grid points and the status word's bits (include/nusi.h NUSI_BELT_*, detector.BELT_*)
+BELT_GRID_MAX = 64
+BELT_NO_GRID, BELT_NO_FIT, BELT_BAD_POINT, BELT_EMPTY, BELT_LO_EDGE, BELT_HI_EDGE, BELT_GAPS = 1, 2, 4, 8, 16, 32, 64
 DRAW_DATASETS_MAX = 1 << 26     # Plan.draw: the toys per bin (the generator's counter holds p * 64 + c)
 DRAW_COUNTS_MAX = ((1 << 31) - 1) * 256     # ... and the counts of a call, rows * P * C (one launch, 256 counts a block)
 
@@ -189,6 +193,11 @@ def load():
                                           vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_inject_host": (i, [vp, dp, i, dp, i, dp, dp, dp, i, ctypes.c_ulonglong, i, ip, i, dp,
                                                dp, dp, ip, ip, dp, dp, ip, dp]),
+        "nusi_belt_shape": (i, [i, i, i, i, i, ctypes.POINTER(ctypes.c_longlong)]),
+        "nusi_plan_response_belt": (i, [vp, vp, i, dp, i, dp, dp, i, dp, i, ctypes.c_ulonglong, i, d,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_belt_host": (i, [vp, dp, i, dp, i, dp, dp, i, dp, i, ctypes.c_ulonglong, i, d,
+                                             dp, dp, ip, ip, ip, ip, dp, dp, ip, dp, dp, ip, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

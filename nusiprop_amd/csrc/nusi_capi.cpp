@@ -2535,6 +2535,157 @@ int nusi_plan_response_inject_host(nusi_plan* pl, const double* R, int ntab, con
                        });
 }
 
+// The toy-calibrated interval (nusi_detector.hip k_belt, then k_belt_accept).  The size limits are a pure function, which
+// the call applies with the detector's C.  data rides in events_stage's data slot (P = 1), frac [G] and ref [ntab][Q]
+// (where given) as its extra vectors.  The interval needs exceed, tally and words_obs: one the caller does not give
+// lives in the plan's scratch (d_toys), and the call then runs in chunks of whole (t, q) pairs.
+int nusi_belt_shape(int C, int ntab, int Q, int G, int P, long long* units)
+{
+    const std::string w = "response belt: ";
+    if (C < 1 || C > NUSI_DETECTOR_BINS_MAX) return fail(NUSI_EPARAM, w + "C outside 1 .. NUSI_DETECTOR_BINS_MAX");
+    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, w + "need ntab >= 1 and 1 <= Q <= 2^19");
+    if (G < 1 || G > NUSI_BELT_GRID_MAX) return fail(NUSI_EPARAM, w + "G outside 1 .. NUSI_BELT_GRID_MAX");
+    if (P < 1 || P > NUSI_DRAW_DATASETS_MAX) return fail(NUSI_EPARAM, w + "P outside 1 .. NUSI_DRAW_DATASETS_MAX");
+    const long long rows = (long long)Q * G;   // (<= 2^25)
+    if ((long long)ntab * rows >= (1ll << 31)) return fail(NUSI_EPARAM, w + "too many records (ntab Q G >= 2^31)");
+    const long long QB = nusi::belt_block(C);
+    if (units) *units = (long long)ntab * ((rows + QB - 1) / QB);
+    return NUSI_OK;
+}
+
+struct BeltPlan {
+    int pairs, ppc;                       // the (t, q) pairs of the call and of a chunk
+    bool accept, ex_scr, ty_scr, wo_scr;  // the interval is asked for; what it needs from the scratch
+    size_t per;                           // the scratch's bytes a pair
+};
+static int belt_check(const nusi_plan* pl, const void* R, int ntab, const double* S, int Q, const double* data,
+                      const double* frac, int G, int P, int mode, double alpha, bool any_out)
+{
+    const std::string w = "response belt: ";
+    if (int r = detector_plan(pl, "response belt")) return r;
+    if (int r = nusi_belt_shape(pl->det_C, ntab, Q, G, P, nullptr)) return r;
+    if (!R || !S || !data || !frac) return fail(NUSI_EPARAM, w + "R, S, data and frac must not be NULL");
+    for (int g = 0; g < G; ++g)
+        if (!(frac[g] >= 0.0) || !std::isfinite(frac[g]) || (g > 0 && !(frac[g] > frac[g - 1])))
+            return fail(NUSI_EPARAM, w + "frac must be finite, >= 0 and strictly ascending");
+    if (mode != NUSI_INJECT_TWO_SIDED && mode != NUSI_INJECT_UPPER)
+        return fail(NUSI_EPARAM, w + "mode must be NUSI_INJECT_TWO_SIDED or NUSI_INJECT_UPPER");
+    if (!(alpha > 0.0 && alpha < 1.0)) return fail(NUSI_EPARAM, w + "alpha must lie in (0, 1)");
+    if (!any_out) return fail(NUSI_EPARAM, w + "every output is NULL: nothing to do");
+    return events_check(pl, "response belt", (const double*)R, ntab, S, Q, nullptr, data, 1);
+}
+static int belt_plan(const nusi_plan* pl, int ntab, int Q, int G, bool accept, const void* exceed, const void* tally,
+                     const void* words_obs, BeltPlan& bp)
+{
+    bp.pairs = ntab * Q;   // (< 2^31: nusi_belt_shape)
+    bp.accept = accept;
+    bp.ex_scr = accept && !exceed;
+    bp.ty_scr = accept && !tally;
+    bp.wo_scr = accept && !words_obs;
+    bp.per = sizeof(int) * ((bp.ex_scr ? (size_t)G : 0) + (bp.ty_scr ? (size_t)4 * G : 0) + (bp.wo_scr ? (size_t)G + 1 : 0));
+    bp.ppc = std::min(bp.pairs, std::max(kToysChunkSpectra / G, 1));   // (also with every array given)
+    if (bp.per) {
+        const size_t budget = pl->toys_b > 0 ? (size_t)pl->toys_b : pl->toys_mb > 0 ? (size_t)pl->toys_mb << 20 : kToysScratchBytes;
+        if (budget < bp.per)
+            return fail(NUSI_EPARAM, "response belt: NUSI_OPT_ENSEMBLE_LIMIT_MB / _BYTES is below one (t, q) pair's scratch (4 G, 16 G and 4 (1 + G) bytes for exceed, tally and words_obs)");
+        bp.ppc = (int)std::min<size_t>(budget / bp.per, (size_t)bp.ppc);
+    }
+    return NUSI_OK;
+}
+
+int nusi_plan_response_belt(nusi_plan* pl, const double* d_R, int ntab, const double* S, int Q, const double* data,
+                            const double* frac, int G, const double* ref, int P, unsigned long long seed, int mode,
+                            double alpha, double* d_lo, double* d_hi, int* d_idx, int* d_status, int* d_exceed, int* d_tally,
+                            double* d_q_obs, double* d_theta_obs, int* d_words_obs, double* d_theta_all, double* d_stat_all,
+                            int* d_words_all, double* d_data_all, void* stream)
+{
+    const bool accept = d_lo || d_hi || d_idx || d_status;
+    const bool any_out = accept || d_exceed || d_tally || d_q_obs || d_theta_obs || d_words_obs || d_theta_all || d_stat_all ||
+                         d_words_all || d_data_all;
+    if (int r = belt_check(pl, d_R, ntab, S, Q, data, frac, G, P, mode, alpha, any_out)) return r;
+    BeltPlan bp;
+    if (int r = belt_plan(pl, ntab, Q, G, accept, d_exceed, d_tally, d_words_obs, bp)) return r;
+    const size_t nn = (size_t)ntab * Q;
+    std::vector<double> extra((size_t)G + (ref ? nn : 0));
+    memcpy(extra.data(), frac, sizeof(double) * G);
+    if (ref) memcpy(extra.data() + G, ref, sizeof(double) * nn);
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    const int C = pl->det_C;
+    if (int r = events_stage(pl, S, Q, nullptr, data, 1, s, extra.data(), extra.size())) return r;
+    const EvtLayout l = evt_layout(pl, Q, 1, extra.size());
+    const double* dS = pl->d_evt;
+    const double* d_data = pl->d_evt + l.data;
+    const double* d_frac = pl->d_evt + l.extra;
+    const double* d_ref = ref ? d_frac + G : nullptr;
+    // (every earlier detector call has finished: events_stage -- the scratch is free)
+    const size_t need = bp.per * (size_t)bp.ppc;
+    if (pl->toys_bytes < need) {
+        hipFree(pl->d_toys);
+        pl->d_toys = nullptr;
+        pl->toys_bytes = 0;
+        HIPCHECK(hipMalloc(&pl->d_toys, need));
+        pl->toys_bytes = need;
+    }
+    // the scratch of a chunk: exceed [ppc][G], tally [ppc][G][4], words_obs [ppc][1 + G], those of them that live there
+    int* scr = (int*)pl->d_toys;
+    int* ex = d_exceed;
+    int* ty = d_tally;
+    int* wo = d_words_obs;
+    size_t off = 0;
+    if (bp.ex_scr) ex = scr + off, off += (size_t)bp.ppc * G;
+    if (bp.ty_scr) ty = scr + off, off += (size_t)bp.ppc * G * 4;
+    if (bp.wo_scr) wo = scr + off, off += (size_t)bp.ppc * (G + 1);
+    if (d_exceed) HIPCHECK(hipMemsetAsync(d_exceed, 0, sizeof(int) * nn * G, s));
+    if (d_tally) HIPCHECK(hipMemsetAsync(d_tally, 0, sizeof(int) * nn * G * 4, s));
+    int ncu = 0;
+    HIPCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device));
+    const long long want = (long long)kEnsBlocksPerCU * (ncu > 0 ? ncu : 1);
+    const int QB = nusi::belt_block(C);
+    for (int pr0 = 0; pr0 < bp.pairs; pr0 += bp.ppc) {
+        const int pr1 = pr0 + std::min(bp.ppc, bp.pairs - pr0);
+        const long long nu = ((long long)(pr1 - pr0) * G + QB - 1) / QB;
+        const int ps = pl->ens_pslices > 0 ? std::min(pl->ens_pslices, P)
+                                           : (int)std::min<long long>(std::max(P / kEnsSliceDatasets, 1), (want + nu - 1) / nu);
+        if (bp.ex_scr || bp.ty_scr)   // (the counts in the scratch are one block: exceed, then tally)
+            HIPCHECK(hipMemsetAsync(scr, 0, sizeof(int) * (size_t)bp.ppc * G * ((bp.ex_scr ? 1 : 0) + (bp.ty_scr ? 4 : 0)), s));
+        HIPCHECK(nusi::launch_belt(pl->gd, d_R, dS, Q, d_data, d_frac, G, d_ref, P, seed, mode, detector_bg(pl), C, pl->fit_K,
+                                   pl->d_tpl, pl->fit_m, pl->fit_w, pr0, pr1, ps, ex, bp.ex_scr, ty, bp.ty_scr, wo, bp.wo_scr,
+                                   d_q_obs, d_theta_obs, d_theta_all, d_stat_all, d_words_all, d_data_all, s));
+        if (accept)
+            HIPCHECK(nusi::launch_belt_accept(d_frac, G, d_ref, P, alpha, pr0, pr1, ex, bp.ex_scr, ty, bp.ty_scr, wo, bp.wo_scr,
+                                              d_lo, d_hi, d_idx, d_status, s));
+    }
+    return detector_mark(pl, s);
+}
+
+int nusi_plan_response_belt_host(nusi_plan* pl, const double* R, int ntab, const double* S, int Q, const double* data,
+                                 const double* frac, int G, const double* ref, int P, unsigned long long seed, int mode,
+                                 double alpha, double* lo, double* hi, int* idx, int* status, int* exceed, int* tally,
+                                 double* q_obs, double* theta_obs, int* words_obs, double* theta_all, double* stat_all,
+                                 int* words_all, double* data_all)
+{
+    const bool accept = lo || hi || idx || status;
+    const bool any_out = accept || exceed || tally || q_obs || theta_obs || words_obs || theta_all || stat_all || words_all ||
+                         data_all;
+    if (int r = belt_check(pl, R, ntab, S, Q, data, frac, G, P, mode, alpha, any_out)) return r;
+    BeltPlan bp;   // (the budget's refusal too, before the device buffers)
+    if (int r = belt_plan(pl, ntab, Q, G, accept, exceed, tally, words_obs, bp)) return r;
+    const size_t nn = (size_t)ntab * Q, ng = nn * G, NC = (size_t)pl->fit_K + 1;
+    return events_host(pl, R, ntab,
+                       {{lo, nn, sizeof(double)}, {hi, nn, sizeof(double)}, {idx, nn * 2, sizeof(int)}, {status, nn, sizeof(int)},
+                        {exceed, ng, sizeof(int)}, {tally, ng * 4, sizeof(int)}, {q_obs, ng, sizeof(double)},
+                        {theta_obs, nn * (G + 1) * NC, sizeof(double)}, {words_obs, nn * (G + 1), sizeof(int)},
+                        {theta_all, ng * P, sizeof(double)}, {stat_all, ng * P, sizeof(double)},
+                        {words_all, ng * P * 2, sizeof(int)}, {data_all, ng * P * pl->det_C, sizeof(double)}},
+                       "response belt", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_belt(pl, dI, ntab, S, Q, data, frac, G, ref, P, seed, mode, alpha,
+                                                          (double*)d[0], (double*)d[1], (int*)d[2], (int*)d[3], (int*)d[4],
+                                                          (int*)d[5], (double*)d[6], (double*)d[7], (int*)d[8], (double*)d[9],
+                                                          (double*)d[10], (int*)d[11], (double*)d[12], nullptr);
+                       });
+}
+
 int nusi_plan_profile_begin(nusi_plan* pl, int max_calls)
 {
     HIPCHECK(hipSetDevice(pl->device));

@@ -23,6 +23,10 @@
 //   k_inject<NC>          per (table, spectrum) P toys drawn from the injected expectation where they are fitted: the
 //                         best fit, one conditional fit and the statistic per toy; k_toys_band then selects the order
 //                         statistics of theta_hat_0 and of the statistic (nusi_plan_response_inject)
+//   k_belt<NC>, k_belt_accept
+//                         k_inject's toy body once against the data and then per toy, on records (table, spectrum, grid
+//                         point of the test scale), the toys drawn from the observed conditional fit's expectation; then
+//                         per (table, spectrum) the accepted grid points as an interval (nusi_plan_response_belt)
 //
 // The iterations several of these kernels run exist once, as text the kernels #include inside their bodies (not as
 // __device__ helpers, which moved the kernels' registers: DESIGN.md sec. 4, "The shared iterations"):
@@ -31,7 +35,8 @@
 //   nusi_profile_chain4.inc      k_detector_profile's, four chains a lane: k_detector_profile, k_ensemble_profile
 //   nusi_profile_chain1.inc      k_detector_profile's, one chain a lane: the best fit at NC = 1 of k_interval,
 //                                k_toys_limit, k_inject
-//   nusi_conditional_newton.inc  k_conditional_fit's rounds: k_conditional_fit, k_inject
+//   nusi_conditional_newton.inc  k_conditional_fit's rounds: k_conditional_fit, k_inject, k_belt
+//   nusi_toy_body.inc            one data set's best fit, conditional fit and statistic: k_inject, k_belt
 //   nusi_search_setup.inc, nusi_search_side.inc
 //                                the search for a limit: k_interval, k_toys_limit
 //   nusi_ldlt_solve.inc          the Newton direction, inside the fit's, the conditional fit's and the search's text
@@ -1512,100 +1517,7 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
         const double d = in ? draw::poisson(mup, draw::ident(ii.seed, (unsigned)t, (unsigned)qc, (unsigned)p, (unsigned)c)) : 0.0;
         if (o.data && in && q < Q) o.data[(rq * P + p) * C + c] = d;
 
-        // ---- the best fit --------------------------------------------------------------------------------------------
-        double thh[NC], muh;
-        int sth;
-        if constexpr (NC == 1) {
-            double S1[1] = {S1h[0]};
-#include "nusi_profile_chain1.inc"
-            thh[0] = a[0];
-            muh = m;
-            sth = st;
-        } else {
-            constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
-            double S1[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) S1[j] = S1h[j];
-#include "nusi_fit_newton.inc"
-#pragma unroll
-            for (int j = 0; j < NC; ++j) thh[j] = th[j];
-            muh = m;
-            sth = st;
-        }
-
-        // ---- the conditional fit at a_test, from the header's cold start ------------------------------------------------
-        double th[KA];
-        int st = 0;   // (the conditional fit's word; sth: the best fit's)
-        if constexpr (KT > 0) {
-            constexpr int NS = KT + KT * (KT + 1) / 2;
-            const bool sup = b > 0.0 || (atest > 0.0 && X[0] > 0.0) || supt;
-            const bool act = d > 0.0 && sup;
-            double dsum[1] = {act ? d : 0.0}, dmin[1] = {act ? d : 1.0};
-            det_butterfly(dsum, lgC, add);
-            det_butterfly(dmin, lgC, min);
-            const double D0 = dsum[0], dq = 0.0625 * (dmin[0] < 1.0 ? dmin[0] : 1.0);
-            double the[KT], pp[KT];
-#pragma unroll
-            for (int i = 0; i < KT; ++i) {
-                const double x = D0 / ((double)nlt * S1h[i + 1]);
-                th[i] = S1h[i + 1] > 0.0 ? x : 0.0;
-                the[i] = th[i];
-                pp[i] = 0.0;
-            }
-            double tt = 1.0;
-            int steps = 0, halv = 0, trials = 0;
-            bool run = true, first = true, quad = false;
-#define CF_N KT
-#define CF_X(i) X[(i) + 1]
-#define CF_S1(i) S1h[(i) + 1]
-#define CF_LIVE(i) (S1h[(i) + 1] > 0.0)
-#include "nusi_conditional_newton.inc"
-#undef CF_N
-#undef CF_X
-#undef CF_S1
-#undef CF_LIVE
-            st |= steps | ((halv < NUSI_FIT_TRIALS_MASK ? halv : NUSI_FIT_TRIALS_MASK) << NUSI_FIT_TRIALS_SHIFT);
-        } else {
-            th[0] = 0.0;
-        }
-        double mu = asig;
-#pragma unroll
-        for (int i = 0; i < KT; ++i) mu = mu + th[i] * X[i + 1];
-        mu = mu + b;
-        if constexpr (KT > 0) {
-#pragma unroll
-            for (int i = 0; i < KT; ++i)
-                if (th[i] == 0.0) st |= NUSI_FIT_ZERO << (i + 1);
-            if (any(in && d > 0.0 && mu == 0.0)) st |= NUSI_FIT_INFINITE;
-        }
-
-        // ---- lambda from ratios against the best fit's counts (k_interval's), and the statistic -----------------------
-        double lv[1];
-        {
-            const bool lact = in && d > 0.0 && muh > 0.0;
-            const double dmu = mu - muh;
-            const double ratio = mu / muh;
-            const double lr = ratio > 0.0 ? nm::log_i(ratio) : -__builtin_inf();
-            const double pl = d * lr;
-            const double tl = dmu - pl;
-            lv[0] = lact ? tl : dmu;
-        }
-        det_butterfly(lv, lgC, add);
-        double lam = lv[0];
-#pragma unroll
-        for (int j = 0; j < KT; ++j)
-            if (pr.w[j + 1] > 0.0) {
-                const double dj = th[j] - thh[(j + 1) < NC ? j + 1 : 0];
-                const double sj = (th[j] - pr.m[j + 1]) + (thh[(j + 1) < NC ? j + 1 : 0] - pr.m[j + 1]);
-                const double pd = ((0.5 * pr.w[j + 1]) * dj) * sj;
-                lam = lam + pd;
-            }
-        double stat = lam > 0.0 ? 2.0 * lam : 0.0, th0 = thh[0];
-        if ((ii.mode == 1 && th0 > atest) || (ii.mode == 2 && th0 < atest)) stat = 0.0;
-        const bool nofit = (sth & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) != 0;
-        const bool nocond = (st & (NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR)) != 0;
-        if (nofit) th0 = __builtin_nan("");
-        if (nofit || nocond) stat = __builtin_nan("");
+#include "nusi_toy_body.inc"
         if (c == 0 && q < Q) {
             if (o.theta) o.theta[rth + p] = th0;
             if (o.stat) o.stat[rst + p] = stat;
@@ -1647,6 +1559,238 @@ hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int
     case 3: hipLaunchKernelGGL((k_inject<4>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nqb, M, C, lg, Q, P); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_belt<NC>: the toy-calibrated interval's records (nusi_plan_response_belt), NC = 1 + K = 1 .. 4, on k_inject<NC>'s
+// block shape.  A record is (t, q, g) with row r = q G + g of the table's Q G rows; unit u is table u / nrb and row block
+// u % nrb, nrb = ceil(Q G / QB); a group of the block takes one row.  The test scale is a = frac[g] ref[t][q], agood =
+// ref >= 0 && a < inf, at = agood ? a : 0.  The loop over the toys has one pass in front, against the staged data d[c]
+// (nusi_toy_body.inc, the text of the toys' own pass): it gives the record's observed side, q_obs, and mu_inj, the
+// conditional fit's own mu -- then toy p of lane c is draw::poisson(mu_inj[c]; seed, stream = t, row = r, p, c).  Every
+// p-slice runs the observed pass and slice 0 stores it.  A record that is invalid (!agood, or NOT_CONVERGED | SINGULAR
+// in either observed word) stays in the loop with mu_inj = 0, which draws nothing: it adds to no count, and what it
+// stores to the raw arrays is their NaN / 0.  A row outside the table (r >= Q G) or outside the launch's pairs
+// pr0 <= t Q + q < pr1 stores nothing; every load index is clamped (cc, rc and with it q and g).
+// exceed [.][G], tally [.][G][4] and words_obs [.][1 + G] are indexed by the pair t Q + q, or by t Q + q - pr0 where the
+// array is the chunk's scratch (compact); the caller zeroes exceed and tally.
+// ---------------------------------------------------------------------------
+struct BeltOut {
+    int *exceed, *tally, *wobs;            // or nullptr
+    int exceed_compact, tally_compact, wobs_compact;
+    double *qobs, *thobs;                  // [ntab][Q][G], [ntab][Q][1 + G][NC] or nullptr
+    double *theta, *stat;                  // [ntab][Q][G][P] or nullptr
+    int* words;                            // [ntab][Q][G][P][2] or nullptr
+    double* data;                          // [ntab][Q][G][P][C] or nullptr
+};
+struct BeltIn {
+    const double *data, *frac, *ref;       // [C], [G], [ntab][Q] (ref: nullptr = 1)
+    unsigned long long seed;
+    int mode, G, pr0, pr1;
+};
+
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) __attribute__((amdgpu_waves_per_eu(NC == 1 ? 4 : NC == 4 ? 2 : 3)))
+void k_belt(const double* __restrict__ R, const double* __restrict__ S, const double* __restrict__ bg,
+            const double* __restrict__ T, const FitPrior pr, const double ku, const BeltIn ii, const BeltOut o, int u0, int nrb,
+            int M, int C, int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    constexpr int KT = NC - 1, KA = KT > 0 ? KT : 1;
+    const int G = ii.G, QG = Q * G;
+    const int tid = (int)threadIdx.x, u = u0 + (int)blockIdx.x, t = u / nrb;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, row = (u - t * nrb) * QB + grp;
+    const int cc = c < C ? c : C - 1, rc = row < QG ? row : QG - 1, q = rc / G, gp = rc - q * G;   // q < Q, gp < G
+    const int pair = t * Q + q;
+    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)q * M;
+    const bool in = c < C;
+    const bool mine = row < QG && pair >= ii.pr0 && pair < ii.pr1;   // the record is this launch's to store
+    int p0, p1;
+    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
+    double X[NC];
+    {
+        double s0 = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
+        X[0] = in ? s0 : 0.0;
+    }
+#pragma unroll
+    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
+    const double b = in ? bg[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+    double S1h[NC];   // tree(X_j): the data do not enter
+#pragma unroll
+    for (int j = 0; j < NC; ++j) S1h[j] = X[j];
+    det_butterfly(S1h, lgC, add);
+    const double rf = ii.ref ? ii.ref[pair] : 1.0;
+    const double agrid = ii.frac[gp] * rf;
+    const bool agood = rf >= 0.0 && agrid < __builtin_inf();
+    const double atest = agood ? agrid : 0.0;
+    const size_t rg = (size_t)pair * G + gp;                    // the record's row of the call's [ntab][Q][G] arrays
+    const double asig = atest * X[0];   // the held term of the conditional fit's den
+    bool supt = false;                  // a live template supports the bin
+    int nlt = 0;                        // the live templates
+#pragma unroll
+    for (int i = 0; i < KT; ++i) {
+        if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) supt = true;
+        nlt += S1h[i + 1] > 0.0 ? 1 : 0;
+    }
+    double mu_inj = 0.0, qobs = __builtin_nan("");   // both set by the observed pass
+    bool valid = false;
+
+#pragma unroll 1
+    for (int p = p0 - 1; p < p1; ++p) {
+        const bool obs = p < p0;   // (uniform over the block: the pass against the data)
+        double d;
+        if (obs) {
+            d = in ? ii.data[cc] : 0.0;
+        } else {
+            // (the expectation through an opaque copy, as in k_inject)
+            double mup = mu_inj;
+            asm volatile("" : "+v"(mup));
+            d = in ? draw::poisson(mup, draw::ident(ii.seed, (unsigned)t, (unsigned)rc, (unsigned)p, (unsigned)c)) : 0.0;
+            if (o.data && in && mine) o.data[(rg * P + p) * C + c] = valid ? d : 0.0;
+        }
+
+#include "nusi_toy_body.inc"
+        if (obs) {
+            valid = agood && !nofit && !nocond;
+            qobs = valid ? stat : __builtin_nan("");
+            mu_inj = valid ? mu : 0.0;
+            if (c == 0 && mine && blockIdx.z == 0) {
+                const size_t ro = (size_t)pair * (1 + G);
+                if (gp == 0) {
+                    if (o.thobs) {
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) o.thobs[ro * NC + j] = thh[j];
+                    }
+                    if (o.wobs) o.wobs[(size_t)(pair - (o.wobs_compact ? ii.pr0 : 0)) * (1 + G)] = sth;
+                }
+                if (o.thobs) {
+                    o.thobs[(ro + 1 + gp) * NC] = agood ? atest : __builtin_nan("");
+#pragma unroll
+                    for (int j = 0; j < KT; ++j) o.thobs[(ro + 1 + gp) * NC + 1 + j] = agood ? th[j] : __builtin_nan("");
+                }
+                if (o.wobs) o.wobs[(size_t)(pair - (o.wobs_compact ? ii.pr0 : 0)) * (1 + G) + 1 + gp] = agood ? st : 0;
+                if (o.qobs) o.qobs[rg] = qobs;
+            }
+        } else if (c == 0 && mine) {
+            if (o.theta) o.theta[rg * P + p] = valid ? th0 : __builtin_nan("");
+            if (o.stat) o.stat[rg * P + p] = valid ? stat : __builtin_nan("");
+            if (o.words) {
+                o.words[(rg * P + p) * 2] = valid ? sth : 0;
+                o.words[(rg * P + p) * 2 + 1] = valid ? st : 0;
+            }
+            if (o.tally && valid) {
+                int* ty = o.tally + ((size_t)(pair - (o.tally_compact ? ii.pr0 : 0)) * G + gp) * 4;
+                if (nofit) atomicAdd(ty + 0, 1);
+                if (nocond && !nofit) atomicAdd(ty + 1, 1);
+                if (sth & (NUSI_FIT_BOUNDARY | NUSI_FIT_FLAT)) atomicAdd(ty + 2, 1);
+                if (sth & NUSI_FIT_INFINITE) atomicAdd(ty + 3, 1);
+            }
+            if (o.exceed && valid && stat >= qobs)
+                atomicAdd(o.exceed + (size_t)(pair - (o.exceed_compact ? ii.pr0 : 0)) * G + gp, 1);
+        }
+    }
+}
+
+// k_belt_accept: per pair (t, q) of pr0 .. pr1 - 1 the acceptance rule over the G points, g ascending, from the counts and
+// the observed words (detector.belt_accept with belt_host's valid and flags): a = frac[g] ref[t][q]; valid = agood and
+// neither word[0] nor word[1 + g] flagged; nv = P - tally[0] - tally[1]; accepted iff valid, nv > 0 and (double)exceed >
+// alpha (double)nv.  lo, hi [ntab][Q], idx [ntab][Q][2], status [ntab][Q]; any may be nullptr.
+constexpr int kBeltAcceptThreads = 256;
+
+__global__ __launch_bounds__(kBeltAcceptThreads) void k_belt_accept(const BeltIn ii, const int* __restrict__ exceed,
+                                                                    int exceed_compact, const int* __restrict__ tally,
+                                                                    int tally_compact, const int* __restrict__ wobs,
+                                                                    int wobs_compact, int P, double alpha,
+                                                                    double* __restrict__ lo, double* __restrict__ hi,
+                                                                    int* __restrict__ idx, int* __restrict__ status)
+{
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * kBeltAcceptThreads + threadIdx.x + ii.pr0;
+    if (i >= ii.pr1) return;
+    const int pair = (int)i, G = ii.G, fail = NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR;
+    const int* ex = exceed + (size_t)(pair - (exceed_compact ? ii.pr0 : 0)) * G;
+    const int* ty = tally + (size_t)(pair - (tally_compact ? ii.pr0 : 0)) * G * 4;
+    const int* wo = wobs + (size_t)(pair - (wobs_compact ? ii.pr0 : 0)) * (1 + G);
+    const double rf = ii.ref ? ii.ref[pair] : 1.0;
+    const bool nofit = (wo[0] & fail) != 0;
+    int st = nofit ? NUSI_BELT_NO_FIT : 0, first = -1, last = -1, nacc = 0;
+    for (int g = 0; g < G; ++g) {
+        const double a = ii.frac[g] * rf;
+        const bool agood = rf >= 0.0 && a < __builtin_inf();
+        const bool nocond = (wo[1 + g] & fail) != 0;
+        if (!agood) st |= NUSI_BELT_NO_GRID;
+        if (agood && !nofit && nocond) st |= NUSI_BELT_BAD_POINT;
+        const int nv = P - ty[g * 4] - ty[g * 4 + 1];
+        if (nv <= 0) st |= NUSI_BELT_BAD_POINT;
+        const double lim = alpha * (double)nv;
+        if (agood && !nofit && !nocond && nv > 0 && (double)ex[g] > lim) {
+            if (first < 0) first = g;
+            last = g;
+            ++nacc;
+        }
+    }
+    if (nacc == 0) st |= NUSI_BELT_EMPTY;
+    if (first == 0) st |= NUSI_BELT_LO_EDGE;
+    if (last == G - 1) st |= NUSI_BELT_HI_EDGE;
+    if (nacc > 0 && nacc != last - first + 1) st |= NUSI_BELT_GAPS;
+    if (lo) lo[pair] = nacc > 0 ? ii.frac[first] * rf : __builtin_nan("");
+    if (hi) hi[pair] = nacc > 0 ? ii.frac[last] * rf : __builtin_nan("");
+    if (idx) {
+        idx[(size_t)pair * 2] = first;
+        idx[(size_t)pair * 2 + 1] = last;
+    }
+    if (status) status[pair] = st;
+}
+
+int belt_block(int C) { return kEvThreads >> ceil_log2(C); }
+
+hipError_t launch_belt(const GridDev& g, const double* R, const double* S, int Q, const double* data, const double* frac,
+                       int G, const double* ref, int P, unsigned long long seed, int mode, const double* bg, int C, int K,
+                       const double* T, const double* pm, const double* pw, int pr0, int pr1, int pslices, int* exceed,
+                       bool exceed_compact, int* tally, bool tally_compact, int* wobs, bool wobs_compact, double* qobs,
+                       double* thobs, double* theta, double* stat, int* words, double* data_all, hipStream_t s)
+{
+    if (pr1 <= pr0 || Q <= 0 || G <= 0 || P <= 0) return hipSuccess;
+    const int lg = ceil_log2(C), QB = kEvThreads >> lg, nrb = (int)(((long long)Q * G + QB - 1) / QB);
+    // the units that hold the rows of the pairs pr0 .. pr1 - 1 (a unit at the chunk's edge may hold other pairs' rows too)
+    const int t0 = pr0 / Q, q0 = pr0 - t0 * Q, t1 = (pr1 - 1) / Q, q1 = (pr1 - 1) - t1 * Q;
+    const long long ua = (long long)t0 * nrb + ((long long)q0 * G) / QB, ub = (long long)t1 * nrb + ((long long)q1 * G + G - 1) / QB;
+    if (ub - ua + 1 > 0x7fffffffll) return hipErrorInvalidValue;
+    const FitPrior pr = fit_prior(K, pm, pw);
+    const BeltIn ii{data, frac, ref, seed, mode, G, pr0, pr1};
+    const BeltOut o{exceed, tally, wobs, exceed_compact ? 1 : 0, tally_compact ? 1 : 0, wobs_compact ? 1 : 0,
+                    qobs, thobs, theta, stat, words, data_all};
+    const double ku = fit_ku(lg, K);
+    const dim3 grid((unsigned)(ub - ua + 1), 1, (unsigned)pslices), block(kEvThreads);
+    const int M = g.T + 1, u0 = (int)ua;
+    switch (K) {
+    case 0: hipLaunchKernelGGL((k_belt<1>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
+    case 1: hipLaunchKernelGGL((k_belt<2>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
+    case 2: hipLaunchKernelGGL((k_belt<3>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
+    case 3: hipLaunchKernelGGL((k_belt<4>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_belt_accept(const double* frac, int G, const double* ref, int P, double alpha, int pr0, int pr1,
+                              const int* exceed, bool exceed_compact, const int* tally, bool tally_compact, const int* wobs,
+                              bool wobs_compact, double* lo, double* hi, int* idx, int* status, hipStream_t s)
+{
+    if (pr1 <= pr0) return hipSuccess;
+    const BeltIn ii{nullptr, frac, ref, 0ull, 0, G, pr0, pr1};
+    const unsigned nb = (unsigned)(((long long)(pr1 - pr0) + kBeltAcceptThreads - 1) / kBeltAcceptThreads);
+    hipLaunchKernelGGL(k_belt_accept, dim3(nb), dim3(kBeltAcceptThreads), 0, s, ii, exceed, exceed_compact ? 1 : 0, tally,
+                       tally_compact ? 1 : 0, wobs, wobs_compact ? 1 : 0, P, alpha, lo, hi, idx, status);
     return hipGetLastError();
 }
 

@@ -218,6 +218,23 @@ hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int
                          int C, int K, const double* T, const double* pm, const double* pw, int u0, int nu, int pslices,
                          double* theta, bool theta_compact, double* stat, bool stat_compact, int* words, int* tally, int* exceed,
                          double* data, hipStream_t s);
+// k_belt<1 + K> and k_belt_accept (include/nusi.h nusi_plan_response_belt).  A record is (t, q, g) with row q G + g of a
+// table's Q G rows; a unit is one table and belt_block(C) rows.  launch_belt runs the units that hold the rows of the
+// pairs t Q + q = pr0 .. pr1 - 1 and stores those pairs' records alone: the observed side to qobs [ntab][Q][G], thobs
+// [ntab][Q][1 + G][1 + K] and wobs [.][1 + G]; the toys' records to theta, stat [ntab][Q][G][P], words [..][P][2] and
+// data_all [..][P][C]; the counts are ADDED to exceed [.][G] and tally [.][G][4].  exceed, tally and wobs are indexed by
+// the pair, or by pair - pr0 where compact (the chunk's scratch).  data [C], frac [G] and ref [ntab][Q] (nullptr: 1) in
+// device memory.  launch_belt_accept forms lo, hi [ntab][Q], idx [ntab][Q][2] and status [ntab][Q] of those pairs from
+// exceed, tally and wobs.  Any output may be nullptr.
+int belt_block(int C);
+hipError_t launch_belt(const GridDev& g, const double* R, const double* S, int Q, const double* data, const double* frac,
+                       int G, const double* ref, int P, unsigned long long seed, int mode, const double* bg, int C, int K,
+                       const double* T, const double* pm, const double* pw, int pr0, int pr1, int pslices, int* exceed,
+                       bool exceed_compact, int* tally, bool tally_compact, int* wobs, bool wobs_compact, double* qobs,
+                       double* thobs, double* theta, double* stat, int* words, double* data_all, hipStream_t s);
+hipError_t launch_belt_accept(const double* frac, int G, const double* ref, int P, double alpha, int pr0, int pr1,
+                              const int* exceed, bool exceed_compact, const int* tally, bool tally_compact, const int* wobs,
+                              bool wobs_compact, double* lo, double* hi, int* idx, int* status, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

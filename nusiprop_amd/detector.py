@@ -1232,8 +1232,8 @@ def belt_accept(exceed, tally, a, alpha, valid, P, flags=0):
 def belt_host(R, S, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, templates=None, prior=None, background=None,
               exp=np.exp, log=np.log, raw=False):
     """The toy-calibrated confidence interval of the signal's scale -- the Feldman-Cousins interval by the profile
-    construction -- on a grid of test scales, as a loop of the existing host forms (numpy only; there is no device call
-    yet: DESIGN.md sec. 4, "The calibrated interval: the host form").  Per table t, spectrum q and grid point g the test
+    construction -- on a grid of test scales, as a loop of the existing host forms (numpy only; Plan.belt is the device
+    call that reproduces it: DESIGN.md sec. 4, "The calibrated interval").  Per table t, spectrum q and grid point g the test
     scale is a = frac[g] * ref[t, q]; the data get inject_host's loop body at a (fit_host / profile_host,
     fit_fixed_host, _limit_lambda), which gives the observed records and q_obs; the toys are draw_host of the conditional
     fit's own mu with stream = t at row q G + g, and each gets the same loop body at a.

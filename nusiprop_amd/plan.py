@@ -700,6 +700,83 @@ class Plan:
             dev(d_stat_all_ptr), dev(d_words_all_ptr), dev(d_data_all_ptr), dev(stream_ptr)))
         return len(S), len(r)
 
+    # --- the toy-calibrated interval (include/nusi.h nusi_plan_response_belt) ---
+    def _belt_args(self, spectra, data, frac, ref, ntab):
+        S, _ = self._spectra(spectra, None)
+        d = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+        C = self.detector_bins()
+        if C and d.shape != (C,):                                   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("belt: data must have shape (%d,), got %s" % (C, np.shape(data)))
+        fr = np.ascontiguousarray(frac, dtype=np.float64).reshape(-1)
+        rf = None
+        if ref is not None:
+            rf = np.asarray(ref, dtype=np.float64)
+            if rf.ndim == 1:                                        # (Q,): one reference per spectrum, every table
+                rf = rf[None, :]
+            rf = np.ascontiguousarray(np.broadcast_to(rf, (ntab, len(S))))
+        return S, d, fr, rf
+
+    def belt(self, R, spectra, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, raw=False):
+        """The toy-calibrated confidence interval of the signal's scale -- the Feldman-Cousins interval by the profile
+        construction -- on a grid of test scales, in one call on the GPU.  Per table t, spectrum q and grid point g the
+        test scale is a = frac[g] * ref[t, q]; the data (C,) get ``inject``'s steps at a (``fit`` / ``profile``,
+        ``fit_fixed``, the statistic), which gives the observed records and q_obs; P toys are drawn on the device from
+        the conditional fit's own expectation (stream = t, row = q G + g) and each gets the same steps at a; a point is
+        accepted iff exceed > alpha * (P - tally[0] - tally[1]).  frac: (G,), finite, >= 0, strictly ascending, G <=
+        _lib.BELT_GRID_MAX.  ref: None (1), a number, (Q,) or (ntab, Q) -- e.g. ``limit``'s upper limit; NaN, infinite
+        or negative: BELT_NO_GRID.  mode: "two-sided" or "upper".  Returns detector.belt_host's tuple: (lo (ntab, Q), hi
+        (ntab, Q), idx (ntab, Q, 2) int32, status (ntab, Q) int32 -- _lib.BELT_* --, exceed (ntab, Q, G) int32, tally
+        (ntab, Q, G, 4) int32, q_obs (ntab, Q, G), theta_obs (ntab, Q, 1 + G, 1 + K), words_obs (ntab, Q, 1 + G) int32)
+        and with raw also (theta_all (ntab, Q, G, P), stat_all (ntab, Q, G, P), words_all (ntab, Q, G, P, 2) int32,
+        data_all (ntab, Q, G, P, C)).  No axis is squeezed."""
+        R, C = self._folded(R, "belt")
+        ntab, P = R.shape[0], int(P)
+        S, d, fr, rf = self._belt_args(spectra, data, frac, ref, ntab)
+        Q, G, NC, Pa = len(S), len(fr), self.templates() + 1, max(P, 0)
+        lo, hi = np.full((ntab, Q), np.nan), np.full((ntab, Q), np.nan)
+        idx, status = np.full((ntab, Q, 2), -1, dtype=np.int32), np.zeros((ntab, Q), dtype=np.int32)
+        exceed, tally = np.zeros((ntab, Q, G), dtype=np.int32), np.zeros((ntab, Q, G, 4), dtype=np.int32)
+        q_obs, th_obs = np.full((ntab, Q, G), np.nan), np.full((ntab, Q, 1 + G, NC), np.nan)
+        w_obs = np.zeros((ntab, Q, 1 + G), dtype=np.int32)
+        th_all = st_all = words = toys = None
+        if raw:
+            th_all, st_all = np.full((ntab, Q, G, Pa), np.nan), np.full((ntab, Q, G, Pa), np.nan)
+            words, toys = np.zeros((ntab, Q, G, Pa, 2), dtype=np.int32), np.zeros((ntab, Q, G, Pa, C))
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+
+        def ptr(x, t):
+            return x.ctypes.data_as(t) if x is not None else None
+        _lib.check(_lib.load().nusi_plan_response_belt_host(
+            self._h, R.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp), fr.ctypes.data_as(dp), G,
+            ptr(rf, dp), P, int(seed) & (2 ** 64 - 1), self._mode(mode), float(alpha), ptr(lo, dp), ptr(hi, dp), ptr(idx, ip),
+            ptr(status, ip), ptr(exceed, ip), ptr(tally, ip), ptr(q_obs, dp), ptr(th_obs, dp), ptr(w_obs, ip),
+            ptr(th_all, dp), ptr(st_all, dp), ptr(words, ip), ptr(toys, dp)))
+        out = (lo, hi, idx, status, exceed, tally, q_obs, th_obs, w_obs)
+        return out + ((th_all, st_all, words, toys) if raw else ())
+
+    def belt_device(self, d_R_ptr, ntab, spectra, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1,
+                    d_lo_ptr=None, d_hi_ptr=None, d_idx_ptr=None, d_status_ptr=None, d_exceed_ptr=None, d_tally_ptr=None,
+                    d_q_obs_ptr=None, d_theta_obs_ptr=None, d_words_obs_ptr=None, d_theta_all_ptr=None,
+                    d_stat_all_ptr=None, d_words_all_ptr=None, d_data_all_ptr=None, stream_ptr=None):
+        """Asynchronous ``belt`` on device-resident folded matrices d_R [ntab][M][C]: the outputs are raw pointers (d_lo,
+        d_hi [ntab][Q], d_q_obs [ntab][Q][G], d_theta_obs [ntab][Q][1 + G][1 + K], d_theta_all, d_stat_all
+        [ntab][Q][G][P] and d_data_all [ntab][Q][G][P][C] doubles; d_idx [ntab][Q][2], d_status [ntab][Q], d_exceed
+        [ntab][Q][G], d_tally [ntab][Q][G][4], d_words_obs [ntab][Q][1 + G] and d_words_all [ntab][Q][G][P][2] ints), any
+        may be 0 / None but not all.  The other arguments are host data and are copied.  Returns (Q, G)."""
+        S, d, fr, rf = self._belt_args(spectra, data, frac, ref, int(ntab))
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+
+        def dev(x):
+            return vp(x) if x else None
+        _lib.check(_lib.load().nusi_plan_response_belt(
+            self._h, vp(d_R_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp), fr.ctypes.data_as(dp),
+            len(fr), rf.ctypes.data_as(dp) if rf is not None else None, int(P), int(seed) & (2 ** 64 - 1), self._mode(mode),
+            float(alpha), dev(d_lo_ptr), dev(d_hi_ptr), dev(d_idx_ptr), dev(d_status_ptr), dev(d_exceed_ptr),
+            dev(d_tally_ptr), dev(d_q_obs_ptr), dev(d_theta_obs_ptr), dev(d_words_obs_ptr), dev(d_theta_all_ptr),
+            dev(d_stat_all_ptr), dev(d_words_all_ptr), dev(d_data_all_ptr), dev(stream_ptr)))
+        return len(S), len(fr)
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since
