@@ -626,6 +626,59 @@ int nusi_plan_draw_counts(nusi_plan *plan, const double *mu /* [rows][C] */, int
                           unsigned long long seed, unsigned stream_id, double *d_out /* [rows][P][C] */, void *stream);
 int nusi_plan_draw_counts_host(nusi_plan *plan, const double *mu, int rows, int C, int P, unsigned long long seed,
                                unsigned stream_id, double *out);
+/* Drawing normals (k_normal_draw; nusi_draw.hpp draw::normal0, detector.draw_normal_host): a normal variate around
+ * center >= 0 of width sigma, truncated to x >= 0, on the same Philox blocks -- the auxiliary measurements and the
+ * nuisance parameters of the toys (NUSI_OPT_TOY_NUISANCE, below).  Marsaglia's polar method; every operation rounded on its
+ * own (no fma), log the library's (nm::log_i; the oracle's ora_log), sqrt IEEE's.
+ *   Identity.  (seed, stream, row, p, j): j = 0 .. J - 1, the component, stands in the bin's place of the counter word
+ *     p 64 + j (J <= NUSI_DETECTOR_BINS_MAX = 64: the word holds j in 6 bits).  The counter's block word is 0x80000000 + r
+ *     for round r = 0, 1, ..  The counts use blocks 0 .. 63 only (inversion block 0, PTRS rounds 0 .. 63), so under one
+ *     seed the two families never share a block, and no count's bits depend on a normal draw.
+ *   sigma == +inf (no prior): the result is center, and no bits are drawn.
+ *   Round r, on the uniforms U0, U1 of block 0x80000000 + r:
+ *     u = 2 U0 - 1, v = 2 U1 - 1 (both exact);  s = u u + v v (three roundings);  reject if !(s < 1) || s == 0;
+ *     f = sqrt((-2 log(s)) / s) (the product exact; the quotient and the root each rounded);  z = u f;
+ *     x = center + sigma z (the product, then the sum);  reject if !(x >= 0), else the draw is x.
+ *   After NUSI_NORMAL_ROUNDS = 64 rejected rounds the draw is center.
+ *
+ * nusi_plan_draw_normals: d_out[row][p][j] = the draw around center[row][j] of width sigma[j] with the identity (seed,
+ * stream_id, row, p, j), p < P: rows P J doubles in device memory.  center [rows][J] and sigma [J] are host arrays and are
+ * copied; they share nusi_plan_draw_counts' staging buffer and its ordering (a draw waits for the one before).  No
+ * detector is needed.  NUSI_EPARAM for a NULL center, sigma or d_out, rows < 1, J outside 1 .. NUSI_DETECTOR_BINS_MAX, P
+ * outside 1 .. NUSI_DRAW_DATASETS_MAX, rows P J above NUSI_DRAW_COUNTS_MAX, a center that is negative or not finite, or a
+ * sigma that is NaN or not > 0 (+inf is allowed); a refused call changes nothing.  _host: the output in host memory,
+ * synchronous. */
+#define NUSI_NORMAL_ROUNDS 64
+int nusi_plan_draw_normals(nusi_plan *plan, const double *center /* [rows][J] */, const double *sigma /* [J] */, int rows,
+                           int J, int P, unsigned long long seed, unsigned stream_id, double *d_out /* [rows][P][J] */,
+                           void *stream);
+int nusi_plan_draw_normals_host(nusi_plan *plan, const double *center, const double *sigma, int rows, int J, int P,
+                                unsigned long long seed, unsigned stream_id, double *out);
+/* The toys' treatment of constrained nuisances (NUSI_OPT_TOY_NUISANCE, a plan option; nusi_plan_response_inject,
+ * nusi_plan_response_belt and their _host forms).  A prior (m_j, sigma_j) on template j stands for an auxiliary
+ * measurement m_j.  Template j is CONSTRAINED where its prior has a weight w_j = 1 / sigma_j^2 > 0; sigma_j = +inf
+ * otherwise.  The row of a toy's identity is the one its counts use: q in inject, q G + g in belt; the stream is t; the
+ * component is the template, j = 0 .. K - 1.
+ *   NUSI_TOYS_FIXED (0, the default): every toy redraws the counts and keeps the means m_j: the calls as written below.
+ *   NUSI_TOYS_GLOBAL (1): the auxiliary measurements ("global observables") are redrawn per toy.  Per toy p and
+ *     constrained template j, m*_j = the normal draw ("Drawing normals") around center_j of width sigma_j with the identity
+ *     (seed, t, row, p, j).  The centre is the value the toys are thrown from: theta_inj[j] in inject, and in belt the
+ *     observed conditional fit's theta_j(a) of the record -- d_theta_obs[t][q][1 + g][1 + j].  The counts are drawn from
+ *     the unchanged mu_inj: every integer is FIXED's.  The toy's steps 2 - 4 -- the best fit, the conditional fit,
+ *     lambda's penalties and the stops' magnitudes -- see the plan's priors with the mean of every constrained template
+ *     replaced by m*_j: the toy's record is, bit for bit, what nusi_plan_response_fit / _fit_fixed give on a plan whose
+ *     templates were set with the prior (m*, sigma) (m* >= 0 by the truncation).  belt's observed pass uses the plan's means.
+ *   NUSI_TOYS_PRIOR (2; inject only): the nuisances are thrown from their priors (Cousins-Highland).  Per toy,
+ *     theta*_j = the normal draw around m_j of width sigma_j with that identity for a constrained template, theta_inj[j]
+ *     otherwise; the counts are drawn from a_inj s + sum_j theta*_j T_j + B in the usual order with the usual identity;
+ *     the fits use the plan's means.  nusi_plan_response_belt under this value returns NUSI_EPARAM and does no device
+ *     work: the profile construction has no such variant.
+ * With K = 0 or no constrained template every value gives FIXED's bits (and runs FIXED's kernels).  A draw's identity is
+ * global: every scratch budget, chunking and p-slicing give the same bits.  Any other value is refused. */
+#define NUSI_OPT_TOY_NUISANCE 17
+#define NUSI_TOYS_FIXED 0
+#define NUSI_TOYS_GLOBAL 1
+#define NUSI_TOYS_PRIOR 2
 /* nusi_plan_response_inject (k_inject, k_toys_band): the distribution of the statistic q(a) at a hypothesis, on toys drawn
  * from that hypothesis's own expectation -- critical values, toy-calibrated p-values, the coverage of a delta, discovery
  * power under an injected signal.  The toys exist only in registers: each is drawn where it is fitted.  The front half
@@ -930,6 +983,8 @@ int nusi_plan_set_cascade(nusi_plan *plan, int kind);
  *                          closer than to the whole call. */
 #define NUSI_OPT_ENSEMBLE_LIMIT_MB 15
 #define NUSI_OPT_ENSEMBLE_LIMIT_BYTES 16
+/*   NUSI_OPT_TOY_NUISANCE  (17, defined with the calls it governs, above: "The toys' treatment of constrained
+ *                          nuisances") NUSI_TOYS_FIXED = 0 (default), NUSI_TOYS_GLOBAL = 1, NUSI_TOYS_PRIOR = 2. */
 int nusi_plan_set_option(nusi_plan *plan, int option, int value);
 /* per-point NUSI_WARN_* bits of the last call */
 int nusi_plan_warnings(nusi_plan *plan, int *out, int n);

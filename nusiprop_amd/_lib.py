@@ -82,6 +82,7 @@ EXPORTS = [
     "nusi_plan_response_ensemble", "nusi_plan_response_ensemble_host",
     "nusi_plan_response_ensemble_limit", "nusi_plan_response_ensemble_limit_host",
     "nusi_plan_draw_counts", "nusi_plan_draw_counts_host",
+    "nusi_plan_draw_normals", "nusi_plan_draw_normals_host",
     "nusi_plan_response_inject", "nusi_plan_response_inject_host",
     "nusi_belt_shape", "nusi_plan_response_belt", "nusi_plan_response_belt_host",
 ]
@@ -98,6 +99,11 @@ OPT_ENSEMBLE_QSLICES, OPT_ENSEMBLE_PSLICES = 13, 14    # Plan.ensemble's grid (t
 ENSEMBLE_DATASETS_MAX = 65536
 # Plan.ensemble_limit: its scratch budget in MiB (0 = 256) or, where > 0, in bytes; the most ranks of a band and data sets
 OPT_ENSEMBLE_LIMIT_MB, OPT_ENSEMBLE_LIMIT_BYTES = 15, 16
+# the toys of Plan.inject and Plan.belt under a prior (include/nusi.h NUSI_OPT_TOY_NUISANCE, NUSI_TOYS_*): the prior means
+# stay, are redrawn per toy (global observables), or the nuisances are thrown from the priors (inject only)
+OPT_TOY_NUISANCE = 17
+TOYS_FIXED, TOYS_GLOBAL, TOYS_PRIOR = 0, 1, 2
+NORMAL_ROUNDS = 64              # Plan.draw_normal: the rounds of the polar method before the draw is the center
 BAND_RANKS_MAX = 16
 BAND_DATASETS_MAX = 4096
 INJECT_TWO_SIDED, INJECT_UPPER, INJECT_DISCOVERY = 0, 1, 2     # Plan.inject's mode (include/nusi.h NUSI_INJECT_*)
@@ -189,6 +195,8 @@ def load():
         "nusi_plan_response_ensemble_limit_host": (i, [vp, dp, i, dp, i, dp, i, d, i, ip, i, dp, dp, ip, dp, dp, ip]),
         "nusi_plan_draw_counts": (i, [vp, dp, i, i, i, ctypes.c_ulonglong, ctypes.c_uint, vp, vp]),
         "nusi_plan_draw_counts_host": (i, [vp, dp, i, i, i, ctypes.c_ulonglong, ctypes.c_uint, dp]),
+        "nusi_plan_draw_normals": (i, [vp, dp, dp, i, i, i, ctypes.c_ulonglong, ctypes.c_uint, vp, vp]),
+        "nusi_plan_draw_normals_host": (i, [vp, dp, dp, i, i, i, ctypes.c_ulonglong, ctypes.c_uint, dp]),
         "nusi_plan_response_inject": (i, [vp, vp, i, dp, i, dp, dp, dp, i, ctypes.c_ulonglong, i, ip, i, dp,
                                           vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_inject_host": (i, [vp, dp, i, dp, i, dp, dp, dp, i, ctypes.c_ulonglong, i, ip, i, dp,

@@ -472,6 +472,8 @@ struct nusi_plan {
     int ens_pslices = 0;
     void* d_ens = nullptr;          // the ensemble's q-slice records [qslices][P][ntab] (at most kEnsScratchBytes when
     size_t ens_bytes = 0;           // the slices are automatic)
+    int toy_nuis = NUSI_TOYS_FIXED;   // NUSI_OPT_TOY_NUISANCE: the ensemble of inject's and belt's toys
+    double fit_s[NUSI_FIT_TEMPLATES_MAX] = {};   // the priors' widths sigma where fit_w > 0, +inf elsewhere (the toys' normals)
     int toys_mb = 0, toys_b = 0;   // NUSI_OPT_ENSEMBLE_LIMIT_MB, _BYTES: the ensemble limit's scratch budget (0 = kToysScratchBytes)
     double* d_toys = nullptr;       // a chunk's limits per side kept here [units QB][P] (grown on demand)
     size_t toys_bytes = 0;
@@ -1989,7 +1991,8 @@ int nusi_plan_set_templates(nusi_plan* pl, int K, const double* T, const double*
     if (int r = detector_plan(pl, "templates")) return r;
     const bool clear = !T || K == 0;
     const int C = pl->det_C;
-    double m[NUSI_FIT_TEMPLATES_MAX] = {}, w[NUSI_FIT_TEMPLATES_MAX] = {};
+    double m[NUSI_FIT_TEMPLATES_MAX] = {}, w[NUSI_FIT_TEMPLATES_MAX] = {}, sw[NUSI_FIT_TEMPLATES_MAX];
+    for (double& x : sw) x = HUGE_VAL;
     if (!clear) {
         if (K < 0 || K > NUSI_FIT_TEMPLATES_MAX) return fail(NUSI_EPARAM, "templates: K outside 0 .. NUSI_FIT_TEMPLATES_MAX");
         for (int j = 0; j < K; ++j) {
@@ -2007,6 +2010,7 @@ int nusi_plan_set_templates(nusi_plan* pl, int K, const double* T, const double*
                 if (!(sg > 0.0)) return fail(NUSI_EPARAM, "templates: a prior width is not > 0");
                 w[j] = 1.0 / (sg * sg);
                 m[j] = (w[j] > 0.0 && prior_mean) ? prior_mean[j] : 0.0;
+                if (w[j] > 0.0) sw[j] = sg;
             }
         }
     } else if (K < 0 || K > NUSI_FIT_TEMPLATES_MAX) {
@@ -2033,6 +2037,7 @@ int nusi_plan_set_templates(nusi_plan* pl, int K, const double* T, const double*
     pl->fit_K = clear ? 0 : K;
     memcpy(pl->fit_m, m, sizeof(m));
     memcpy(pl->fit_w, w, sizeof(w));
+    memcpy(pl->fit_s, sw, sizeof(sw));
     return NUSI_OK;
 }
 
@@ -2391,6 +2396,63 @@ int nusi_plan_draw_counts_host(nusi_plan* pl, const double* mu, int rows, int C,
     return r;
 }
 
+// nusi_plan_draw_normals: nusi_plan_draw_counts' checks, staging (center, then sigma, in d_draw) and ordering
+static int normals_check(const nusi_plan* pl, const double* center, const double* sigma, int rows, int J, int P, const void* out)
+{
+    if (!pl) return no_plan();
+    if (!center || !sigma || !out) return fail(NUSI_EPARAM, "draw normals: center, sigma and the output must not be NULL");
+    if (rows < 1 || J < 1 || J > NUSI_DETECTOR_BINS_MAX || P < 1 || P > NUSI_DRAW_DATASETS_MAX)
+        return fail(NUSI_EPARAM, "draw normals: need rows >= 1, 1 <= J <= NUSI_DETECTOR_BINS_MAX and 1 <= P <= NUSI_DRAW_DATASETS_MAX");
+    if ((unsigned long long)rows * P * J > (unsigned long long)NUSI_DRAW_COUNTS_MAX)
+        return fail(NUSI_EPARAM, "draw normals: rows P J above NUSI_DRAW_COUNTS_MAX");
+    for (size_t e = 0; e < (size_t)rows * J; ++e)
+        if (!(center[e] >= 0.0) || !std::isfinite(center[e])) return fail(NUSI_EPARAM, "draw normals: a center is negative or not finite");
+    for (int j = 0; j < J; ++j)
+        if (!(sigma[j] > 0.0)) return fail(NUSI_EPARAM, "draw normals: a sigma is NaN or not > 0");
+    return NUSI_OK;
+}
+
+int nusi_plan_draw_normals(nusi_plan* pl, const double* center, const double* sigma, int rows, int J, int P,
+                           unsigned long long seed, unsigned stream_id, double* d_out, void* stream)
+{
+    if (int r = normals_check(pl, center, sigma, rows, J, P, d_out)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (pl->draw_ran) HIPCHECK(hipEventSynchronize(pl->ev_draw));
+    const size_t nc = (size_t)rows * J, need = nc + (size_t)J;
+    if (pl->draw_doubles < need) {
+        hipFree(pl->d_draw);
+        pl->d_draw = nullptr;
+        pl->draw_doubles = 0;
+        HIPCHECK(hipMalloc(&pl->d_draw, sizeof(double) * need));
+        pl->draw_doubles = need;
+    }
+    pl->h_draw.assign(center, center + nc);
+    pl->h_draw.insert(pl->h_draw.end(), sigma, sigma + J);
+    HIPCHECK(hipMemcpyAsync(pl->d_draw, pl->h_draw.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
+    HIPCHECK(nusi::launch_normal_draw(pl->d_draw, rows, J, P, seed, stream_id, d_out, s));
+    if (!pl->ev_draw) HIPCHECK(hipEventCreateWithFlags(&pl->ev_draw, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(pl->ev_draw, s));
+    pl->draw_ran = true;
+    return NUSI_OK;
+}
+
+int nusi_plan_draw_normals_host(nusi_plan* pl, const double* center, const double* sigma, int rows, int J, int P,
+                                unsigned long long seed, unsigned stream_id, double* out)
+{
+    if (int r = normals_check(pl, center, sigma, rows, J, P, out)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    const size_t n = (size_t)rows * P * J;
+    double* dO = nullptr;
+    if (hipMalloc(&dO, sizeof(double) * n) != hipSuccess) return fail(NUSI_EHIP, "draw normals: no device memory");
+    int r = nusi_plan_draw_normals(pl, center, sigma, rows, J, P, seed, stream_id, dO, nullptr);
+    if (!r && hipStreamSynchronize(pl->stream) != hipSuccess) r = fail(NUSI_EHIP, "draw normals: the stream failed");
+    if (!r && hipMemcpy(out, dO, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess)
+        r = fail(NUSI_EHIP, "draw normals: copy to the host failed");
+    hipFree(dO);
+    return r;
+}
+
 // The calibration call (nusi_detector.hip k_inject, then k_toys_band): the ensemble limit's units, chunks, scratch budget
 // and p-slices; the toys are drawn in the kernel.  The host vectors ride in d_evt behind the spectra (evt_layout): a_inj
 // in the scales' place, then a_test [Q] and q_obs [ntab][Q] (with exceed) as the extra vectors.
@@ -2503,7 +2565,7 @@ int nusi_plan_response_inject(nusi_plan* pl, const double* d_R, int ntab, const 
         const int ps = pl->ens_pslices > 0 ? std::min(pl->ens_pslices, P)
                                            : (int)std::min<long long>(std::max(P / kEnsSliceDatasets, 1), (want + nu - 1) / nu);
         HIPCHECK(nusi::launch_inject(pl->gd, d_R, dS, Q, d_ainj, d_atest, th_inj, d_qobs, P, seed, mode, detector_bg(pl), C,
-                                     pl->fit_K, pl->d_tpl, pl->fit_m, pl->fit_w, u0, nu, ps, th, ip.th_scr, st, ip.st_scr,
+                                     pl->fit_K, pl->d_tpl, pl->fit_m, pl->fit_w, pl->fit_s, pl->toy_nuis, u0, nu, ps, th, ip.th_scr, st, ip.st_scr,
                                      d_words_all, d_tally, d_exceed, d_data_all, s));
         if (NR > 0)
             HIPCHECK(nusi::launch_toys_band(C, Q, P, u0, nu, d_band_theta ? th : nullptr, ip.th_scr, d_band_stat ? st : nullptr,
@@ -2564,6 +2626,8 @@ static int belt_check(const nusi_plan* pl, const void* R, int ntab, const double
     const std::string w = "response belt: ";
     if (int r = detector_plan(pl, "response belt")) return r;
     if (int r = nusi_belt_shape(pl->det_C, ntab, Q, G, P, nullptr)) return r;
+    if (pl->toy_nuis == NUSI_TOYS_PRIOR)
+        return fail(NUSI_EPARAM, w + "NUSI_OPT_TOY_NUISANCE = NUSI_TOYS_PRIOR: the profile construction has no such variant (FIXED or GLOBAL)");
     if (!R || !S || !data || !frac) return fail(NUSI_EPARAM, w + "R, S, data and frac must not be NULL");
     for (int g = 0; g < G; ++g)
         if (!(frac[g] >= 0.0) || !std::isfinite(frac[g]) || (g > 0 && !(frac[g] > frac[g - 1])))
@@ -2650,7 +2714,7 @@ int nusi_plan_response_belt(nusi_plan* pl, const double* d_R, int ntab, const do
         if (bp.ex_scr || bp.ty_scr)   // (the counts in the scratch are one block: exceed, then tally)
             HIPCHECK(hipMemsetAsync(scr, 0, sizeof(int) * (size_t)bp.ppc * G * ((bp.ex_scr ? 1 : 0) + (bp.ty_scr ? 4 : 0)), s));
         HIPCHECK(nusi::launch_belt(pl->gd, d_R, dS, Q, d_data, d_frac, G, d_ref, P, seed, mode, detector_bg(pl), C, pl->fit_K,
-                                   pl->d_tpl, pl->fit_m, pl->fit_w, pr0, pr1, ps, ex, bp.ex_scr, ty, bp.ty_scr, wo, bp.wo_scr,
+                                   pl->d_tpl, pl->fit_m, pl->fit_w, pl->fit_s, pl->toy_nuis, pr0, pr1, ps, ex, bp.ex_scr, ty, bp.ty_scr, wo, bp.wo_scr,
                                    d_q_obs, d_theta_obs, d_theta_all, d_stat_all, d_words_all, d_data_all, s));
         if (accept)
             HIPCHECK(nusi::launch_belt_accept(d_frac, G, d_ref, P, alpha, pr0, pr1, ex, bp.ex_scr, ty, bp.ty_scr, wo, bp.wo_scr,
@@ -2797,6 +2861,10 @@ int nusi_plan_set_option(nusi_plan* pl, int option, int value)
     case NUSI_OPT_ENSEMBLE_LIMIT_BYTES:
         if (value < 0 || value > (1 << 30)) return fail(NUSI_EPARAM, "NUSI_OPT_ENSEMBLE_LIMIT_BYTES outside [0, 2^30]");
         pl->toys_b = value;
+        return NUSI_OK;
+    case NUSI_OPT_TOY_NUISANCE:
+        if (value < NUSI_TOYS_FIXED || value > NUSI_TOYS_PRIOR) return fail(NUSI_EPARAM, "NUSI_OPT_TOY_NUISANCE outside [0, 2]");
+        pl->toy_nuis = value;
         return NUSI_OK;
     case NUSI_OPT_REFERENCE_ORDER:
         if (value < 0 || value > 1) return fail(NUSI_EPARAM, "NUSI_OPT_REFERENCE_ORDER outside [0, 1]");

@@ -23,6 +23,10 @@
 //   k_inject<NC>          per (table, spectrum) P toys drawn from the injected expectation where they are fitted: the
 //                         best fit, one conditional fit and the statistic per toy; k_toys_band then selects the order
 //                         statistics of theta_hat_0 and of the statistic (nusi_plan_response_inject)
+//   k_normal_draw         truncated normal variates from the same generator (nusi_plan_draw_normals)
+//   k_nuis_inject<NC, MODE>, k_nuis_belt<NC>
+//                         k_inject and k_belt with the toys' constrained nuisances randomised (NUSI_OPT_TOY_NUISANCE): the
+//                         prior means redrawn per toy, or the nuisances thrown from their priors
 //   k_belt<NC>, k_belt_accept
 //                         k_inject's toy body once against the data and then per toy, on records (table, spectrum, grid
 //                         point of the test scale), the toys drawn from the observed conditional fit's expectation; then
@@ -36,7 +40,10 @@
 //   nusi_profile_chain1.inc      k_detector_profile's, one chain a lane: the best fit at NC = 1 of k_interval,
 //                                k_toys_limit, k_inject
 //   nusi_conditional_newton.inc  k_conditional_fit's rounds: k_conditional_fit, k_inject, k_belt
-//   nusi_toy_body.inc            one data set's best fit, conditional fit and statistic: k_inject, k_belt
+//   nusi_toy_body.inc            one data set's best fit, conditional fit and statistic: k_inject, k_belt and their
+//                                k_nuis_ forms
+//   nusi_inject_setup.inc, nusi_inject_store.inc, nusi_belt_setup.inc, nusi_belt_store.inc
+//                                what stands around the toy's draw in k_inject and k_belt: those and k_nuis_inject, k_nuis_belt
 //   nusi_search_setup.inc, nusi_search_side.inc
 //                                the search for a limit: k_interval, k_toys_limit
 //   nusi_ldlt_solve.inc          the Newton direction, inside the fit's, the conditional fit's and the search's text
@@ -1428,6 +1435,31 @@ hipError_t launch_poisson_draw(const double* mu, int rows, int C, int P, unsigne
 }
 
 // ---------------------------------------------------------------------------
+// k_normal_draw: out[row][p][j] = draw::normal0(center[row][j], sigma[j]) under the identity (seed, stream, row, p, j)
+// (nusi_plan_draw_normals): k_poisson_draw's shape, one lane per variate.  cs = center [rows][J], then sigma [J].
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kDrawThreads) void k_normal_draw(const double* __restrict__ cs, double* __restrict__ out, int rows,
+                                                              int J, int P, unsigned long long n, unsigned long long seed,
+                                                              unsigned stream)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * kDrawThreads + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long rp = i / (unsigned)J;
+    const unsigned j = (unsigned)(i - rp * (unsigned)J), row = (unsigned)(rp / (unsigned)P), p = (unsigned)(rp - (unsigned long long)row * (unsigned)P);
+    out[i] = draw::normal0(cs[(size_t)row * J + j], cs[(size_t)rows * J + j], draw::ident(seed, stream, row, p, j));
+}
+
+hipError_t launch_normal_draw(const double* cs, int rows, int J, int P, unsigned long long seed, unsigned stream, double* out,
+                              hipStream_t s)
+{
+    if (rows <= 0 || J <= 0 || P <= 0) return hipSuccess;
+    const unsigned long long n = (unsigned long long)rows * P * J, nb = (n + kDrawThreads - 1) / kDrawThreads;
+    if (nb > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_normal_draw, dim3((unsigned)nb), dim3(kDrawThreads), 0, s, cs, out, rows, J, P, n, seed, stream);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // k_inject<NC>: the calibration call (nusi_plan_response_inject), NC = 1 + K = 1 .. 4, on k_toys_limit<NC>'s block
 // shape, units and p-slices.  Per (t, q) and toy p the datum of lane c is DRAWN where it is fitted: draw::poisson of
 // mu_inj[c] = a_inj[q] s_c + sum_j theta_inj[j] T_jc + B_c (the conditional fit's order for mu) under the identity
@@ -1462,53 +1494,7 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
                                                        int u0, int nqb, int M, int C, int lgC, int Q, int P)
 {
 #pragma clang fp contract(off)
-    constexpr int KT = NC - 1, KA = KT > 0 ? KT : 1;
-    const int tid = (int)threadIdx.x, u = u0 + (int)blockIdx.x, t = u / nqb;
-    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
-    const int QB = kEvThreads >> lgC, qb0 = (u - t * nqb) * QB, q = qb0 + grp;
-    const int cc = c < C ? c : C - 1, qc = q < Q ? q : Q - 1;
-    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
-    const double* __restrict__ Sq = S + (size_t)qc * M;
-    const bool in = c < C;
-    int p0, p1;
-    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
-    double X[NC];
-    {
-        double s0 = 0.0;
-#pragma unroll 4
-        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
-        X[0] = in ? s0 : 0.0;
-    }
-#pragma unroll
-    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
-    const double b = in ? bg[cc] : 0.0;
-    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
-    auto add = [](double x, double y) { return x + y; };
-    auto min = [](double x, double y) { return y < x ? y : x; };
-    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
-    double S1h[NC];   // tree(X_j): the data do not enter
-#pragma unroll
-    for (int j = 0; j < NC; ++j) S1h[j] = X[j];
-    det_butterfly(S1h, lgC, add);
-    const size_t rq = (size_t)t * Q + qc;                     // the spectrum's row of the call's arrays
-    const size_t rc = (size_t)(u - u0) * QB + grp;            // ... and of the chunk's scratch
-    const size_t rth = (o.theta_compact ? rc : rq) * P, rst = (o.stat_compact ? rc : rq) * P;
-    const double atest = ii.a_test[qc];
-    const double qobs = ii.qobs ? ii.qobs[rq] : __builtin_nan("");
-    // the expectation the toys are drawn from (padding lanes: 0, which draws nothing)
-    double mu_inj = ii.a_inj[qc] * X[0];
-#pragma unroll
-    for (int j = 1; j < NC; ++j) mu_inj = mu_inj + ii.th_inj[j] * X[j];
-    mu_inj = mu_inj + b;
-    const double asig = atest * X[0];   // the held term of the conditional fit's den
-    bool supt = false;                  // a live template supports the bin
-    int nlt = 0;                        // the live templates
-#pragma unroll
-    for (int i = 0; i < KT; ++i) {
-        if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) supt = true;
-        nlt += S1h[i + 1] > 0.0 ? 1 : 0;
-    }
-
+#include "nusi_inject_setup.inc"
 #pragma unroll 1
     for (int p = p0; p < p1; ++p) {
         // (the expectation through an opaque copy: the sampler's set-up is formed per toy and not held across the fits)
@@ -1518,30 +1504,80 @@ __global__ __launch_bounds__(kEvThreads) void k_inject(const double* __restrict_
         if (o.data && in && q < Q) o.data[(rq * P + p) * C + c] = d;
 
 #include "nusi_toy_body.inc"
-        if (c == 0 && q < Q) {
-            if (o.theta) o.theta[rth + p] = th0;
-            if (o.stat) o.stat[rst + p] = stat;
-            if (o.words) {
-                o.words[(rq * P + p) * 2] = sth;
-                o.words[(rq * P + p) * 2 + 1] = st;
-            }
-            if (o.tally) {
-                int* ty = o.tally + rq * 4;
-                if (nofit) atomicAdd(ty + 0, 1);
-                if (nocond && !nofit) atomicAdd(ty + 1, 1);
-                if (sth & (NUSI_FIT_BOUNDARY | NUSI_FIT_FLAT)) atomicAdd(ty + 2, 1);
-                if (sth & NUSI_FIT_INFINITE) atomicAdd(ty + 3, 1);
-            }
-            if (o.exceed && stat >= qobs) atomicAdd(o.exceed + rq, 1);
-        }
+#include "nusi_inject_store.inc"
     }
+}
+
+// k_nuis_inject<NC, MODE>: k_inject<NC> under NUSI_OPT_TOY_NUISANCE = MODE, NUSI_TOYS_GLOBAL or NUSI_TOYS_PRIOR, NC = 2 .. 4,
+// launched only where a template is constrained (a w_j > 0): the same set-up, toy body and stores by #include, with the
+// toy's draws in front.  The toy's prior means (GLOBAL: m*_j) or its nuisances (PRIOR: theta*_j) are draw::normal0 of
+// the identity (seed, stream = t, row = q, p, j), j = 0 .. K - 1 the template, formed by every lane of the group --
+// uniform over it by construction, like theta.  `pr`, which the included texts read, is the toy's own copy of the plan's
+// priors prp: its means are vector values where a draw replaced them.  sg: the widths sigma_j (+inf: no prior).
+struct ToySigma {
+    double s[NUSI_FIT_TEMPLATES_MAX + 1];   // [0] unused
+};
+
+template <int NC, int MODE>
+__global__ __launch_bounds__(kEvThreads) void k_nuis_inject(const double* __restrict__ R, const double* __restrict__ S,
+                                                            const double* __restrict__ bg, const double* __restrict__ T,
+                                                            const FitPrior prp, const ToySigma sg, const double ku,
+                                                            const InjectIn ii, const InjectOut o, int u0, int nqb, int M, int C,
+                                                            int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    static_assert(NC > 1 && (MODE == NUSI_TOYS_GLOBAL || MODE == NUSI_TOYS_PRIOR), "k_nuis_inject: templates and a randomised ensemble");
+#include "nusi_inject_setup.inc"
+#pragma unroll 1
+    for (int p = p0; p < p1; ++p) {
+        FitPrior pr = prp;
+        // (the expectation through an opaque copy, as in k_inject)
+        double mup = mu_inj;
+        if constexpr (MODE == NUSI_TOYS_GLOBAL) {
+#pragma unroll
+            for (int j = 1; j < NC; ++j)
+                if (prp.w[j] > 0.0)
+                    pr.m[j] = draw::normal0(ii.th_inj[j], sg.s[j], draw::ident(ii.seed, (unsigned)t, (unsigned)qc, (unsigned)p, (unsigned)(j - 1)));
+        } else {
+            mup = ii.a_inj[qc] * X[0];
+#pragma unroll
+            for (int j = 1; j < NC; ++j) {
+                double thj = ii.th_inj[j];
+                if (prp.w[j] > 0.0)
+                    thj = draw::normal0(prp.m[j], sg.s[j], draw::ident(ii.seed, (unsigned)t, (unsigned)qc, (unsigned)p, (unsigned)(j - 1)));
+                mup = mup + thj * X[j];
+            }
+            mup = mup + b;
+        }
+        asm volatile("" : "+v"(mup));
+        const double d = in ? draw::poisson(mup, draw::ident(ii.seed, (unsigned)t, (unsigned)qc, (unsigned)p, (unsigned)c)) : 0.0;
+        if (o.data && in && q < Q) o.data[(rq * P + p) * C + c] = d;
+
+#include "nusi_toy_body.inc"
+#include "nusi_inject_store.inc"
+    }
+}
+
+// a call's widths as the kernels take them (fit_prior's slots)
+static ToySigma toy_sigma(int K, const double* ps)
+{
+    ToySigma sg;
+    for (int j = 0; j <= NUSI_FIT_TEMPLATES_MAX; ++j) sg.s[j] = (j >= 1 && j <= K) ? ps[j - 1] : __builtin_inf();
+    return sg;
+}
+// does the ensemble `toys` differ from NUSI_TOYS_FIXED on these priors?  (K = 0, or no constrained template: no)
+static bool toy_randomised(int toys, int K, const double* pw)
+{
+    bool any = false;
+    for (int j = 0; j < K; ++j) any = any || pw[j] > 0.0;
+    return toys != NUSI_TOYS_FIXED && any;
 }
 
 hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int Q, const double* a_inj, const double* a_test,
                          const double* th_inj, const double* qobs, int P, unsigned long long seed, int mode, const double* bg,
-                         int C, int K, const double* T, const double* pm, const double* pw, int u0, int nu, int pslices,
-                         double* theta, bool theta_compact, double* stat, bool stat_compact, int* words, int* tally, int* exceed,
-                         double* data, hipStream_t s)
+                         int C, int K, const double* T, const double* pm, const double* pw, const double* ps, int toys, int u0,
+                         int nu, int pslices, double* theta, bool theta_compact, double* stat, bool stat_compact, int* words,
+                         int* tally, int* exceed, double* data, hipStream_t s)
 {
     if (nu <= 0 || Q <= 0 || P <= 0) return hipSuccess;
     const int lg = ceil_log2(C), QB = kEvThreads >> lg, nqb = (Q + QB - 1) / QB;
@@ -1552,6 +1588,22 @@ hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int
     const InjectOut o{theta, stat, theta_compact ? 1 : 0, stat_compact ? 1 : 0, words, tally, exceed, data};
     const dim3 grid((unsigned)nu, 1, (unsigned)pslices), block(kEvThreads);
     const int M = g.T + 1;
+    if (toy_randomised(toys, K, pw)) {
+        const ToySigma sg = toy_sigma(K, ps);
+#define NUSI_NUIS_INJECT(NC, MODE) \
+    hipLaunchKernelGGL((k_nuis_inject<NC, MODE>), grid, block, 0, s, R, S, bg, T, pr, sg, ku, ii, o, u0, nqb, M, C, lg, Q, P)
+        switch (K * 4 + toys) {
+        case 1 * 4 + NUSI_TOYS_GLOBAL: NUSI_NUIS_INJECT(2, NUSI_TOYS_GLOBAL); break;
+        case 2 * 4 + NUSI_TOYS_GLOBAL: NUSI_NUIS_INJECT(3, NUSI_TOYS_GLOBAL); break;
+        case 3 * 4 + NUSI_TOYS_GLOBAL: NUSI_NUIS_INJECT(4, NUSI_TOYS_GLOBAL); break;
+        case 1 * 4 + NUSI_TOYS_PRIOR: NUSI_NUIS_INJECT(2, NUSI_TOYS_PRIOR); break;
+        case 2 * 4 + NUSI_TOYS_PRIOR: NUSI_NUIS_INJECT(3, NUSI_TOYS_PRIOR); break;
+        case 3 * 4 + NUSI_TOYS_PRIOR: NUSI_NUIS_INJECT(4, NUSI_TOYS_PRIOR); break;
+        default: return hipErrorInvalidValue;
+        }
+#undef NUSI_NUIS_INJECT
+        return hipGetLastError();
+    }
     switch (K) {
     case 0: hipLaunchKernelGGL((k_inject<1>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nqb, M, C, lg, Q, P); break;
     case 1: hipLaunchKernelGGL((k_inject<2>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nqb, M, C, lg, Q, P); break;
@@ -1597,53 +1649,7 @@ void k_belt(const double* __restrict__ R, const double* __restrict__ S, const do
             int M, int C, int lgC, int Q, int P)
 {
 #pragma clang fp contract(off)
-    constexpr int KT = NC - 1, KA = KT > 0 ? KT : 1;
-    const int G = ii.G, QG = Q * G;
-    const int tid = (int)threadIdx.x, u = u0 + (int)blockIdx.x, t = u / nrb;
-    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
-    const int QB = kEvThreads >> lgC, row = (u - t * nrb) * QB + grp;
-    const int cc = c < C ? c : C - 1, rc = row < QG ? row : QG - 1, q = rc / G, gp = rc - q * G;   // q < Q, gp < G
-    const int pair = t * Q + q;
-    const double* __restrict__ Rt = R + (size_t)t * M * C + cc;
-    const double* __restrict__ Sq = S + (size_t)q * M;
-    const bool in = c < C;
-    const bool mine = row < QG && pair >= ii.pr0 && pair < ii.pr1;   // the record is this launch's to store
-    int p0, p1;
-    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
-    double X[NC];
-    {
-        double s0 = 0.0;
-#pragma unroll 4
-        for (int n = 1; n < M; ++n) s0 = s0 + Rt[(size_t)n * C] * Sq[n];
-        X[0] = in ? s0 : 0.0;
-    }
-#pragma unroll
-    for (int j = 1; j < NC; ++j) X[j] = in ? T[(size_t)(j - 1) * C + cc] : 0.0;
-    const double b = in ? bg[cc] : 0.0;
-    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
-    auto add = [](double x, double y) { return x + y; };
-    auto min = [](double x, double y) { return y < x ? y : x; };
-    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
-    double S1h[NC];   // tree(X_j): the data do not enter
-#pragma unroll
-    for (int j = 0; j < NC; ++j) S1h[j] = X[j];
-    det_butterfly(S1h, lgC, add);
-    const double rf = ii.ref ? ii.ref[pair] : 1.0;
-    const double agrid = ii.frac[gp] * rf;
-    const bool agood = rf >= 0.0 && agrid < __builtin_inf();
-    const double atest = agood ? agrid : 0.0;
-    const size_t rg = (size_t)pair * G + gp;                    // the record's row of the call's [ntab][Q][G] arrays
-    const double asig = atest * X[0];   // the held term of the conditional fit's den
-    bool supt = false;                  // a live template supports the bin
-    int nlt = 0;                        // the live templates
-#pragma unroll
-    for (int i = 0; i < KT; ++i) {
-        if (S1h[i + 1] > 0.0 && X[i + 1] > 0.0) supt = true;
-        nlt += S1h[i + 1] > 0.0 ? 1 : 0;
-    }
-    double mu_inj = 0.0, qobs = __builtin_nan("");   // both set by the observed pass
-    bool valid = false;
-
+#include "nusi_belt_setup.inc"
 #pragma unroll 1
     for (int p = p0 - 1; p < p1; ++p) {
         const bool obs = p < p0;   // (uniform over the block: the pass against the data)
@@ -1659,44 +1665,50 @@ void k_belt(const double* __restrict__ R, const double* __restrict__ S, const do
         }
 
 #include "nusi_toy_body.inc"
+#include "nusi_belt_store.inc"
+    }
+}
+
+// k_nuis_belt<NC>: k_belt<NC> under NUSI_TOYS_GLOBAL, NC = 2 .. 4, as k_nuis_inject<NC, NUSI_TOYS_GLOBAL> is k_inject<NC>'s.
+// The centre of a toy's m*_j is the observed conditional fit's theta_j(a) of the record, kept from the observed pass,
+// which itself reads the plan's means; the identity is (seed, stream = t, row = q G + g, p, j).
+template <int NC>
+__global__ __launch_bounds__(kEvThreads) __attribute__((amdgpu_waves_per_eu(NC == 4 ? 2 : 3)))
+void k_nuis_belt(const double* __restrict__ R, const double* __restrict__ S, const double* __restrict__ bg,
+                 const double* __restrict__ T, const FitPrior prp, const ToySigma sg, const double ku, const BeltIn ii,
+                 const BeltOut o, int u0, int nrb, int M, int C, int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    static_assert(NC > 1, "k_nuis_belt: templates");
+#include "nusi_belt_setup.inc"
+    double cen[KT];   // the centres: set by the observed pass (an invalid record has no toys to store: 0)
+#pragma unroll
+    for (int j = 0; j < KT; ++j) cen[j] = 0.0;
+
+#pragma unroll 1
+    for (int p = p0 - 1; p < p1; ++p) {
+        const bool obs = p < p0;   // (uniform over the block: the pass against the data)
+        FitPrior pr = prp;
+        double d;
         if (obs) {
-            valid = agood && !nofit && !nocond;
-            qobs = valid ? stat : __builtin_nan("");
-            mu_inj = valid ? mu : 0.0;
-            if (c == 0 && mine && blockIdx.z == 0) {
-                const size_t ro = (size_t)pair * (1 + G);
-                if (gp == 0) {
-                    if (o.thobs) {
+            d = in ? ii.data[cc] : 0.0;
+        } else {
 #pragma unroll
-                        for (int j = 0; j < NC; ++j) o.thobs[ro * NC + j] = thh[j];
-                    }
-                    if (o.wobs) o.wobs[(size_t)(pair - (o.wobs_compact ? ii.pr0 : 0)) * (1 + G)] = sth;
-                }
-                if (o.thobs) {
-                    o.thobs[(ro + 1 + gp) * NC] = agood ? atest : __builtin_nan("");
-#pragma unroll
-                    for (int j = 0; j < KT; ++j) o.thobs[(ro + 1 + gp) * NC + 1 + j] = agood ? th[j] : __builtin_nan("");
-                }
-                if (o.wobs) o.wobs[(size_t)(pair - (o.wobs_compact ? ii.pr0 : 0)) * (1 + G) + 1 + gp] = agood ? st : 0;
-                if (o.qobs) o.qobs[rg] = qobs;
-            }
-        } else if (c == 0 && mine) {
-            if (o.theta) o.theta[rg * P + p] = valid ? th0 : __builtin_nan("");
-            if (o.stat) o.stat[rg * P + p] = valid ? stat : __builtin_nan("");
-            if (o.words) {
-                o.words[(rg * P + p) * 2] = valid ? sth : 0;
-                o.words[(rg * P + p) * 2 + 1] = valid ? st : 0;
-            }
-            if (o.tally && valid) {
-                int* ty = o.tally + ((size_t)(pair - (o.tally_compact ? ii.pr0 : 0)) * G + gp) * 4;
-                if (nofit) atomicAdd(ty + 0, 1);
-                if (nocond && !nofit) atomicAdd(ty + 1, 1);
-                if (sth & (NUSI_FIT_BOUNDARY | NUSI_FIT_FLAT)) atomicAdd(ty + 2, 1);
-                if (sth & NUSI_FIT_INFINITE) atomicAdd(ty + 3, 1);
-            }
-            if (o.exceed && valid && stat >= qobs)
-                atomicAdd(o.exceed + (size_t)(pair - (o.exceed_compact ? ii.pr0 : 0)) * G + gp, 1);
+            for (int j = 1; j < NC; ++j)
+                if (prp.w[j] > 0.0)
+                    pr.m[j] = draw::normal0(cen[j - 1], sg.s[j], draw::ident(ii.seed, (unsigned)t, (unsigned)rc, (unsigned)p, (unsigned)(j - 1)));
+            // (the expectation through an opaque copy, as in k_inject)
+            double mup = mu_inj;
+            asm volatile("" : "+v"(mup));
+            d = in ? draw::poisson(mup, draw::ident(ii.seed, (unsigned)t, (unsigned)rc, (unsigned)p, (unsigned)c)) : 0.0;
+            if (o.data && in && mine) o.data[(rg * P + p) * C + c] = valid ? d : 0.0;
         }
+
+#include "nusi_toy_body.inc"
+#include "nusi_belt_store.inc"
+        if (obs)
+#pragma unroll
+            for (int j = 0; j < KT; ++j) cen[j] = valid ? th[j] : 0.0;
     }
 }
 
@@ -1755,9 +1767,10 @@ int belt_block(int C) { return kEvThreads >> ceil_log2(C); }
 
 hipError_t launch_belt(const GridDev& g, const double* R, const double* S, int Q, const double* data, const double* frac,
                        int G, const double* ref, int P, unsigned long long seed, int mode, const double* bg, int C, int K,
-                       const double* T, const double* pm, const double* pw, int pr0, int pr1, int pslices, int* exceed,
-                       bool exceed_compact, int* tally, bool tally_compact, int* wobs, bool wobs_compact, double* qobs,
-                       double* thobs, double* theta, double* stat, int* words, double* data_all, hipStream_t s)
+                       const double* T, const double* pm, const double* pw, const double* ps, int toys, int pr0, int pr1,
+                       int pslices, int* exceed, bool exceed_compact, int* tally, bool tally_compact, int* wobs,
+                       bool wobs_compact, double* qobs, double* thobs, double* theta, double* stat, int* words, double* data_all,
+                       hipStream_t s)
 {
     if (pr1 <= pr0 || Q <= 0 || G <= 0 || P <= 0) return hipSuccess;
     const int lg = ceil_log2(C), QB = kEvThreads >> lg, nrb = (int)(((long long)Q * G + QB - 1) / QB);
@@ -1772,6 +1785,17 @@ hipError_t launch_belt(const GridDev& g, const double* R, const double* S, int Q
     const double ku = fit_ku(lg, K);
     const dim3 grid((unsigned)(ub - ua + 1), 1, (unsigned)pslices), block(kEvThreads);
     const int M = g.T + 1, u0 = (int)ua;
+    if (toy_randomised(toys, K, pw)) {
+        if (toys != NUSI_TOYS_GLOBAL) return hipErrorInvalidValue;
+        const ToySigma sg = toy_sigma(K, ps);
+        switch (K) {
+        case 1: hipLaunchKernelGGL((k_nuis_belt<2>), grid, block, 0, s, R, S, bg, T, pr, sg, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
+        case 2: hipLaunchKernelGGL((k_nuis_belt<3>), grid, block, 0, s, R, S, bg, T, pr, sg, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
+        case 3: hipLaunchKernelGGL((k_nuis_belt<4>), grid, block, 0, s, R, S, bg, T, pr, sg, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (K) {
     case 0: hipLaunchKernelGGL((k_belt<1>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;
     case 1: hipLaunchKernelGGL((k_belt<2>), grid, block, 0, s, R, S, bg, T, pr, ku, ii, o, u0, nrb, M, C, lg, Q, P); break;

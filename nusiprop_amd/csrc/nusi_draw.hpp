@@ -3,6 +3,8 @@
 // PTRS from there (numpy's split and its random_loggam).  Every operation is rounded on its own (no contraction), exp
 // and log are nm::exp_i and nm::log_i, so detector.draw_host gives the same bits with the same exp and log.  A draw is
 // identified by (seed, stream, row, p, c) alone: it does not depend on the launch, a chunk or a slice.
+// normal0 (include/nusi.h, "Drawing normals") is a truncated normal variate on the same blocks' generator, in a counter
+// domain of its own; detector.draw_normal_host gives the same bits with the same log.
 #pragma once
 
 #include "nusi_libm.hpp"
@@ -136,6 +138,38 @@ NUSI_FN double poisson(double mu, const Ident& id)
         if (lhs <= rhs) return k;
     }
     return k > 0.0 ? k : 0.0;
+}
+
+// one normal variate around center >= 0 of width sigma, truncated to x >= 0 (include/nusi.h, "Drawing normals"):
+// Marsaglia's polar method, round r on block kNormalBlock0 + r -- the counts use blocks 0 .. 63, so under one identity
+// the two families share no block.  sigma == +inf (no prior): center, no bits drawn.  After kNormalRounds rejected
+// rounds: center.  used: nullptr, or receives the blocks consumed.
+constexpr unsigned kNormalBlock0 = 0x80000000u;
+constexpr int kNormalRounds = 64;
+
+NUSI_FN double normal0(double center, double sigma, const Ident& id, int* used = nullptr)
+{
+#pragma clang fp contract(off)
+    if (used) *used = 0;
+    if (sigma == 1.0 / 0.0) return center;
+    for (int r = 0; r < kNormalRounds; ++r) {
+        double u0, u1;
+        uniforms(id, kNormalBlock0 + (unsigned)r, u0, u1);
+        if (used) *used = r + 1;
+        const double u = 2.0 * u0 - 1.0, v = 2.0 * u1 - 1.0;   // (exact)
+        const double uu = u * u, vv = v * v;
+        const double s = uu + vv;
+        if (!(s < 1.0) || s == 0.0) continue;
+        const double l2 = -2.0 * nm::log_i(s);
+        const double q = l2 / s;
+        const double f = __builtin_sqrt(q);
+        const double z = u * f;
+        const double sz = sigma * z;
+        const double x = center + sz;
+        if (!(x >= 0.0)) continue;
+        return x;
+    }
+    return center;
 }
 
 }   // namespace draw

@@ -206,6 +206,12 @@ hipError_t launch_toys_band(int C, int Q, int P, int u0, int nu, const double* l
 // include/nusi.h ("Drawing counts"); mu [rows][C] and out [rows][P][C] in device memory, rows P C <= NUSI_DRAW_COUNTS_MAX
 hipError_t launch_poisson_draw(const double* mu, int rows, int C, int P, unsigned long long seed, unsigned stream, double* out,
                                hipStream_t s);
+// k_normal_draw: out[row][p][j] = draw::normal0(center[row][j], sigma[j]) under the identity (seed, stream, row, p, j) of
+// include/nusi.h ("Drawing normals"); cs = center [rows][J] then sigma [J], and out [rows][P][J], in device memory
+hipError_t launch_normal_draw(const double* cs, int rows, int J, int P, unsigned long long seed, unsigned stream, double* out,
+                              hipStream_t s);
+// (launch_inject, launch_belt: ps [K] the priors' widths, +inf = none, and toys = NUSI_TOYS_*, the toys' ensemble; where
+// it randomises nothing -- NUSI_TOYS_FIXED, K = 0, no pw > 0 -- the FIXED instance runs)
 // k_inject<1 + K>: the calibration call (include/nusi.h nusi_plan_response_inject) on launch_toys_limit's units u0 ..
 // u0 + nu - 1 and p-slices: per (t, q, p) a toy drawn from a_inj[q] s + sum_j th_inj[j] T_j + bg under (seed, stream = t,
 // row = q, p, c), its best fit, the conditional fit at a_test[q] and the statistic under `mode`.  a_inj, a_test [Q] and
@@ -215,9 +221,9 @@ hipError_t launch_poisson_draw(const double* mu, int rows, int C, int P, unsigne
 // counts are ADDED to tally [ntab][Q][4] and exceed [ntab][Q] (any may be nullptr).
 hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int Q, const double* a_inj, const double* a_test,
                          const double* th_inj, const double* qobs, int P, unsigned long long seed, int mode, const double* bg,
-                         int C, int K, const double* T, const double* pm, const double* pw, int u0, int nu, int pslices,
-                         double* theta, bool theta_compact, double* stat, bool stat_compact, int* words, int* tally, int* exceed,
-                         double* data, hipStream_t s);
+                         int C, int K, const double* T, const double* pm, const double* pw, const double* ps, int toys, int u0,
+                         int nu, int pslices, double* theta, bool theta_compact, double* stat, bool stat_compact, int* words,
+                         int* tally, int* exceed, double* data, hipStream_t s);
 // k_belt<1 + K> and k_belt_accept (include/nusi.h nusi_plan_response_belt).  A record is (t, q, g) with row q G + g of a
 // table's Q G rows; a unit is one table and belt_block(C) rows.  launch_belt runs the units that hold the rows of the
 // pairs t Q + q = pr0 .. pr1 - 1 and stores those pairs' records alone: the observed side to qobs [ntab][Q][G], thobs
@@ -229,9 +235,10 @@ hipError_t launch_inject(const GridDev& g, const double* R, const double* S, int
 int belt_block(int C);
 hipError_t launch_belt(const GridDev& g, const double* R, const double* S, int Q, const double* data, const double* frac,
                        int G, const double* ref, int P, unsigned long long seed, int mode, const double* bg, int C, int K,
-                       const double* T, const double* pm, const double* pw, int pr0, int pr1, int pslices, int* exceed,
-                       bool exceed_compact, int* tally, bool tally_compact, int* wobs, bool wobs_compact, double* qobs,
-                       double* thobs, double* theta, double* stat, int* words, double* data_all, hipStream_t s);
+                       const double* T, const double* pm, const double* pw, const double* ps, int toys, int pr0, int pr1,
+                       int pslices, int* exceed, bool exceed_compact, int* tally, bool tally_compact, int* wobs,
+                       bool wobs_compact, double* qobs, double* thobs, double* theta, double* stat, int* words, double* data_all,
+                       hipStream_t s);
 hipError_t launch_belt_accept(const double* frac, int G, const double* ref, int P, double alpha, int pr0, int pr1,
                               const int* exceed, bool exceed_compact, const int* tally, bool tally_compact, const int* wobs,
                               bool wobs_compact, double* lo, double* hi, int* idx, int* status, hipStream_t s);

@@ -1088,7 +1088,93 @@ def draw_host(mu, P, seed, stream=0, exp=np.exp, log=np.log, rounds=None):
     return out[0] if one else out
 
 
+# --- the generator of nusi_plan_draw_normals (include/nusi.h "Drawing normals"), operation for operation ---
+NORMAL_ROUNDS = 64             # NUSI_NORMAL_ROUNDS
+NORMAL_BLOCK0 = 0x80000000     # the block word of round 0: the counts use blocks 0 .. 63
+
+
+def _normal_one(center, sigma, seed, stream, row, p, j, log, rounds=None):
+    """One normal variate around ``center`` of width ``sigma``, truncated to x >= 0, of the identity (seed, stream, row,
+    p, j), as a float: Marsaglia's polar method, round r on block NORMAL_BLOCK0 + r.  rounds: None, or a list that
+    receives the number of blocks the draw consumed."""
+    used, x = 0, center
+    if sigma != np.inf:
+        for r in range(NORMAL_ROUNDS):
+            u0, u1 = _uniform2(seed, stream, row, p, j, NORMAL_BLOCK0 + r)
+            used = r + 1
+            u, v = 2.0 * u0 - 1.0, 2.0 * u1 - 1.0
+            uu, vv = u * u, v * v
+            sq = uu + vv
+            if not sq < 1.0 or sq == 0.0:
+                continue
+            l2 = -2.0 * float(log(sq))
+            f = float(np.sqrt(l2 / sq))
+            z = u * f
+            sz = sigma * z
+            y = center + sz
+            if not y >= 0.0:
+                continue
+            x = y
+            break
+    if rounds is not None:
+        rounds.append(used)
+    return x
+
+
+def draw_normal_host(center, sigma, P, seed, stream=0, log=np.log, rounds=None):
+    """nusi_plan_draw_normals on the CPU: P normal variates around every entry of center (rows, J) or (J,), of the widths
+    sigma (J,) or a number, truncated to x >= 0, by the rule include/nusi.h defines, operation for operation: round r = 0,
+    1, .. takes the uniforms U0, U1 of the Philox block (NORMAL_BLOCK0 + r, p 64 + j, row, stream) under the key ``seed``;
+    u = 2 U0 - 1, v = 2 U1 - 1, s = u u + v v, rejected unless 0 < s < 1; x = center + sigma (u sqrt((-2 log s) / s)),
+    rejected unless x >= 0; after NORMAL_ROUNDS rejected rounds the draw is the center.  sigma = inf: the center, no bits
+    drawn.  The blocks are none of draw_host's (0 .. 63), so the two families are independent under one seed.  Returns
+    float64 (rows, P, J), or (P, J) for a vector; entry [row, p, j] depends on (seed, stream, row, p, j), center[row, j]
+    and sigma[j] alone.  log: a scalar function of a float (the oracle's ora_log gives Plan.draw_normal's bits).  rounds:
+    None, or a list that receives the blocks each draw consumed, in the output's order."""
+    c = np.asarray(center, dtype=np.float64)
+    one = c.ndim == 1
+    if one:
+        c = c[None]
+    if c.ndim != 2 or c.shape[0] < 1 or not 1 <= c.shape[1] <= BINS_MAX:
+        raise ValueError("draw_normal_host: center must have shape (J,) or (rows, J), 1 <= J <= %d, got %s" % (BINS_MAX, c.shape))
+    if not np.all(np.isfinite(c)) or np.any(c < 0):
+        raise ValueError("draw_normal_host: a center is negative or not finite")
+    rows, J = c.shape
+    sg = np.array(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (J,)))
+    if np.any(np.isnan(sg)) or np.any(sg <= 0):
+        raise ValueError("draw_normal_host: a sigma is NaN or not > 0")
+    P, seed, stream = int(P), int(seed), int(stream)
+    if not 1 <= P <= DRAW_DATASETS_MAX:
+        raise ValueError("draw_normal_host: P must be 1 .. %d" % DRAW_DATASETS_MAX)
+    if not 0 <= seed < 2 ** 64 or not 0 <= stream < 2 ** 32:
+        raise ValueError("draw_normal_host: seed must fit 64 bits and stream 32, unsigned")
+    out = np.zeros((rows, P, J))
+    with np.errstate(all="ignore"):
+        for row in range(rows):
+            for p in range(P):
+                for j in range(J):
+                    out[row, p, j] = _normal_one(float(c[row, j]), float(sg[j]), seed, stream, row, p, j, log, rounds)
+    return out[0] if one else out
+
+
 INJECT_TWO_SIDED, INJECT_UPPER, INJECT_DISCOVERY = 0, 1, 2     # NUSI_INJECT_*
+TOYS_FIXED, TOYS_GLOBAL, TOYS_PRIOR = 0, 1, 2                  # NUSI_TOYS_* (NUSI_OPT_TOY_NUISANCE)
+
+
+def _toys(who, nuisance, allowed):
+    ens = {"fixed": TOYS_FIXED, "global": TOYS_GLOBAL, "prior": TOYS_PRIOR}.get(nuisance, nuisance)
+    if isinstance(ens, bool) or ens not in allowed:
+        raise ValueError("%s: nuisance must be one of %s or the TOYS_* ints" % (
+            who, ", ".join(repr(n) for n, v in (("fixed", 0), ("global", 1), ("prior", 2)) if v in allowed)))
+    return int(ens)
+
+
+def _prior_sigma(K, prior, w):
+    """The widths (K,) the toys' normals take: sigma_j where template j is constrained (w_j > 0), +inf elsewhere."""
+    sg = np.full(K, np.inf)
+    if prior is not None and prior[1] is not None:
+        sg = np.where(w[1:] > 0, np.broadcast_to(np.asarray(prior[1], dtype=np.float64), (K,)), np.inf)
+    return sg
 
 
 def inject_tally(words):
@@ -1128,7 +1214,7 @@ def _inject_one(Rt, Sq, at, d, T, prior, B, m, w, md, log):
 
 
 def inject_host(R, S, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sided", ranks=None, q_obs=None,
-                templates=None, prior=None, background=None, exp=np.exp, log=np.log, raw=False):
+                templates=None, prior=None, background=None, exp=np.exp, log=np.log, raw=False, nuisance="fixed"):
     """nusi_plan_response_inject on the CPU: per table t the toys draw_host(mu_inj[t], P, seed, stream=t) around
     mu_inj[t, q] = a_inj[q] s + sum_j theta_inj[j] T_j + B, and per toy a loop of the existing host forms: the best fit
     (fit_host; profile_host without templates), the conditional fit at a_test[q] (fit_fixed_host; without templates the
@@ -1142,7 +1228,17 @@ def inject_host(R, S, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sid
     NR), band_stat (ntab, Q, NR), tally (ntab, Q, 4) int32 -- inject_tally), with q_obs also exceed (ntab, Q) int32, the
     toys with stat >= q_obs, and with raw also (theta_all (ntab, Q, P), stat_all (ntab, Q, P), words_all (ntab, Q, P, 2)
     int32, data_all (ntab, Q, P, C)).  A failed best fit: theta_hat_0 and stat are NaN; a failed conditional fit: stat is
-    NaN.  No axis is squeezed."""
+    NaN.  No axis is squeezed.
+
+    nuisance: the toys' ensemble (NUSI_OPT_TOY_NUISANCE) for the constrained templates, those with a prior of finite
+    width (w_j > 0): "fixed", "global", "prior" or TOYS_*.  "global": per toy the prior means are redrawn, m*_j =
+    draw_normal_host(theta_inj, sigma, P, seed, stream=t)[q, p, j]; the counts are "fixed"'s, and the toy's fits and
+    lambda take prior = (m*, sigma).  "prior": per toy theta*_j = draw_normal_host(prior means, sigma, P, seed,
+    stream=t)[q, p, j] for a constrained template (theta_inj[j] otherwise), the counts are draw_host of a_inj s + sum_j
+    theta*_j T_j + B, and the fits take the plan's prior.  With raw and an ensemble other than "fixed" one more array is
+    appended: nuis_all (ntab, Q, P, K), the drawn m* or theta*, and the centre where a template is unconstrained.  With K
+    = 0 or no constrained template every ensemble gives "fixed"'s values."""
+    ens = _toys("inject_host", nuisance, (TOYS_FIXED, TOYS_GLOBAL, TOYS_PRIOR))
     R = np.asarray(R, dtype=np.float64)
     S = np.asarray(S, dtype=np.float64)
     if R.ndim == 2:
@@ -1173,23 +1269,42 @@ def inject_host(R, S, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sid
     s = np.reshape(events_host(R, S), (ntab, Q, C))
     th_all, st_all = np.full((ntab, Q, P), np.nan), np.full((ntab, Q, P), np.nan)
     words, data_all = np.zeros((ntab, Q, P, 2), dtype=np.int32), np.zeros((ntab, Q, P, C))
+    sg = _prior_sigma(K, prior, w)
+    nuis_all = np.zeros((ntab, Q, P, K))
     with np.errstate(all="ignore"):
         for t in range(ntab):
-            mu_inj = ai[:, None] * s[t]
-            for j in range(K):
-                mu_inj = mu_inj + ti[j] * T[j][None, :]
-            mu_inj = mu_inj + B[None, :]
-            data_all[t] = draw_host(mu_inj, P, seed, stream=t, exp=exp, log=log)
+            if K and ens != TOYS_FIXED:       # (an unconstrained template: sigma = inf, the centre itself)
+                centre = ti if ens == TOYS_GLOBAL else np.where(w[1:] > 0, m[1:], ti)
+                nuis_all[t] = draw_normal_host(np.broadcast_to(centre, (Q, K)), sg, P, seed, stream=t, log=log)
+            if K and ens == TOYS_PRIOR:
+                for p in range(P):            # toy p's expectation, every spectrum; its counts are the draw's [q, p]
+                    mu_p = ai[:, None] * s[t]
+                    for j in range(K):
+                        mu_p = mu_p + nuis_all[t, :, p, j][:, None] * T[j][None, :]
+                    mu_p = mu_p + B[None, :]
+                    for q in range(Q):
+                        for c in range(C):
+                            data_all[t, q, p, c] = _draw_one(float(mu_p[q, c]), int(seed), t, q, p, c, exp, log)
+            else:
+                mu_inj = ai[:, None] * s[t]
+                for j in range(K):
+                    mu_inj = mu_inj + ti[j] * T[j][None, :]
+                mu_inj = mu_inj + B[None, :]
+                data_all[t] = draw_host(mu_inj, P, seed, stream=t, exp=exp, log=log)
             for q in range(Q):
                 for p in range(P):
-                    th0, stat, sth, stc = _inject_one(R[t], S[q], at[q], data_all[t, q, p], T, prior, B, m, w, md, log)[:4]
+                    pr_p, m_p = prior, m
+                    if K and ens == TOYS_GLOBAL:
+                        pr_p = (nuis_all[t, q, p], sg)
+                        m_p = _prior(K, pr_p)[0]
+                    th0, stat, sth, stc = _inject_one(R[t], S[q], at[q], data_all[t, q, p], T, pr_p, B, m_p, w, md, log)[:4]
                     th_all[t, q, p], st_all[t, q, p], words[t, q, p] = th0, stat, (sth, stc)
     out = (order_stat(th_all, r), order_stat(st_all, r), inject_tally(words))
     if q_obs is not None:
         qo = np.broadcast_to(np.asarray(q_obs, dtype=np.float64), (ntab, Q))
         with np.errstate(invalid="ignore"):
             out = out + ((st_all >= qo[..., None]).sum(axis=-1).astype(np.int32),)
-    return out + ((th_all, st_all, words, data_all) if raw else ())
+    return out + ((th_all, st_all, words, data_all) + ((nuis_all,) if ens != TOYS_FIXED else ()) if raw else ())
 
 
 BELT_GRID_MAX = 64                                             # the most grid points of belt_host; its status bits:
@@ -1230,7 +1345,7 @@ def belt_accept(exceed, tally, a, alpha, valid, P, flags=0):
 
 
 def belt_host(R, S, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, templates=None, prior=None, background=None,
-              exp=np.exp, log=np.log, raw=False):
+              exp=np.exp, log=np.log, raw=False, nuisance="fixed"):
     """The toy-calibrated confidence interval of the signal's scale -- the Feldman-Cousins interval by the profile
     construction -- on a grid of test scales, as a loop of the existing host forms (numpy only; Plan.belt is the device
     call that reproduces it: DESIGN.md sec. 4, "The calibrated interval").  Per table t, spectrum q and grid point g the test
@@ -1245,7 +1360,14 @@ def belt_host(R, S, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, 
     (ntab, Q, G), theta_obs (ntab, Q, 1 + G, 1 + K), words_obs (ntab, Q, 1 + G) int32) and with raw also (theta_all
     (ntab, Q, G, P), stat_all (ntab, Q, G, P), words_all (ntab, Q, G, P, 2) int32, data_all (ntab, Q, G, P, C)).  A point
     without toys (no grid value, a failed observed fit) has q_obs NaN, counts of 0 and raw outputs of NaN / 0.  No axis
-    is squeezed."""
+    is squeezed.
+
+    nuisance: "fixed" or "global" (TOYS_FIXED, TOYS_GLOBAL), as for inject_host; "prior" is refused -- the profile
+    construction has no such variant.  "global": toy p of a valid point takes prior = (m*, sigma) with m*_j =
+    draw_normal_host(centres, sigma, P, seed, stream=t)[q G + g, p, j] for a constrained template, the centre the observed
+    conditional fit's theta_j(a), theta_obs[t, q, 1 + g, 1 + j]; the counts are "fixed"'s and the observed pass uses the
+    prior as given.  With raw, "global" appends nuis_all (ntab, Q, G, P, K) (0 at a point without toys)."""
+    ens = _toys("belt_host", nuisance, (TOYS_FIXED, TOYS_GLOBAL))
     R = np.asarray(R, dtype=np.float64)
     S = np.asarray(S, dtype=np.float64)
     if R.ndim == 2:
@@ -1284,6 +1406,8 @@ def belt_host(R, S, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, 
     words, data_all = np.zeros((ntab, Q, G, P, 2), dtype=np.int32), np.zeros((ntab, Q, G, P, C))
     valid = np.zeros((ntab, Q, G), dtype=bool)
     flags = np.zeros((ntab, Q), dtype=np.int32)
+    sg = _prior_sigma(K, prior, w)
+    nuis_all = np.zeros((ntab, Q, G, P, K))
     with np.errstate(all="ignore"):
         for t in range(ntab):
             mu_inj = np.zeros((Q, G, C))
@@ -1303,16 +1427,24 @@ def belt_host(R, S, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, 
                     if not (sth | stc) & fail:
                         valid[t, q, g], q_obs[t, q, g], mu_inj[q, g] = True, stat, muc
             toys = np.reshape(draw_host(mu_inj.reshape(Q * G, C), P, seed, stream=t, exp=exp, log=log), (Q, G, P, C))
+            if K and ens == TOYS_GLOBAL:
+                centre = np.where(valid[t][..., None], theta_obs[t, :, 1:, 1:], 0.0).reshape(Q * G, K)
+                nuis = np.reshape(draw_normal_host(centre, sg, P, seed, stream=t, log=log), (Q, G, P, K))
+                nuis_all[t] = np.where(valid[t][..., None, None], nuis, 0.0)
             for q, g in zip(*np.nonzero(valid[t])):
                 data_all[t, q, g] = toys[q, g]
                 for p in range(P):
-                    th0, stat, sth, stc = _inject_one(R[t], S[q], float(a[t, q, g]), toys[q, g, p], T, prior, B, m, w, md, log)[:4]
+                    pr_p, m_p = prior, m
+                    if K and ens == TOYS_GLOBAL:
+                        pr_p = (nuis_all[t, q, g, p], sg)
+                        m_p = _prior(K, pr_p)[0]
+                    th0, stat, sth, stc = _inject_one(R[t], S[q], float(a[t, q, g]), toys[q, g, p], T, pr_p, B, m_p, w, md, log)[:4]
                     th_all[t, q, g, p], st_all[t, q, g, p], words[t, q, g, p] = th0, stat, (sth, stc)
     tally = np.where(valid[..., None], inject_tally(words), 0).astype(np.int32)
     with np.errstate(invalid="ignore"):
         exceed = (st_all >= q_obs[..., None]).sum(axis=-1).astype(np.int32)
     out = belt_accept(exceed, tally, a, alpha, valid, P, flags) + (exceed, tally, q_obs, theta_obs, words_obs)
-    return out + ((th_all, st_all, words, data_all) if raw else ())
+    return out + ((th_all, st_all, words, data_all) + ((nuis_all,) if ens != TOYS_FIXED else ()) if raw else ())
 
 
 def matrix(lo, hi, aeff, migration=None, exposure=1.0):

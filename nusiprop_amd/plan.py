@@ -618,7 +618,50 @@ class Plan:
                                                      vp(stream_ptr) if stream_ptr else None))
         return m.shape
 
+    @staticmethod
+    def _normal_args(center, sigma):
+        c = np.ascontiguousarray(center, dtype=np.float64)
+        one = c.ndim == 1
+        if one:
+            c = c[None]
+        if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+            raise ValueError("draw_normal: center must have shape (J,) or (rows, J), got %s" % (np.shape(center),))
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (c.shape[1],)))
+        return c, sg, one
+
+    def draw_normal(self, center, sigma, P, seed, stream=0):
+        """P normal variates around every center (rows, J) or (J,), of the widths sigma (J,) or a number, truncated to
+        x >= 0, drawn on the GPU by the generator include/nusi.h defines ("Drawing normals"): float64 (rows, P, J), or
+        (P, J) for a vector.  The variate of (row, p, j) depends on (seed, stream, row, p, j) alone and is
+        detector.draw_normal_host's, every bit; its Philox blocks are none of ``draw``'s.  center finite and >= 0, sigma
+        > 0 (inf: the center itself, no bits drawn), J <= 64.  No detector is needed."""
+        c, sg, one = self._normal_args(center, sigma)
+        out = np.zeros((c.shape[0], int(P), c.shape[1]))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_draw_normals_host(self._h, c.ctypes.data_as(dp), sg.ctypes.data_as(dp), c.shape[0],
+                                                           c.shape[1], int(P), int(seed) & (2 ** 64 - 1),
+                                                           int(stream) & (2 ** 32 - 1), out.ctypes.data_as(dp)))
+        return out[0] if one else out
+
+    def draw_normal_device(self, center, sigma, P, seed, d_out_ptr, stream=0, stream_ptr=None):
+        """Asynchronous ``draw_normal`` into device memory: d_out [rows][P][J] doubles (a raw pointer); center and sigma
+        are host data and are copied.  Returns (rows, J)."""
+        c, sg, _ = self._normal_args(center, sigma)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_draw_normals(self._h, c.ctypes.data_as(dp), sg.ctypes.data_as(dp), c.shape[0],
+                                                      c.shape[1], int(P), int(seed) & (2 ** 64 - 1),
+                                                      int(stream) & (2 ** 32 - 1), vp(d_out_ptr) if d_out_ptr else None,
+                                                      vp(stream_ptr) if stream_ptr else None))
+        return c.shape
+
     # --- the calibration call (include/nusi.h nusi_plan_response_inject) ---
+    def _nuisance(self, nuisance):
+        """nuisance: None leaves the plan's NUSI_OPT_TOY_NUISANCE alone; "fixed", "global", "prior" or _lib.TOYS_* sets it."""
+        if nuisance is not None:
+            self.set_option(_lib.OPT_TOY_NUISANCE, int({"fixed": _lib.TOYS_FIXED, "global": _lib.TOYS_GLOBAL,
+                                                        "prior": _lib.TOYS_PRIOR}.get(nuisance, nuisance)))
+
     @staticmethod
     def _mode(mode):
         return int({"two-sided": _lib.INJECT_TWO_SIDED, "upper": _lib.INJECT_UPPER,
@@ -638,7 +681,7 @@ class Plan:
         return S, ai, ti, at, self._ranks(ranks, max(int(P), 1)), qo
 
     def inject(self, R, spectra, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sided", ranks=None, q_obs=None,
-               raw=False):
+               raw=False, nuisance=None):
         """The distribution of the statistic q(a_test) on toys drawn from a hypothesis's own expectation, in one call on
         the GPU.  For every table t, spectrum q and toy p < P the counts are drawn on the device from
         a_inj[q] s + sum_j theta_inj[j] T_j + B -- ``draw`` of that expectation with stream = t at [q, p] --, fitted
@@ -651,7 +694,13 @@ class Plan:
         fit) last, and the toys whose best fit failed, whose conditional fit alone failed, with theta_hat_0 = 0 and with an
         infinite best fit --, with q_obs also exceed (ntab, Q) int32, the toys with stat >= q_obs (the p-value:
         exceed / (P - tally[..., 0] - tally[..., 1])), and with raw also (theta_all (ntab, Q, P), stat_all (ntab, Q, P),
-        words_all (ntab, Q, P, 2) int32, data_all (ntab, Q, P, C)).  detector.inject_host is the same in numpy."""
+        words_all (ntab, Q, P, 2) int32, data_all (ntab, Q, P, C)).  detector.inject_host is the same in numpy.
+
+        nuisance: the toys' ensemble for templates under a prior -- "fixed" (the prior means stay), "global" (the means,
+        as auxiliary measurements, are redrawn per toy around theta_inj: ``draw_normal`` with stream = t at [q, p, j]) or
+        "prior" (the nuisances themselves are drawn around the prior means and the counts follow them;
+        Cousins-Highland), or _lib.TOYS_*; it sets the plan's OPT_TOY_NUISANCE, None leaves it alone."""
+        self._nuisance(nuisance)
         R, C = self._folded(R, "inject")
         ntab, P = R.shape[0], int(P)
         S, ai, ti, at, r, qo = self._inject_args(spectra, a_inj, theta_inj, a_test, ranks, P, q_obs, ntab)
@@ -678,12 +727,13 @@ class Plan:
     def inject_device(self, d_R_ptr, ntab, spectra, a_inj, P, seed, theta_inj=None, a_test=None, mode="two-sided",
                       ranks=None, q_obs=None, d_band_theta_ptr=None, d_band_stat_ptr=None, d_tally_ptr=None,
                       d_exceed_ptr=None, d_theta_all_ptr=None, d_stat_all_ptr=None, d_words_all_ptr=None,
-                      d_data_all_ptr=None, stream_ptr=None):
+                      d_data_all_ptr=None, stream_ptr=None, nuisance=None):
         """Asynchronous ``inject`` on device-resident folded matrices d_R [ntab][M][C]: the outputs are raw pointers
         (d_band_theta, d_band_stat [ntab][Q][NR], d_theta_all, d_stat_all [ntab][Q][P] and d_data_all [ntab][Q][P][C]
         doubles; d_tally [ntab][Q][4], d_exceed [ntab][Q] and d_words_all [ntab][Q][P][2] ints), any may be 0 / None; with
         ranks one band is needed, and d_exceed comes with q_obs.  ranks: ints (None: detector.band_ranks(P); an empty
-        list: no band).  The other arguments are host data and are copied.  Returns (Q, NR)."""
+        list: no band).  The other arguments are host data and are copied.  nuisance: as for ``inject``.  Returns (Q, NR)."""
+        self._nuisance(nuisance)
         S, ai, ti, at, r, qo = self._inject_args(spectra, a_inj, theta_inj, a_test, ranks, P, q_obs, int(ntab))
         dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
         vp = ctypes.c_void_p
@@ -716,7 +766,7 @@ class Plan:
             rf = np.ascontiguousarray(np.broadcast_to(rf, (ntab, len(S))))
         return S, d, fr, rf
 
-    def belt(self, R, spectra, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, raw=False):
+    def belt(self, R, spectra, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, raw=False, nuisance=None):
         """The toy-calibrated confidence interval of the signal's scale -- the Feldman-Cousins interval by the profile
         construction -- on a grid of test scales, in one call on the GPU.  Per table t, spectrum q and grid point g the
         test scale is a = frac[g] * ref[t, q]; the data (C,) get ``inject``'s steps at a (``fit`` / ``profile``,
@@ -728,7 +778,12 @@ class Plan:
         (ntab, Q), idx (ntab, Q, 2) int32, status (ntab, Q) int32 -- _lib.BELT_* --, exceed (ntab, Q, G) int32, tally
         (ntab, Q, G, 4) int32, q_obs (ntab, Q, G), theta_obs (ntab, Q, 1 + G, 1 + K), words_obs (ntab, Q, 1 + G) int32)
         and with raw also (theta_all (ntab, Q, G, P), stat_all (ntab, Q, G, P), words_all (ntab, Q, G, P, 2) int32,
-        data_all (ntab, Q, G, P, C)).  No axis is squeezed."""
+        data_all (ntab, Q, G, P, C)).  No axis is squeezed.
+
+        nuisance: "fixed" or "global" (the prior means redrawn per toy around the observed conditional fit's theta_j(a),
+        theta_obs[t, q, 1 + g, 1 + j]: ``draw_normal`` with stream = t at [q G + g, p, j]), as for ``inject``; under
+        "prior" the call is refused."""
+        self._nuisance(nuisance)
         R, C = self._folded(R, "belt")
         ntab, P = R.shape[0], int(P)
         S, d, fr, rf = self._belt_args(spectra, data, frac, ref, ntab)
@@ -757,12 +812,14 @@ class Plan:
     def belt_device(self, d_R_ptr, ntab, spectra, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1,
                     d_lo_ptr=None, d_hi_ptr=None, d_idx_ptr=None, d_status_ptr=None, d_exceed_ptr=None, d_tally_ptr=None,
                     d_q_obs_ptr=None, d_theta_obs_ptr=None, d_words_obs_ptr=None, d_theta_all_ptr=None,
-                    d_stat_all_ptr=None, d_words_all_ptr=None, d_data_all_ptr=None, stream_ptr=None):
+                    d_stat_all_ptr=None, d_words_all_ptr=None, d_data_all_ptr=None, stream_ptr=None, nuisance=None):
         """Asynchronous ``belt`` on device-resident folded matrices d_R [ntab][M][C]: the outputs are raw pointers (d_lo,
         d_hi [ntab][Q], d_q_obs [ntab][Q][G], d_theta_obs [ntab][Q][1 + G][1 + K], d_theta_all, d_stat_all
         [ntab][Q][G][P] and d_data_all [ntab][Q][G][P][C] doubles; d_idx [ntab][Q][2], d_status [ntab][Q], d_exceed
         [ntab][Q][G], d_tally [ntab][Q][G][4], d_words_obs [ntab][Q][1 + G] and d_words_all [ntab][Q][G][P][2] ints), any
-        may be 0 / None but not all.  The other arguments are host data and are copied.  Returns (Q, G)."""
+        may be 0 / None but not all.  The other arguments are host data and are copied.  nuisance: as for ``belt``.
+        Returns (Q, G)."""
+        self._nuisance(nuisance)
         S, d, fr, rf = self._belt_args(spectra, data, frac, ref, int(ntab))
         dp = ctypes.POINTER(ctypes.c_double)
         vp = ctypes.c_void_p
@@ -796,8 +853,8 @@ class Plan:
         cascade: its step-pass FIFO budget in KiB, 0 = 1 GiB; the tables run in chunks that fit), OPT_ENSEMBLE_QSLICES
         and OPT_ENSEMBLE_PSLICES (``ensemble``'s grid is (tables, q-slices, p-slices): 0 = automatic, n >= 1 = exactly
         min(n, what there is to split); any value gives the same bits), OPT_ENSEMBLE_LIMIT_MB (``ensemble_limit``'s
-        scratch budget in MiB, 0 = 256; the call runs in chunks that fit; OPT_ENSEMBLE_LIMIT_BYTES: the same in bytes);
-        include/nusi.h."""
+        scratch budget in MiB, 0 = 256; the call runs in chunks that fit; OPT_ENSEMBLE_LIMIT_BYTES: the same in bytes),
+        OPT_TOY_NUISANCE (the toys of ``inject`` and ``belt``: TOYS_FIXED, TOYS_GLOBAL or TOYS_PRIOR); include/nusi.h."""
         _lib.check(_lib.load().nusi_plan_set_option(self._h, int(option), int(value)))
 
     def profile_begin(self, max_calls):
