@@ -123,9 +123,10 @@ def test_bs_c5_block(nusi, oracle_mod):
 
 @pytest.mark.parametrize("N,lEmin", [(200, 12.0), (700, 12.0), (1200, 10.0)])
 def test_bs_step_passes(nusi, oracle_mod, N, lEmin):
-    """Grids beyond 48 redshift steps (N = 200: 32 steps, 700: 109, C3's 1200 at lE 10 -> 17: 134) in step passes,
-    one point per workgroup and gamma batches where a batch's accumulators fit the register file (N = 200; the
-    FIFO carries each pass' last step to the next pass)."""
+    """Step passes: N = 200 (32 steps: one pass unless forced, then two of 16; the gamma batch's passes of 6) and
+    the grids beyond 48 redshift steps (N = 700: 109, C3's 1200 at lE 10 -> 17: 134), one point per workgroup and
+    gamma batches where a batch's accumulators fit the register file (N = 200; the FIFO carries each pass' last
+    step to the next pass)."""
     pts = [dict(cases.C2B_100, N_bins_E=N, lEmin=lEmin, mphi=m, g=g, majorana=maj)
            for m, g, maj in ((6e5, 0.01, True), (1e5, 0.05, True), (2e6, 0.3, False))]
     pts += [dict(pts[0], si=s) for s in (2.0, 2.2, 2.7)]
