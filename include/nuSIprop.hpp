@@ -175,6 +175,14 @@ public:
         check(nusi_set_params(h_, mphi, g, mntot, si, norm));
         check(nusi_response(h_, w, G, G_fla));
     }
+    // The same resolved by the source's mass state (include/nusi.h, nusi_response_mass): G3 / G3_fla [3][M][3][N_bins_E]
+    // (either may be null), G3[j] the response to a source emitted wholly into mass state j.  The response of a flavour
+    // composition phi is sum_j kappa_j G3[j] with kappa = nusi_mass_fractions(normal_ordering, phi).
+    void response_mass(double* G3, double* G3_fla = nullptr, const double* w = nullptr)
+    {
+        check(nusi_set_params(h_, mphi, g, mntot, si, norm));
+        check(nusi_response_mass(h_, w, G3, G3_fla));
+    }
 
 private:
     nusi_handle* h_ = nullptr;

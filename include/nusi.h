@@ -123,6 +123,9 @@ int nusi_set_source(nusi_handle *h, const double *S, const double *w);
  * [M][3][N] host arrays (either may be NULL), w [Nz] or NULL.  The object's
  * fluxes, its source (nusi_set_source) and the plan's slots are not involved. */
 int nusi_response(nusi_handle *h, const double *w, double *G, double *G_fla);
+/* ... and its mass-resolved response (nusi_plan_response_mass_host, below):
+ * G3 / G3_fla [3][M][3][N] host arrays, either may be NULL. */
+int nusi_response_mass(nusi_handle *h, const double *w, double *G3, double *G3_fla);
 /* results of the last evolve(), row-major [k][b] (mass basis) / [f][b] (flavour) */
 int nusi_get_flux(const nusi_handle *h, double *out_3xN);      /* get_flux(i,j)     :359-381 */
 int nusi_get_flux_fla(const nusi_handle *h, double *out_3xN);  /* get_flux_fla(i,j) :383-405 */
@@ -231,6 +234,90 @@ int nusi_plan_response_apply(nusi_plan *plan, const double *d_G, int ntab, const
                              const double *scale /* [Q] or NULL */, double *d_out, void *stream);
 int nusi_plan_response_apply_host(nusi_plan *plan, const double *G, int ntab, const double *S, int Q,
                                   const double *scale, double *out);
+/* Mass-resolved response matrices: the source's flavour composition (no
+ * reference counterpart).  Every built-in source and every tabulated one is
+ * emitted in equal thirds into the three mass states (nuSIprop.hpp:737; the
+ * norm / 3.0 of the source terms).  The flux is linear in the source PER MASS
+ * STATE, so the response resolved by the source's mass state j serves any
+ * composition.
+ *
+ * The matrix.  G3[p][j][n][k][b] is the mass-basis flux of state k in bin b
+ * that the cascade of point p gives when the source term of (step i, bin b,
+ * state k') is
+ *     delta_{k' j} * [b + i == n] * sig3[i],
+ *     sig3[i] = step_c[i] * (w[i] / (1 + z[i]))  for i >= 1
+ * -- tabulated_src(step_c[i], 3.0, w[i], z[i], 1.0), the same bits: the WHOLE
+ * unit source goes into state j, with no third.  The solve is the existing
+ * one with the source per row,
+ *     v_k = (f_k + (s_k + u_k * add)) * rz_k,   s_k = (k == j) ? src : 0.0,
+ * and everything after it is unchanged.  G3_fla[p][j][n][f][b] goes through
+ * the finalise's |U|^2 expression.
+ * Layout: [p][j][n][3][N], n_points * 3 * M * 3 * N doubles, so G3 viewed as
+ * (3 n_points, M, 3, N) is a stack of ordinary response matrices, which
+ * nusi_plan_response_apply and nusi_plan_response_fold accept as it stands
+ * (ntab = 3 n_points).  As for G: column n = 0 is zero, and entries with
+ * b >= n are +0.0, sign bit clear.
+ * Sign.  The block k = j is non-negative.  For k != j an entry may be
+ * NEGATIVE: M = I + offdiag has positive off-diagonals (nuSIprop.hpp:302-303,
+ * without the step factor), and where a column's state k != j meets a zero
+ * right-hand side -- the column's top bin of a step, b = n - i -- the 3x3 solve
+ * gives -m_kj * x_j.  This is the reference's arithmetic on a source the
+ * reference never had, and it is not clamped.
+ *
+ * nusi_plan_response_mass evolves G3 / G3_fla of n points into DEVICE arrays
+ * (either may be NULL) like nusi_plan_response: the same Stage A with the same
+ * deduplication; nusi_plan_tables / _warnings / _stage_ms / _kernels refer to
+ * the call afterwards.  The cascade is k_cascade_mass_impulse (the impulse
+ * instance with the source in one row: a workgroup per table, source state
+ * and 16 source-axis bins; a FIFO of three times the plain response's per
+ * table, launches of whole tables under NUSI_OPT_RESPONSE_FIFO_KB, any budget
+ * the same bits); grids it does not fit and plans set to
+ * NUSI_CASCADE_WAVEFRONT / REG / LDS run the scalar k_cascade_mass.
+ * nusi_response_mass_shape is the call's size check as a pure function
+ * (M = N + Nz - 1; *doubles, where not NULL, = n * 3 * M * 3 * N): NUSI_EPARAM
+ * when n * 3 * M exceeds 2^31 - 1; the call applies it.  _host: host arrays,
+ * synchronous.  nusi_response_mass: the same for an object's point.
+ *
+ * nusi_plan_response_compose: Qc compositions of ntab triples of rows of any
+ * length X (X = M * 3 * N for G3 / G3_fla, X = M * C for a folded R3),
+ *     out[t][c][x] = (kappa[t][c][0] * A[t][0][x] + kappa[t][c][1] * A[t][1][x])
+ *                    + kappa[t][c][2] * A[t][2][x],
+ * products and sums rounded separately, no fma.  d_A [ntab][3][X] and d_out
+ * [ntab][Qc][X] are DEVICE pointers; kappa [ntab][Qc][3] is a host array,
+ * copied; every entry finite and >= 0 (else NUSI_EPARAM); it need not sum to
+ * 1.  With Qc = 1 the result is an ordinary stack of ntab response matrices
+ * that every call taking G, G_fla or R takes unchanged.
+ *   - +0.0 entries stay +0.0 (a sum of non-negative multiples of +0.0).
+ *   - With some kappa_k = 0 the result may carry the negative entries above:
+ *     the non-negativity that the fold's bound and the detector calls assume
+ *     then holds only up to them.  With every kappa_k > 0 of ordinary size it
+ *     holds (the entry's k = j partner outweighs it by ~ 1 / m_kj).
+ * The call is ordered on `stream` like nusi_plan_response_apply.
+ *
+ * nusi_mixing: the |U_fk|^2 of an ordering, U2[3 f + k] (the matrix the
+ * finalise and the couplings u_k = U2[3 flav + k] use).
+ * nusi_mass_fractions: the share of a source of flavour composition phi =
+ * (phi_e, phi_mu, phi_tau) emitted into mass state k,
+ *     kappa_k = ((phi_e U2[0][k] + phi_mu U2[1][k]) + phi_tau U2[2][k])
+ *               / ((phi_e + phi_mu) + phi_tau);
+ * pure functions, no plan and no device.  NUSI_EPARAM for a negative or
+ * non-finite phi, or when all phi are zero.  Equal thirds give kappa = 1/3 to
+ * rounding, and composing G3 with it gives G to rounding.
+ * nusi_plan_step_constants: the grid's step_c [Nz] and step_s [Nz] (either
+ * may be NULL; index 0 unused), which a host evaluation of the definition
+ * above needs (nusiprop_amd/response.py cascade_host). */
+int nusi_mixing(int normal_ordering, double *U2 /* [9] */);
+int nusi_mass_fractions(int normal_ordering, const double *phi /* [3] */, double *kappa /* [3] */);
+int nusi_response_mass_shape(int N, int Nz, int n, long long *doubles /* or NULL */);
+int nusi_plan_step_constants(const nusi_plan *plan, double *step_c /* [Nz] */, double *step_s /* [Nz] */);
+int nusi_plan_response_mass(nusi_plan *plan, const nusi_params *pts, int n, const double *w /* [Nz] or NULL */,
+                            double *d_G3, double *d_G3_fla, void *stream);
+int nusi_plan_response_mass_host(nusi_plan *plan, const nusi_params *pts, int n, const double *w, double *G3,
+                                 double *G3_fla);
+int nusi_plan_response_compose(nusi_plan *plan, const double *d_A, int ntab, long long X,
+                               const double *kappa /* [ntab][Qc][3] */, int Qc, double *d_out, void *stream);
+int nusi_plan_response_compose_host(nusi_plan *plan, const double *A, int ntab, long long X, const double *kappa, int Qc,
+                                    double *out);
 /* The detector of a plan (no reference counterpart): folding fluxes and response matrices into expected event counts
  * per reconstructed-energy bin, on the device.
  * nusi_plan_set_detector registers D [C][3][N] and a background B [C] (NULL = 0): D[c][f][b] is the expected number

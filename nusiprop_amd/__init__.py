@@ -9,6 +9,7 @@ from ._lib import (NusiError, NusiParams, SOURCE_DSNB, SOURCE_POWER_LAW, SOURCE_
 from . import detector, response, sources  # noqa: F401
 from .plan import Plan, unpack_alpha  # noqa: F401
 from .pyprop import pyprop  # noqa: F401
+from .sources import mixing  # noqa: F401
 
-__all__ = ["pyprop", "Plan", "unpack_alpha", "NusiError", "NusiParams", "make_params", "load", "sources", "response", "detector",
+__all__ = ["pyprop", "Plan", "mixing", "unpack_alpha", "NusiError", "NusiParams", "make_params", "load", "sources", "response", "detector",
            "SOURCE_DSNB", "SOURCE_POWER_LAW", "SOURCE_TABULATED"]

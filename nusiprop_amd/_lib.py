@@ -73,6 +73,9 @@ EXPORTS = [
     "nusi_plan_source_axis", "nusi_plan_set_source", "nusi_source_axis", "nusi_set_source",
     "nusi_plan_response", "nusi_plan_response_host", "nusi_plan_response_apply", "nusi_plan_response_apply_host",
     "nusi_response",
+    "nusi_mixing", "nusi_mass_fractions", "nusi_response_mass_shape", "nusi_plan_step_constants",
+    "nusi_plan_response_mass", "nusi_plan_response_mass_host", "nusi_plan_response_compose",
+    "nusi_plan_response_compose_host", "nusi_response_mass",
     "nusi_plan_set_detector", "nusi_plan_detector_bins", "nusi_plan_fold_flux", "nusi_plan_fold_flux_host",
     "nusi_plan_response_fold", "nusi_plan_response_fold_host", "nusi_plan_response_events",
     "nusi_plan_response_events_host", "nusi_plan_response_profile", "nusi_plan_response_profile_host",
@@ -171,6 +174,15 @@ def load():
         "nusi_plan_response_apply": (i, [vp, vp, i, dp, i, dp, vp, vp]),
         "nusi_plan_response_apply_host": (i, [vp, dp, i, dp, i, dp, dp]),
         "nusi_response": (i, [vp, dp, dp, dp]),
+        "nusi_mixing": (i, [i, dp]),
+        "nusi_mass_fractions": (i, [i, dp, dp]),
+        "nusi_response_mass_shape": (i, [i, i, i, ctypes.POINTER(ctypes.c_longlong)]),
+        "nusi_plan_step_constants": (i, [vp, dp, dp]),
+        "nusi_plan_response_mass": (i, [vp, pp, i, dp, vp, vp, vp]),
+        "nusi_plan_response_mass_host": (i, [vp, pp, i, dp, dp, dp]),
+        "nusi_plan_response_compose": (i, [vp, vp, i, ctypes.c_longlong, dp, i, vp, vp]),
+        "nusi_plan_response_compose_host": (i, [vp, dp, i, ctypes.c_longlong, dp, i, dp]),
+        "nusi_response_mass": (i, [vp, dp, dp, dp]),
         "nusi_plan_set_detector": (i, [vp, i, dp, dp]),
         "nusi_plan_detector_bins": (i, [vp]),
         "nusi_plan_fold_flux": (i, [vp, vp, i, vp, vp]),

@@ -460,6 +460,11 @@ struct nusi_plan {
     std::vector<double> h_app;
     hipEvent_t ev_app = nullptr;    // end of the latest apply (the next one reuses d_app / h_app)
     bool app_ran = false;
+    double* d_kap = nullptr;        // compose: the mass fractions kappa [ntab][Qc][3]
+    size_t kap_doubles = 0;
+    std::vector<double> h_kap;
+    hipEvent_t ev_cmp = nullptr;    // end of the latest compose (the next one reuses d_kap / h_kap)
+    bool cmp_ran = false;
     // the detector (nusi_plan_set_detector) and its calls (fold, events)
     int det_C = 0;                  // reconstructed bins; 0 = no detector
     double* d_det = nullptr;        // Dt [3 N][detector_ld(C)] (K-major, zero-padded columns), then the background [C]
@@ -939,6 +944,8 @@ void nusi_plan_destroy(nusi_plan* pl)
     if (pl->h_smap) hipHostFree(pl->h_smap);
     hipFree(pl->d_fh);
     if (pl->ev_app) hipEventDestroy(pl->ev_app);
+    if (pl->ev_cmp) hipEventDestroy(pl->ev_cmp);
+    hipFree(pl->d_kap);
     hipFree(pl->d_rw);
     hipFree(pl->d_rslots);
     hipFree(pl->d_rpts);
@@ -1183,9 +1190,10 @@ int nusi_plan_set_source(nusi_plan* pl, int slot, const double* S, const double*
 // nusi_plan_response's part of a call (plan_run): the redshift weights (validated; NULL = get_SFR)
 struct ResponseCall {
     const double* w;
+    bool mass;   // nusi_plan_response_mass: the response resolved by the source's mass state, G3[p][j][n][3][N]
 };
 static int response_prepare(nusi_plan* pl, const ResponseCall& rc, int n, hipStream_t s);
-static int response_cascade(nusi_plan* pl, int n, bool all_nr, double* d_G, double* d_G_fla, hipStream_t s);
+static int response_cascade(nusi_plan* pl, int n, bool all_nr, bool mass, double* d_G, double* d_G_fla, hipStream_t s);
 
 // One call of a plan: Stage A for the points' distinct tables (deduplication, batches, every NUSI_OPT_*), then the
 // cascade -- the points' own sources into d_flux / d_fla (nusi_plan_evolve; rc == nullptr), or the impulse cascade
@@ -1457,7 +1465,7 @@ static int plan_run(nusi_plan* pl, const nusi_params* pts, int n, double* d_flux
     if (bs && any_tab) HIPCHECK(nusi::launch_source_tab(pl->gd, pl->d_pts, n, pl->d_slots, pl->d_src, s));
     const char* gb_name = nullptr;
     if (rc) {
-        if (int r = response_cascade(pl, n, all_nr, d_flux, d_fla, s)) return r;
+        if (int r = response_cascade(pl, n, all_nr, rc->mass, d_flux, d_fla, s)) return r;
     } else if (bs) {
         const int Pk[3] = {16, 2, 1};
         static const char* const names[8] = {"", "k_cascade_bs_gamma", "k_cascade_bs_pairs", "k_cascade_bs_gamma + pairs",
@@ -1509,10 +1517,11 @@ static bool response_impulse(const nusi_plan* pl)
     const int kind = pl->cascade_kind == NUSI_CASCADE_AUTO ? NUSI_CASCADE_MFMA : pl->cascade_kind;
     return kind == NUSI_CASCADE_MFMA && nusi::cascade_impulse_fits(pl->gd);
 }
-// tables per launch of the impulse cascade: whole tables whose FIFOs fit the budget (at least one)
-static int response_chunk(const nusi_plan* pl, int n)
+// tables per launch of the impulse cascade: whole tables whose FIFOs fit the budget (at least one); the mass-resolved
+// cascade's table has three times the workgroups, hence three times the FIFO
+static int response_chunk(const nusi_plan* pl, int n, bool mass)
 {
-    const size_t per = sizeof(double) * nusi::cascade_impulse_scratch_doubles(pl->gd);
+    const size_t per = sizeof(double) * nusi::cascade_impulse_scratch_doubles(pl->gd) * (mass ? 3 : 1);
     const size_t budget = pl->response_fifo_kb > 0 ? (size_t)pl->response_fifo_kb << 10 : kResponseFifoBytes;
     return (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / per));
 }
@@ -1522,12 +1531,15 @@ static int response_prepare(nusi_plan* pl, const ResponseCall& rc, int n, hipStr
 {
     const HostGrid& G = pl->grid;
     const nusi::GridDev& g = pl->gd;
-    if ((long long)n * (G.T + 1) > (long long)INT_MAX) return fail(NUSI_EPARAM, "response: points x source-axis bins exceed 2^31 - 1");
+    if (rc.mass) {
+        if (int r = nusi_response_mass_shape(G.N, G.Nz, n, nullptr)) return r;
+    } else if ((long long)n * (G.T + 1) > (long long)INT_MAX)
+        return fail(NUSI_EPARAM, "response: points x source-axis bins exceed 2^31 - 1");
     pl->h_rw.assign(rc.w ? rc.w : G.sfr.data(), (rc.w ? rc.w : G.sfr.data()) + G.Nz);
     if (response_impulse(pl)) {
         if (!pl->d_rw) HIPCHECK(hipMalloc(&pl->d_rw, sizeof(double) * G.Nz));
         if (g.Nz - 1 > 6) {   // (one pass of 6 steps hands nothing on)
-            const size_t fhd = nusi::cascade_impulse_scratch_doubles(g) * (size_t)response_chunk(pl, n);
+            const size_t fhd = nusi::cascade_impulse_scratch_doubles(g) * (rc.mass ? 3 : 1) * (size_t)response_chunk(pl, n, rc.mass);
             if (fhd > pl->fh_doubles) {
                 hipFree(pl->d_fh);
                 pl->d_fh = nullptr;
@@ -1553,19 +1565,47 @@ static int response_prepare(nusi_plan* pl, const ResponseCall& rc, int n, hipStr
     return NUSI_OK;
 }
 
-// The cascade of a response call: G[p][n][3][N] / G_fla (either may be NULL) of the call's n points.
-static int response_cascade(nusi_plan* pl, int n, bool all_nr, double* d_G, double* d_Gf, hipStream_t s)
+// The cascade of a response call: G[p][n][3][N] / G_fla (either may be NULL) of the call's n points; mass:
+// G3[p][j][n][3][N] / G3_fla, a matrix per source mass state j.
+static int response_cascade(nusi_plan* pl, int n, bool all_nr, bool mass, double* d_G, double* d_Gf, hipStream_t s)
 {
     const nusi::GridDev& g = pl->gd;
     const size_t N3 = (size_t)3 * g.N, M = (size_t)g.T + 1;
     if (response_impulse(pl)) {
         // column 0 (bin 0 is never read): zeros; the kernel writes the columns 1 .. T
         for (double* out : {d_G, d_Gf})
-            if (out) HIPCHECK(hipMemset2DAsync(out, sizeof(double) * M * N3, 0, sizeof(double) * N3, (size_t)n, s));
-        const int chunk = response_chunk(pl, n);
-        for (int p0 = 0; p0 < n; p0 += chunk)   // whole tables under the FIFO budget, one after the other on s
+            if (out) HIPCHECK(hipMemset2DAsync(out, sizeof(double) * M * N3, 0, sizeof(double) * N3, (size_t)n * (mass ? 3 : 1), s));
+        const int chunk = response_chunk(pl, n, mass);
+        for (int p0 = 0; p0 < n; p0 += chunk) {   // whole tables under the FIFO budget, one after the other on s
+            if (mass)
+                HIPCHECK(nusi::launch_cascade_mass_impulse(g, pl->d_pts, p0, std::min(chunk, n - p0), pl->d_rw, pl->tabs,
+                                                           pl->d_fh, d_G, d_Gf, s, all_nr));
+            else
             HIPCHECK(nusi::launch_cascade_impulse(g, pl->d_pts, p0, std::min(chunk, n - p0), pl->d_rw, pl->tabs, pl->d_fh,
                                                   d_G, d_Gf, s, all_nr));
+        }
+        return NUSI_OK;
+    }
+    if (mass) {
+        // k_cascade_mass on temporary points: column c = (p 3 + j) M + n is point p on the private slot n with the
+        // whole unit source (norm = 3: no third) in row j, which the kernel takes from the column's index
+        std::vector<nusi::Point> tmp;
+        const size_t ncol = (size_t)n * 3 * M;
+        for (size_t c0 = 0; c0 < ncol; c0 += kResponseChunk) {
+            const size_t cnt = std::min<size_t>(kResponseChunk, ncol - c0);
+            tmp.resize(cnt);
+            for (size_t c = 0; c < cnt; ++c) {
+                const size_t p = (c0 + c) / (3 * M), m = (c0 + c) % M;
+                tmp[c] = pl->h_pts[p];
+                tmp[c].source = NUSI_SOURCE_TABULATED + (int)m;
+                tmp[c].norm = tmp[c].norm_total = 3.0;
+            }
+            HIPCHECK(hipMemcpyAsync(pl->d_rpts, tmp.data(), sizeof(nusi::Point) * cnt, hipMemcpyHostToDevice, s));
+            HIPCHECK(hipStreamSynchronize(s));   // (tmp is reused; the slow path)
+            HIPCHECK(nusi::launch_cascade_mass_exact(g, pl->d_rpts, (int)cnt, pl->tabs, pl->d_rslots,
+                                                     d_G ? d_G + c0 * N3 : pl->d_rscr, d_Gf ? d_Gf + c0 * N3 : pl->d_rscr,
+                                                     (long long)c0, s));
+        }
         return NUSI_OK;
     }
     // the unchanged scalar k_cascade on temporary points: column c = p M + n is point p on the private slot n
@@ -1589,6 +1629,7 @@ static int response_cascade(nusi_plan* pl, int n, bool all_nr, double* d_G, doub
     return NUSI_OK;
 }
 
+static int no_plan();
 static int check_weights(const nusi_plan* pl, const double* w)
 {
     if (w)
@@ -1602,8 +1643,141 @@ int nusi_plan_response(nusi_plan* pl, const nusi_params* pts, int n, const doubl
 {
     if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
     if (int r = check_weights(pl, w)) return r;
-    const ResponseCall rc{w};
+    const ResponseCall rc{w, false};
     return plan_run(pl, pts, n, d_G, d_G_fla, stream, &rc);
+}
+
+// ---------------------------------------------------------------------------
+// The mass-resolved response and the source's flavour composition (include/nusi.h)
+// ---------------------------------------------------------------------------
+int nusi_mixing(int normal_ordering, double* U2)
+{
+    if (!U2) return fail(NUSI_EPARAM, "mixing: U2 must not be NULL");
+    pmns_sq(normal_ordering != 0, U2);
+    return NUSI_OK;
+}
+
+int nusi_mass_fractions(int normal_ordering, const double* phi, double* kappa)
+{
+    if (!phi || !kappa) return fail(NUSI_EPARAM, "mass fractions: phi and kappa must not be NULL");
+    for (int f = 0; f < 3; ++f)
+        if (!(phi[f] >= 0.0) || !std::isfinite(phi[f])) return fail(NUSI_EPARAM, "mass fractions: a flavour share is negative or not finite");
+    const double tot = (phi[0] + phi[1]) + phi[2];
+    if (!(tot > 0.0) || !std::isfinite(tot)) return fail(NUSI_EPARAM, "mass fractions: the flavour shares are all zero (or their sum overflows)");
+    double U2[9];
+    pmns_sq(normal_ordering != 0, U2);
+    for (int k = 0; k < 3; ++k) kappa[k] = ((phi[0] * U2[k] + phi[1] * U2[3 + k]) + phi[2] * U2[6 + k]) / tot;
+    return NUSI_OK;
+}
+
+int nusi_response_mass_shape(int N, int Nz, int n, long long* doubles)
+{
+    if (N < 1 || Nz < 2 || n < 1) return fail(NUSI_EPARAM, "response mass: need N >= 1, Nz >= 2 and n >= 1");
+    const long long M = (long long)N + Nz - 1;
+    if ((long long)n * 3 * M > (long long)INT_MAX)
+        return fail(NUSI_EPARAM, "response mass: points x 3 x source-axis bins exceed 2^31 - 1");
+    if (doubles) *doubles = (long long)n * 3 * M * 3 * N;
+    return NUSI_OK;
+}
+
+int nusi_plan_step_constants(const nusi_plan* pl, double* step_c, double* step_s)
+{
+    if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
+    const HostGrid& G = pl->grid;
+    if (step_c) memcpy(step_c, G.step_c.data(), sizeof(double) * G.Nz);
+    if (step_s) memcpy(step_s, G.step_s.data(), sizeof(double) * G.Nz);
+    return NUSI_OK;
+}
+
+int nusi_plan_response_mass(nusi_plan* pl, const nusi_params* pts, int n, const double* w, double* d_G3, double* d_G3_fla,
+                            void* stream)
+{
+    if (!pl) return fail(NUSI_EPARAM, "plan is NULL");
+    if (int r = check_weights(pl, w)) return r;
+    const ResponseCall rc{w, true};
+    return plan_run(pl, pts, n, d_G3, d_G3_fla, stream, &rc);
+}
+
+int nusi_plan_response_mass_host(nusi_plan* pl, const nusi_params* pts, int n, const double* w, double* G3, double* G3_fla)
+{
+    if (!pl) return no_plan();
+    if (n < 1 || n > pl->max_points) return fail(NUSI_EPARAM, "number of points outside [1, max_points]");
+    if (int r = nusi_response_mass_shape(pl->grid.N, pl->grid.Nz, n, nullptr)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    const size_t nb = sizeof(double) * (size_t)n * 3 * (pl->grid.T + 1) * 3 * pl->grid.N;
+    double* d[2] = {nullptr, nullptr};
+    double* h[2] = {G3, G3_fla};
+    int r = NUSI_OK;
+    for (int k = 0; k < 2 && !r; ++k)
+        if (h[k] && hipMalloc(&d[k], nb) != hipSuccess) r = fail(NUSI_EHIP, "response mass: no device memory for the result");
+    if (!r) r = nusi_plan_response_mass(pl, pts, n, w, d[0], d[1], nullptr);
+    if (!r && hipStreamSynchronize(pl->stream) != hipSuccess) r = fail(NUSI_EHIP, "response mass: the stream failed");
+    for (int k = 0; k < 2 && !r; ++k)
+        if (h[k] && hipMemcpy(h[k], d[k], nb, hipMemcpyDeviceToHost) != hipSuccess) r = fail(NUSI_EHIP, "response mass: copy to the host failed");
+    hipFree(d[0]);
+    hipFree(d[1]);
+    if (r) return r;
+    std::vector<int> wn(n);
+    r = nusi_plan_warnings(pl, wn.data(), n);
+    if (r) return r;
+    for (int v : wn)
+        if (v & nusi::kWarnSplineOOB) return fail(NUSI_EINTERP, "Error at interp: a phi-phi table lookup fell outside the node range");
+    return NUSI_OK;
+}
+
+// out[t][c][x] = (kappa[t][c][0] A[t][0][x] + kappa[t][c][1] A[t][1][x]) + kappa[t][c][2] A[t][2][x] (k_response_compose)
+static int compose_check(const nusi_plan* pl, const void* A, const void* out, int ntab, long long X, const double* kappa, int Qc)
+{
+    if (!pl) return no_plan();
+    if (!A || !out || !kappa) return fail(NUSI_EPARAM, "response compose: A, kappa and out must not be NULL");
+    if (ntab < 1 || Qc < 1 || X < 1) return fail(NUSI_EPARAM, "response compose: need ntab >= 1, Qc >= 1 and X >= 1");
+    if ((long long)ntab * ((X + 255) / 256) > (long long)INT_MAX) return fail(NUSI_EPARAM, "response compose: too many elements (ntab X / 256 >= 2^31)");
+    if ((long long)ntab * Qc > (long long)INT_MAX / 3) return fail(NUSI_EPARAM, "response compose: too many compositions (3 ntab Qc >= 2^31)");
+    for (size_t e = 0; e < (size_t)ntab * Qc * 3; ++e)
+        if (!(kappa[e] >= 0.0) || !std::isfinite(kappa[e])) return fail(NUSI_EPARAM, "response compose: a mass fraction is negative or not finite");
+    return NUSI_OK;
+}
+
+int nusi_plan_response_compose(nusi_plan* pl, const double* d_A, int ntab, long long X, const double* kappa, int Qc,
+                               double* d_out, void* stream)
+{
+    if (int r = compose_check(pl, d_A, d_out, ntab, X, kappa, Qc)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    if (!pl->ev_cmp) HIPCHECK(hipEventCreateWithFlags(&pl->ev_cmp, hipEventDisableTiming));
+    if (pl->cmp_ran) HIPCHECK(hipEventSynchronize(pl->ev_cmp));   // d_kap / h_kap are reused
+    const size_t need = (size_t)ntab * Qc * 3;
+    if (pl->kap_doubles < need) {
+        hipFree(pl->d_kap);
+        pl->d_kap = nullptr;
+        pl->kap_doubles = 0;
+        HIPCHECK(hipMalloc(&pl->d_kap, sizeof(double) * need));
+        pl->kap_doubles = need;
+    }
+    pl->h_kap.assign(kappa, kappa + need);
+    HIPCHECK(hipMemcpyAsync(pl->d_kap, pl->h_kap.data(), sizeof(double) * need, hipMemcpyHostToDevice, s));
+    HIPCHECK(nusi::launch_response_compose(d_A, ntab, (size_t)X, pl->d_kap, Qc, d_out, s));
+    HIPCHECK(hipEventRecord(pl->ev_cmp, s));
+    pl->cmp_ran = true;
+    return NUSI_OK;
+}
+
+int nusi_plan_response_compose_host(nusi_plan* pl, const double* A, int ntab, long long X, const double* kappa, int Qc,
+                                    double* out)
+{
+    if (int r = compose_check(pl, A, out, ntab, X, kappa, Qc)) return r;
+    HIPCHECK(hipSetDevice(pl->device));
+    const size_t ab = sizeof(double) * (size_t)ntab * 3 * (size_t)X, ob = sizeof(double) * (size_t)ntab * Qc * (size_t)X;
+    double *dA = nullptr, *dO = nullptr;
+    int r = NUSI_OK;
+    if (hipMalloc(&dA, ab) != hipSuccess || hipMalloc(&dO, ob) != hipSuccess) r = fail(NUSI_EHIP, "response compose: no device memory");
+    if (!r && hipMemcpy(dA, A, ab, hipMemcpyHostToDevice) != hipSuccess) r = fail(NUSI_EHIP, "response compose: copy to the device failed");
+    if (!r) r = nusi_plan_response_compose(pl, dA, ntab, X, kappa, Qc, dO, nullptr);
+    if (!r && hipStreamSynchronize(pl->stream) != hipSuccess) r = fail(NUSI_EHIP, "response compose: the stream failed");
+    if (!r && hipMemcpy(out, dO, ob, hipMemcpyDeviceToHost) != hipSuccess) r = fail(NUSI_EHIP, "response compose: copy to the host failed");
+    hipFree(dA);
+    hipFree(dO);
+    return r;
 }
 
 int nusi_plan_response_host(nusi_plan* pl, const nusi_params* pts, int n, const double* w, double* G, double* G_fla)
@@ -3190,6 +3364,12 @@ int nusi_response(nusi_handle* h, const double* w, double* G, double* G_fla)
 {
     if (!h) return fail(NUSI_EPARAM, "object is NULL");
     return nusi_plan_response_host(h->plan, &h->p, 1, w, G, G_fla);
+}
+// ... and its mass-resolved response (nusi_plan_response_mass_host)
+int nusi_response_mass(nusi_handle* h, const double* w, double* G3, double* G3_fla)
+{
+    if (!h) return fail(NUSI_EPARAM, "object is NULL");
+    return nusi_plan_response_mass_host(h->plan, &h->p, 1, w, G3, G3_fla);
 }
 
 int nusi_check_energy_conservation(nusi_handle* h, double* out)

@@ -6,12 +6,16 @@
 //                         long grids (NUSI_CASCADE_AUTO / MFMA, every shape)
 //   k_cascade_bs_impulse  its impulse-source instance: 16 source-axis bins of a table per workgroup, the response
 //                         matrix of nusi_plan_response (both kernels include nusi_cascade_bs_body.inc)
+//   k_cascade_mass_impulse  ... with the unit source in one mass state per workgroup: the mass-resolved response of
+//                         nusi_plan_response_mass (the third kernel that includes the body)
 //   k_response_apply      spectra on resident response matrices (nusi_plan_response_apply)
+//   k_response_compose    a source's flavour composition on mass-resolved rows (nusi_plan_response_compose)
 //   k_source_dsnb         the DSNB source terms it reads
 //   k_source_tab          ... and the tabulated sources' (nusi_plan_set_source)
 //   k_cascade             the bit-exact scalar cascade, one wavefront per point, any N (NUSI_CASCADE_WAVEFRONT /
 //                         REG / LDS).  (The per-stage kernels of rounds 1-3 -- k_cascade_wf, _reg, _ws, _wsp, _gb --
 //                         are gone; DESIGN.md Appendix A keeps their measurements.)
+//   k_cascade_mass        its copy with the source per mass state (nusi_plan_response_mass's scalar fallback)
 #include <hip/hip_runtime.h>
 
 #include <utility>
@@ -238,6 +242,43 @@ NUSI_FN void cascade_solve_id(double f0, double f1, double f2, double add, doubl
     x0 = x0 - u01 * x1 - u02 * x2;
 }
 
+// cascade_solve and cascade_solve_id with the source per mass state (s0, s1, s2: the mass-resolved response of
+// nusi_plan_response_mass; include/nusi.h).  Everything after the right-hand sides is the text above.
+NUSI_FN void cascade_solve3(double f0, double f1, double f2, double add, double s0, double s1, double s2, double u0,
+                            double u1, double u2, double rz0, double rz1, double rz2, int pmb, double l10, double l20,
+                            double l21, double u01, double u02, double u12, double ru00, double ru11, double ru22,
+                            double& x0, double& x1, double& x2)
+{
+    const double v0 = (f0 + (s0 + u0 * add)) * rz0;
+    const double v1 = (f1 + (s1 + u1 * add)) * rz1;
+    const double v2 = (f2 + (s2 + u2 * add)) * rz2;
+    const int p0 = pmb & 3, p1 = (pmb >> 2) & 3, p2 = (pmb >> 4) & 3;
+    x0 = (p0 == 0) ? v0 : (p0 == 1) ? v1 : v2;
+    x1 = (p1 == 0) ? v0 : (p1 == 1) ? v1 : v2;
+    x2 = (p2 == 0) ? v0 : (p2 == 1) ? v1 : v2;
+    x1 = x1 - l10 * x0;
+    x2 = x2 - l20 * x0;
+    x2 = x2 - l21 * x1;
+    x2 = x2 * ru22;
+    x1 = (x1 - u12 * x2) * ru11;
+    x0 = (x0 - u01 * x1 - u02 * x2) * ru00;
+}
+NUSI_FN void cascade_solve3_id(double f0, double f1, double f2, double add, double s0, double s1, double s2, double u0,
+                               double u1, double u2, double rz0, double rz1, double rz2, double l10, double l20,
+                               double l21, double u01, double u02, double u12, double ru11, double ru22, double& x0,
+                               double& x1, double& x2)
+{
+    x0 = (f0 + (s0 + u0 * add)) * rz0;
+    x1 = (f1 + (s1 + u1 * add)) * rz1;
+    x2 = (f2 + (s2 + u2 * add)) * rz2;
+    x1 = x1 - l10 * x0;
+    x2 = x2 - l20 * x0;
+    x2 = x2 - l21 * x1;
+    x2 = x2 * ru22;
+    x1 = (x1 - u12 * x2) * ru11;
+    x0 = x0 - u01 * x1 - u02 * x2;
+}
+
 // The tabulated source term of bin b at step i (NUSI_SOURCE_TABULATED + slot, include/nusi.h): c = step_c[i],
 // w = the slot's redshift weight w[i] (get_SFR(z_i) where none was given), z = z[i], S = the slot's bin integral
 // S[b + i] -- the source-frame bin [E_b (1 + z_i), E_{b+1} (1 + z_i)] is source-axis bin b + i (the index-shift
@@ -335,6 +376,132 @@ __global__ __launch_bounds__(64) void k_cascade(GridDev g, const Point* __restri
                 const double v0 = (F0[b] + (src0 + u0 * add)) * pre[PR_RZ0 * 64 + l];
                 const double v1 = (F1[b] + (src0 + u1 * add)) * pre[PR_RZ1 * 64 + l];
                 const double v2 = (F2[b] + (src0 + u2 * add)) * pre[PR_RZ2 * 64 + l];
+                const int pmv = perm[l];
+                const int p0 = pmv & 3, p1 = (pmv >> 2) & 3, p2 = (pmv >> 4) & 3;
+                double x0 = (p0 == 0) ? v0 : (p0 == 1) ? v1 : v2;
+                double x1 = (p1 == 0) ? v0 : (p1 == 1) ? v1 : v2;
+                double x2 = (p2 == 0) ? v0 : (p2 == 1) ? v1 : v2;
+                x1 = x1 - pre[PR_L10 * 64 + l] * x0;
+                x2 = x2 - pre[PR_L20 * 64 + l] * x0;
+                x2 = x2 - pre[PR_L21 * 64 + l] * x1;
+                x2 = x2 * pre[PR_RU22 * 64 + l];
+                x1 = (x1 - pre[PR_U12 * 64 + l] * x2) * pre[PR_RU11 * 64 + l];
+                x0 = (x0 - pre[PR_U01 * 64 + l] * x1 - pre[PR_U02 * 64 + l] * x2) * pre[PR_RU00 * 64 + l];
+                if (lane == 0) { F0[b] = x0; F1[b] = x1; F2[b] = x2; }
+                px0 = x0; px1 = x1; px2 = x2;
+                if (nonres && b > 0) {
+                    const double Tb = (u0 * x0 + u1 * x1 + u2 * x2) * pre[PR_SDE * 64 + l];
+                    const int r = b + i - 1;                       // table column of bin b
+                    const double* col = Al + (size_t)r * (r - 1) / 2 + (i - 1);
+                    next_acc = accb_lds + col[b - 1] * Tb;
+                    for (int bp = lane; bp < b - 1; bp += 64) acc[bp] += col[bp] * Tb;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // finalise (nuSIprop.hpp:328-336)
+    for (int b = lane; b < N; b += 64) {
+        const double dE = g.Emax[b] - g.Emin[b];
+        const double f0 = F0[b] / dE, f1 = F1[b] / dE, f2 = F2[b] / dE;
+        double* fo = flux + (size_t)p * 3 * N;
+        double* fl = flux_fla + (size_t)p * 3 * N;
+        fo[b] = f0;
+        fo[N + b] = f1;
+        fo[2 * N + b] = f2;
+        for (int f = 0; f < 3; ++f) fl[f * N + b] = P.U2[3 * f + 0] * f0 + P.U2[3 * f + 1] * f1 + P.U2[3 * f + 2] * f2;
+    }
+}
+
+// k_cascade with the source per mass state: the scalar fallback of nusi_plan_response_mass.  A COPY of k_cascade's
+// text, not an include of it (k_cascade is the bit-exact yardstick of the test suite and its instructions stay where
+// they are); the differences are the three marked lines.  Workgroup c is column col0 + c of the call in the layout
+// [p][j][n]: its point record pts[c] is a tabulated point on the private unit-vector slot n with norm = 3 (the whole
+// unit source, no third), and the source goes into row j = ((col0 + c) / M) % 3 alone.
+__global__ __launch_bounds__(64) void k_cascade_mass(GridDev g, const Point* __restrict__ pts, TablesDev t,
+                                                     const double* __restrict__ slots, double* __restrict__ flux,
+                                                     double* __restrict__ flux_fla, long long col0, int M)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int N = g.N, Nz = g.Nz, T = g.T;
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int mj = (int)(((col0 + p) / M) % 3);   // (mass) the row that takes the source
+    const Point& P = pts[p];
+    double* F0 = lds;
+    double* F1 = lds + N;
+    double* F2 = lds + 2 * N;
+    double* acc = lds + 3 * N;
+    double* pre = lds + 4 * N;
+    int* perm = (int*)(pre + kPreFields * 64);
+    const double u0 = P.u[0], u1 = P.u[1], u2 = P.u[2];
+    const double uk[3] = {u0, u1, u2};
+    const double* __restrict__ Gt = t.G + (size_t)P.tslot * T;
+    const double* __restrict__ At = t.At + (size_t)P.tslot * T;
+    const double* __restrict__ Al = t.A + (size_t)P.tslot * g.PT;
+    const bool nonres = P.non_resonant;
+    const double* __restrict__ tS = slots + (size_t)(P.source - NUSI_SOURCE_TABULATED) * source_slot_doubles(T, Nz);
+    const double* __restrict__ tw = tS + T + 1;
+
+    for (int b = lane; b < N; b += 64) F0[b] = F1[b] = F2[b] = 0.0;
+
+    for (int i = Nz - 1; i > 0; --i) {
+        const double c = g.step_c[i], s = g.step_s[i], zi = g.z[i];
+        for (int b = lane; b < N; b += 64) acc[b] = 0.0;
+        double next_acc = 0.0;     // acc of the next (lower) bin, carried in registers
+        double racc = 0.0;         // resonant-only running sum (nuSIprop.hpp:261-278)
+        double px0 = 0.0, px1 = 0.0, px2 = 0.0;   // F[:, b+1] of this step
+        for (int base = ((N - 1) / 64) * 64; base >= 0; base -= 64) {
+            __syncthreads();
+            {   // ---- parallel: flux-independent quantities for bins base..base+63
+                const int b = base + lane;
+                if (b < N) {
+                    const double dEb = g.Emax[b] - g.Emin[b];
+                    const double Gw = s * Gt[b + i - 1], Aw = s * At[b + i - 1];
+                    double Zd[3], M[3][3];
+                    for (int k = 0; k < 3; ++k) Zd[k] = 1.0 + c * (Gw * uk[k] - Aw * (uk[k] * uk[k])) / dEb;
+                    for (int k = 0; k < 3; ++k)
+                        for (int l = 0; l < 3; ++l) M[k][l] = (k == l) ? 1.0 : (Aw * uk[k] * uk[l] / dEb) / Zd[k];
+                    int pm[3];
+                    lu3_factor(M, pm);
+                    const double src0 = tabulated_src(c, P.norm_total, tw[i], zi, tS[b + i]);
+                    pre[PR_RZ0 * 64 + lane] = 1.0 / Zd[0];
+                    pre[PR_RZ1 * 64 + lane] = 1.0 / Zd[1];
+                    pre[PR_RZ2 * 64 + lane] = 1.0 / Zd[2];
+                    pre[PR_SRC * 64 + lane] = src0;
+                    pre[PR_L10 * 64 + lane] = M[1][0];
+                    pre[PR_L20 * 64 + lane] = M[2][0];
+                    pre[PR_L21 * 64 + lane] = M[2][1];
+                    pre[PR_U01 * 64 + lane] = M[0][1];
+                    pre[PR_U02 * 64 + lane] = M[0][2];
+                    pre[PR_U12 * 64 + lane] = M[1][2];
+                    pre[PR_RU00 * 64 + lane] = 1.0 / M[0][0];
+                    pre[PR_RU11 * 64 + lane] = 1.0 / M[1][1];
+                    pre[PR_RU22 * 64 + lane] = 1.0 / M[2][2];
+                    pre[PR_SDE * 64 + lane] = nonres ? s / dEb : dEb;
+                    perm[lane] = pm[0] | (pm[1] << 2) | (pm[2] << 4);
+                }
+            }
+            __syncthreads();
+            const int top = (base + 63 < N - 1) ? base + 63 : N - 1;
+            for (int b = top; b >= base; --b) {
+                const int l = b - base;
+                const double accb_lds = (b > 0) ? acc[b - 1] : 0.0;   // for next_acc (before this bin's pushes)
+                const double src0 = pre[PR_SRC * 64 + l];
+                const double s0 = mj == 0 ? src0 : 0.0, s1 = mj == 1 ? src0 : 0.0, s2 = mj == 2 ? src0 : 0.0;   // (mass)
+                double add;   // c * (coupling of this bin to the bins above)
+                if (nonres) {
+                    add = c * next_acc;
+                } else {
+                    if (b != N - 1) {
+                        const double Sres = u0 * px0 + u1 * px1 + u2 * px2;
+                        const size_t rd = (size_t)(b + i) * (b + i - 1) / 2 + (b + i - 1);   // alpha(b+i-1, b+i)
+                        racc += Sres * (s * Al[rd]) / (g.Emax[b + 1] - g.Emin[b + 1]) / pre[PR_SDE * 64 + l];
+                    }
+                    add = c * racc * pre[PR_SDE * 64 + l];
+                }
+                const double v0 = (F0[b] + (s0 + u0 * add)) * pre[PR_RZ0 * 64 + l];   // (mass)
+                const double v1 = (F1[b] + (s1 + u1 * add)) * pre[PR_RZ1 * 64 + l];
+                const double v2 = (F2[b] + (s2 + u2 * add)) * pre[PR_RZ2 * 64 + l];
                 const int pmv = perm[l];
                 const int p0 = pmv & 3, p1 = (pmv >> 2) & 3, p2 = (pmv >> 4) & 3;
                 double x0 = (p0 == 0) ? v0 : (p0 == 1) ? v1 : v2;
@@ -563,7 +730,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_cascade_bs(GridDev g, const Point* __restrict__ pts, const int* __restrict__ gidx, const int2* __restrict__ grp,
                   TablesDev t, double* __restrict__ fh, double* __restrict__ flux, double* __restrict__ flux_fla)
 {
-    constexpr bool kImp = false;
+    constexpr bool kImp = false, kMass = false;
     const ImpulseArgs ia{};
 #include "nusi_cascade_bs_body.inc"
 }
@@ -575,7 +742,22 @@ void k_cascade_bs_impulse(GridDev g, const Point* __restrict__ pts, ImpulseArgs 
                           double* __restrict__ flux, double* __restrict__ flux_fla)
 {
     constexpr int NJ = 6, P = 16, SPL = 1, RT = 2, CW = 2;
-    constexpr bool kImp = true;
+    constexpr bool kImp = true, kMass = false;
+    const int* const gidx = nullptr;
+    const int2* const grp = nullptr;
+#include "nusi_cascade_bs_body.inc"
+}
+// The mass-resolved impulse instance (nusi_plan_response_mass): k_cascade_bs_impulse with the unit source in one mass
+// state per workgroup (kMass in the body): three times its workgroups, (table, source state j, bin group) decoded from
+// blockIdx.x and ia.ngrp.  flux = G3, flux_fla = G3_fla, [p][j][n][3][N].  (Its name keeps clear of the patterns that
+// count the k_cascade_bs and k_cascade_bs_impulse instances in the resource tests.)
+template <bool kNR>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_cascade_mass_impulse(GridDev g, const Point* __restrict__ pts, ImpulseArgs ia, TablesDev t, double* __restrict__ fh,
+                            double* __restrict__ flux, double* __restrict__ flux_fla)
+{
+    constexpr int NJ = 6, P = 16, SPL = 1, RT = 2, CW = 2;
+    constexpr bool kImp = true, kMass = true;
     const int* const gidx = nullptr;
     const int2* const grp = nullptr;
 #include "nusi_cascade_bs_body.inc"
@@ -688,6 +870,26 @@ hipError_t launch_cascade_impulse(const GridDev& g, const Point* pts, int p0, in
     return hipGetLastError();
 }
 
+// The mass-resolved impulse cascade: 3 cascade_impulse_groups workgroups and 3 cascade_impulse_scratch_doubles of
+// FIFO per table of the launch
+hipError_t launch_cascade_mass_impulse(const GridDev& g, const Point* pts, int p0, int npts, const double* w, TablesDev t,
+                                       double* fh, double* G3, double* G3_fla, hipStream_t s, bool all_nr)
+{
+    if (npts <= 0) return hipSuccess;
+    if (!cascade_impulse_fits(g)) return hipErrorInvalidValue;
+    t_cascade_kernel = "k_cascade_mass_impulse";
+    const int ngrp = cascade_impulse_groups(g), nthr = 64 * (bs_push_waves(g, 2) + 2 + 1);
+    if ((long long)npts * 3 * ngrp > 2147483647LL) return hipErrorInvalidValue;
+    const ImpulseArgs ia{w, p0, ngrp};
+    if (all_nr)
+        hipLaunchKernelGGL((k_cascade_mass_impulse<true>), dim3(npts * 3 * ngrp), dim3(nthr), imp_lds(g), s, g, pts, ia, t,
+                           fh, G3, G3_fla);
+    else
+        hipLaunchKernelGGL((k_cascade_mass_impulse<false>), dim3(npts * 3 * ngrp), dim3(nthr), imp_lds(g), s, g, pts, ia, t,
+                           fh, G3, G3_fla);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // k_response_apply: spectra on resident response matrices (nusi_plan_response_apply),
 //     out[t][q][r] = scale[q] * acc,  acc = 0.0;  for n = 1 .. M-1 ascending: acc = acc + G[t][n][r] * S[q][n]
@@ -734,6 +936,53 @@ hipError_t launch_response_apply(const GridDev& g, const double* G, int ntab, co
     const int nrb = (3 * g.N + kApplyThreads - 1) / kApplyThreads;
     hipLaunchKernelGGL(k_response_apply, dim3((unsigned)ntab * nrb, (Q + kApplyQ - 1) / kApplyQ), dim3(kApplyThreads), 0, s,
                        G, S, scale, out, g.T + 1, g.N, Q, nrb);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_response_compose: a source's flavour composition on mass-resolved response matrices (nusi_plan_response_compose),
+//     out[t][c][x] = (kappa[t][c][0] A[t][0][x] + kappa[t][c][1] A[t][1][x]) + kappa[t][c][2] A[t][2][x]
+// (products and sums rounded separately).  Bandwidth-bound and elementwise: lanes on x, a workgroup reads its three
+// values of A once and writes the Qc compositions of them; kappa[t][c][:] is wave-uniform (scalar loads).
+// ---------------------------------------------------------------------------
+constexpr int kComposeThreads = 256;
+__global__ __launch_bounds__(kComposeThreads) void k_response_compose(const double* __restrict__ A,
+                                                                      const double* __restrict__ kappa,
+                                                                      double* __restrict__ out, size_t X, int Qc,
+                                                                      unsigned nxb)
+{
+#pragma clang fp contract(off)
+    const size_t t = blockIdx.x / nxb, xb = blockIdx.x - t * nxb;
+    const size_t x = xb * kComposeThreads + threadIdx.x;
+    if (x >= X) return;
+    const double* __restrict__ At = A + t * 3 * X + x;
+    const double a0 = At[0], a1 = At[X], a2 = At[2 * X];
+    const double* __restrict__ kt = kappa + t * (size_t)Qc * 3;
+    double* __restrict__ ot = out + t * (size_t)Qc * X + x;
+    for (int c = 0; c < Qc; ++c) {
+        const double k0 = kt[3 * c], k1 = kt[3 * c + 1], k2 = kt[3 * c + 2];
+        ot[(size_t)c * X] = (k0 * a0 + k1 * a1) + k2 * a2;
+    }
+}
+// (the caller has checked ntab x ceil(X / 256) < 2^31)
+hipError_t launch_response_compose(const double* A, int ntab, size_t X, const double* kappa, int Qc, double* out,
+                                   hipStream_t s)
+{
+    if (ntab <= 0 || Qc <= 0 || X == 0) return hipSuccess;
+    const size_t nxb = (X + kComposeThreads - 1) / kComposeThreads;
+    hipLaunchKernelGGL(k_response_compose, dim3((unsigned)(nxb * ntab)), dim3(kComposeThreads), 0, s, A, kappa, out, X, Qc,
+                       (unsigned)nxb);
+    return hipGetLastError();
+}
+
+// the scalar cascade with the source per mass state (k_cascade_mass): the columns col0 .. col0 + npts - 1 of a
+// mass-resolved response, M = T + 1
+hipError_t launch_cascade_mass_exact(const GridDev& g, const Point* pts, int npts, TablesDev t, const double* slots,
+                                     double* flux, double* flux_fla, long long col0, hipStream_t s)
+{
+    t_cascade_kernel = "k_cascade_mass";
+    const size_t lds = cascade_lds_bytes(g.N);
+    hipLaunchKernelGGL(k_cascade_mass, dim3(npts), dim3(64), lds, s, g, pts, t, slots, flux, flux_fla, col0, g.T + 1);
     return hipGetLastError();
 }
 

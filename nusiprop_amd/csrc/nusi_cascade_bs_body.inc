@@ -1,9 +1,12 @@
 // The body of k_cascade_bs and of k_cascade_bs_impulse (nusi_cascade.hip includes it in both: a call to a shared
 // __device__ body, inlined, did not compile to the ordinary instances' code).  In scope: the instance's NJ, P, SPL, RT,
-// CW, kNR and kImp, the kernel's arguments g, pts, gidx, grp, t, fh, flux, flux_fla, and ia (ImpulseArgs).
+// CW, kNR, kImp and kMass, the kernel's arguments g, pts, gidx, grp, t, fh, flux, flux_fla, and ia (ImpulseArgs).
 // kImp (the impulse-source instance): column p of the workgroup carries the unit source S = e_n, n = n0 + p, with
 // norm = 1: its source term at (step i, bin b) is sig[i] = tabulated_src(step_c[i], 1, w[i], z[i], 1) where b + i = n
 // and 0 elsewhere -- no pw[] rows in LDS, no srcb / Src traffic, no pow() prologue; flux / flux_fla may be nullptr.
+// kMass (k_cascade_mass_impulse, with kImp): the workgroup's unit sources go into ONE mass state mj, whole (norm = 3:
+// no third), and the other two rows get 0.0 -- workgroup k of the launch is (table k / (3 ngrp), state (k / ngrp) % 3,
+// bin group k % ngrp), and its columns are written at "point" ((p 3 + mj) (T + 1) + n), the layout G3[p][j][n][3][N].
     extern __shared__ __attribute__((aligned(16))) double lds[];
     using Cfg = BsCfg<NJ, P, SPL, RT, CW>;
     // the power-law sources: formed on the record wave (into srcb, a block ahead) where that is one round of 64 (one
@@ -23,7 +26,9 @@
     // kImp: the workgroup's first source-axis bin n0; its table's point and its columns n0 .. min(T, n0 + P - 1)
     const int ing = kImp ? ia.ngrp : 1;
     const int in0 = kImp ? 1 + P * ((int)blockIdx.x % ing) : 0;
-    const int2 gr = kImp ? make_int2(ia.p0 + (int)blockIdx.x / ing, min(P, T + 1 - in0))
+    const int itj = (int)blockIdx.x / ing;    // kMass: 3 (table of the launch) + source state
+    const int mj = kMass ? itj % 3 : 0;       // kMass: the mass state that takes the source (wave-uniform)
+    const int2 gr = kImp ? make_int2(ia.p0 + (kMass ? itj / 3 : itj), min(P, T + 1 - in0))
                          : grp ? grp[blockIdx.x] : make_int2((int)blockIdx.x, 1);
     const int R = gr.y;                                   // points of this workgroup (<= P), one table
     auto pidx = [&](int p) {                              // (gidx == nullptr: point blockIdx.x; kImp: the table's point)
@@ -79,11 +84,12 @@
             for (int p = tid; p < P; p += nthr) {   // no source factors, not the DSNB; the column's output index
                 pinf[p] = pinf[P + p] = 0.0;
                 pinf[2 * P + p] = 1.0;
-                pinf[3 * P + p] = (double)(gr.x * (T + 1) + in0 + p);
+                pinf[3 * P + p] = (double)((kMass ? gr.x * 3 + mj : gr.x) * (T + 1) + in0 + p);
 #pragma unroll
                 for (int f = 0; f < 9; ++f) pinf[(4 + f) * P + p] = P0.U2[f];
             }
-            for (int i = tid; i < Nz; i += nthr) sig[i] = i ? tabulated_src(g.step_c[i], 1.0, ia.w[i], g.z[i], 1.0) : 0.0;
+            for (int i = tid; i < Nz; i += nthr)
+                sig[i] = i ? tabulated_src(g.step_c[i], kMass ? 3.0 : 1.0, ia.w[i], g.z[i], 1.0) : 0.0;
         } else {
         for (int p = tid; p < P; p += nthr) {   // the points' source factors (src_factors), kind and index
             const int pid = p < R ? pidx(p) : 0;
@@ -212,6 +218,16 @@
                                            b == N - 1);
                     }
                     double x0, x1, x2;
+                    if constexpr (kMass) {   // the source per row: the unit source in row mj, 0.0 in the others
+                        const double s0 = mj == 0 ? in.src : 0.0, s1 = mj == 1 ? in.src : 0.0, s2 = mj == 2 ? in.src : 0.0;
+                        if (__all(in.pmb == kIdPerm))
+                            cascade_solve3_id(f0, f1, f2, add, s0, s1, s2, u0, u1, u2, in.rz0, in.rz1, in.rz2, in.l10,
+                                              in.l20, in.l21, in.u01, in.u02, in.u12, in.ru11, in.ru22, x0, x1, x2);
+                        else
+                            cascade_solve3(f0, f1, f2, add, s0, s1, s2, u0, u1, u2, in.rz0, in.rz1, in.rz2, in.pmb,
+                                           in.l10, in.l20, in.l21, in.u01, in.u02, in.u12, in.ru00, in.ru11, in.ru22, x0,
+                                           x1, x2);
+                    } else
                     if (__all(in.pmb == kIdPerm))   // (every active lane: no row exchange -- always, in practice)
                         cascade_solve_id(f0, f1, f2, add, in.src, u0, u1, u2, in.rz0, in.rz1, in.rz2, in.l10, in.l20,
                                          in.l21, in.u01, in.u02, in.u12, in.ru11, in.ru22, x0, x1, x2);

@@ -256,6 +256,20 @@ hipError_t launch_source_tab(const GridDev& g, const Point* pts, int npts, const
 hipError_t launch_cascade_exact(const GridDev& g, const Point* pts, int npts, TablesDev t, const double* slots,
                                 double* flux, double* flux_fla, hipStream_t s);
 
+// The mass-resolved response (nusi_plan_response_mass; include/nusi.h): G3[p][j][n][3][N], the response to a unit source
+// in mass state j alone.  k_cascade_mass_impulse is the impulse cascade with the source in one row (three times its
+// workgroups and FIFO per table; p0, npts, w, fh as launch_cascade_impulse); k_cascade_mass is the scalar cascade with
+// the source per row, on the columns col0 .. col0 + npts - 1 of the call in the order [p][j][n] (pts[c]: the column's
+// tabulated point record on the unit-vector slot n, norm = 3).
+hipError_t launch_cascade_mass_impulse(const GridDev& g, const Point* pts, int p0, int npts, const double* w, TablesDev t,
+                                       double* fh, double* G3, double* G3_fla, hipStream_t s, bool all_nr);
+hipError_t launch_cascade_mass_exact(const GridDev& g, const Point* pts, int npts, TablesDev t, const double* slots,
+                                     double* flux, double* flux_fla, long long col0, hipStream_t s);
+// k_response_compose: out[t][c][x] = (kappa[t][c][0] A[t][0][x] + kappa[t][c][1] A[t][1][x]) + kappa[t][c][2] A[t][2][x],
+// no fma; A [ntab][3][X], kappa [ntab][Qc][3] and out [ntab][Qc][X] in device memory, ntab ceil(X / 256) < 2^31
+hipError_t launch_response_compose(const double* A, int ntab, size_t X, const double* kappa, int Qc, double* out,
+                                   hipStream_t s);
+
 // 4 x 4 windows of a 3-D spline table f [n0][n1][n2] into fw [n0 n1 n2][16] (synchronous)
 hipError_t spline_windows_build(const float* f, int n0, int n1, int n2, float* fw);
 

@@ -183,6 +183,75 @@ class Plan:
                                                         ctypes.c_void_p(stream_ptr) if stream_ptr else None))
         return len(S)
 
+    # --- mass-resolved responses and the source's flavour composition (include/nusi.h "Mass-resolved response") ---
+    def step_constants(self):
+        """(step_c, step_s): the grid's per-step constants [Nz] (index 0 unused), which response.cascade_host needs."""
+        dp = ctypes.POINTER(ctypes.c_double)
+        c, s = np.zeros(self.Nz), np.zeros(self.Nz)
+        _lib.check(_lib.load().nusi_plan_step_constants(self._h, c.ctypes.data_as(dp), s.ctypes.data_as(dp)))
+        return c, s
+
+    def response_mass(self, points, z_weight=None):
+        """The response matrices of the points resolved by the source's mass state: host arrays (G3, G3_fla) of shape
+        (n, 3, M, 3, N), G3[p, j, n, k, b] the flux of mass state k in bin b per unit of S[n] emitted WHOLLY into mass
+        state j.  ``G3.reshape(3 * n, M, 3, N)`` is a stack of ordinary response matrices (apply_response,
+        fold_response); ``compose_response`` combines the three of a point into the response of a flavour composition
+        (sources.mass_fractions).  Entries with k != j may be slightly negative (include/nusi.h, "Sign")."""
+        arr = points if isinstance(points, ctypes.Array) else self.params_array(points)
+        n, M = len(arr), self.T + 1
+        G, Gf = np.zeros((n, 3, M, 3, self.N)), np.zeros((n, 3, M, 3, self.N))
+        w = self._weights(z_weight)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_mass_host(self._h, arr, n, w.ctypes.data_as(dp) if w is not None else None,
+                                                            G.ctypes.data_as(dp), Gf.ctypes.data_as(dp)))
+        return G, Gf
+
+    def response_mass_device(self, arr, d_G3_ptr, d_G3_fla_ptr, z_weight=None, stream_ptr=None):
+        """Asynchronous response_mass into device buffers of n * 3 * M * 3 * N doubles (raw pointers; either may be 0)."""
+        w = self._weights(z_weight)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_mass(self._h, arr, len(arr), w.ctypes.data_as(dp) if w is not None else None,
+                                                       ctypes.c_void_p(d_G3_ptr) if d_G3_ptr else None,
+                                                       ctypes.c_void_p(d_G3_fla_ptr) if d_G3_fla_ptr else None,
+                                                       ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+
+    @staticmethod
+    def _kappa(kappa, ntab):
+        k = np.asarray(kappa, dtype=np.float64)
+        if k.ndim == 0 or k.ndim > 3 or k.shape[-1] != 3 or (k.ndim == 3 and k.shape[0] != ntab):
+            raise ValueError("compose_response: kappa must have shape (3,), (Qc, 3) or (ntab, Qc, 3), got %s" % (k.shape,))
+        if k.ndim == 1:
+            k = k[None]
+        return np.ascontiguousarray(np.broadcast_to(k, (ntab,) + k.shape[-2:]))
+
+    def compose_response(self, A3, kappa):
+        """The composition of mass-resolved rows on the GPU: A3 of shape (ntab, 3, ...) -- G3 / G3_fla of
+        ``response_mass``, or a folded stack reshaped to (ntab, 3, M, C) -- and mass fractions kappa of shape (3,),
+        (Qc, 3) or (ntab, Qc, 3) (sources.mass_fractions): out[t, c] = (kappa[t, c, 0] A3[t, 0] + kappa[t, c, 1] A3[t, 1])
+        + kappa[t, c, 2] A3[t, 2], bit for bit response.compose_host.  Returns (ntab, ...) for a kappa of shape (3,),
+        else (ntab, Qc, ...)."""
+        A = np.ascontiguousarray(A3, dtype=np.float64)
+        if A.ndim < 3 or A.shape[1] != 3:
+            raise ValueError("compose_response: A3 must have shape (ntab, 3, ...), got %s" % (A.shape,))
+        ntab, rest = A.shape[0], A.shape[2:]
+        k = self._kappa(kappa, ntab)
+        Qc, X = k.shape[1], int(np.prod(rest))
+        out = np.zeros((ntab, Qc) + rest)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_compose_host(self._h, A.ctypes.data_as(dp), ntab, X, k.ctypes.data_as(dp),
+                                                               Qc, out.ctypes.data_as(dp)))
+        return out[:, 0] if np.ndim(kappa) == 1 else out
+
+    def compose_response_device(self, d_A_ptr, ntab, X, kappa, d_out_ptr, stream_ptr=None):
+        """Asynchronous compose on device-resident rows: d_A [ntab][3][X], d_out [ntab][Qc][X] (raw pointers); kappa as
+        for compose_response (host data, copied).  Returns Qc."""
+        k = self._kappa(kappa, int(ntab))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_compose(self._h, ctypes.c_void_p(d_A_ptr), int(ntab), int(X),
+                                                          k.ctypes.data_as(dp), k.shape[1], ctypes.c_void_p(d_out_ptr),
+                                                          ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+        return k.shape[1]
+
     # --- the detector (include/nusi.h "The detector of a plan") ---
     def set_detector(self, D, background=None):
         """Register the detector: D (C, 3, N), D[c, f, b] = expected events in reconstructed bin c per unit of

@@ -159,6 +159,22 @@ class pyprop:  # noqa: N801  (name of the reference class)
                                    Gf.ctypes.data_as(dp)))
         return G, Gf
 
+    def response_mass(self, z_weight=None):
+        """Extension (no reference counterpart): the response matrices of this object's parameter point resolved by the
+        source's mass state, (G3, G3_fla) of shape (3, M, 3, N) -- G3[j] is the response to a source emitted wholly into
+        mass state j (Plan.response_mass); ``response.compose_host(G3, sources.mass_fractions(flavour))`` is the
+        response matrix of a source of that flavour composition.  The object's fluxes and source are untouched."""
+        from . import sources
+        L = _lib.load()
+        dp = ctypes.POINTER(ctypes.c_double)
+        _, _, z = self.source_axis()
+        w = sources.weight_vector(z_weight, z)
+        M, N = self._n() + len(z) - 1, self._n()
+        G, Gf = np.zeros((3, M, 3, N)), np.zeros((3, M, 3, N))
+        _lib.check(L.nusi_response_mass(self._h, w.ctypes.data_as(dp) if w is not None else None, G.ctypes.data_as(dp),
+                                        Gf.ctypes.data_as(dp)))
+        return G, Gf
+
     def kernels(self):
         """Extension (no reference counterpart): names of the alpha-table and cascade kernels the last
         evolve() launched, e.g. ('k_alpha_batch', 'k_cascade_bs')."""

@@ -29,6 +29,31 @@ def tabulated(slot):
     return SOURCE_TABULATED + slot
 
 
+def mixing(normal_ordering=True):
+    """|U_fk|^2 of the ordering, shape (3, 3) indexed [flavour e / mu / tau][mass state] (nusi_mixing: the matrix the
+    library's flavour fluxes and couplings use)."""
+    import ctypes
+    from . import _lib
+    U2 = np.zeros(9)
+    _lib.check(_lib.load().nusi_mixing(1 if normal_ordering else 0, U2.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return U2.reshape(3, 3)
+
+
+def mass_fractions(flavour, normal_ordering=True):
+    """The shares kappa [3] of a source of flavour composition ``flavour`` = (phi_e, phi_mu, phi_tau) emitted into the
+    three mass states, kappa_k = sum_f phi_f |U_fk|^2 / sum_f phi_f (nusi_mass_fractions) -- e.g. (1, 2, 0) for pion
+    decay, (0, 1, 0) muon-damped, (1, 0, 0) neutron decay.  The kappa of Plan.compose_response / response.compose_host."""
+    import ctypes
+    from . import _lib
+    dp = ctypes.POINTER(ctypes.c_double)
+    phi = np.ascontiguousarray(flavour, dtype=np.float64)
+    if phi.shape != (3,):
+        raise ValueError("mass_fractions: flavour must be (phi_e, phi_mu, phi_tau)")
+    kappa = np.zeros(3)
+    _lib.check(_lib.load().nusi_mass_fractions(1 if normal_ordering else 0, phi.ctypes.data_as(dp), kappa.ctypes.data_as(dp)))
+    return kappa
+
+
 def bin_integrals(fn, lo, hi, order=12):
     """Integral of ``fn`` (a vectorised callable dN/dE(E)) over each bin [lo[n], hi[n]]: Gauss-Legendre of the
     given order in E, per bin."""
