@@ -460,8 +460,10 @@ int nusi_plan_response_profile_host(nusi_plan *plan, const double *R, int ntab, 
  * |g_j(theta_hat)| <= (kappa + ceil(log2 C) + 2 K + 9) u scale_j for the free j, and g_j >= -that for the others.
  * S, data and the outputs are as for nusi_plan_response_profile; d_theta [ntab][Q][1 + K] must not be NULL.
  * NUSI_ESTATE without a detector or without templates (that case is nusi_plan_response_profile). */
-enum {   /* (the fit's own constants; the status word's NUSI_FIT_* macros above are shared with the profile) */
+enum {   /* (the fit's own constants; the status word's NUSI_FIT_* macros above are shared with the profile;
+            NUSI_FIT_SIGNALS_MAX: the signal components of nusi_plan_response_fit_components) */
     NUSI_FIT_TEMPLATES_MAX = 3,
+    NUSI_FIT_SIGNALS_MAX = 3,
     NUSI_FIT_TRIALS_MAX = 64,
     NUSI_FIT_SINGULAR = 0x1000,
     NUSI_FIT_ZERO = 0x10000,
@@ -477,6 +479,46 @@ int nusi_plan_response_fit(nusi_plan *plan, const double *d_R /* [ntab][M][C] */
                            int *d_status /* [ntab][Q] or NULL */, void *stream);
 int nusi_plan_response_fit_host(nusi_plan *plan, const double *R, int ntab, const double *S, int Q, const double *data,
                                 double *theta, double *nll, double *mu, int *status);
+/* nusi_plan_response_fit_components (k_components_fit): the fit with J = 2 .. NUSI_FIT_SIGNALS_MAX SIGNAL COMPONENTS per
+ * table and spectrum, each a stack of rows of its own, floating together with the plan's K = 0 .. NUSI_FIT_TEMPLATES_MAX
+ * templates, every normalisation >= 0:
+ *     mu_c(theta) = sum_{j<J} theta_j s_jc + sum_{i=1..K} theta_{J+i-1} T_i[c] + B_c,   theta >= 0
+ * d_R3 [ntab][J][M][C] is any stack of folded matrices, entries >= 0: the folded rows of nusi_plan_response_mass, or those
+ * rows composed (nusi_plan_response_compose) onto the three pure source flavours -- then theta_j >= 0 is exactly the
+ * physical flavour triangle and theta_j / sum_j theta_j the fitted composition.  It is nusi_plan_response_fit's iteration,
+ * every operation and its order as defined there, with these differences and nothing else:
+ *   X_j      = s_j for j < J,  s_j[c] = sum_{n=1}^{M-1} R3[t][j][n][c] S[q][n] ascending in n from 0.0 (the events call's
+ *            accumulator on the rows R3[.][j]);  X_{J+i-1} = T_i for i = 1 .. K;  n = J + K.  den adds the products
+ *            x_j X_jc in ascending j, then B_c
+ *   live     a signal component j < J is live when S1_j > 0 and some bin has data_c > 0 and s_jc > 0; a template is live
+ *            when S1_j > 0.  The start gives every live component an equal share, n_live counting both kinds
+ *   priors   w_j = m_j = 0 for j < J; template i's prior is component J + i - 1's
+ *   kappa    = 2 (ceil(log2 C) + J - 1 + K) + 18: den has J - 1 more products than the fit's; where it
+ *            stopped by `stop`, in exact arithmetic |g_j(theta_hat)| <= (3 ceil(log2 C) + 4 (J - 1 + K) + 27) u scale_j
+ *            for the free j, and g_j >= -that for the others
+ *   status   the fit's word with NUSI_FIT_FLAT when NO signal component is live (the templates are fitted all the same),
+ *            NUSI_FIT_BOUNDARY when some signal component is live and every signal theta_j ends at 0, and
+ *            NUSI_FIT_ZERO << j for every j < J + K with theta_j == 0: bits 16 .. 21, below NUSI_FIT_TRIALS_SHIFT
+ *   mu, nll  as there: mu = den(theta_hat), nll the statistic of that mu, then the penalties of the templates with
+ *            w > 0, ascending
+ * (detector.fit_components_host is the same text in numpy; with J = 1 and K >= 1 that host form is detector.fit_host to
+ * the bit).  Two components whose rows are proportional on the bins with data, or more live components than bins with
+ * data, leave the Newton system singular: NUSI_FIT_SINGULAR, as for the fit.
+ * nusi_fit_components_shape is the size check the call applies (pure: no plan, no device): NUSI_EPARAM for J outside
+ * 2 .. NUSI_FIT_SIGNALS_MAX (J = 1 is nusi_plan_response_fit / _profile), K outside 0 .. NUSI_FIT_TEMPLATES_MAX, C outside
+ * 1 .. NUSI_DETECTOR_BINS_MAX, ntab < 1, Q outside 1 .. 2^19, or ntab Q, or the element count of any output (theta
+ * [J + K] or mu [C] a record), at or beyond 2^31; *records (unless NULL) = ntab Q.
+ * The call: K is nusi_plan_templates, and 0 is allowed.  S, data and the outputs are as for nusi_plan_response_fit;
+ * d_theta [ntab][Q][J + K] must not be NULL.  NUSI_ESTATE without a detector; NUSI_EPARAM as the shape check says, for
+ * NULL d_R3, S, data or d_theta, and for a negative or non-finite entry of data or S. */
+int nusi_fit_components_shape(int C, int J, int K, int ntab, int Q, long long *records /* or NULL */);
+int nusi_plan_response_fit_components(nusi_plan *plan, const double *d_R3 /* [ntab][J][M][C] */, int ntab, int J,
+                                      const double *S /* [Q][M] */, int Q, const double *data /* [C] */,
+                                      double *d_theta /* [ntab][Q][J + K] */, double *d_nll /* [ntab][Q] or NULL */,
+                                      double *d_mu /* [ntab][Q][C] or NULL */, int *d_status /* [ntab][Q] or NULL */,
+                                      void *stream);
+int nusi_plan_response_fit_components_host(nusi_plan *plan, const double *R3, int ntab, int J, const double *S, int Q,
+                                           const double *data, double *theta, double *nll, double *mu, int *status);
 /* nusi_plan_response_fit_fixed (k_conditional_fit): the CONDITIONAL fit -- the fit above with the signal's scale HELD at
  * a given a = scale[q] >= 0 and only the K templates floating: theta_1 .. theta_K >= 0 minimising f(a, .) for every table
  * t and spectrum q.  At a = 0 it is the background-only fit; at any a it is the inner problem of the statistic

@@ -29,6 +29,7 @@ FIT_STEPS_MASK = 0xFF
 FIT_FLAT, FIT_BOUNDARY, FIT_NOT_CONVERGED, FIT_INFINITE = 0x100, 0x200, 0x400, 0x800
 # ... and of Plan.fit: a singular Newton system, FIT_ZERO << j for a component that ends at zero, the halvings from bit 24
 FIT_TEMPLATES_MAX = 3
+FIT_SIGNALS_MAX = 3         # the signal components of Plan.fit_components
 FIT_TRIALS_MAX = 64
 FIT_SINGULAR, FIT_ZERO, FIT_TRIALS_SHIFT, FIT_TRIALS_MASK = 0x1000, 0x10000, 24, 0x7F
 # Plan.limit (NUSI_LIMIT_*): the sides, the outer cap, and a side's status word: the outer steps in the low 8 bits, the flags,
@@ -80,6 +81,7 @@ EXPORTS = [
     "nusi_plan_response_fold", "nusi_plan_response_fold_host", "nusi_plan_response_events",
     "nusi_plan_response_events_host", "nusi_plan_response_profile", "nusi_plan_response_profile_host",
     "nusi_plan_set_templates", "nusi_plan_templates", "nusi_plan_response_fit", "nusi_plan_response_fit_host",
+    "nusi_fit_components_shape", "nusi_plan_response_fit_components", "nusi_plan_response_fit_components_host",
     "nusi_plan_response_fit_fixed", "nusi_plan_response_fit_fixed_host",
     "nusi_plan_response_limit", "nusi_plan_response_limit_host",
     "nusi_plan_response_ensemble", "nusi_plan_response_ensemble_host",
@@ -197,6 +199,9 @@ def load():
         "nusi_plan_templates": (i, [vp]),
         "nusi_plan_response_fit": (i, [vp, vp, i, dp, i, dp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_fit_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, ip]),
+        "nusi_fit_components_shape": (i, [i, i, i, i, i, ctypes.POINTER(ctypes.c_longlong)]),
+        "nusi_plan_response_fit_components": (i, [vp, vp, i, i, dp, i, dp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_fit_components_host": (i, [vp, dp, i, i, dp, i, dp, dp, dp, dp, ip]),
         "nusi_plan_response_fit_fixed": (i, [vp, vp, i, dp, i, dp, dp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_fit_fixed_host": (i, [vp, dp, i, dp, i, dp, dp, dp, dp, dp, ip]),
         "nusi_plan_response_limit": (i, [vp, vp, i, dp, i, dp, d, i, vp, vp, vp, vp, vp, vp]),

@@ -2246,6 +2246,54 @@ int nusi_plan_response_fit_host(nusi_plan* pl, const double* R, int ntab, const 
                        });
 }
 
+// The fit with J signal components per (table, spectrum) (nusi_detector.hip k_components_fit).  The size limits are a
+// pure function, which the call applies with the detector's C and the plan's K.
+int nusi_fit_components_shape(int C, int J, int K, int ntab, int Q, long long* records)
+{
+    const std::string w = "response fit components: ";
+    if (C < 1 || C > NUSI_DETECTOR_BINS_MAX) return fail(NUSI_EPARAM, w + "C outside 1 .. NUSI_DETECTOR_BINS_MAX");
+    if (J < 2 || J > NUSI_FIT_SIGNALS_MAX) return fail(NUSI_EPARAM, w + "J outside 2 .. NUSI_FIT_SIGNALS_MAX (J = 1 is nusi_plan_response_fit / _profile)");
+    if (K < 0 || K > NUSI_FIT_TEMPLATES_MAX) return fail(NUSI_EPARAM, w + "K outside 0 .. NUSI_FIT_TEMPLATES_MAX");
+    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, w + "need ntab >= 1 and 1 <= Q <= 2^19");
+    const long long nn = (long long)ntab * Q;
+    const long long widest = C > J + K ? C : J + K;   // (mu [C] or theta [J + K]: the largest output)
+    if (nn >= (1ll << 31) || nn * widest >= (1ll << 31))
+        return fail(NUSI_EPARAM, w + "too many records (ntab Q, or an output's elements, >= 2^31)");
+    if (records) *records = nn;
+    return NUSI_OK;
+}
+
+int nusi_plan_response_fit_components(nusi_plan* pl, const double* d_R3, int ntab, int J, const double* S, int Q,
+                                      const double* data, double* d_theta, double* d_nll, double* d_mu, int* d_status,
+                                      void* stream)
+{
+    if (int r = detector_plan(pl, "response fit components")) return r;
+    if (int r = nusi_fit_components_shape(pl->det_C, J, pl->fit_K, ntab, Q, nullptr)) return r;
+    if (!data || !d_theta) return fail(NUSI_EPARAM, "response fit components: data and theta must not be NULL");
+    EventsArgs a;
+    if (int r = events_begin(pl, "response fit components", d_R3, ntab, S, Q, nullptr, data, 1, stream, a)) return r;
+    HIPCHECK(nusi::launch_components_fit(pl->gd, d_R3, ntab, J, a.S, Q, a.data, a.bg, pl->det_C, pl->fit_K, pl->d_tpl,
+                                         pl->fit_m, pl->fit_w, d_theta, d_nll, d_mu, d_status, a.s));
+    return detector_mark(pl, a.s);
+}
+
+int nusi_plan_response_fit_components_host(nusi_plan* pl, const double* R3, int ntab, int J, const double* S, int Q,
+                                           const double* data, double* theta, double* nll, double* mu, int* status)
+{
+    if (int r = detector_plan(pl, "response fit components")) return r;
+    if (int r = nusi_fit_components_shape(pl->det_C, J, pl->fit_K, ntab, Q, nullptr)) return r;
+    if (!R3) return fail(NUSI_EPARAM, "response fit components: R3 must not be NULL");
+    if (!data || !theta) return fail(NUSI_EPARAM, "response fit components: data and theta must not be NULL");
+    const size_t nn = (size_t)ntab * Q, nmu = nn * pl->det_C, nth = nn * (J + pl->fit_K);
+    // (R3 is ntab J folded matrices in a row)
+    return events_host(pl, R3, ntab * J,
+                       {{theta, nth, sizeof(double)}, {nll, nn, sizeof(double)}, {mu, nmu, sizeof(double)}, {status, nn, sizeof(int)}},
+                       "response fit components", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_fit_components(pl, dI, ntab, J, S, Q, data, (double*)d[0], (double*)d[1],
+                                                                    (double*)d[2], (int*)d[3], nullptr);
+                       });
+}
+
 // The ensemble (nusi_detector.hip k_ensemble_profile / k_ensemble_fit / k_ensemble_best).  The grid is (tables,
 // q-slices, p-slices).  Automatic slices: the grid should hold kEnsBlocksPerCU blocks per compute unit, several rounds
 // of what is resident at once, so that the last round's tail is short (measured: DESIGN.md sec. 4).  Spectrum blocks

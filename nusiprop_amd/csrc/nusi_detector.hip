@@ -9,6 +9,9 @@
 //                         sums over the bins as butterflies inside a wave (nusi_plan_response_profile)
 //   k_detector_fit<NC>    that statistic minimised over NC = 1 + K normalisations, the signal's and K background
 //                         templates' under Gaussian priors: a damped Newton iteration per (t, q) (nusi_plan_response_fit)
+//   k_components_fit<J, NC>
+//                         that fit with J = 2 .. 3 signal components per (t, q), each a stack of rows of its own, in front
+//                         of the K = NC - J templates (nusi_plan_response_fit_components)
 //   k_ensemble_profile, k_ensemble_fit<NC>, k_ensemble_best
 //                         those two iterations for P data sets on one front half, and per (data set, table) the best
 //                         spectrum's record only (nusi_plan_response_ensemble)
@@ -35,7 +38,7 @@
 // The iterations several of these kernels run exist once, as text the kernels #include inside their bodies (not as
 // __device__ helpers, which moved the kernels' registers: DESIGN.md sec. 4, "The shared iterations"):
 //   nusi_fit_newton.inc          k_detector_fit's iteration: k_detector_fit, k_ensemble_fit, and for NC > 1 the best fit
-//                                of k_interval, k_toys_limit, k_inject
+//                                of k_interval, k_toys_limit, k_inject; k_components_fit with FN_NSIG = J signal components
 //   nusi_profile_chain4.inc      k_detector_profile's, four chains a lane: k_detector_profile, k_ensemble_profile
 //   nusi_profile_chain1.inc      k_detector_profile's, one chain a lane: the best fit at NC = 1 of k_interval,
 //                                k_toys_limit, k_inject
@@ -47,7 +50,8 @@
 //   nusi_search_setup.inc, nusi_search_side.inc
 //                                the search for a limit: k_interval, k_toys_limit
 //   nusi_ldlt_solve.inc          the Newton direction, inside the fit's, the conditional fit's and the search's text
-//   nusi_fit_statistic.inc       the statistic's serial sum from LDS: k_detector_fit, k_conditional_fit, k_interval
+//   nusi_fit_statistic.inc       the statistic's serial sum from LDS: k_detector_fit, k_components_fit, k_conditional_fit,
+//                                k_interval
 #include <hip/hip_runtime.h>
 
 #include "nusi_internal.hpp"
@@ -499,7 +503,9 @@ __global__ __launch_bounds__(kEvThreads) void k_detector_fit(const double* __res
 #pragma unroll
     for (int j = 0; j < NC; ++j) S1[j] = X[j];
     det_butterfly(S1, lgC, add);
+#define FN_NSIG 1
 #include "nusi_fit_newton.inc"
+#undef FN_NSIG
     if (in) {
         smu[grp * RS + c] = m;
         if (mu && q < Q) mu[((size_t)t * Q + q) * C + c] = m;
@@ -539,6 +545,130 @@ hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, cons
     case 3: hipLaunchKernelGGL((k_detector_fit<4>), grid, block, 0, s, R, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_components_fit<J, NC>: the fit with J = 2 .. 3 SIGNAL components in front of the K = NC - J templates
+// (nusi_plan_response_fit_components): every (table, spectrum) brings J rows of its own, R3[t][j], and all NC
+// normalisations float, non-negative.  It has k_detector_fit's shape -- lanes on (c, one spectrum), one det_butterfly of
+// the round's NC + NC (NC + 1) / 2 sums (27 at NC = 6), everything behind it redundant on a group's lanes, no LDS and no
+// barrier inside the iteration -- and its text: nusi_fit_newton.inc with FN_NSIG = J, which makes the liveness rule and
+// the FLAT / BOUNDARY flags run over the J signal components and leaves everything else as it is.  The front half loads
+// S[q][n] once per n and J values R3[t][j][n][c] into J accumulators, each in events' order.  The priors arrive as the
+// fit's FitPrior (template i in slot i); pr below shifts them behind the signal components' compile-time zeros.
+// LDS: a row per spectrum of the block, fit_row(C, NC) doubles: its mu and theta_1 .. theta_{NC-1} -- the signal
+// components behind the first ride along so that nusi_fit_statistic.inc serves as it is (their weights are 0: no term).
+// NC = 5 and 6 do not fit the 128 registers of four waves per SIMD: those instances ask for three and two.
+// ---------------------------------------------------------------------------
+constexpr int comp_waves(int NC) { return NC <= 4 ? 4 : NC == 5 ? 3 : 2; }
+
+template <int J, int NC>
+__global__ __launch_bounds__(kEvThreads) __attribute__((amdgpu_waves_per_eu(comp_waves(NC))))
+void k_components_fit(const double* __restrict__ R3, const double* __restrict__ S, const double* __restrict__ data,
+                      const double* __restrict__ bg, const double* __restrict__ T, const FitPrior tp, const double ku,
+                      double* __restrict__ theta, double* __restrict__ nll, double* __restrict__ mu,
+                      int* __restrict__ status, int M, int C, int lgC, int Q)
+{
+#pragma clang fp contract(off)
+    static_assert(J >= 2 && J <= NUSI_FIT_SIGNALS_MAX && NC >= J && NC - J <= NUSI_FIT_TEMPLATES_MAX, "k_components_fit: J signal components and NC - J templates");
+    constexpr int NS = NC + NC * (NC + 1) / 2;   // a round's sums: S2_j, then H_jk (j <= k, row-major)
+    __shared__ double smu[fit_lds_max(NC)];
+    const int tid = (int)threadIdx.x, t = (int)blockIdx.x;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, qb0 = (int)blockIdx.y * QB, q = qb0 + grp;
+    const int cc = c < C ? c : C - 1, RS = fit_row(C, NC);
+    const double* __restrict__ Rt = R3 + (size_t)t * J * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)(q < Q ? q : Q - 1) * M;
+    const bool in = c < C;
+    double X[NC];
+    {
+        double s0[J];
+#pragma unroll
+        for (int j = 0; j < J; ++j) s0[j] = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) {
+            const double sv = Sq[n];
+#pragma unroll
+            for (int j = 0; j < J; ++j) s0[j] = s0[j] + Rt[((size_t)j * M + n) * C] * sv;
+        }
+#pragma unroll
+        for (int j = 0; j < J; ++j) X[j] = in ? s0[j] : 0.0;
+    }
+#pragma unroll
+    for (int j = J; j < NC; ++j) X[j] = in ? T[(size_t)(j - J) * C + cc] : 0.0;
+    struct {
+        double m[NC], w[NC];
+    } pr;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+        pr.m[j] = j < J ? 0.0 : tp.m[j < J ? 0 : j - J + 1];
+        pr.w[j] = j < J ? 0.0 : tp.w[j < J ? 0 : j - J + 1];
+    }
+    const double b = in ? bg[cc] : 0.0, d = in ? data[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+
+    double S1[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) S1[j] = X[j];
+    det_butterfly(S1, lgC, add);
+#define FN_NSIG J
+#include "nusi_fit_newton.inc"
+#undef FN_NSIG
+    if (in) {
+        smu[grp * RS + c] = m;
+        if (mu && q < Q) mu[((size_t)t * Q + q) * C + c] = m;
+    }
+    if (c == 0) {
+#pragma unroll
+        for (int j = 1; j < NC; ++j) smu[grp * RS + C + j - 1] = th[j];
+        if (q < Q) {
+#pragma unroll
+            for (int j = 0; j < NC; ++j) theta[((size_t)t * Q + q) * NC + j] = th[j];
+            if (status) status[(size_t)t * Q + q] = st;
+        }
+    }
+    if (!nll) return;   // (uniform)
+    __syncthreads();
+    // (a block owns QB <= kEvThreads spectra)
+    if (tid < QB && qb0 + tid < Q) {
+        constexpr int NP = NC;
+#include "nusi_fit_statistic.inc"
+        nll[(size_t)t * Q + qb0 + tid] = sum;
+    }
+}
+
+// (J = 2 .. 3, K = 0 .. NUSI_FIT_TEMPLATES_MAX: eight instances; ku = kappa u with J - 1 + K in kappa, one more product
+// in den per further signal component)
+hipError_t launch_components_fit(const GridDev& g, const double* R3, int ntab, int J, const double* S, int Q,
+                                 const double* data, const double* bg, int C, int K, const double* T, const double* pm,
+                                 const double* pw, double* theta, double* nll, double* mu, int* status, hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0) return hipSuccess;
+    const DetGeom ge(C, 1, ntab, Q);
+    const FitPrior pr = fit_prior(K, pm, pw);
+    const double ku = fit_ku(ge.lg, J - 1 + K);
+    const dim3 grid = ge.grid, block(kEvThreads);
+    const int M = g.T + 1;
+#define NUSI_COMP_FIT(JJ, KK) \
+    case (JJ) * 4 + (KK): \
+        hipLaunchKernelGGL((k_components_fit<JJ, JJ + KK>), grid, block, 0, s, R3, S, data, bg, T, pr, ku, theta, nll, mu, status, M, C, ge.lg, Q); \
+        break;
+    switch (J * 4 + K) {
+        NUSI_COMP_FIT(2, 0)
+        NUSI_COMP_FIT(2, 1)
+        NUSI_COMP_FIT(2, 2)
+        NUSI_COMP_FIT(2, 3)
+        NUSI_COMP_FIT(3, 0)
+        NUSI_COMP_FIT(3, 1)
+        NUSI_COMP_FIT(3, 2)
+        NUSI_COMP_FIT(3, 3)
+    default: return hipErrorInvalidValue;
+    }
+#undef NUSI_COMP_FIT
     return hipGetLastError();
 }
 
@@ -804,7 +934,9 @@ __global__ __launch_bounds__(kEvThreads) __attribute__((amdgpu_waves_per_eu(NC =
         for (int pi = p0; pi < p1; ++pi, ++it) {
             const double* __restrict__ dat = data + (size_t)pi * C;
             const double d = in ? dat[cc] : 0.0;
+#define FN_NSIG 1
 #include "nusi_fit_newton.inc"
+#undef FN_NSIG
             const int buf = it & 1;
             double* rows = srow + buf * kRows;
             double term = m;   // the statistic's term of (spectrum, c), on the bin's own lane
@@ -1134,7 +1266,9 @@ __global__ __launch_bounds__(kEvThreads) void k_interval(const double* __restric
 #pragma unroll
         for (int j = 0; j < NC; ++j) S1[j] = X[j];
         det_butterfly(S1, lgC, add);
+#define FN_NSIG 1
 #include "nusi_fit_newton.inc"
+#undef FN_NSIG
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
             thh[j] = th[j];
@@ -1278,7 +1412,9 @@ __global__ __launch_bounds__(kEvThreads) void k_toys_limit(const double* __restr
             double S1[NC];
 #pragma unroll
             for (int j = 0; j < NC; ++j) S1[j] = S1h[j];
+#define FN_NSIG 1
 #include "nusi_fit_newton.inc"
+#undef FN_NSIG
 #pragma unroll
             for (int j = 0; j < NC; ++j) thh[j] = th[j];
             muh = m;

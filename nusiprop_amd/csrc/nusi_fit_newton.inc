@@ -3,17 +3,21 @@
 // for NC > 1, in the best fit of k_interval, k_toys_limit and k_inject: one text, so the five agree by construction (a
 // call to a shared __device__ body, inlined, moved the kernels' registers: DESIGN.md sec. 4).  The Newton direction
 // inside it is nusi_ldlt_solve.inc, shared with the conditional fit's and the search's text.
-// In scope: NC and NS = NC + NC (NC + 1) / 2 (constexpr); X[NC], S1[NC] = tree(X), b, d, in; pr (FitPrior), ku; lgC and
-// the lambdas add, min, any(bool).
+// k_components_fit<J, NC> includes it too, with J signal components in front of the templates (include/nusi.h,
+// nusi_plan_response_fit_components): the includer #defines FN_NSIG, the number of signal components (a constant
+// expression, 1 .. NC), in front of the #include and #undefs it behind; the five above define it as 1, where the loops over
+// the signal components 1 .. FN_NSIG - 1 below are empty and the text is what it was.
+// In scope: NC and NS = NC + NC (NC + 1) / 2 (constexpr); X[NC], S1[NC] = tree(X), b, d, in; pr (m[], w[]: NC entries at
+// least, the signal components' zeros in front), ku; lgC and the lambdas add, min, any(bool).
 // It leaves behind: th[NC] (the estimate), live[NC], m (the estimate's mu_c), st (the status word, complete), steps,
-// halv; and, of no further use, sup, nl, act, D0, dq, the[NC], pp[NC] (the direction), tt, trials, run, first, quad.
+// halv; and, of no further use, slive, szero, sup, nl, act, D0, dq, the[NC], pp[NC] (the direction), tt, trials, run, first, quad.
     bool live[NC];
     live[0] = any(d > 0.0 && X[0] > 0.0) && S1[0] > 0.0;
     bool sup = b > 0.0;
     int nl = 0;
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-        if (j > 0) live[j] = S1[j] > 0.0;
+        if (j > 0) live[j] = j < FN_NSIG ? (any(d > 0.0 && X[j] > 0.0) && S1[j] > 0.0) : S1[j] > 0.0;
         sup = sup || (live[j] && X[j] > 0.0);
         nl += live[j] ? 1 : 0;
     }
@@ -145,9 +149,15 @@
 #pragma unroll
     for (int j = 1; j < NC; ++j) m = m + th[j] * X[j];
     m = m + b;
-    if (!live[0])
+    bool slive = live[0], szero = th[0] == 0.0;   // some signal component is live; every one ends at zero
+#pragma unroll
+    for (int j = 1; j < FN_NSIG; ++j) {
+        slive = slive || live[j];
+        szero = szero && th[j] == 0.0;
+    }
+    if (!slive)
         st |= NUSI_FIT_FLAT;
-    else if (th[0] == 0.0)
+    else if (szero)
         st |= NUSI_FIT_BOUNDARY;
 #pragma unroll
     for (int j = 0; j < NC; ++j)

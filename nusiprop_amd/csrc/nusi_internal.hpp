@@ -165,6 +165,11 @@ hipError_t launch_detector_profile(const GridDev& g, const double* R, int ntab, 
 hipError_t launch_detector_fit(const GridDev& g, const double* R, int ntab, const double* S, int Q, const double* data,
                                const double* bg, int C, int K, const double* T, const double* pm, const double* pw,
                                double* theta, double* nll, double* mu, int* status, hipStream_t s);
+// k_components_fit<J, J + K>: the fit with J = 2 .. 3 signal components per (table, spectrum), R3 [ntab][J][M][C], and
+// K = 0 .. 3 templates (T, pm, pw: unread at K = 0); theta [ntab][Q][J + K]
+hipError_t launch_components_fit(const GridDev& g, const double* R3, int ntab, int J, const double* S, int Q,
+                                 const double* data, const double* bg, int C, int K, const double* T, const double* pm,
+                                 const double* pw, double* theta, double* nll, double* mu, int* status, hipStream_t s);
 // k_ensemble_profile (K = 0) / k_ensemble_fit<1 + K>: P data sets data [P][C] (device memory), per (p, t) the best
 // spectrum's record under the key of include/nusi.h: q, nll, status [P][ntab], theta [P][ntab][1 + K] in device memory,
 // theta and status may be nullptr.  Grid (ntab, qslices, pslices): 1 <= qslices <= ensemble_blocks(C, K, Q) (the

@@ -18,7 +18,9 @@
             double S1[NC];
 #pragma unroll
             for (int j = 0; j < NC; ++j) S1[j] = S1h[j];
+#define FN_NSIG 1
 #include "nusi_fit_newton.inc"
+#undef FN_NSIG
 #pragma unroll
             for (int j = 0; j < NC; ++j) thh[j] = th[j];
             muh = m;

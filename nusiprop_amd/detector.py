@@ -22,6 +22,13 @@ same for nusi_plan_response_fit, the fit that floats K background templates with
     plan.set_templates(T, prior=(mean, sigma))                           # (K, C), K <= FIT_TEMPLATES_MAX
     theta, nll, mu, st = plan.fit(R, spectra, data=counts)              # fit_host on the CPU: theta (ntab, Q, 1 + K)
 
+``fit_components_host`` is nusi_plan_response_fit_components, that fit with J = 2 .. 3 signal components per table and
+spectrum -- a stack R3 (ntab, J, M, C), e.g. the folded mass-resolved rows composed onto the pure flavours -- whose shares
+``composition`` reads off, and ``composition_statistic`` the statistic of a held composition against that free fit::
+
+    theta, nll, mu, st = plan.fit_components(R3, spectra, data=counts)  # fit_components_host: theta (ntab, Q, J + K)
+    total, frac = detector.composition(theta, 3)                         # the scale and the fitted shares
+
 ``ensemble_host`` loops either over P data sets and keeps, per data set and table, the best spectrum's record under
 ``argbest``'s key (isnan(nll), nll, q) -- nusi_plan_response_ensemble's selection rule; ``pseudo_data`` draws the toys::
 
@@ -54,6 +61,7 @@ FIT_FLAT, FIT_BOUNDARY, FIT_NOT_CONVERGED, FIT_INFINITE = 0x100, 0x200, 0x400, 0
 # the fit with floating templates (nusi_plan_response_fit) adds: a singular Newton system, one bit per component that ends
 # at zero (FIT_ZERO << j) and the halvings of all its steps (saturating at FIT_TRIALS_MASK) from bit FIT_TRIALS_SHIFT
 FIT_TEMPLATES_MAX = 3
+FIT_SIGNALS_MAX = 3  # the signal components of fit_components_host (NUSI_FIT_SIGNALS_MAX)
 FIT_TRIALS_MAX = 64
 FIT_SINGULAR = 0x1000
 FIT_ZERO = 0x10000
@@ -227,16 +235,18 @@ def profile_host(R, S, data, background=None, log=np.log):
     return _squeeze(one_tab, one_q, a, nll, mu, steps | flags)
 
 
-def fit_kappa(C, K):
+def fit_kappa(C, K, J=1):
     """kappa(C, K) = 2 (ceil(log2 C) + K) + 18: the stop of nusi_plan_response_fit, |g_j| <= kappa u scale_j on the
-    computed gradient (include/nusi.h; derived in DESIGN.md sec. 4, "The fit with floating templates")."""
-    return 2 * (_ceil_log2(C) + K) + 18
+    computed gradient (include/nusi.h; derived in DESIGN.md sec. 4, "The fit with floating templates").  With J signal
+    components (fit_components_host) den has J - 1 more products: K -> J - 1 + K."""
+    return 2 * (_ceil_log2(C) + J - 1 + K) + 18
 
 
-def K_fit(C, K):
+def K_fit(C, K, J=1):
     """The bound on the EXACT residual of a converged fit, in units of u scale_j: the stop's kappa plus the rounding of
-    the computed gradient, ceil(log2 C) + 2 K + 8, plus one for the computed scale."""
-    return fit_kappa(C, K) + _ceil_log2(C) + 2 * K + 9
+    the computed gradient, ceil(log2 C) + 2 K + 8, plus one for the computed scale (K -> J - 1 + K with J signal
+    components: 3 ceil(log2 C) + 4 (J - 1 + K) + 27)."""
+    return fit_kappa(C, K, J) + _ceil_log2(C) + 2 * (J - 1 + K) + 9
 
 
 def _prior(K, prior):
@@ -301,12 +311,14 @@ def _fit_solve(A, g, fs, n):
     return p, False
 
 
-def _fit_one(X, B, d, m, w, ku):
+def _fit_one(X, B, d, m, w, ku, J=1):
     """One fit of nusi_plan_response_fit: X (1 + K, C) the signal and the templates, B, d (C,), m, w (1 + K,) the
-    priors' means and weights (0 in front), ku = kappa u.  Returns (theta list, status)."""
+    priors' means and weights (0 in front), ku = kappa u.  Returns (theta list, status).  J > 1: the fit of
+    nusi_plan_response_fit_components, X (J + K, C) with J signal components in front, each under the signal's liveness
+    rule; FIT_FLAT when none of them is live, FIT_BOUNDARY when one is and all end at zero."""
     n, C = X.shape
     S1 = [float(v) for v in tree(X)]
-    live = [S1[0] > 0.0 and bool(np.any((d > 0) & (X[0] > 0)))] + [S1[j] > 0.0 for j in range(1, n)]
+    live = [S1[j] > 0.0 and bool(np.any((d > 0) & (X[j] > 0))) for j in range(J)] + [S1[j] > 0.0 for j in range(J, n)]
     sup = B > 0
     for j in range(n):
         if live[j]:
@@ -392,9 +404,9 @@ def _fit_one(X, B, d, m, w, ku):
         quad = (not clipped) and -acc <= 0.0625 * dmin
         trials = 0
         the = [(0.0 if (clipped and fs[j] and p[j] < 0.0 and ratio[j] == t) else th[j] + t * p[j]) for j in range(n)]
-    if not live[0]:
+    if not any(live[:J]):
         flags |= FIT_FLAT
-    elif th[0] == 0.0:
+    elif all(th[j] == 0.0 for j in range(J)):
         flags |= FIT_BOUNDARY
     for j in range(n):
         if th[j] == 0.0:
@@ -445,6 +457,123 @@ def fit_host(R, S, data, templates, prior=None, background=None, log=np.log):
             dl = theta[..., j] - m[j]
             nll = nll + ((0.5 * w[j]) * dl) * dl
     return _squeeze(one_tab, one_q, theta, nll, mu, status)
+
+
+def fit_components_host(R3, S, data, templates=None, prior=None, background=None, log=np.log):
+    """The fit with J signal components per table and spectrum, by the iteration nusi_plan_response_fit_components
+    defines (include/nusi.h) -- nusi_plan_response_fit's with the liveness rule on every signal component and J - 1 + K
+    in kappa -- operation for operation: theta, mu and status agree with the GPU bit for bit and nll to the last bits of
+    the log.
+
+        mu_c(theta) = sum_{j<J} theta_j s_jc + sum_i theta_{J+i-1} T_i[c] + B_c,  theta >= 0,
+        s_j = events_host(R3[:, j], S)
+
+    R3: (J, M, C) or (ntab, J, M, C), J = 1 .. FIT_SIGNALS_MAX, entries finite and >= 0: folded mass-resolved rows,
+    ``compose_response`` output (onto the pure flavours: theta_j >= 0 is then the physical flavour triangle), or any
+    stack of folded matrices.  S: (M,) or (Q, M).  data: (C,).  templates: None (K = 0, allowed here) or (K, C).  prior,
+    background, log: as for fit_host (the priors are the templates').  Returns (theta (ntab, Q, J + K), nll, mu,
+    status), squeezed as fit_host squeezes: FIT_FLAT when no signal component is live (the templates are fitted all the
+    same), FIT_BOUNDARY when one is and every signal theta_j ends at 0, FIT_ZERO << j for j < J + K.  With J = 1 and
+    K >= 1 it is fit_host to the bit."""
+    R3 = np.asarray(R3, dtype=np.float64)
+    one_tab = R3.ndim == 3
+    Rt = R3[None] if one_tab else R3
+    if Rt.ndim != 4 or not 1 <= Rt.shape[1] <= FIT_SIGNALS_MAX:
+        raise ValueError("fit_components_host: R3 must have shape (.., J, M, C), J = 1 .. %d, got %s" % (FIT_SIGNALS_MAX, R3.shape))
+    if not np.all(np.isfinite(Rt)) or np.any(Rt < 0):
+        raise ValueError("fit_components_host: an entry of R3 is negative or not finite")
+    J = Rt.shape[1]
+    s0, data, _, one_q = _signal("fit_components_host", Rt[:, 0], S, data)
+    ntab, Q, C = s0.shape
+    Sq = np.asarray(S, dtype=np.float64)
+    Sq = Sq[None] if one_q else Sq
+    s = [s0] + [events_host(Rt[:, j], Sq) for j in range(1, J)]
+    T = np.zeros((0, C)) if templates is None else _templates(templates, C)
+    K = T.shape[0]
+    m1, w1 = _prior(K, prior)                                  # (the fit's, one zero in front: J - 1 more)
+    m, w = np.concatenate([np.zeros(J - 1), m1]), np.concatenate([np.zeros(J - 1), w1])
+    B = np.zeros(C) if background is None else np.array(np.broadcast_to(np.asarray(background, dtype=np.float64), (C,)))
+    ku = fit_kappa(C, K, J) * 2.0 ** -53
+    n = J + K
+    theta = np.zeros((ntab, Q, n))
+    status = np.zeros((ntab, Q), dtype=np.int32)
+    mu = np.zeros((ntab, Q, C))
+    X = np.zeros((n, C))
+    X[J:] = T
+    with np.errstate(all="ignore"):
+        for t in range(ntab):
+            for q in range(Q):
+                for j in range(J):
+                    X[j] = s[j][t, q]
+                th, st = _fit_one(X, B, data, m, w, ku, J)
+                theta[t, q], status[t, q] = th, st
+                den = th[0] * X[0]
+                for j in range(1, n):
+                    den = den + th[j] * X[j]
+                mu[t, q] = den + B
+    status[np.any((data > 0) & (mu == 0), axis=-1)] |= FIT_INFINITE
+    nll = poisson_host(mu, data, log=log)
+    for j in range(J, n):                                      # the templates' penalties, ascending, each operation rounded
+        if w[j] > 0:
+            dl = theta[..., j] - m[j]
+            nll = nll + ((0.5 * w[j]) * dl) * dl
+    return _squeeze(one_tab, one_q, theta, nll, mu, status)
+
+
+def composition(theta, J):
+    """(total, fractions) of a component fit's theta (..., J + K): the sum of the J signal scales (ascending j) and
+    their shares theta_j / total, shape (..., J) -- on rows composed onto the pure flavours, the fitted flavour
+    composition.  NaN where the total is 0."""
+    th = np.asarray(theta, dtype=np.float64)
+    if th.ndim < 1 or not 1 <= J <= th.shape[-1]:
+        raise ValueError("composition: theta must have shape (.., J + K) with J = %r signal components in front, got %s" % (J, th.shape))
+    total = th[..., 0]
+    for j in range(1, J):
+        total = total + th[..., j]
+    with np.errstate(all="ignore"):
+        frac = np.where(total[..., None] > 0, th[..., :J] / total[..., None], np.nan)
+    return total, frac
+
+
+def composition_statistic(mu, theta, mu_hat, theta_hat, data, prior=None, log=np.log):
+    """(lam, mag): lambda = f(theta) - f(theta_hat) of a fit at a held composition against the free component fit, formed
+    as nusi_plan_response_limit forms it (``_limit_lambda``, vectorised): per bin (mu - mu_hat) - data log(mu / mu_hat)
+    over the bins with data_c > 0 and mu_hat_c > 0 (mu - mu_hat on the others), ``tree()``, then the templates'
+    penalty differences ascending; mag is the same sum over the terms' magnitudes.  q = 2 lambda.
+
+    mu, mu_hat: (..., C).  theta: (..., 1 + K) of ``fit`` (or ahat[..., None] of ``profile``), theta_hat: (..., J + K) of
+    the component fit: the templates are the last K = theta.shape[-1] - 1 entries of both.  prior: the templates'
+    (mean, sigma) as for fit_host, None = no penalty.  All leading axes broadcast."""
+    mu, muh = np.asarray(mu, dtype=np.float64), np.asarray(mu_hat, dtype=np.float64)
+    th, thh = np.asarray(theta, dtype=np.float64), np.asarray(theta_hat, dtype=np.float64)
+    d = np.asarray(data, dtype=np.float64)
+    K = th.shape[-1] - 1
+    if mu.shape[-1] != d.shape[0] or muh.shape[-1] != d.shape[0] or K < 0 or thh.shape[-1] < K + 1:
+        raise ValueError("composition_statistic: mu, mu_hat (.., C), theta (.., 1 + K) and theta_hat (.., J + K) do not match")
+    m, w = _prior(K, prior)
+    mu, muh = np.broadcast_arrays(mu, muh)
+    with np.errstate(all="ignore"):
+        lact = (d > 0) & (muh > 0)
+        dmu = mu - muh
+        ratio = np.where(lact, mu / muh, 1.0)
+        lr = np.zeros(ratio.shape)
+        flat_r, flat_l, flat_a = ratio.reshape(-1), lr.reshape(-1), lact.reshape(-1)
+        for i in np.nonzero(flat_a)[0]:
+            flat_l[i] = float(log(flat_r[i])) if flat_r[i] > 0.0 else -np.inf
+        lr = flat_l.reshape(ratio.shape)
+        pl = np.where(lact, d * lr, 0.0)
+        term = np.where(lact, dmu - pl, dmu)
+        mag = np.where(lact, np.abs(dmu) + np.abs(pl), np.abs(dmu))
+        lam, mg = tree(term), tree(mag)
+        for j in range(1, 1 + K):
+            if w[j] > 0:
+                tj, hj = th[..., j], thh[..., thh.shape[-1] - K + j - 1]
+                dj = tj - hj
+                sj = (tj - m[j]) + (hj - m[j])
+                pd = ((0.5 * w[j]) * dj) * sj
+                lam = lam + pd
+                mg = mg + np.abs(pd)
+    return lam, mg
 
 
 def _fit_fixed_one(a, s, X, B, d, m, w, ku, start=None):

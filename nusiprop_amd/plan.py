@@ -457,6 +457,96 @@ class Plan:
         return self._minimise_device("fit", d_R_ptr, ntab, spectra, data, d_theta_ptr, d_nll_ptr, d_mu_ptr, d_status_ptr,
                                      stream_ptr)
 
+    def _stack(self, R3, who):
+        """(R3 as a contiguous (ntab, J, M, C) array, J, C) for the call ``who``."""
+        R3 = np.ascontiguousarray(R3, dtype=np.float64)
+        C = self.detector_bins()
+        if R3.ndim != 4 or (C and R3.shape[2:] != (self.T + 1, C)):   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("%s: R3 must have shape (ntab, J, %d, %d), got %s" % (who, self.T + 1, C, R3.shape))
+        return R3, R3.shape[1], C
+
+    def fit_components(self, R3, spectra, data):
+        """``fit`` with J = 2 .. 3 SIGNAL components per table and spectrum, on the GPU: R3 (ntab, J, M, C) is a stack
+        of folded matrices -- the folded rows of ``response_mass``, or those rows composed onto the pure flavours
+        (``compose_response`` with sources.mass_fractions of e, mu, tau) -- and every normalisation floats, >= 0, together
+        with the plan's K = 0 .. 3 templates: mu = sum_j theta_j s_j + sum_i theta_{J+i-1} T_i + background.  Returns
+        (theta (ntab, Q, J + K), nll (ntab, Q), mu (ntab, Q, C), status (ntab, Q) int32) as ``fit`` does; FIT_FLAT: no
+        signal component is live (the templates are fitted all the same), FIT_BOUNDARY: every signal theta_j ends at 0,
+        FIT_ZERO << j for j < J + K, FIT_SINGULAR: the data do not tell the components apart (proportional rows, or
+        fewer bins with data than components).  theta, mu and status equal detector.fit_components_host bit for bit;
+        detector.composition(theta, J) gives the total and the fitted shares.  J = 1 is ``fit`` / ``profile``."""
+        R3, J, C = self._stack(R3, "fit_components")
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data) if C else np.ascontiguousarray(data, dtype=np.float64)     # (no detector: as above)
+        ntab, Q = R3.shape[0], len(S)
+        theta, nll, mu = np.zeros((ntab, Q, J + self.templates())), np.zeros((ntab, Q)), np.zeros((ntab, Q, C))
+        status = np.zeros((ntab, Q), dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(_lib.load().nusi_plan_response_fit_components_host(
+            self._h, R3.ctypes.data_as(dp), ntab, J, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp) if d is not None else None,
+            theta.ctypes.data_as(dp), nll.ctypes.data_as(dp), mu.ctypes.data_as(dp),
+            status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return theta, nll, mu, status
+
+    def fit_components_device(self, d_R3_ptr, ntab, J, spectra, data, d_theta_ptr, d_nll_ptr=None, d_mu_ptr=None,
+                              d_status_ptr=None, stream_ptr=None):
+        """Asynchronous fit_components on a device-resident stack: d_R3 [ntab][J][M][C], d_theta [ntab][Q][J + K], d_nll
+        [ntab][Q], d_mu [ntab][Q][C] (doubles) and d_status [ntab][Q] (ints) are raw pointers, every output but d_theta
+        may be 0 / None; the spectra and data are host data and are copied.  Returns Q."""
+        S, _ = self._spectra(spectra, None)
+        d = self._data(data)
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+        _lib.check(_lib.load().nusi_plan_response_fit_components(
+            self._h, vp(d_R3_ptr), int(ntab), int(J), S.ctypes.data_as(dp), len(S),
+            d.ctypes.data_as(dp) if d is not None else None, vp(d_theta_ptr) if d_theta_ptr else None,
+            vp(d_nll_ptr) if d_nll_ptr else None, vp(d_mu_ptr) if d_mu_ptr else None,
+            vp(d_status_ptr) if d_status_ptr else None, vp(stream_ptr) if stream_ptr else None))
+        return len(S)
+
+    def composition_scan(self, R3, spectra, data, phi, prior=None):
+        """The statistic q(phi) = 2 (min f at the composition phi - the free minimum) that draws a contour in the flavour
+        triangle.  R3 (ntab, 3, M, C): three folded rows per table; phi (Qc, 3) or (ntab, Qc, 3): weights >= 0 on those
+        rows.  It composes R = compose_response(R3, phi), fits every composed matrix with the scale floating -- ``profile``
+        without templates, ``fit`` with them -- fits the components freely with ``fit_components`` on R3, and forms
+        lambda with detector.composition_statistic.  prior: the (mean, sigma) given to set_templates (the plan does not
+        hand them back), None = no penalty terms.
+
+        The free fit spans a_j >= 0 on the GIVEN rows: on raw mass-resolved rows that is the cone of mass fractions >= 0,
+        which is larger than what any flavour composition reaches.  To restrict it to the physical flavour triangle, pass
+        rows composed onto the pure flavours, R3 = compose_response(R3_mass, [mass_fractions(e_f) for f in e, mu, tau]),
+        with phi then the flavour fractions themselves.
+
+        Returns (q (ntab, Qc, Q) = max(2 lambda, 0), fixed, free, word): fixed = (theta (ntab, Qc, Q, 1 + K), nll, mu,
+        status) of the fits at the held compositions, free = fit_components' four arrays, word (ntab, Qc, Q) int32 = the
+        FIT_NOT_CONVERGED, FIT_SINGULAR and FIT_INFINITE flags of either fit, ORed per entry (0: q is a statistic)."""
+        from . import detector as _det
+        R3, J, C = self._stack(R3, "composition_scan")
+        if J != 3:
+            raise ValueError("composition_scan: R3 must have shape (ntab, 3, M, C), got %s" % (R3.shape,))
+        ntab, M = R3.shape[0], R3.shape[2]
+        k = self._kappa(phi, ntab)
+        if np.ndim(phi) == 1:
+            raise ValueError("composition_scan: phi must have shape (Qc, 3) or (ntab, Qc, 3)")
+        Qc, K = k.shape[1], self.templates()
+        R = self.compose_response(R3, k).reshape(ntab * Qc, M, C)
+        if K:
+            th, nll, mu, st = self.fit(R, spectra, data)
+        else:
+            ah, nll, mu, st = self.profile(R, spectra, data)
+            th = ah[..., None]
+        Q = nll.shape[1]
+        fixed = (th.reshape(ntab, Qc, Q, 1 + K), nll.reshape(ntab, Qc, Q), mu.reshape(ntab, Qc, Q, C),
+                 st.reshape(ntab, Qc, Q))
+        free = self.fit_components(R3, spectra, data)
+        lam, _ = _det.composition_statistic(fixed[2], fixed[0], free[2][:, None], free[0][:, None],
+                                            np.asarray(data, dtype=np.float64), prior=prior, log=np.log)
+        with np.errstate(invalid="ignore"):
+            q = np.where(np.isnan(lam), np.nan, np.maximum(2.0 * lam, 0.0))
+        bad = _lib.FIT_NOT_CONVERGED | _lib.FIT_SINGULAR | _lib.FIT_INFINITE
+        word = ((fixed[3] & bad) | (free[3][:, None] & bad)).astype(np.int32)
+        return q, fixed, free, word
+
     def _held(self, who, scale, Q):
         if scale is None:
             raise ValueError("%s: the held scale is required (a number or (Q,))" % who)
