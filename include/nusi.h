@@ -803,7 +803,9 @@ int nusi_plan_draw_normals_host(nusi_plan *plan, const double *center, const dou
  *     the fits use the plan's means.  nusi_plan_response_belt under this value returns NUSI_EPARAM and does no device
  *     work: the profile construction has no such variant.
  * With K = 0 or no constrained template every value gives FIXED's bits (and runs FIXED's kernels).  A draw's identity is
- * global: every scratch budget, chunking and p-slicing give the same bits.  Any other value is refused. */
+ * global: every scratch budget, chunking and p-slicing give the same bits.  Any other value is refused.
+ * nusi_plan_response_composition_belt builds the FIXED ensemble only: under GLOBAL or PRIOR with a constrained template
+ * it returns NUSI_EPARAM and does no device work; without one it runs as under FIXED. */
 #define NUSI_OPT_TOY_NUISANCE 17
 #define NUSI_TOYS_FIXED 0
 #define NUSI_TOYS_GLOBAL 1
@@ -950,6 +952,95 @@ int nusi_plan_response_belt_host(nusi_plan *plan, const double *R, int ntab, con
                                  double alpha, double *lo, double *hi, int *idx, int *status, int *exceed, int *tally,
                                  double *q_obs, double *theta_obs, int *words_obs, double *theta_all, double *stat_all,
                                  int *words_all, double *data_all);
+/* nusi_plan_response_composition_belt (k_composition_belt, k_composition_accept): the toy-calibrated confidence region
+ * of the source's flavour composition -- the Feldman-Cousins region by the profile construction -- on a grid of
+ * compositions, in one call.  What nusi_plan_response_belt does for the signal's scale, this call does for the point
+ * phi of the flavour triangle: per table t and spectrum q the set of grid points whose toy p-value of the data exceeds
+ * alpha.  The statistic is q(phi) = 2 (min f at the held composition phi - the free minimum) of
+ * nusi_plan_response_fit_components, which is chi^2 only away from the boundary theta_j >= 0 -- where most fits end --,
+ * so the toys calibrate it.  detector.composition_belt_host / detector.composition_accept (numpy) are the same rules, and
+ * the call reproduces them: the toys, theta, the words' flags, the counts and the mask to the bit, q_obs and stat to the
+ * last bits of the log.  K = nusi_plan_templates(plan) = 0 .. 3.
+ *
+ *   The input.  d_R3 [ntab][3][M][C], a folded stack: nusi_plan_response_fit_components' input with J = 3 (J = 2 is not
+ *     built).  phi [G][3], or [ntab][G][3] where phi_tables != 0: weights on the three rows, finite, >= 0 and not all
+ *     three zero; G = 1 .. NUSI_REGION_GRID_MAX.
+ *   A record (t, q, g) goes through four steps.
+ *   1. The held signal: the composed row in nusi_plan_response_compose's expression, then the events call's accumulator,
+ *         r[n][c] = (phi_0 R3[t][0][n][c] + phi_1 R3[t][1][n][c]) + phi_2 R3[t][2][n][c],  s_phi[c] = sum_n r[n][c] S[q][n],
+ *     n ascending from 1, every product and sum rounded: bit for bit the front half that nusi_plan_response_fit /
+ *     _profile compute on the composed matrix.  The three components s_j[c] are nusi_plan_response_fit_components'.
+ *   2. The free fit against a data set d: nusi_plan_response_fit_components' record with J = 3 and the K templates,
+ *     theta_hat [3 + K], mu_hat, word.
+ *   3. The held fit at phi_g: with templates nusi_plan_response_fit's record on X = [s_phi, T_1 .. T_K]; at K = 0
+ *     nusi_plan_response_profile's on s_phi.  The composition is held; its overall scale and the templates float.  theta
+ *     [1 + K], mu, word.
+ *   4. The statistic: lambda as nusi_plan_response_limit forms it -- per bin (mu - mu_hat) - d log(mu / mu_hat) over the
+ *     bins with d > 0 and mu_hat > 0 (mu - mu_hat on the others), the tree sum, then the templates' penalty differences
+ *     ascending, the held theta_j against theta_hat_{3 + j - 1} --, stat = lambda > 0 ? 2 lambda : +0.0, and NaN where
+ *     either word has NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR.  There is no one-sided mode.
+ *   The observed side.  Steps 2 - 4 on data [C] give d_q_obs [ntab][Q][G]; d_theta_obs [ntab][Q][1 + G][3 + K]: [0] is
+ *     the free fit's theta_hat, [1 + g] the held fit's theta in slots 0 .. K with the other slots +0.0; d_words_obs
+ *     [ntab][Q][1 + G] the words.  A point is VALID iff neither observed word is flagged: a flagged free fit gives
+ *     NUSI_REGION_NO_FIT for the pair, a flagged held fit after a good free fit NUSI_REGION_BAD_POINT.  An invalid point
+ *     has q_obs = NaN, no toys, counts of 0 and raw outputs of NaN (doubles) and 0 (ints and the counts of data_all).
+ *   The toys.  Toy p < P of a valid point is the draw ("Drawing counts") of the observed held fit's own mu with the
+ *     identity (seed, stream = t, row = q G + g, p, c) -- nusi_plan_response_belt's convention -- and gets steps 2 - 4 at
+ *     phi_g.  d_theta_all [ntab][Q][G][P][3 + K] (the free fit's theta_hat, NaN where it failed), d_stat_all
+ *     [ntab][Q][G][P], d_words_all [..][P][2] (the free fit's word, the held fit's) and d_data_all [..][P][C] are the raw
+ *     records.  d_exceed [ntab][Q][G]: the toys with stat >= q_obs (a NaN on either side never counts).  d_tally
+ *     [ntab][Q][G][4]: [0] the free fit failed, [1] the held fit failed and the free fit did not, [2] the free fit ends
+ *     with a SIGNAL component at zero (NUSI_FIT_ZERO << j for a j < 3, NUSI_FIT_BOUNDARY or NUSI_FIT_FLAT: how far from
+ *     Wilks' theorem the record is), [3] the free fit is NUSI_FIT_INFINITE.  Both are zeroed on the stream and added to
+ *     with integer atomics.
+ *   Acceptance.  nv = P - tally[0] - tally[1]; a point is accepted iff it is valid, nv > 0 and (double)exceed > alpha
+ *     (double)nv -- one multiplication, one strict comparison; alpha in (0, 1).  d_accept [ntab][Q][G]: 0 or 1.  d_status
+ *     [ntab][Q]: NUSI_REGION_NO_FIT, _BAD_POINT (above, or a valid point with nv <= 0), _EMPTY (no point accepted), _ALL
+ *     (there is a valid point and every valid point is accepted: the grid does not bound the region).  d_best [ntab][Q]:
+ *     the g of the smallest q_obs among the valid points, ties to the lowest g, or -1.  Nothing is interpolated.
+ *
+ * Every output is a DEVICE pointer and may be NULL, but not all of them; d_accept, d_status or d_best need d_exceed,
+ * d_tally, d_q_obs and d_words_obs (no plan scratch, no budget chunking).  The grid is nusi_plan_response_belt's: units of
+ * one table and QB rows of its Q G, cut into launches of at most 2^22 units, p-slices on the grid's z
+ * (NUSI_OPT_ENSEMBLE_PSLICES, or automatic); every p-slice recomputes a record's observed side and slice 0 stores it.  A
+ * draw's identity is global, so every slicing gives the same bits.  Only the FIXED toy ensemble is built: where
+ * NUSI_OPT_TOY_NUISANCE is not NUSI_TOYS_FIXED and a template is constrained, the call returns NUSI_EPARAM.
+ *
+ * nusi_composition_belt_shape: the call's size limits as a pure function -- no plan, no device; the call itself applies
+ * it with the detector's C and the plan's K.  NUSI_OK and *units (if not NULL) = ntab ceil(Q G / QB), or NUSI_EPARAM for
+ * C outside 1 .. NUSI_DETECTOR_BINS_MAX, K outside 0 .. NUSI_FIT_TEMPLATES_MAX, ntab < 1, Q outside 1 .. 2^19, G outside
+ * 1 .. NUSI_REGION_GRID_MAX, P outside 1 .. NUSI_DRAW_DATASETS_MAX, ntab Q G >= 2^31 (a record's row in an int), or an
+ * observed-side output's element count -- ntab Q (1 + G) (3 + K), the widest -- >= 2^31, nusi_fit_components_shape's rule
+ * (the raw arrays' counts are size_t).
+ *
+ * S, data and phi are host arrays and are copied.  Asynchronous and ordered with the plan's other detector calls like
+ * nusi_plan_response_fit.  NUSI_ESTATE without a detector; NUSI_EPARAM for the shape limits, a NULL d_R3, S, data or phi,
+ * a phi entry that is negative or not finite or a point with all three zero, an alpha outside (0, 1), a negative or
+ * non-finite entry of S or data, every output NULL, the dependency rule above, or the toy ensemble; a refused call
+ * changes nothing and does no device work.  _host: R3 and the outputs in host memory, synchronous. */
+#define NUSI_REGION_GRID_MAX 1024
+#define NUSI_REGION_NO_FIT 1
+#define NUSI_REGION_BAD_POINT 2
+#define NUSI_REGION_EMPTY 4
+#define NUSI_REGION_ALL 8
+int nusi_composition_belt_shape(int C, int K, int ntab, int Q, int G, int P, long long *units);
+int nusi_plan_response_composition_belt(nusi_plan *plan, const double *d_R3 /* [ntab][3][M][C] */, int ntab,
+                                        const double *S /* [Q][M] */, int Q, const double *data /* [C] */,
+                                        const double *phi /* [G][3] or [ntab][G][3] */, int phi_tables, int G, int P,
+                                        unsigned long long seed, double alpha, int *d_accept /* [ntab][Q][G] */,
+                                        int *d_status /* [ntab][Q] */, int *d_best /* [ntab][Q] */,
+                                        int *d_exceed /* [ntab][Q][G] */, int *d_tally /* [ntab][Q][G][4] */,
+                                        double *d_q_obs /* [ntab][Q][G] */,
+                                        double *d_theta_obs /* [ntab][Q][1 + G][3 + K] */,
+                                        int *d_words_obs /* [ntab][Q][1 + G] */,
+                                        double *d_theta_all /* [ntab][Q][G][P][3 + K] */,
+                                        double *d_stat_all /* [ntab][Q][G][P] */, int *d_words_all /* [ntab][Q][G][P][2] */,
+                                        double *d_data_all /* [ntab][Q][G][P][C] */, void *stream);
+int nusi_plan_response_composition_belt_host(nusi_plan *plan, const double *R3, int ntab, const double *S, int Q,
+                                             const double *data, const double *phi, int phi_tables, int G, int P,
+                                             unsigned long long seed, double alpha, int *accept, int *status, int *best,
+                                             int *exceed, int *tally, double *q_obs, double *theta_obs, int *words_obs,
+                                             double *theta_all, double *stat_all, int *words_all, double *data_all);
 /* Kernel times (ms) of the last nusi_plan_evolve* / nusi_plan_response*: [0] Gamma/alphaTilde
  * tables, [1] alpha table, [2] cascade.  Synchronises the plan's stream. */
 int nusi_plan_stage_ms(nusi_plan *plan, float *ms3);

@@ -90,6 +90,7 @@ EXPORTS = [
     "nusi_plan_draw_normals", "nusi_plan_draw_normals_host",
     "nusi_plan_response_inject", "nusi_plan_response_inject_host",
     "nusi_belt_shape", "nusi_plan_response_belt", "nusi_plan_response_belt_host",
+    "nusi_composition_belt_shape", "nusi_plan_response_composition_belt", "nusi_plan_response_composition_belt_host",
 ]
 
 # nusi_plan_set_cascade kinds and nusi_plan_set_option options (include/nusi.h)
@@ -115,6 +116,9 @@ INJECT_TWO_SIDED, INJECT_UPPER, INJECT_DISCOVERY = 0, 1, 2     # Plan.inject's m
 # Plan.belt: the most grid points and the status word's bits (include/nusi.h NUSI_BELT_*, detector.BELT_*)
 BELT_GRID_MAX = 64
 BELT_NO_GRID, BELT_NO_FIT, BELT_BAD_POINT, BELT_EMPTY, BELT_LO_EDGE, BELT_HI_EDGE, BELT_GAPS = 1, 2, 4, 8, 16, 32, 64
+# Plan.composition_belt: the most points of the composition grid and the status word's bits (NUSI_REGION_*, detector.REGION_*)
+REGION_GRID_MAX = 1024
+REGION_NO_FIT, REGION_BAD_POINT, REGION_EMPTY, REGION_ALL = 1, 2, 4, 8
 DRAW_DATASETS_MAX = 1 << 26     # Plan.draw: the toys per bin (the generator's counter holds p * 64 + c)
 DRAW_COUNTS_MAX = ((1 << 31) - 1) * 256     # ... and the counts of a call, rows * P * C (one launch, 256 counts a block)
 
@@ -223,6 +227,11 @@ def load():
                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "nusi_plan_response_belt_host": (i, [vp, dp, i, dp, i, dp, dp, i, dp, i, ctypes.c_ulonglong, i, d,
                                              dp, dp, ip, ip, ip, ip, dp, dp, ip, dp, dp, ip, dp]),
+        "nusi_composition_belt_shape": (i, [i, i, i, i, i, i, ctypes.POINTER(ctypes.c_longlong)]),
+        "nusi_plan_response_composition_belt": (i, [vp, vp, i, dp, i, dp, dp, i, i, i, ctypes.c_ulonglong, d,
+                                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "nusi_plan_response_composition_belt_host": (i, [vp, dp, i, dp, i, dp, dp, i, i, i, ctypes.c_ulonglong, d,
+                                                         ip, ip, ip, ip, ip, dp, dp, ip, dp, dp, ip, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

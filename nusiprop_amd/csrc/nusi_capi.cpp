@@ -2972,6 +2972,122 @@ int nusi_plan_response_belt_host(nusi_plan* pl, const double* R, int ntab, const
                        });
 }
 
+// The toy-calibrated region of the flavour composition (nusi_detector.hip k_composition_belt, then
+// k_composition_accept).  The size limits are a pure function, which the call applies with the detector's C and the
+// plan's K.  data rides in events_stage's data slot (P = 1) and phi as its extra vector.  No plan scratch: the mask needs
+// exceed, tally, q_obs and words_obs from the caller.
+int nusi_composition_belt_shape(int C, int K, int ntab, int Q, int G, int P, long long* units)
+{
+    const std::string w = "response composition belt: ";
+    if (C < 1 || C > NUSI_DETECTOR_BINS_MAX) return fail(NUSI_EPARAM, w + "C outside 1 .. NUSI_DETECTOR_BINS_MAX");
+    if (K < 0 || K > NUSI_FIT_TEMPLATES_MAX) return fail(NUSI_EPARAM, w + "K outside 0 .. NUSI_FIT_TEMPLATES_MAX");
+    if (ntab < 1 || Q < 1 || Q > (1 << 19)) return fail(NUSI_EPARAM, w + "need ntab >= 1 and 1 <= Q <= 2^19");
+    if (G < 1 || G > NUSI_REGION_GRID_MAX) return fail(NUSI_EPARAM, w + "G outside 1 .. NUSI_REGION_GRID_MAX");
+    if (P < 1 || P > NUSI_DRAW_DATASETS_MAX) return fail(NUSI_EPARAM, w + "P outside 1 .. NUSI_DRAW_DATASETS_MAX");
+    const long long rows = (long long)Q * G;   // (<= 2^29)
+    if ((long long)ntab * rows >= (1ll << 31)) return fail(NUSI_EPARAM, w + "too many records (ntab Q G >= 2^31)");
+    // (theta_obs [ntab][Q][1 + G][3 + K] is the widest of the observed side's outputs; ntab Q (1 + G) < 2^32, 3 + K <= 6)
+    if ((long long)ntab * Q * (1 + G) * (3 + K) >= (1ll << 31))
+        return fail(NUSI_EPARAM, w + "too many records (an output's elements, ntab Q (1 + G) (3 + K), >= 2^31)");
+    const long long QB = nusi::composition_belt_block(C);
+    if (units) *units = (long long)ntab * ((rows + QB - 1) / QB);
+    return NUSI_OK;
+}
+
+static int composition_belt_check(const nusi_plan* pl, const void* R3, int ntab, const double* S, int Q, const double* data,
+                                  const double* phi, int phi_tables, int G, int P, double alpha, bool any_out, bool mask,
+                                  bool mask_inputs)
+{
+    const std::string w = "response composition belt: ";
+    if (int r = detector_plan(pl, "response composition belt")) return r;
+    if (int r = nusi_composition_belt_shape(pl->det_C, pl->fit_K, ntab, Q, G, P, nullptr)) return r;
+    if (pl->toy_nuis != NUSI_TOYS_FIXED) {
+        bool constrained = false;
+        for (int j = 0; j < pl->fit_K; ++j) constrained = constrained || pl->fit_w[j] > 0.0;
+        if (constrained)
+            return fail(NUSI_EPARAM, w + "NUSI_OPT_TOY_NUISANCE is not NUSI_TOYS_FIXED and a template is constrained: only the FIXED toy ensemble is built");
+    }
+    if (!R3 || !S || !data || !phi) return fail(NUSI_EPARAM, w + "R3, S, data and phi must not be NULL");
+    const size_t np = (size_t)(phi_tables ? ntab : 1) * G;
+    for (size_t e = 0; e < np; ++e) {
+        const double* f = phi + 3 * e;
+        for (int j = 0; j < 3; ++j)
+            if (!(f[j] >= 0.0) || !std::isfinite(f[j])) return fail(NUSI_EPARAM, w + "an entry of phi is negative or not finite");
+        if (f[0] == 0.0 && f[1] == 0.0 && f[2] == 0.0) return fail(NUSI_EPARAM, w + "a point of phi has all three weights zero");
+    }
+    if (!(alpha > 0.0 && alpha < 1.0)) return fail(NUSI_EPARAM, w + "alpha must lie in (0, 1)");
+    if (!any_out) return fail(NUSI_EPARAM, w + "every output is NULL: nothing to do");
+    if (mask && !mask_inputs) return fail(NUSI_EPARAM, w + "accept, status and best need exceed, tally, q_obs and words_obs");
+    return events_check(pl, "response composition belt", (const double*)R3, ntab, S, Q, nullptr, data, 1);
+}
+
+int nusi_plan_response_composition_belt(nusi_plan* pl, const double* d_R3, int ntab, const double* S, int Q, const double* data,
+                                        const double* phi, int phi_tables, int G, int P, unsigned long long seed, double alpha,
+                                        int* d_accept, int* d_status, int* d_best, int* d_exceed, int* d_tally, double* d_q_obs,
+                                        double* d_theta_obs, int* d_words_obs, double* d_theta_all, double* d_stat_all,
+                                        int* d_words_all, double* d_data_all, void* stream)
+{
+    const bool mask = d_accept || d_status || d_best;
+    const bool any_out = mask || d_exceed || d_tally || d_q_obs || d_theta_obs || d_words_obs || d_theta_all || d_stat_all ||
+                         d_words_all || d_data_all;
+    if (int r = composition_belt_check(pl, d_R3, ntab, S, Q, data, phi, phi_tables, G, P, alpha, any_out, mask,
+                                       d_exceed && d_tally && d_q_obs && d_words_obs))
+        return r;
+    const size_t nn = (size_t)ntab * Q, np = (size_t)(phi_tables ? ntab : 1) * G * 3;
+    HIPCHECK(hipSetDevice(pl->device));
+    hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+    const int C = pl->det_C;
+    if (int r = events_stage(pl, S, Q, nullptr, data, 1, s, phi, np)) return r;
+    const EvtLayout l = evt_layout(pl, Q, 1, np);
+    const double* dS = pl->d_evt;
+    const double* d_data = pl->d_evt + l.data;
+    const double* d_phi = pl->d_evt + l.extra;
+    if (d_exceed) HIPCHECK(hipMemsetAsync(d_exceed, 0, sizeof(int) * nn * G, s));
+    if (d_tally) HIPCHECK(hipMemsetAsync(d_tally, 0, sizeof(int) * nn * G * 4, s));
+    int ncu = 0;
+    HIPCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device));
+    const long long want = (long long)kEnsBlocksPerCU * (ncu > 0 ? ncu : 1);
+    const long long QB = nusi::composition_belt_block(C), nu = (long long)ntab * (((long long)Q * G + QB - 1) / QB);
+    const int ps = pl->ens_pslices > 0 ? std::min(pl->ens_pslices, P)
+                                       : (int)std::min<long long>(std::max(P / kEnsSliceDatasets, 1), (want + nu - 1) / nu);
+    HIPCHECK(nusi::launch_composition_belt(pl->gd, d_R3, ntab, dS, Q, d_data, d_phi, phi_tables != 0, G, P, seed,
+                                           detector_bg(pl), C, pl->fit_K, pl->d_tpl, pl->fit_m, pl->fit_w, ps, d_exceed, d_tally,
+                                           d_words_obs, d_q_obs, d_theta_obs, d_theta_all, d_stat_all, d_words_all, d_data_all,
+                                           s));
+    if (mask)
+        HIPCHECK(nusi::launch_composition_accept((int)nn, G, P, alpha, d_exceed, d_tally, d_words_obs, d_q_obs, d_accept,
+                                                 d_status, d_best, s));
+    return detector_mark(pl, s);
+}
+
+int nusi_plan_response_composition_belt_host(nusi_plan* pl, const double* R3, int ntab, const double* S, int Q,
+                                             const double* data, const double* phi, int phi_tables, int G, int P,
+                                             unsigned long long seed, double alpha, int* accept, int* status, int* best,
+                                             int* exceed, int* tally, double* q_obs, double* theta_obs, int* words_obs,
+                                             double* theta_all, double* stat_all, int* words_all, double* data_all)
+{
+    const bool mask = accept || status || best;
+    const bool any_out = mask || exceed || tally || q_obs || theta_obs || words_obs || theta_all || stat_all || words_all ||
+                         data_all;
+    if (int r = composition_belt_check(pl, R3, ntab, S, Q, data, phi, phi_tables, G, P, alpha, any_out, mask,
+                                       exceed && tally && q_obs && words_obs))
+        return r;
+    const size_t nn = (size_t)ntab * Q, ng = nn * G, NC = (size_t)pl->fit_K + 3;
+    // (R3 is ntab 3 folded matrices in a row)
+    return events_host(pl, R3, ntab * 3,
+                       {{accept, ng, sizeof(int)}, {status, nn, sizeof(int)}, {best, nn, sizeof(int)}, {exceed, ng, sizeof(int)},
+                        {tally, ng * 4, sizeof(int)}, {q_obs, ng, sizeof(double)}, {theta_obs, nn * (G + 1) * NC, sizeof(double)},
+                        {words_obs, nn * (G + 1), sizeof(int)}, {theta_all, ng * P * NC, sizeof(double)},
+                        {stat_all, ng * P, sizeof(double)}, {words_all, ng * P * 2, sizeof(int)},
+                        {data_all, ng * P * pl->det_C, sizeof(double)}},
+                       "response composition belt", [&](const double* dI, void* const* d) {
+                           return nusi_plan_response_composition_belt(pl, dI, ntab, S, Q, data, phi, phi_tables, G, P, seed, alpha,
+                                                                      (int*)d[0], (int*)d[1], (int*)d[2], (int*)d[3], (int*)d[4],
+                                                                      (double*)d[5], (double*)d[6], (int*)d[7], (double*)d[8],
+                                                                      (double*)d[9], (int*)d[10], (double*)d[11], nullptr);
+                       });
+}
+
 int nusi_plan_profile_begin(nusi_plan* pl, int max_calls)
 {
     HIPCHECK(hipSetDevice(pl->device));

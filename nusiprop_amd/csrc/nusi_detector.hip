@@ -34,6 +34,10 @@
 //                         k_inject's toy body once against the data and then per toy, on records (table, spectrum, grid
 //                         point of the test scale), the toys drawn from the observed conditional fit's expectation; then
 //                         per (table, spectrum) the accepted grid points as an interval (nusi_plan_response_belt)
+//   k_composition_belt<NCF>, k_composition_accept
+//                         k_belt's construction for the flavour composition: per (table, spectrum, point of the composition
+//                         grid) the free fit of three signal components and the fit at the held composition, against the
+//                         data and then per toy; then the accepted points (nusi_plan_response_composition_belt)
 //
 // The iterations several of these kernels run exist once, as text the kernels #include inside their bodies (not as
 // __device__ helpers, which moved the kernels' registers: DESIGN.md sec. 4, "The shared iterations"):
@@ -45,6 +49,8 @@
 //   nusi_conditional_newton.inc  k_conditional_fit's rounds: k_conditional_fit, k_inject, k_belt
 //   nusi_toy_body.inc            one data set's best fit, conditional fit and statistic: k_inject, k_belt and their
 //                                k_nuis_ forms
+//   nusi_composition_body.inc    one data set's free fit, held fit and statistic: k_composition_belt (it #includes
+//                                nusi_fit_newton.inc twice and nusi_profile_chain1.inc)
 //   nusi_inject_setup.inc, nusi_inject_store.inc, nusi_belt_setup.inc, nusi_belt_store.inc
 //                                what stands around the toy's draw in k_inject and k_belt: those and k_nuis_inject, k_nuis_belt
 //   nusi_search_setup.inc, nusi_search_side.inc
@@ -1951,6 +1957,259 @@ hipError_t launch_belt_accept(const double* frac, int G, const double* ref, int 
     const unsigned nb = (unsigned)(((long long)(pr1 - pr0) + kBeltAcceptThreads - 1) / kBeltAcceptThreads);
     hipLaunchKernelGGL(k_belt_accept, dim3(nb), dim3(kBeltAcceptThreads), 0, s, ii, exceed, exceed_compact ? 1 : 0, tally,
                        tally_compact ? 1 : 0, wobs, wobs_compact ? 1 : 0, P, alpha, lo, hi, idx, status);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_composition_belt<NCF>: the toy-calibrated region of the flavour composition (nusi_plan_response_composition_belt),
+// NCF = 3 + K = 3 .. 6, on k_belt's block shape: a record is (t, q, g) with row r = q G + g of the table's Q G rows, unit
+// u is table u / nrb and row block u % nrb, a group of the block takes one row, p-slices on the grid's z.  g is a point
+// phi[g] (or phi[t][g]) of the composition grid.  The front half runs once per row with FOUR accumulators, each in
+// events' order: the three components s_j of k_components_fit<3, .> and the held signal s_phi, the composed row
+// r = (phi_0 R3[t][0][n][c] + phi_1 R3[t][1][n][c]) + phi_2 R3[t][2][n][c] in k_response_compose's expression -- what
+// nusi_plan_response_fit / _profile accumulate on the composed matrix, to the bit.  Then one pass against the staged data
+// and one per toy, each nusi_composition_body.inc: the free fit, the held fit, lambda.  The observed pass gives the
+// record's observed side, q_obs and mu_inj, the held fit's own mu; toy p of lane c is draw::poisson(mu_inj[c]; seed,
+// stream = t, row = r, p, c).  Every p-slice runs the observed pass and slice 0 stores it.  An invalid record
+// (NOT_CONVERGED | SINGULAR in either observed word) stays in the loop with mu_inj = 0, which draws nothing: it adds to
+// no count and stores the raw arrays' NaN / 0.  A row outside the table (r >= Q G) stores nothing; every load index is
+// clamped (cc, rc and with it q and g).  No LDS.
+// Both fits' registers are live across the toy loop with XF, S1F, s_phi, mu_inj and q_obs: the instances ask for as few
+// waves per SIMD as that takes (comp_belt_waves; DESIGN.md sec. 4, "The composition region").
+// ---------------------------------------------------------------------------
+struct CompBeltOut {
+    int *exceed, *tally, *wobs;            // [ntab][Q][G], [ntab][Q][G][4], [ntab][Q][1 + G] or nullptr
+    double *qobs, *thobs;                  // [ntab][Q][G], [ntab][Q][1 + G][NCF] or nullptr
+    double *theta, *stat;                  // [ntab][Q][G][P][NCF], [ntab][Q][G][P] or nullptr
+    int* words;                            // [ntab][Q][G][P][2] or nullptr
+    double* data;                          // [ntab][Q][G][P][C] or nullptr
+};
+struct CompBeltIn {
+    const double *data, *phi;              // [C], [G][3] or [ntab][G][3]
+    unsigned long long seed;
+    int G, phi_tables;
+};
+
+constexpr int comp_belt_waves(int NCF) { return NCF == 3 ? 3 : NCF <= 5 ? 2 : 1; }
+
+template <int NCF>
+__global__ __launch_bounds__(kEvThreads) __attribute__((amdgpu_waves_per_eu(comp_belt_waves(NCF))))
+void k_composition_belt(const double* __restrict__ R3, const double* __restrict__ S, const double* __restrict__ bg,
+                        const double* __restrict__ T, const FitPrior tp, const double kuf, const double kuh,
+                        const CompBeltIn ii, const CompBeltOut o, int u0, int nrb, int M, int C, int lgC, int Q, int P)
+{
+#pragma clang fp contract(off)
+    static_assert(NCF >= 3 && NCF - 3 <= NUSI_FIT_TEMPLATES_MAX, "k_composition_belt: three signal components and NCF - 3 templates");
+    constexpr int KT = NCF - 3;
+    const int G = ii.G, QG = Q * G;
+    const int tid = (int)threadIdx.x, u = u0 + (int)blockIdx.x, t = u / nrb;
+    const int c = tid & ((1 << lgC) - 1), grp = tid >> lgC;
+    const int QB = kEvThreads >> lgC, row = (u - t * nrb) * QB + grp;
+    const int cc = c < C ? c : C - 1, rc = row < QG ? row : QG - 1, q = rc / G, gp = rc - q * G;   // q < Q, gp < G
+    const int pair = t * Q + q;
+    const double* __restrict__ Rt = R3 + (size_t)t * 3 * M * C + cc;
+    const double* __restrict__ Sq = S + (size_t)q * M;
+    const double* __restrict__ ph = ii.phi + ((size_t)(ii.phi_tables ? t : 0) * G + gp) * 3;
+    const bool in = c < C;
+    const bool mine = row < QG;   // the record is this block's to store
+    int p0, p1;
+    ens_share(P, (int)blockIdx.z, (int)gridDim.z, p0, p1);
+    double XF[NCF], sphi;
+    {
+        const double f0 = ph[0], f1 = ph[1], f2 = ph[2];
+        double s0[3], sp = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) s0[j] = 0.0;
+#pragma unroll 4
+        for (int n = 1; n < M; ++n) {
+            const double sv = Sq[n];
+            double rv[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                rv[j] = Rt[((size_t)j * M + n) * C];
+                s0[j] = s0[j] + rv[j] * sv;
+            }
+            const double r = (f0 * rv[0] + f1 * rv[1]) + f2 * rv[2];
+            sp = sp + r * sv;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) XF[j] = in ? s0[j] : 0.0;
+        sphi = in ? sp : 0.0;
+    }
+#pragma unroll
+    for (int j = 3; j < NCF; ++j) XF[j] = in ? T[(size_t)(j - 3) * C + cc] : 0.0;
+    struct {
+        double m[NCF], w[NCF];
+    } prf;   // the free fit's priors: template i's behind the signal components' zeros
+#pragma unroll
+    for (int j = 0; j < NCF; ++j) {
+        prf.m[j] = j < 3 ? 0.0 : tp.m[j < 3 ? 0 : j - 2];
+        prf.w[j] = j < 3 ? 0.0 : tp.w[j < 3 ? 0 : j - 2];
+    }
+    const double b = in ? bg[cc] : 0.0;
+    const unsigned long long gmask = (lgC == 6 ? ~0ull : (1ull << (1 << lgC)) - 1) << ((tid & 63) & ~((1 << lgC) - 1));
+    auto add = [](double x, double y) { return x + y; };
+    auto min = [](double x, double y) { return y < x ? y : x; };
+    auto any = [&](bool x) { return (__ballot(x) & gmask) != 0; };
+    double S1F[NCF], S1p;   // tree(XF_j), tree(s_phi): the data do not enter
+    {
+        double sv[NCF + 1];
+#pragma unroll
+        for (int j = 0; j < NCF; ++j) sv[j] = XF[j];
+        sv[NCF] = sphi;
+        det_butterfly(sv, lgC, add);
+#pragma unroll
+        for (int j = 0; j < NCF; ++j) S1F[j] = sv[j];
+        S1p = sv[NCF];
+    }
+    const size_t rg = (size_t)pair * G + gp;   // the record's row of the call's [ntab][Q][G] arrays
+    double mu_inj = 0.0, qobs = __builtin_nan("");   // both set by the observed pass
+    bool valid = false;
+
+#pragma unroll 1
+    for (int p = p0 - 1; p < p1; ++p) {
+        const bool obs = p < p0;   // (uniform over the block: the pass against the data)
+        double d;
+        if (obs) {
+            d = in ? ii.data[cc] : 0.0;
+        } else {
+            // (the expectation through an opaque copy, as in k_inject)
+            double mup = mu_inj;
+            asm volatile("" : "+v"(mup));
+            d = in ? draw::poisson(mup, draw::ident(ii.seed, (unsigned)t, (unsigned)rc, (unsigned)p, (unsigned)c)) : 0.0;
+            if (o.data && in && mine) o.data[(rg * P + p) * C + c] = valid ? d : 0.0;
+        }
+
+#include "nusi_composition_body.inc"
+
+        if (obs) {
+            valid = !nofit && !nocond;
+            qobs = valid ? stat : __builtin_nan("");
+            mu_inj = valid ? mu : 0.0;
+            if (c == 0 && mine && blockIdx.z == 0) {
+                const size_t ro = (size_t)pair * (1 + G);
+                if (gp == 0) {
+                    if (o.thobs) {
+#pragma unroll
+                        for (int j = 0; j < NCF; ++j) o.thobs[ro * NCF + j] = thh[j];
+                    }
+                    if (o.wobs) o.wobs[ro] = sth;
+                }
+                if (o.thobs) {
+#pragma unroll
+                    for (int j = 0; j < NCF; ++j) o.thobs[(ro + 1 + gp) * NCF + j] = j <= KT ? thc[j <= KT ? j : 0] : 0.0;
+                }
+                if (o.wobs) o.wobs[ro + 1 + gp] = stc;
+                if (o.qobs) o.qobs[rg] = qobs;
+            }
+        } else if (c == 0 && mine) {
+            if (o.theta) {
+#pragma unroll
+                for (int j = 0; j < NCF; ++j) o.theta[(rg * P + p) * NCF + j] = (valid && !nofit) ? thh[j] : __builtin_nan("");
+            }
+            if (o.stat) o.stat[rg * P + p] = valid ? stat : __builtin_nan("");
+            if (o.words) {
+                o.words[(rg * P + p) * 2] = valid ? sth : 0;
+                o.words[(rg * P + p) * 2 + 1] = valid ? stc : 0;
+            }
+            if (o.tally && valid) {
+                int* ty = o.tally + rg * 4;
+                if (nofit) atomicAdd(ty + 0, 1);
+                if (nocond && !nofit) atomicAdd(ty + 1, 1);
+                if (sth & (NUSI_FIT_ZERO * 7 | NUSI_FIT_BOUNDARY | NUSI_FIT_FLAT)) atomicAdd(ty + 2, 1);
+                if (sth & NUSI_FIT_INFINITE) atomicAdd(ty + 3, 1);
+            }
+            if (o.exceed && valid && stat >= qobs) atomicAdd(o.exceed + rg, 1);
+        }
+    }
+}
+
+// k_composition_accept: per pair (t, q) the acceptance rule over the G points, g ascending, from the counts, the observed
+// words and q_obs (detector.composition_accept): valid = neither word[0] nor word[1 + g] flagged; nv = P - tally[0] -
+// tally[1]; accepted iff valid, nv > 0 and (double)exceed > alpha (double)nv.  accept [ntab][Q][G], status and best
+// [ntab][Q]; any may be nullptr.
+__global__ __launch_bounds__(kBeltAcceptThreads) void k_composition_accept(const int* __restrict__ exceed,
+                                                                           const int* __restrict__ tally,
+                                                                           const int* __restrict__ wobs,
+                                                                           const double* __restrict__ qobs, int G, int P,
+                                                                           double alpha, int npairs, int* __restrict__ accept,
+                                                                           int* __restrict__ status, int* __restrict__ best)
+{
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * kBeltAcceptThreads + threadIdx.x;
+    if (i >= npairs) return;
+    const size_t pair = (size_t)i;
+    const int fail = NUSI_FIT_NOT_CONVERGED | NUSI_FIT_SINGULAR;
+    const int* ex = exceed + pair * G;
+    const int* ty = tally + pair * G * 4;
+    const int* wo = wobs + pair * (1 + G);
+    const double* qo = qobs + pair * G;
+    const bool nofit = (wo[0] & fail) != 0;
+    int st = nofit ? NUSI_REGION_NO_FIT : 0, nacc = 0, nvalid = 0, bg = -1;
+    double bq = 0.0;
+    for (int g = 0; g < G; ++g) {
+        const bool nocond = (wo[1 + g] & fail) != 0, valid = !nofit && !nocond;
+        if (!nofit && nocond) st |= NUSI_REGION_BAD_POINT;
+        const int nv = P - ty[g * 4] - ty[g * 4 + 1];
+        if (valid && nv <= 0) st |= NUSI_REGION_BAD_POINT;
+        const double lim = alpha * (double)nv;
+        const bool acc = valid && nv > 0 && (double)ex[g] > lim;
+        if (accept) accept[pair * G + g] = acc ? 1 : 0;
+        nvalid += valid ? 1 : 0;
+        nacc += acc ? 1 : 0;
+        if (valid && (bg < 0 || qo[g] < bq)) {
+            bg = g;
+            bq = qo[g];
+        }
+    }
+    if (nacc == 0) st |= NUSI_REGION_EMPTY;
+    if (nvalid > 0 && nacc == nvalid) st |= NUSI_REGION_ALL;
+    if (status) status[pair] = st;
+    if (best) best[pair] = bg;
+}
+
+int composition_belt_block(int C) { return kEvThreads >> ceil_log2(C); }
+
+hipError_t launch_composition_belt(const GridDev& g, const double* R3, int ntab, const double* S, int Q, const double* data,
+                                   const double* phi, bool phi_tables, int G, int P, unsigned long long seed, const double* bg,
+                                   int C, int K, const double* T, const double* pm, const double* pw, int pslices,
+                                   int* exceed, int* tally, int* wobs, double* qobs, double* thobs, double* theta, double* stat,
+                                   int* words, double* data_all, hipStream_t s)
+{
+    if (ntab <= 0 || Q <= 0 || G <= 0 || P <= 0) return hipSuccess;
+    const int lg = ceil_log2(C), QB = kEvThreads >> lg, nrb = (int)(((long long)Q * G + QB - 1) / QB);
+    const long long units = (long long)ntab * nrb;
+    if (units > 0x7fffffffll) return hipErrorInvalidValue;
+    const FitPrior pr = fit_prior(K, pm, pw);
+    const CompBeltIn ii{data, phi, seed, G, phi_tables ? 1 : 0};
+    const CompBeltOut o{exceed, tally, wobs, qobs, thobs, theta, stat, words, data_all};
+    const double kuf = fit_ku(lg, 2 + K), kuh = fit_ku(lg, K);
+    const dim3 block(kEvThreads);
+    const int M = g.T + 1;
+    constexpr long long kRange = 1ll << 22;   // units a launch: 2^22 blocks of 256 threads stay below 2^32 threads on x
+    for (long long ua = 0; ua < units; ua += kRange) {
+        const dim3 grid((unsigned)(units - ua < kRange ? units - ua : kRange), 1, (unsigned)pslices);
+        const int u0 = (int)ua;
+        switch (K) {
+        case 0: hipLaunchKernelGGL((k_composition_belt<3>), grid, block, 0, s, R3, S, bg, T, pr, kuf, kuh, ii, o, u0, nrb, M, C, lg, Q, P); break;
+        case 1: hipLaunchKernelGGL((k_composition_belt<4>), grid, block, 0, s, R3, S, bg, T, pr, kuf, kuh, ii, o, u0, nrb, M, C, lg, Q, P); break;
+        case 2: hipLaunchKernelGGL((k_composition_belt<5>), grid, block, 0, s, R3, S, bg, T, pr, kuf, kuh, ii, o, u0, nrb, M, C, lg, Q, P); break;
+        case 3: hipLaunchKernelGGL((k_composition_belt<6>), grid, block, 0, s, R3, S, bg, T, pr, kuf, kuh, ii, o, u0, nrb, M, C, lg, Q, P); break;
+        default: return hipErrorInvalidValue;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_composition_accept(int npairs, int G, int P, double alpha, const int* exceed, const int* tally,
+                                     const int* wobs, const double* qobs, int* accept, int* status, int* best, hipStream_t s)
+{
+    if (npairs <= 0) return hipSuccess;
+    const unsigned nb = (unsigned)(((long long)npairs + kBeltAcceptThreads - 1) / kBeltAcceptThreads);
+    hipLaunchKernelGGL(k_composition_accept, dim3(nb), dim3(kBeltAcceptThreads), 0, s, exceed, tally, wobs, qobs, G, P, alpha,
+                       npairs, accept, status, best);
     return hipGetLastError();
 }
 

@@ -247,6 +247,21 @@ hipError_t launch_belt(const GridDev& g, const double* R, const double* S, int Q
 hipError_t launch_belt_accept(const double* frac, int G, const double* ref, int P, double alpha, int pr0, int pr1,
                               const int* exceed, bool exceed_compact, const int* tally, bool tally_compact, const int* wobs,
                               bool wobs_compact, double* lo, double* hi, int* idx, int* status, hipStream_t s);
+// k_composition_belt<3 + K>, k_composition_accept (include/nusi.h nusi_plan_response_composition_belt): R3
+// [ntab][3][M][C], S [Q][M], data [C] and phi [G][3] (phi_tables: [ntab][G][3]) in device memory; a unit is one table
+// and composition_belt_block(C) of its Q G rows, and the launcher cuts the units into ranges a grid can hold.  The
+// observed side goes to qobs [ntab][Q][G], thobs [ntab][Q][1 + G][3 + K] and wobs [ntab][Q][1 + G]; the toys' records to
+// theta [ntab][Q][G][P][3 + K], stat [..][P], words [..][P][2] and data_all [..][P][C]; the counts are ADDED to exceed
+// [ntab][Q][G] and tally [..][4].  launch_composition_accept forms accept [ntab][Q][G], status and best [ntab][Q] from
+// exceed, tally, wobs and qobs.  Any output may be nullptr.
+int composition_belt_block(int C);
+hipError_t launch_composition_belt(const GridDev& g, const double* R3, int ntab, const double* S, int Q, const double* data,
+                                   const double* phi, bool phi_tables, int G, int P, unsigned long long seed, const double* bg,
+                                   int C, int K, const double* T, const double* pm, const double* pw, int pslices,
+                                   int* exceed, int* tally, int* wobs, double* qobs, double* thobs, double* theta, double* stat,
+                                   int* words, double* data_all, hipStream_t s);
+hipError_t launch_composition_accept(int npairs, int G, int P, double alpha, const int* exceed, const int* tally,
+                                     const int* wobs, const double* qobs, int* accept, int* status, int* best, hipStream_t s);
 size_t cascade_src_doubles(const GridDev& g);   // t.Src doubles per point
 hipError_t launch_source_dsnb(const GridDev& g, const Point* pts, int npts, double* src, hipStream_t s);
 // Tabulated sources (NUSI_SOURCE_TABULATED + slot): `slots` is the plan's slot storage in device memory,

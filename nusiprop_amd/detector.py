@@ -1576,6 +1576,149 @@ def belt_host(R, S, data, frac, P, seed, ref=None, mode="two-sided", alpha=0.1, 
     return out + ((th_all, st_all, words, data_all) + ((nuis_all,) if ens != TOYS_FIXED else ()) if raw else ())
 
 
+REGION_GRID_MAX = 1024                                         # the most points of composition_belt_host's grid; its status bits:
+REGION_NO_FIT, REGION_BAD_POINT, REGION_EMPTY, REGION_ALL = 1, 2, 4, 8
+
+
+def composition_tally(words):
+    """tally[..., 4] of nusi_plan_response_composition_belt from the words (..., P, 2): the toys whose free fit failed
+    (FIT_NOT_CONVERGED | FIT_SINGULAR in word 0), whose held fit failed (word 1) and whose free fit did not, whose free
+    fit ends with a SIGNAL component at zero (FIT_ZERO << j for a j < 3, FIT_BOUNDARY or FIT_FLAT) and whose free fit is
+    FIT_INFINITE (int32)."""
+    w = np.asarray(words)
+    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
+    nofit, nocond = (w[..., 0] & fail) != 0, (w[..., 1] & fail) != 0
+    edge = FIT_ZERO | (FIT_ZERO << 1) | (FIT_ZERO << 2) | FIT_BOUNDARY | FIT_FLAT
+    cols = [nofit, nocond & ~nofit, (w[..., 0] & edge) != 0, (w[..., 0] & FIT_INFINITE) != 0]
+    return np.stack([c.sum(axis=-1) for c in cols], axis=-1).astype(np.int32)
+
+
+def composition_accept(exceed, tally, valid, alpha, P, q_obs, flags=0):
+    """The acceptance rule of composition_belt_host on arrays.  exceed (..., G) and tally (..., G, 4): the counts of P
+    toys a point; valid (..., G) bool (or None: all): the points whose observed fits held -- the others have no toys;
+    q_obs (..., G); flags (...): the observed side's bits (REGION_NO_FIT, REGION_BAD_POINT of a failed held fit), OR-ed
+    into the word.  nv = P - tally[..., 0] - tally[..., 1]; a point is accepted iff it is valid, nv > 0 and float(exceed) >
+    alpha * float(nv), one multiplication and one strict comparison.  Returns (accept (..., G) bool, status (...) int32,
+    best (...) int32): REGION_BAD_POINT also where a valid point has nv <= 0, REGION_EMPTY where no point is accepted,
+    REGION_ALL where there is a valid point and every valid point is accepted; best = the g of the smallest q_obs among
+    the valid points, ties to the lowest g, -1 without one.  Nothing is interpolated."""
+    ex = np.asarray(exceed)
+    ty = np.asarray(tally)
+    qo = np.asarray(q_obs, dtype=np.float64)
+    if ty.shape != ex.shape + (4,) or qo.shape != ex.shape:
+        raise ValueError("composition_accept: exceed (..., G), tally (..., G, 4) and q_obs (..., G) do not match")
+    ok = np.ones(ex.shape, dtype=bool) if valid is None else np.broadcast_to(np.asarray(valid, dtype=bool), ex.shape)
+    nv = int(P) - ty[..., 0].astype(np.int64) - ty[..., 1].astype(np.int64)
+    acc = ok & (nv > 0) & (ex.astype(np.float64) > np.float64(alpha) * nv.astype(np.float64))
+    nacc, nok = acc.sum(axis=-1), ok.sum(axis=-1)
+    st = np.array(np.broadcast_to(np.asarray(flags, dtype=np.int32), nacc.shape))
+    st[np.any(ok & (nv <= 0), axis=-1)] |= REGION_BAD_POINT
+    st[nacc == 0] |= REGION_EMPTY
+    st[(nok > 0) & (nacc == nok)] |= REGION_ALL
+    best = np.where(nok > 0, np.argmin(np.where(ok, qo, np.inf), axis=-1), -1)   # (argmin: the first of equal values)
+    return acc, st.astype(np.int32), best.astype(np.int32)
+
+
+def _composition_one(R3t, Rc, Sq, d, T, prior, B, log):
+    """One data set d (C,) through steps 2 - 4 of nusi_plan_response_composition_belt for one table's stack R3t (3, M, C),
+    its composed rows Rc (G, M, C) and spectra Sq (Q, M): the free fit (fit_components_host), the held fits (fit_host;
+    profile_host without templates), lambda (composition_statistic) and the statistic.  Returns (theta_hat (Q, 3 + K),
+    its words (Q,), theta (G, Q, 1 + K), words (G, Q), mu (G, Q, C), stat (G, Q), mag (G, Q)); stat is NaN where either
+    word has FIT_NOT_CONVERGED | FIT_SINGULAR."""
+    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
+    tpl = T if len(T) else None
+    thh, _, muh, sth = fit_components_host(R3t[None], Sq, d, templates=tpl, prior=prior, background=B, log=log)
+    if len(T):
+        th, _, mu, st = fit_host(Rc, Sq, d, T, prior=prior, background=B, log=log)
+    else:
+        ah, _, mu, st = profile_host(Rc, Sq, d, background=B, log=log)
+        th = ah[..., None]
+    lam, mag = composition_statistic(mu, th, muh, thh, d, prior=prior if len(T) else None, log=log)
+    with np.errstate(invalid="ignore"):
+        stat = np.where(lam > 0.0, 2.0 * lam, 0.0)
+    stat = np.where(((sth[0][None, :] | st) & fail) != 0, np.nan, stat)
+    return thh[0], sth[0], th, st, mu, stat, mag
+
+
+def composition_belt_host(R3, S, data, phi, P, seed, alpha=0.1, templates=None, prior=None, background=None, exp=np.exp,
+                          log=np.log, raw=False):
+    """The toy-calibrated confidence region of the source's flavour composition -- the Feldman-Cousins region by the
+    profile construction -- on a grid of compositions, as a loop of the existing host forms (numpy only;
+    Plan.composition_belt is the device call that reproduces it: DESIGN.md sec. 4, "The composition region").  Per table
+    t, spectrum q and grid point g the held rows are response.compose_host(R3, phi)[t, g]; the data get the free fit
+    (fit_components_host on R3), the held fit (fit_host on the composed rows; profile_host without templates) and
+    composition_statistic, which gives the observed records and q_obs = max(2 lambda, 0); the toys are draw_host of the
+    held fit's own mu with stream = t at row q G + g, and each gets the same steps at phi_g.
+
+    R3: (3, M, C) or (ntab, 3, M, C).  S: (M,) or (Q, M).  data: (C,).  phi: (G, 3) or (ntab, G, 3), finite, >= 0, no
+    point all zeros, G <= REGION_GRID_MAX.  alpha in (0, 1).  templates, prior, background, log: as for fit_host; exp: as
+    for draw_host.  Returns (accept (ntab, Q, G) bool, status (ntab, Q) int32 -- REGION_* --, best (ntab, Q) int32,
+    exceed (ntab, Q, G) int32, tally (ntab, Q, G, 4) int32 -- composition_tally --, q_obs (ntab, Q, G), theta_obs (ntab,
+    Q, 1 + G, 3 + K): [0] the free fit, [1 + g] the held fit's theta in slots 0 .. K and +0.0 behind, words_obs (ntab, Q,
+    1 + G) int32) and with raw also (theta_all (ntab, Q, G, P, 3 + K): the free fit's, NaN where it failed, stat_all
+    (ntab, Q, G, P), words_all (ntab, Q, G, P, 2) int32, data_all (ntab, Q, G, P, C)).  A point without toys (a failed
+    observed fit) has q_obs NaN, counts of 0 and raw outputs of NaN / 0.  No axis is squeezed."""
+    from .response import compose_host
+    R3 = np.asarray(R3, dtype=np.float64)
+    S = np.asarray(S, dtype=np.float64)
+    if R3.ndim == 3:
+        R3 = R3[None]
+    if S.ndim == 1:
+        S = S[None]
+    if R3.ndim != 4 or R3.shape[1] != 3 or S.ndim != 2 or R3.shape[2] != S.shape[1]:
+        raise ValueError("composition_belt_host: R3 (.., 3, M, C) and S (.., M) do not match: %s, %s" % (R3.shape, S.shape))
+    ntab, C, Q, P = R3.shape[0], R3.shape[3], S.shape[0], int(P)
+    if not 1 <= P:
+        raise ValueError("composition_belt_host: P must be >= 1")
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("composition_belt_host: alpha must lie in (0, 1)")
+    ph = np.asarray(phi, dtype=np.float64)
+    if ph.ndim not in (2, 3) or ph.shape[-1] != 3 or (ph.ndim == 3 and ph.shape[0] != ntab):
+        raise ValueError("composition_belt_host: phi must have shape (G, 3) or (ntab, G, 3), got %s" % (ph.shape,))
+    G = ph.shape[-2]
+    if not 1 <= G <= REGION_GRID_MAX or not np.all(np.isfinite(ph)) or np.any(ph < 0) or np.any(np.all(ph == 0, axis=-1)):
+        raise ValueError("composition_belt_host: phi must hold 1 .. %d points, finite, >= 0 and none all zeros" % REGION_GRID_MAX)
+    d = np.asarray(data, dtype=np.float64).reshape(-1)
+    if d.shape != (C,) or not np.all(np.isfinite(d)) or np.any(d < 0):
+        raise ValueError("composition_belt_host: data must be (C,), finite and >= 0")
+    K = 0 if templates is None else _templates(templates, C).shape[0]
+    T = np.zeros((0, C)) if K == 0 else _templates(templates, C)
+    B = np.zeros(C) if background is None else np.array(np.broadcast_to(np.asarray(background, dtype=np.float64), (C,)))
+    Rc = compose_host(R3, ph)                                   # (ntab, G, M, C)
+    fail = FIT_NOT_CONVERGED | FIT_SINGULAR
+    NC = 3 + K
+    q_obs = np.full((ntab, Q, G), np.nan)
+    theta_obs, words_obs = np.zeros((ntab, Q, 1 + G, NC)), np.zeros((ntab, Q, 1 + G), dtype=np.int32)
+    th_all, st_all = np.full((ntab, Q, G, P, NC), np.nan), np.full((ntab, Q, G, P), np.nan)
+    words, data_all = np.zeros((ntab, Q, G, P, 2), dtype=np.int32), np.zeros((ntab, Q, G, P, C))
+    valid = np.zeros((ntab, Q, G), dtype=bool)
+    flags = np.zeros((ntab, Q), dtype=np.int32)
+    with np.errstate(all="ignore"):
+        for t in range(ntab):
+            thh, sth, th, st, mu, stat, _ = _composition_one(R3[t], Rc[t], S, d, T, prior, B, log)
+            theta_obs[t, :, 0], words_obs[t, :, 0] = thh, sth
+            theta_obs[t, :, 1:, :1 + K], words_obs[t, :, 1:] = np.swapaxes(th, 0, 1), st.T
+            nofit, nocond = (sth & fail) != 0, (st.T & fail) != 0                    # (Q,), (Q, G)
+            flags[t][nofit] |= REGION_NO_FIT
+            flags[t][~nofit & nocond.any(axis=1)] |= REGION_BAD_POINT
+            valid[t] = ~nofit[:, None] & ~nocond
+            q_obs[t] = np.where(valid[t], stat.T, np.nan)
+            mu_inj = np.where(valid[t][..., None], np.swapaxes(mu, 0, 1), 0.0)       # (Q, G, C)
+            toys = np.reshape(draw_host(mu_inj.reshape(Q * G, C), P, seed, stream=t, exp=exp, log=log), (Q, G, P, C))
+            for q, g in zip(*np.nonzero(valid[t])):
+                data_all[t, q, g] = toys[q, g]
+                for p in range(P):
+                    r = _composition_one(R3[t], Rc[t, g:g + 1], S[q:q + 1], toys[q, g, p], T, prior, B, log)
+                    if not int(r[1][0]) & fail:
+                        th_all[t, q, g, p] = r[0][0]
+                    st_all[t, q, g, p], words[t, q, g, p] = r[5][0, 0], (r[1][0], r[3][0, 0])
+    tally = np.where(valid[..., None], composition_tally(words), 0).astype(np.int32)
+    with np.errstate(invalid="ignore"):
+        exceed = (st_all >= q_obs[..., None]).sum(axis=-1).astype(np.int32)
+    out = composition_accept(exceed, tally, valid, alpha, P, q_obs, flags) + (exceed, tally, q_obs, theta_obs, words_obs)
+    return out + ((th_all, st_all, words, data_all) if raw else ())
+
+
 def matrix(lo, hi, aeff, migration=None, exposure=1.0):
     """D[c, f, b] = exposure * (hi_b - lo_b) * aeff[f][b] * migration[c][b], shape (C, 3, N).
 

@@ -993,6 +993,84 @@ class Plan:
             dev(d_stat_all_ptr), dev(d_words_all_ptr), dev(d_data_all_ptr), dev(stream_ptr)))
         return len(S), len(fr)
 
+    # --- the toy-calibrated region of the flavour composition (include/nusi.h nusi_plan_response_composition_belt) ---
+    def _composition_args(self, spectra, data, phi, ntab):
+        S, _ = self._spectra(spectra, None)
+        d = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+        C = self.detector_bins()
+        if C and d.shape != (C,):                                   # (no detector: the library refuses, NUSI_ESTATE)
+            raise ValueError("composition_belt: data must have shape (%d,), got %s" % (C, np.shape(data)))
+        ph = np.ascontiguousarray(phi, dtype=np.float64)
+        if ph.ndim not in (2, 3) or ph.shape[-1] != 3 or (ph.ndim == 3 and ph.shape[0] != ntab):
+            raise ValueError("composition_belt: phi must have shape (G, 3) or (ntab, G, 3), got %s" % (ph.shape,))
+        return S, d, ph
+
+    def composition_belt(self, R3, spectra, data, phi, P, seed, alpha=0.1, raw=False):
+        """The toy-calibrated confidence region of the source's flavour composition -- the Feldman-Cousins region by
+        the profile construction -- on a grid of compositions, in one call on the GPU.  R3 (ntab, 3, M, C): three folded
+        rows per table, ``fit_components``' input; phi (G, 3) or (ntab, G, 3): weights >= 0 on those rows, no point all
+        zeros, G <= _lib.REGION_GRID_MAX.  Per table t, spectrum q and point g the data (C,) get ``composition_scan``'s
+        steps at phi_g -- the free fit of the three components, the fit on the composed rows with the scale and the
+        plan's templates floating, the statistic --, which gives the observed records and q_obs; P toys are drawn on the
+        device from the held fit's own expectation (``draw`` with stream = t at row q G + g) and each gets the same steps
+        at phi_g; a point is accepted iff exceed > alpha * (P - tally[0] - tally[1]).  Returns
+        detector.composition_belt_host's tuple: (accept (ntab, Q, G) bool, status (ntab, Q) int32 -- _lib.REGION_* --,
+        best (ntab, Q) int32, exceed (ntab, Q, G) int32, tally (ntab, Q, G, 4) int32, q_obs (ntab, Q, G), theta_obs (ntab,
+        Q, 1 + G, 3 + K), words_obs (ntab, Q, 1 + G) int32) and with raw also (theta_all (ntab, Q, G, P, 3 + K), stat_all
+        (ntab, Q, G, P), words_all (ntab, Q, G, P, 2) int32, data_all (ntab, Q, G, P, C)).  No axis is squeezed.  Only
+        the "fixed" toy ensemble is built: under another (``set_option(OPT_TOY_NUISANCE, ..)``) with a constrained
+        template the call is refused."""
+        R3, J, C = self._stack(R3, "composition_belt")
+        if J != 3:
+            raise ValueError("composition_belt: R3 must have shape (ntab, 3, M, C), got %s" % (R3.shape,))
+        ntab, P = R3.shape[0], int(P)
+        S, d, ph = self._composition_args(spectra, data, phi, ntab)
+        Q, G, NC, Pa = len(S), ph.shape[-2], self.templates() + 3, max(P, 0)
+        accept, status = np.zeros((ntab, Q, G), dtype=np.int32), np.zeros((ntab, Q), dtype=np.int32)
+        best = np.full((ntab, Q), -1, dtype=np.int32)
+        exceed, tally = np.zeros((ntab, Q, G), dtype=np.int32), np.zeros((ntab, Q, G, 4), dtype=np.int32)
+        q_obs, th_obs = np.full((ntab, Q, G), np.nan), np.full((ntab, Q, 1 + G, NC), np.nan)
+        w_obs = np.zeros((ntab, Q, 1 + G), dtype=np.int32)
+        th_all = st_all = words = toys = None
+        if raw:
+            th_all, st_all = np.full((ntab, Q, G, Pa, NC), np.nan), np.full((ntab, Q, G, Pa), np.nan)
+            words, toys = np.zeros((ntab, Q, G, Pa, 2), dtype=np.int32), np.zeros((ntab, Q, G, Pa, C))
+        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+
+        def ptr(x, t):
+            return x.ctypes.data_as(t) if x is not None else None
+        _lib.check(_lib.load().nusi_plan_response_composition_belt_host(
+            self._h, R3.ctypes.data_as(dp), ntab, S.ctypes.data_as(dp), Q, d.ctypes.data_as(dp), ph.ctypes.data_as(dp),
+            1 if ph.ndim == 3 else 0, G, P, int(seed) & (2 ** 64 - 1), float(alpha), ptr(accept, ip), ptr(status, ip),
+            ptr(best, ip), ptr(exceed, ip), ptr(tally, ip), ptr(q_obs, dp), ptr(th_obs, dp), ptr(w_obs, ip),
+            ptr(th_all, dp), ptr(st_all, dp), ptr(words, ip), ptr(toys, dp)))
+        out = (accept != 0, status, best, exceed, tally, q_obs, th_obs, w_obs)
+        return out + ((th_all, st_all, words, toys) if raw else ())
+
+    def composition_belt_device(self, d_R3_ptr, ntab, spectra, data, phi, P, seed, alpha=0.1, d_accept_ptr=None,
+                                d_status_ptr=None, d_best_ptr=None, d_exceed_ptr=None, d_tally_ptr=None, d_q_obs_ptr=None,
+                                d_theta_obs_ptr=None, d_words_obs_ptr=None, d_theta_all_ptr=None, d_stat_all_ptr=None,
+                                d_words_all_ptr=None, d_data_all_ptr=None, stream_ptr=None):
+        """Asynchronous ``composition_belt`` on a device-resident stack d_R3 [ntab][3][M][C]: the outputs are raw pointers
+        (d_q_obs [ntab][Q][G], d_theta_obs [ntab][Q][1 + G][3 + K], d_theta_all [ntab][Q][G][P][3 + K], d_stat_all
+        [ntab][Q][G][P] and d_data_all [ntab][Q][G][P][C] doubles; d_accept [ntab][Q][G], d_status, d_best [ntab][Q],
+        d_exceed [ntab][Q][G], d_tally [ntab][Q][G][4], d_words_obs [ntab][Q][1 + G] and d_words_all [ntab][Q][G][P][2]
+        ints), any may be 0 / None but not all; d_accept, d_status and d_best need d_exceed, d_tally, d_q_obs and
+        d_words_obs.  The other arguments are host data and are copied.  Returns (Q, G)."""
+        S, d, ph = self._composition_args(spectra, data, phi, int(ntab))
+        dp = ctypes.POINTER(ctypes.c_double)
+        vp = ctypes.c_void_p
+
+        def dev(x):
+            return vp(x) if x else None
+        _lib.check(_lib.load().nusi_plan_response_composition_belt(
+            self._h, vp(d_R3_ptr), int(ntab), S.ctypes.data_as(dp), len(S), d.ctypes.data_as(dp), ph.ctypes.data_as(dp),
+            1 if ph.ndim == 3 else 0, ph.shape[-2], int(P), int(seed) & (2 ** 64 - 1), float(alpha), dev(d_accept_ptr),
+            dev(d_status_ptr), dev(d_best_ptr), dev(d_exceed_ptr), dev(d_tally_ptr), dev(d_q_obs_ptr), dev(d_theta_obs_ptr),
+            dev(d_words_obs_ptr), dev(d_theta_all_ptr), dev(d_stat_all_ptr), dev(d_words_all_ptr), dev(d_data_all_ptr),
+            dev(stream_ptr)))
+        return len(S), ph.shape[-2]
+
     def set_cascade(self, kind):
         """Cascade kernel of later calls: _lib.CASCADE_AUTO (default) = CASCADE_MFMA (the wavefront with its push
         on the fp64 matrix cores, the block-synchronous k_cascade_bs), or CASCADE_{WAVEFRONT,REG,LDS} (since
