@@ -99,8 +99,34 @@ def main():
     out["clausen"] = []
     for x in [1e-12, 1e-8, 1e-3, 0.5, 1.0, 2.0, 3.0, 3.14159, -1.0, -3.0] + [random.uniform(-7, 7) for _ in range(100)]:
         out["clausen"].append([x, f(mp.clsin(2, x))])
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "specfun_kat.json"), "w") as fh:
+    # e_log10.c, pow(x > 0, y) = exp(y log x) and GSL's hypot (nusi_libm.hpp, nusi_gsl.hpp), in a file of their own
+    # (specfun_kat_libm.json; specfun_kat.json stays as it was); drawn after every set above.  pow over the power-law
+    # source's range -- x = E = 10^lE, lE in [4, 17], y = -si, si in [2, 3], corners included --, on the argument the
+    # cascade forms (E / 1e14 (1 + z)), and at large
+    new = {"log10": [], "pow": [], "hypot": []}
+    for x in [10.0 ** k for k in range(-300, 301, 50)] + [1.0, 0.1, 1000.0, 5e-324, 2.0 ** -1022, 1.7976931348623157e308]:
+        new["log10"].append([x, f(mp.log10(x))])
+    for _ in range(120):
+        x = 10 ** random.uniform(-300, 300) if random.random() < 0.7 else 1 + random.uniform(-0.5, 1.0)
+        new["log10"].append([x, f(mp.log10(x))])
+    pw = [(10.0 ** le, -si) for le in (4.0, 17.0) for si in (2.0, 3.0)]
+    pw += [(10 ** random.uniform(4, 17), -random.uniform(2, 3)) for _ in range(150)]
+    pw += [(10 ** random.uniform(16, 17), -random.uniform(2.9, 3)) for _ in range(50)]
+    pw += [(10 ** random.uniform(4, 17) / 1e14 * (1 + random.uniform(0, 5)), -random.uniform(2, 3)) for _ in range(40)]
+    pw += [(10 ** random.uniform(-30, 30), random.uniform(-8, 8)) for _ in range(40)]
+    for x, y in pw:
+        new["pow"].append([x, y, f(mp.power(mp.mpf(x), mp.mpf(y)))])
+    for _ in range(100):
+        a = random.gauss(0, 1) * 10 ** random.uniform(-150, 150)
+        b = a * 10 ** random.uniform(-3, 3) if random.random() < 0.6 else random.gauss(0, 1) * 10 ** random.uniform(-150, 150)
+        new["hypot"].append([a, b, f(mp.sqrt(mp.mpf(a) ** 2 + mp.mpf(b) ** 2))])
+    for a, b in [(3.0, 4.0), (1e-320, 1e-320), (1e300, 1e300), (2.0 ** 500, 2.0 ** -500), (1.0, 2.0 ** -27), (5e-324, 0.0)]:
+        new["hypot"].append([a, b, f(mp.sqrt(mp.mpf(a) ** 2 + mp.mpf(b) ** 2))])
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "specfun_kat.json"), "w") as fh:
         json.dump(out, fh)
+    with open(os.path.join(here, "specfun_kat_libm.json"), "w") as fh:
+        json.dump(new, fh)
 
 
 if __name__ == "__main__":

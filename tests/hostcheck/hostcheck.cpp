@@ -4,6 +4,7 @@
 // libnusi.so; the product runs these functions only inside HIP kernels.
 #include <vector>
 
+#include "nusi_debug_specfun.hpp"
 #include "nusi_physics.hpp"
 
 extern "C" {
@@ -281,4 +282,29 @@ void hc_gsl_krow(int k, double* o)
     o[0] = r.d1; o[1] = r.d2; o[2] = r.y1; o[3] = r.y2; o[4] = r.l1; o[5] = r.l2;
 }
 double hc_gsl_div_k(double a, double d, double y, double l) { return nusi::gsl::div_k<false>(a, d, y, l); }
+}
+
+// The host twin of k_debug_specfun (nusi_debug_specfun.hpp: the same dispatch, one call per element -- on the host a
+// "wave" is the one call).  Returns -1 for an unknown fn
+template <int FN>
+static void specfun_n(int n, const double* a, const double* b, const double* c, double* o0, double* o1)
+{
+    for (int i = 0; i < n; ++i) nusi::debug_specfun<FN>(a[i], b[i], c[i], o0[i], o1[i]);
+}
+template <int FN = 0>
+static int specfun_dispatch(int fn, int n, const double* a, const double* b, const double* c, double* o0, double* o1)
+{
+    if constexpr (FN < nusi::kDsCount) {
+        if (fn == FN) {
+            specfun_n<FN>(n, a, b, c, o0, o1);
+            return 0;
+        }
+        return specfun_dispatch<FN + 1>(fn, n, a, b, c, o0, o1);
+    } else {
+        return -1;
+    }
+}
+extern "C" int hc_specfun_n(int fn, int n, const double* a, const double* b, const double* c, double* o0, double* o1)
+{
+    return specfun_dispatch(fn, n, a, b, c, o0, o1);
 }

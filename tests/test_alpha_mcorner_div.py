@@ -13,7 +13,7 @@ spans gr = g^2 / 16 pi from 2e-8 to 2e-2.
   anything is compared; so is a wave that mixes inverted (|z| >= 1) and non-inverted lanes.
 * the host build of the same call chain (tests/hostcheck_div, built like tests/hostcheck) on the mixed batch's corners and on
   operands outside the member window, against the oracle's member_dc_ref -- Smith's division of (1 + S + t) by (2 + t -
-  i gr), restated here in numpy (oracle/ora_cplx.h zdiv), into the oracle's GSL complex dilogarithm.
+  i gr), restated in numpy (oracle/ora_cplx.h zdiv; tests/specfun_cases.py smith), into the oracle's GSL complex dilogarithm.
 """
 import ctypes
 import os
@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from tests import cases
+from tests.specfun_cases import smith as _smith   # (a + 0 i) / (c + d i) as oracle/ora_cplx.h zdiv forms it, elementwise
 
 BATCH_LABEL = "k_alpha_mcorner + k_alpha_batch[refo]"
 GRID = (45, 12.0, 12.75)
@@ -176,20 +177,6 @@ def hdiv():
     here = os.path.dirname(os.path.abspath(__file__))
     subprocess.check_call(["make", "-s", "-C", os.path.join(here, "hostcheck_div")])
     return ctypes.CDLL(os.path.join(here, "_build", "libhostcheck_div.so"))
-
-
-def _smith(a, c, d):
-    """(a + 0 i) / (c + d i) as oracle/ora_cplx.h zdiv forms it, elementwise"""
-    with np.errstate(all="ignore"):
-        first = np.abs(c) < np.abs(d)
-        ai = np.zeros_like(a)
-        r1 = c / d
-        den1 = (c * r1) + d
-        re1, im1 = ((a * r1) + ai) / den1, ((ai * r1) - a) / den1
-        r2 = d / c
-        den2 = (d * r2) + c
-        re2, im2 = ((ai * r2) + a) / den2, (ai - (a * r2)) / den2
-    return np.where(first, re1, re2), np.where(first, im1, im2)
 
 
 def _host_dc(H, S, t, gr, inline=True):

@@ -23,6 +23,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KAT = json.load(open(os.path.join(HERE, "golden", "specfun_kat.json")))
+KAT.update(json.load(open(os.path.join(HERE, "golden", "specfun_kat_libm.json"))))   # log10, pow, hypot
 D = ctypes.c_double
 
 
@@ -71,6 +72,50 @@ def test_libm_vs_mpmath(olib, name):
 
 def test_atan2_vs_mpmath(olib):
     assert max(_ulps(olib.ora_atan2(p, q), y) for p, q, y in KAT["atan2"]) <= 1.0
+
+
+def test_log10_vs_mpmath(olib):
+    """e_log10.c (ora_log10): <= 1 ulp, fdlibm's claim, over the whole range, exact powers of ten and arguments around 1."""
+    olib.ora_log10.restype = D
+    olib.ora_log10.argtypes = [D]
+    assert len(KAT["log10"]) >= 130
+    worst = max(_ulps(olib.ora_log10(x), y) for x, y in KAT["log10"])
+    assert worst <= 1.0, worst
+
+
+def test_hypot_vs_mpmath(oracle_mod):
+    """GSL's hypot (ora_hypot: sqrt(a^2 + b^2) and one correction step from the exact residual): <= 1 ulp."""
+    assert len(KAT["hypot"]) >= 100
+    worst = max(_ulps(oracle_mod.hypot(a, b), y) for a, b, y in KAT["hypot"])
+    assert worst <= 1.0, worst
+
+
+# pow(x > 0, y) = exp(y log x): log's result L has a relative error of at most 0.52 ulp <= 0.52 2^-52, the product RN(y L)
+# adds at most 2^-53 = 0.5 2^-52, so exp's argument is off by at most |y ln x| 1.02 2^-52 (to first order), which is the
+# relative error it leaves in the result; an ulp of the result is at least 2^-53 of it, so that is at most 2.04 |y ln x|
+# ulp, and exp's own error adds less than 1 ulp
+POW_ULP_PER_UNIT = 2 * (0.52 + 0.5)
+
+
+def test_pow_vs_mpmath(olib):
+    """pow(x > 0, y) = exp(y log x) (ora_pow; only the power-law source uses it) against mpmath: every vector within the
+    bound its two functions' own bounds give, (1 + 2.04 |y ln x|) ulp (derived above) -- not "a few ulp": the error grows
+    with |y ln x|, which reaches 117 at si = 3, E = 10^17.  Measured on these vectors (mpmath 1.3.0, 40 digits): over the
+    power-law source's range (x = E = 10^lE, lE in [4, 17], y = -si, si in [2, 3]; 204 vectors, the four corners included)
+    the worst error is 130 ulp, at |y ln x| = 111.7 (bound there 229 ulp); over all 284 vectors 193 ulp at |y ln x| =
+    369.8 (bound 755), and the largest fraction of the bound reached is 0.59."""
+    olib.ora_pow.restype = D
+    olib.ora_pow.argtypes = [D, D]
+    src = [(x, y, r) for x, y, r in KAT["pow"] if 1e4 <= x <= 1e17 and -3 <= y <= -2]
+    assert len(src) >= 200 and max(abs(y * math.log(x)) for x, y, _ in src) > 117
+    worst = worst_src = 0.0
+    for x, y, r in KAT["pow"]:
+        u, bound = _ulps(olib.ora_pow(x, y), r), 1 + POW_ULP_PER_UNIT * abs(y * math.log(x))
+        assert u <= bound, (x, y, u, bound)
+        worst = max(worst, u)
+        if 1e4 <= x <= 1e17 and -3 <= y <= -2:
+            worst_src = max(worst_src, u)
+    print("pow vs mpmath: worst %g ulp over the source's range, %g ulp over all vectors" % (worst_src, worst))
 
 
 def test_dilog_real_vs_mpmath(oracle_mod):
